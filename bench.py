@@ -15,10 +15,21 @@ Default workload = BASELINE.json configs[2]: se_resnet 40x256, minibatch 4096, b
 (the reference's production AMP mode), one rank per GPU, DDP (+SyncBatchNorm, as keisei-ddp.toml)
 gradient all-reduce over RCCL when N > 1; per-rank batch fixed (weak scaling).
 
-Prints ONE JSON line (rank 0) with the driver contract fields plus
+Prints ONE JSON line (rank 0) with the driver contract fields.  A plain run sets up, warms up, times the K steps and
+prints that line (with --dump-outputs, after writing the outputs); the measurements beyond the headline are taken only
+with --full:
   roofline     -- dominant kernel (conv3x3 implicit-GEMM, fwd+dgrad): achieved MFMA TFLOP/s from the
-                  algorithmic FLOPs per launch / average launch duration (HIP events on the launch stream)
+                  algorithmic FLOPs per launch / average launch duration (HIP events on the launch stream, extra steps)
+  fp32_mode    -- the same workload in the fp32 (parity numerics) mode (one GPU)
+  secondary    -- whole update(), the 6x128 workload, the transformer workload (bounded legs; one GPU, default workload)
   cpu_baseline -- the oracle (CPU restatement of the reference) timed on this host, bounded sample
+Without --full these keys are null or absent.
+
+--dump-outputs DIR writes what the timed path computed in its last timed step as float32 .npy files (27 MB at
+40x256; seeded samples of the large arrays, the same elements in every run and build):
+  policy_logits  -- (min(B, 256), A) rows of the minibatch's policy logits; value_logits (B, 3), score_lead (B, 1)
+  parameters, gradients -- 2**21 elements of all parameters after the optimiser step / of their gradients as .grad
+                   holds them (GradScaler's loss scale included), flattened in named_parameters() order
 """
 from __future__ import annotations
 
@@ -44,6 +55,9 @@ WORKLOADS = {
 PEAK_BF16_TFLOPS = 2500.0      # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_F32_TFLOPS = 157.3
 PEAK_HBM_GBS = 8000.0
+DUMP_ROWS = 256                 # --dump-outputs: policy-logit rows of the last minibatch
+DUMP_FLAT = 1 << 21             # --dump-outputs: parameter / gradient elements
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def kernel_source_id(names=("common.h", "conv3x3.hip")) -> str:
@@ -84,6 +98,30 @@ def synth_dataset(total, seed, device):
         "adv": torch.randn(total, generator=g).to(device), "cats": cats.to(device),
         "score_t": torch.randn(total, generator=g).clamp(-1.5, 1.5).to(device),
     }
+
+
+def dump_index(n: int, k: int, seed: int, sorted_unique: bool = False) -> torch.Tensor:
+    """k indices into range(n) fixed by the seed (all of range(n) when n <= k): the same elements in every run and build."""
+    if n <= k:
+        return torch.arange(n)
+    g = torch.Generator().manual_seed(seed)
+    if sorted_unique:
+        return torch.randperm(n, generator=g)[:k].sort().values
+    return torch.randint(0, n, (k,), generator=g)
+
+
+def write_outputs(arrays: dict, out_dir) -> int:
+    """--dump-outputs: every tensor as out_dir/<name>.npy in float32; returns the bytes written."""
+    import numpy as np
+    host = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in host.items():
+        np.save(out_dir / f"{name}.npy", a)
+    return total
 
 
 def whole_update_rate(algo, adapter, T, N, device, stores=("host", "device")):
@@ -340,11 +378,12 @@ def run_transformer(args, device):
     return out
 
 
-def run_workload(args, dtype, steps, warmup, device, rank, world, dev_index, events_steps):
+def run_workload(args, dtype, steps, warmup, device, rank, world, dev_index, events_steps, dump=False):
     """Build the model + synthetic epoch, run `warmup` untimed and `steps` timed minibatch steps of the product path
     (barrier + synchronize on both sides, MAX over ranks), then -- OUTSIDE the timed region -- `events_steps` more steps
     with a HIP event pair around every conv3x3 / wgrad launch on its launch stream (per-launch durations for the
-    roofline; VERDICT r1: the timed region itself carries no event records)."""
+    roofline; VERDICT r1: the timed region itself carries no event records).  `dump`: keep the last timed step's
+    outputs (the --dump-outputs arrays) in the result's "outputs"."""
     from keisei_amd.training.katago_ppo import KataGoPPOAlgorithm, KataGoPPOParams
     from keisei_amd.training.model_registry import build_model
     from keisei_amd.training.value_adapter import MultiHeadValueAdapter
@@ -378,6 +417,19 @@ def run_workload(args, dtype, steps, warmup, device, rank, world, dev_index, eve
         lo = (i % nmb) * B
         algo._fused_step(fs, perm[lo:lo + B], device)
 
+    outputs, hook = {}, None
+    if dump:
+        rows = dump_index(B, DUMP_ROWS, 1, sorted_unique=True).to(device)
+
+        def keep_last(_module, _inputs, out):
+            # the forward of the last timed step (_fused_step counts the step after it): copies on the stream, in order
+            if fs["n_updates"] == warmup + steps - 1:
+                outputs["policy_logits"] = out.policy_logits.detach().reshape(B, -1).index_select(0, rows).float()
+                outputs["value_logits"] = out.value_logits.detach().to(torch.float32, copy=True)
+                outputs["score_lead"] = out.score_lead.detach().to(torch.float32, copy=True)
+
+        hook = model.register_forward_hook(keep_last)
+
     print(f"[bench] rank {rank}: {dtype} model + dataset ready, {warmup} warm-up + {steps} timed steps", file=sys.stderr, flush=True)
     for i in range(warmup):
         one_step(i)
@@ -402,6 +454,14 @@ def run_workload(args, dtype, steps, warmup, device, rank, world, dev_index, eve
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
+    if dump:
+        # the parameters after the last timed step's optimiser step and that step's gradients, before any further step
+        hook.remove()
+        params = [p for _, p in model.named_parameters()]
+        pick = dump_index(sum(p.numel() for p in params), DUMP_FLAT, 2).to(device)
+        outputs["parameters"] = torch.cat([p.detach().reshape(-1).float() for p in params])[pick]
+        outputs["gradients"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).float()
+                                          for p in params])[pick]
     # ---- per-launch durations: a separate pass, after the timed region
     engine = model._hip_engine
     events, ev_elapsed = None, None
@@ -417,7 +477,7 @@ def run_workload(args, dtype, steps, warmup, device, rank, world, dev_index, eve
     metrics = algo._fused_end(fs)
     return {"elapsed": elapsed, "metrics": metrics, "events": events, "events_elapsed": ev_elapsed, "events_steps": events_steps,
             "B": B, "n_params": n_params, "algo": algo, "adapter": adapter, "model": model, "shape": (nb, C, Rr, G, P, V, S, T, N),
-            "fs": fs}
+            "fs": fs, "outputs": outputs}
 
 
 def main() -> None:
@@ -428,18 +488,26 @@ def main() -> None:
     ap.add_argument("--workload", default="40x256", choices=sorted(WORKLOADS) + ["transformer"])
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--batch", type=int, default=0, help="override the minibatch size")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the measurements beyond the headline: per-launch roofline, fp32 mode, secondary workloads, "
+                         "CPU baseline (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (seeded samples of the large arrays)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--whole-update", action="store_true",
                     help="also time one KataGoPPOAlgorithm.update() from a host rollout buffer (GAE, H2D, gather included)")
     ap.add_argument("--sl-epoch", action="store_true", help="also time one SLTrainer.train_epoch() over synthetic shards")
-    ap.add_argument("--no-kernel-events", action="store_true")
-    ap.add_argument("--no-fp32", action="store_true", help="skip the secondary fp32-mode (parity numerics) run of the same workload")
+    ap.add_argument("--no-kernel-events", action="store_true", help="with --full: skip the per-launch timing pass (roofline)")
+    ap.add_argument("--no-fp32", action="store_true",
+                    help="with --full: skip the secondary fp32-mode (parity numerics) run of the same workload")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the `secondary` block of the default line (whole update(), the 6x128 workload, the transformer workload)")
+                    help="with --full: skip the `secondary` block (whole update(), the 6x128 workload, the transformer workload)")
     ap.add_argument("--dist-dry-run", action="store_true",
                     help="initialise the process group (RCCL when the backend is nccl) even for one rank, wrap the model as the "
                          "N > 1 bench does, run ONE step with its collectives, print the collective counts and exit")
     args = ap.parse_args()
+    if args.dump_outputs and (args.workload == "transformer" or args.dist_dry_run):
+        raise SystemExit("--dump-outputs covers the se_resnet workloads' timed step (not --workload transformer / --dist-dry-run)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))          # the parent never initialises the GPU
@@ -521,15 +589,17 @@ def main() -> None:
         dist.destroy_process_group()
         return
 
-    ev_steps = 0 if args.no_kernel_events else min(args.steps, 4)
-    res = run_workload(args, args.dtype, args.steps, args.warmup, device, rank, world, dev_index, ev_steps)
+    ev_steps = min(args.steps, 4) if args.full and not args.no_kernel_events else 0
+    res = run_workload(args, args.dtype, args.steps, args.warmup, device, rank, world, dev_index, ev_steps,
+                       dump=bool(args.dump_outputs) and rank == 0)
     elapsed, metrics, B, n_params = res["elapsed"], res["metrics"], res["B"], res["n_params"]
     nb, C, Rr, G, P, V, S, T, N = res["shape"]
     total = T * N
     whole = None
     if args.whole_update and rank == 0:
         whole = whole_update_rate(res["algo"], res["adapter"], T, N, device)
-    want_secondary = world == 1 and rank == 0 and args.workload == "40x256" and args.dtype == "bf16" and not args.no_secondary
+    want_secondary = (args.full and world == 1 and rank == 0 and args.workload == "40x256" and args.dtype == "bf16"
+                      and not args.no_secondary)
     if want_secondary and whole is None:
         whole = whole_update_rate(res["algo"], res["adapter"], T, N, device, stores=("device",))
     sl = None
@@ -540,7 +610,7 @@ def main() -> None:
                                                                    obs_channels=50)).to(device), 4 * B, B, args.dtype == "bf16")
     # secondary: the same workload in the fp32 (parity numerics) mode, SURVEY 8d config #3 "use_amp=true AND an fp32 run"
     fp32 = None
-    if world == 1 and args.dtype == "bf16" and not args.no_fp32:
+    if args.full and world == 1 and args.dtype == "bf16" and not args.no_fp32:
         del res["algo"], res["fs"], res["model"]
         torch.cuda.empty_cache()
         r32 = run_workload(args, "f32", 3, 1, device, rank, world, dev_index, 0 if args.no_kernel_events else 1)
@@ -696,7 +766,11 @@ def main() -> None:
         if sl is not None:
             out["sl_epoch"] = sl
         # (N > 1: taken after the timed region and after the process group is gone -- the other ranks have exited)
-        out["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline((nb, C, Rr, G, P, V, S))
+        out["cpu_baseline"] = cpu_baseline((nb, C, Rr, G, P, V, S)) if args.full and not args.no_cpu_baseline else None
+        if args.dump_outputs:
+            nbytes = write_outputs(res["outputs"], args.dump_outputs)
+            print(f"[bench] wrote {len(res['outputs'])} arrays ({nbytes / 2 ** 20:.1f} MB) to {args.dump_outputs}",
+                  file=sys.stderr, flush=True)
         print(json.dumps(out), flush=True)
 
 

@@ -5,6 +5,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +24,7 @@ def run_bench(*args):
 
 
 def test_bench_line_contract():
-    d = run_bench("--workload", "6x128", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
+    d = run_bench("--workload", "6x128", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -35,8 +36,33 @@ def test_bench_line_contract():
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
         assert k in r, k
     assert r["bound"] in ("hbm", "mfma") and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3 and r["launches_timed"] > 0
-    assert d["cpu_baseline"] is None                    # skipped on request; the default run fills it (rank 0, N = 1)
+    assert d["cpu_baseline"] is None                    # skipped on request; --full fills it otherwise (rank 0, N = 1)
     assert all(v == v for v in d["train_metrics"].values())   # finite training metrics: the timed steps really trained
+
+
+def test_plain_line_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run times exactly --steps steps and takes nothing beyond the headline (no roofline pass, fp32 run,
+    secondary legs or CPU baseline); --dump-outputs writes the last timed step's outputs as float32 .npy files within
+    64 MB, and two runs with the same arguments write the same arrays (seeded inputs, fixed-order reductions)."""
+    args = ("--workload", "6x128", "--steps", "3", "--warmup", "1", "--dump-outputs")
+    d = run_bench(*args, str(tmp_path / "a"))
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["dtype"] == "bf16"
+    assert d["unit"] == "samples/s" and d["higher_is_better"] is True and d["value"] > 0
+    assert abs(d["value"] - d["config"]["global_batch"] * 1e3 / d["ms_per_step"]) <= 0.01 * d["value"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    assert not {"fp32_mode", "secondary", "wgrad_kernel", "mfma_step_average"} & set(d)
+    assert all(v == v for v in d["train_metrics"].values())
+    names = ("policy_logits", "value_logits", "score_lead", "parameters", "gradients")
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == sorted(f"{n}.npy" for n in names)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    B = d["config"]["per_gpu_batch"]
+    assert a["policy_logits"].shape == (256, 81 * 139) and a["value_logits"].shape == (B, 3) and a["score_lead"].shape == (B, 1)
+    assert a["parameters"].shape == a["gradients"].shape == (1 << 21,)
+    assert all(x.dtype == np.float32 and np.isfinite(x).all() for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20 and np.count_nonzero(a["gradients"]) > 0
+    run_bench(*args, str(tmp_path / "b"))
+    for n in names:
+        assert np.array_equal(a[n], np.load(tmp_path / "b" / f"{n}.npy")), n
 
 
 def test_bench_gpus_2_starts_itself():
@@ -59,9 +85,9 @@ def test_bench_gpus_2_starts_itself():
 
 
 def test_default_line_carries_the_secondary_measurements():
-    """The driver runs `python bench.py` with no workload flag: SURVEY 8d's "report both" (whole update() beside the minibatch step)
+    """`python bench.py --full` with no workload flag: SURVEY 8d's "report both" (whole update() beside the minibatch step)
     and BASELINE configs[1] / configs[4] ride on that line as bounded legs (`secondary`), next to the headline's own keys."""
-    d = run_bench("--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-fp32")
+    d = run_bench("--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-fp32")
     assert d["metric"].startswith("PPO samples/sec, se_resnet 40x256") and d["roofline"]["launches_timed"] > 0
     sec = d["secondary"]
     assert set(sec) == {"whole_update", "workload_6x128", "transformer"}

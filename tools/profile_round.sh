@@ -1,13 +1,13 @@
 #!/bin/bash
 # the rocprofv3 evidence for one round: tools/profile_round.sh <tag>   (writes gpurun_out/<tag>_*)
-# 1. kernel stats of the default bench command; 2./3. FETCH_SIZE and WRITE_SIZE in separate --pmc passes
+# 1. kernel stats of the --full bench command (headline workload); 2./3. FETCH_SIZE and WRITE_SIZE in separate --pmc passes
 set -e
 tag=${1:-r01}
 root=$(pwd)
 out=$root/gpurun_out
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats -o s -- python3 $root/bench.py --no-cpu-baseline --no-fp32 --no-secondary > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}_stats.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats -o s -- python3 $root/bench.py --full --no-cpu-baseline --no-fp32 --no-secondary > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}_stats.err
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/${tag}_fetch -o f -- python3 $root/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-fp32 --no-secondary --no-kernel-events > $out/${tag}_fetch.log 2>&1
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/${tag}_write -o w -- python3 $root/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-fp32 --no-secondary --no-kernel-events > $out/${tag}_write.log 2>&1
 cd $root
