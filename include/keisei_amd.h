@@ -378,6 +378,27 @@ int ka_pending_settle(float* obs, void* bits, long long* actions, float* log_pro
 int ka_tower_eval_supported(int C, int G, int R, int dtype);
 int ka_tower_eval(const void* x_in, const float* pool_in, void* x_out, float* pool_out, const void* blocks, int nblocks, int B,
                   int C, int G, int R, int dtype, void* stream);
+/* ---- grouped eval forward: many SE-ResNets of one shape over one board batch (league / tournament play: the reference's
+ * concurrent_matches.py:353-364 one forward per resident model, katago_loop.py:404-431 one forward per cohort opponent).
+ * Board b runs model model_of[b] (int32); a board whose index lies outside [0, K) is unseated: it reads no weights and its
+ * outputs are zeros.  Eval mode, bf16 activations, C in {128, 256}; three launches whatever K is, no host synchronisation. */
+int ka_tower_eval_grouped_supported(int C, int G, int R, int dtype);
+/* se_resnet.py:101 relu(input_bn(input_conv(obs))) per board: obs (B, cin, 9, 9) fp32 (cin <= 128); x_out (B, 81, C) bf16,
+ * pool_out (B, 4C) [mean|max|std|0] as ka_tower_eval reads them; stems = device table of K rows of 3 pointers {input_conv
+ * pack (ka_pack_conv3x3 mode 0, Kin = 128), input_bn eval scale, shift}. */
+int ka_stem_eval_grouped(const float* obs, const int* model_of, const void* stems, int K, void* x_out, float* pool_out, int B,
+                         int cin, int C, int dtype, void* stream);
+/* se_resnet.py:67-75 x num_blocks with a model per board: ka_tower_eval over tables = device table (K, nblocks, 14) of
+ * TowerBlock rows (the ka_tower_eval layout, one set of blocks per model). */
+int ka_tower_eval_grouped(const void* x_in, const float* pool_in, void* x_out, float* pool_out, const int* model_of,
+                          const void* tables, int K, int nblocks, int B, int C, int G, int R, int dtype, void* stream);
+/* se_resnet.py:102-106 heads per board: logits (B, 9, 9, 139) = policy_conv2(relu(policy_bn1(policy_conv1(x)))), value
+ * (B, 3) = value_fc2(relu(value_fc1(pool))), score (B, 1) = score_fc2(relu(score_fc1(pool))), all fp32, from the tower's
+ * x (B, 81, C) bf16 and pool (B, 4C); heads = device table of K rows of 13 pointers {policy_conv1.weight (P, C), policy_bn1
+ * eval scale, shift, policy_conv2.weight (139, P), .bias, value_fc1.weight, .bias, value_fc2.weight, .bias, score_fc1.weight,
+ * .bias, score_fc2.weight, .bias}.  P <= 32, V, S <= 512. */
+int ka_heads_eval_grouped(const void* x, const float* pool, const int* model_of, const void* heads, int K, float* logits,
+                          float* value, float* score, int B, int C, int P, int V, int S, int dtype, void* stream);
 
 /* ---- the vectorised shogi environment on the device (shogi-engine/crates/shogi-gym/src/vec_env.rs:556-855
  * VecEnv(num_envs, max_ply, "katago", "spatial"), with the rules of shogi-core/src/{movegen,attack,rules,game}.rs, the

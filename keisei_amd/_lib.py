@@ -93,6 +93,10 @@ _SIGS = {
     "ka_pending_settle": "ppppppppp ppp i p ppppppppppp p iii p",
     "ka_tower_eval_supported": "iiii",
     "ka_tower_eval": "ppppp iiiii i p",
+    "ka_tower_eval_grouped_supported": "iiii",
+    "ka_stem_eval_grouped": "ppp i pp iiii p",
+    "ka_tower_eval_grouped": "pppppp iiiiiii p",
+    "ka_heads_eval_grouped": "pppp i ppp iiiii i p",
     "ka_shogi_env_state_bytes": "",
     "ka_shogi_env_action_space": "i",
     "ka_shogi_env_reset": "ppp ii ii pppp i p",

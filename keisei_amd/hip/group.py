@@ -1,0 +1,151 @@
+"""Device tables of the grouped eval forward (csrc/tower.hip: ka_stem_eval_grouped, ka_tower_eval_grouped,
+ka_heads_eval_grouped): K SE-ResNets of one shape over one board batch, board b on model model_idx[b].
+
+The group owns a snapshot of every model's weights in the form the kernels read: fragment-ordered conv packs (the same
+ka_pack_conv3x3_multi launch SEResNetEngine uses; the stem is packed with its 50 input planes padded to 128, the width of
+the tower's k-chunk), eval BatchNorm scale / shift (ka_bn_eval_coeffs_multi from the running statistics) and copies of the
+FC weights.  The buffers are allocated once, so the pointer tables never change and a captured graph stays valid;
+``refresh`` refills them from the models' current parameters.  A model's own engine keeps its own packs: the group does
+not share them, because they follow the live weights on every forward of that model, and the group's forward is defined
+as the models at the last refresh.
+"""
+from __future__ import annotations
+
+import struct
+from typing import List
+
+import torch
+from torch import nn
+
+from keisei_amd import _lib
+
+_call = _lib.call
+_STEM_KIN = 128            # stem input planes as the kernel reads them (one 128-channel k-chunk)
+_MOVES = 139
+
+
+def _align4(n: int) -> int:
+    return (n + 3) // 4 * 4
+
+
+def _bns(m: nn.Module) -> List[nn.Module]:
+    return [m.input_bn, *(b for blk in m.blocks for b in (blk.bn1, blk.bn2)), m.policy_bn1]
+
+
+def _fc_tensors(m: nn.Module) -> List[torch.Tensor]:
+    """FC weights in table order: per block global_fc[0], global_fc[2], se_fc1, se_fc2 (weight, bias each); then the heads."""
+    out = []
+    for blk in m.blocks:
+        for lin in (blk.global_fc[0], blk.global_fc[2], blk.se_fc1, blk.se_fc2):
+            out += [lin.weight, lin.bias]
+    out += [m.policy_conv1.weight, m.policy_conv2.weight, m.policy_conv2.bias]
+    for lin in (m.value_fc1, m.value_fc2, m.score_fc1, m.score_fc2):
+        out += [lin.weight, lin.bias]
+    return out
+
+
+class GroupTables:
+    """Snapshot buffers and pointer tables of K models on one device (see module docstring)."""
+
+    def __init__(self, models: List[nn.Module], device: torch.device) -> None:
+        self.models = models
+        self.device = device
+        p = models[0].params
+        self.K, self.nb, self.C = len(models), p.num_blocks, p.channels
+        self.cin = p.obs_channels
+        blk0 = models[0].blocks[0]
+        self.G, self.R = blk0.global_fc[0].out_features, blk0.se_fc1.out_features
+        self.P, self.V, self.S = p.policy_channels, p.value_fc_size, p.score_fc_size
+        C, K, nb = self.C, self.K, self.nb
+        # conv packs (bf16 fragments, 16 bytes each): stem then conv1 / conv2 of every block, per model
+        stem_b = 9 * (_STEM_KIN // 32) * (C // 16) * 64 * 16
+        conv_b = 9 * (C // 32) * (C // 16) * 64 * 16
+        per_model = stem_b + 2 * nb * conv_b
+        self.packs = torch.empty(K * per_model, dtype=torch.uint8, device=device)
+        # eval BatchNorm coefficients: (scale, shift) of every BatchNorm layer, C wide (policy_bn1 uses the first P)
+        nbn = len(_bns(models[0]))
+        self.coeffs = torch.empty(K, nbn, 2, C, device=device)
+        # FC weight copies, every tensor at a 16-byte aligned offset (the kernels read rows as float4)
+        shapes = [t.numel() for t in _fc_tensors(models[0])]
+        offs, o = [], 0
+        for n in shapes:
+            offs.append(o)
+            o += _align4(n)
+        self.fc = torch.empty(K, o, device=device)
+        self._fc_views = [[self.fc[k, a:a + n] for a, n in zip(offs, shapes)] for k in range(K)]
+
+        base = self.packs.data_ptr()
+        cbase, fbase = self.coeffs.data_ptr(), self.fc.data_ptr()
+        fc_stride = self.fc.stride(0) * 4
+
+        def coeff(k, i, which):
+            return cbase + ((k * nbn + i) * 2 + which) * C * 4
+
+        stems, tower, heads = [], [], []
+        for k in range(K):
+            mb = base + k * per_model
+            stems.append([mb, coeff(k, 0, 0), coeff(k, 0, 1)])
+            fc = [fbase + k * fc_stride + a * 4 for a in offs]
+            rows = []
+            for i in range(nb):
+                c1, c2 = mb + stem_b + (2 * i) * conv_b, mb + stem_b + (2 * i + 1) * conv_b
+                rows.append([c1, c2, coeff(k, 1 + 2 * i, 0), coeff(k, 1 + 2 * i, 1), coeff(k, 2 + 2 * i, 0),
+                             coeff(k, 2 + 2 * i, 1), *fc[8 * i:8 * i + 8]])
+            tower.append(rows)
+            h = fc[8 * nb:]
+            heads.append([h[0], coeff(k, nbn - 1, 0), coeff(k, nbn - 1, 1), *h[1:]])
+        self.stem_tab = torch.tensor(stems, dtype=torch.int64).to(device)
+        self.tower_tab = torch.tensor(tower, dtype=torch.int64).to(device)
+        self.head_tab = torch.tensor(heads, dtype=torch.int64).to(device)
+        self._stem_b, self._conv_b, self._per_model, self._nbn = stem_b, conv_b, per_model, nbn
+
+    def refresh(self) -> None:
+        """Re-derive packs, BatchNorm coefficients and FC copies from the models' current parameters and statistics
+        (three launches plus one multi-tensor copy, all on the current stream)."""
+        dev = self.device
+        st = _lib.stream_ptr(dev)
+        C = self.C
+        jobs, mx = [], 0
+        crow = []
+        for k, m in enumerate(self.models):
+            mb = self.packs.data_ptr() + k * self._per_model
+            w = m.input_conv.weight
+            jobs.append([w.data_ptr(), mb, C, self.cin, C, _STEM_KIN, 0, 0])
+            for i, blk in enumerate(m.blocks):
+                for j, conv in enumerate((blk.conv1, blk.conv2)):
+                    jobs.append([conv.weight.data_ptr(), mb + self._stem_b + (2 * i + j) * self._conv_b, C, C, C, C, 0, 0])
+            for i, bn in enumerate(_bns(m)):
+                sc = self.coeffs[k, i, 0]
+                eps_bits = struct.unpack("<I", struct.pack("<f", float(bn.eps)))[0]
+                crow.append([bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+                             sc.data_ptr(), self.coeffs[k, i, 1].data_ptr(), bn.num_features, eps_bits])
+        mx = max(self._stem_b, self._conv_b) // 16
+        jt = torch.tensor(jobs, dtype=torch.int64).to(dev)
+        ct = torch.tensor(crow, dtype=torch.int64).to(dev)
+        _call("ka_pack_conv3x3_multi", jt, jt.shape[0], mx, _lib.DTYPE_BF16, st)
+        _call("ka_bn_eval_coeffs_multi", ct, ct.shape[0], C, st)
+        dst, src = [], []
+        for k, m in enumerate(self.models):
+            dst += self._fc_views[k]
+            src += [t.detach().reshape(-1) for t in _fc_tensors(m)]
+        torch._foreach_copy_(dst, src)
+        self._keep = (jt, ct)        # the launches read the job tables asynchronously
+
+    def forward(self, obs: torch.Tensor, model_of: torch.Tensor):
+        """(logits (B,9,9,139), value (B,3), score (B,1)) fp32; model_of (B,) int32 on the device."""
+        dev = self.device
+        st = _lib.stream_ptr(dev)
+        B, C = obs.shape[0], self.C
+        x = torch.empty(B, 81, C, dtype=torch.bfloat16, device=dev)
+        pool = torch.empty(B, 4 * C, device=dev)
+        _call("ka_stem_eval_grouped", obs, model_of, self.stem_tab, self.K, x, pool, B, self.cin, C, _lib.DTYPE_BF16, st)
+        x2 = torch.empty_like(x)
+        pool2 = torch.empty_like(pool)
+        _call("ka_tower_eval_grouped", x, pool, x2, pool2, model_of, self.tower_tab, self.K, self.nb, B, C, self.G, self.R,
+              _lib.DTYPE_BF16, st)
+        logits = torch.empty(B, 9, 9, _MOVES, device=dev)
+        value = torch.empty(B, 3, device=dev)
+        score = torch.empty(B, 1, device=dev)
+        _call("ka_heads_eval_grouped", x2, pool2, model_of, self.head_tab, self.K, logits, value, score, B, C, self.P,
+              self.V, self.S, _lib.DTYPE_BF16, st)
+        return logits, value, score
