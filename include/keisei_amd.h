@@ -493,6 +493,9 @@ int ka_tf_pos_grad(const void* dx, float* scratch, float* drow, float* dcol, int
 int ka_tf_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, long long M,
                         int d, float eps, int dtype, void* stream);
 int ka_tf_layernorm_parts(long long M);
+/* launch counts per kernel form (K = 256 GEMM, big-tile GEMM, super-tile map on / off, LDS epilogue on / off, register /
+   LDS attention forward) into a host array of n counts: tests check that a KA_TF_* switch changed the form */
+int ka_tf_route_counts(long long* out, int n);
 int ka_tf_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
                         const void* dres, void* dx, float* part, float* dgamma, float* dbeta, long long M, int d, int dtype,
                         void* stream);

@@ -118,6 +118,7 @@ _SIGS = {
     "ka_tf_pos_grad": "pppp ii i p",
     "ka_tf_layernorm_fwd": "pppppp q i f i p",
     "ka_tf_layernorm_parts": "q",
+    "ka_tf_route_counts": "p i",
     "ka_tf_layernorm_bwd": "pppppp pppp q i i p",
     "ka_tf_layernorm_bwd_drop": "pppppp pp f q ppp q i i p",
     "ka_tf_drop_apply": "pppp q f q i p",

@@ -18,6 +18,12 @@
 // The fp32 parity mode runs its linear layers on ka_gemm (gemm.hip, exact-f32 MFMA).
 #include "common.h"
 
+// Launch counts per kernel form, read by ka_tf_route_counts: where two forms give bit-identical results, the tests see
+// from these that a KA_TF_* switch selected the other form.  Host-side, one relaxed increment per dispatch.
+enum { kRtK256, kRtBig, kRtMap2d, kRtMap2dOff, kRtLdsEpi, kRtLdsEpiOff, kRtAttnReg, kRtAttnLds, kRtCount };
+static std::atomic<long long> g_tf_routes[kRtCount];
+static inline void tf_route(int r) { g_tf_routes[r].fetch_add(1, std::memory_order_relaxed); }
+
 namespace {
 
 // ------------------------------------------------------------------ dropout: counter-based keep mask
@@ -1978,6 +1984,7 @@ static int tf_gemm_nt_impl(const void* A, const void* B, void* C, const float* b
         }
 #undef KA_K256_FORMS
 #undef KA_K256
+        tf_route(kRtK256);
         return ka_check_launch("tf_gemm_nt (k256)");
     }
     static std::atomic<unsigned long long> done{0};
@@ -1990,6 +1997,7 @@ static int tf_gemm_nt_impl(const void* A, const void* B, void* C, const float* b
         static std::atomic<unsigned long long> dbig{0};
         if (int rc = ka_big_lds_once(reinterpret_cast<const void*>(&gemm_nt_big_kernel), dbig, "tf_gemm_nt (big)")) return rc;
         hipLaunchKernelGGL(gemm_nt_big_kernel, dim3(((supers + 7) / 8) * 8 * 32), dim3(512), kGLds, static_cast<hipStream_t>(stream), g);
+        tf_route(kRtBig);
         return ka_check_launch("tf_gemm_nt (big)");
     }
     const int gx = (N + kBN - 1) / kBN, gy = (M + kBM - 1) / kBM;
@@ -1998,7 +2006,12 @@ static int tf_gemm_nt_impl(const void* A, const void* B, void* C, const float* b
         g.map_gx = gx; g.map_gy = gy;
         const int supers = ((gx + 7) / 8) * ((gy + 7) / 8);
         grid = dim3(((supers + 7) / 8) * 8 * 64, 1, nsplit);
+        tf_route(kRtMap2d);
+    } else if (gx > 8 && gy >= 8) {
+        tf_route(kRtMap2dOff);
     }
+    if (nsplit == 1 && c_bf16 && (N & 7) == 0 && (ldc & 7) == 0 && M >= kBM && N >= kBN)      // has a tile the LDS epilogue can take
+        tf_route(g.lds_epilogue ? kRtLdsEpi : kRtLdsEpiOff);
     hipLaunchKernelGGL(gemm_nt_bf16_kernel, grid, dim3(256), 2 * (kBM + kBN) * kLdsStride, static_cast<hipStream_t>(stream), g);
     return ka_check_launch("tf_gemm_nt");
 }
@@ -2110,6 +2123,13 @@ extern "C" int ka_tf_layernorm_fwd(const void* x, const float* gamma, const floa
                                              static_cast<hipStream_t>(stream), static_cast<const T*>(x), gamma, beta,
                                              static_cast<T*>(y), mean, rstd, M, d, eps));
     return ka_check_launch("tf_layernorm_fwd");
+}
+// out[0 .. n) = launches so far of: the K = 256 GEMM, the big-tile GEMM, the tiled GEMM on its super-tile map and with that map
+// switched off, the tiled GEMM with the LDS epilogue and with it switched off, the register and the LDS attention forward
+extern "C" int ka_tf_route_counts(long long* out, int n) {
+    KA_REQUIRE(out && n >= 0, "tf_route_counts: bad arguments");
+    for (int i = 0; i < n && i < kRtCount; ++i) out[i] = g_tf_routes[i].load(std::memory_order_relaxed);
+    return KA_OK;
 }
 extern "C" int ka_tf_layernorm_parts(long long M) { const long long p = (M + 127) / 128; return (int)(p < 2048 ? p : 2048); }
 // dx = LayerNorm'(dy) [+ dres]; dgamma / dbeta [d] via part (ka_tf_layernorm_parts(M) * 2 * d floats)
@@ -2239,8 +2259,10 @@ extern "C" int ka_tf_attention_fwd(const void* qkv, void* out, float* lse, int B
         const int grid = (B * H + 3) / 4;
         if (dh <= 16) hipLaunchKernelGGL(attention_fwd_reg_kernel<1>, dim3(grid), dim3(256), 4 * kAtWaveLds, st, a);
         else          hipLaunchKernelGGL(attention_fwd_reg_kernel<2>, dim3(grid), dim3(256), 4 * kAtWaveLds, st, a);
+        tf_route(kRtAttnReg);
         return ka_check_launch("tf_attention_fwd");
     }
+    tf_route(kRtAttnLds);
     if (dtype == KA_DTYPE_BF16) {
         static std::atomic<unsigned long long> done{0};
         if (int rc = ka_big_lds_once(reinterpret_cast<const void*>(&attention_fwd_kernel<bf16_t>), done, "tf_attention_fwd")) return rc;

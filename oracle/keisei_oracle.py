@@ -16,6 +16,7 @@ against the reference tests' hand-computed known answers.
 
 Reference citations (relative to the reference repo root):
   * SE-ResNet forward ......... keisei/training/models/se_resnet.py:40-159
+  * transformer forward ....... keisei/training/models/transformer.py:37-95
   * global pool ............... keisei/training/models/se_resnet.py:93-98
   * value adapters ............ keisei/training/value_adapter.py:76-126
   * clip loss / CE / metrics .. keisei/training/katago_ppo.py:33-78
@@ -361,6 +362,72 @@ def seresnet_policy_bf16_storage(sd, obs: torch.Tensor, num_blocks: int, train: 
     scp, shp = coeffs(p1, "policy_bn1")
     p = F.conv2d(torch.relu(aff(p1, scp, shp)), sd["policy_conv2.weight"], sd["policy_conv2.bias"])
     return p.permute(0, 2, 3, 1)
+
+
+# --------------------------------------------------------------------------- transformer
+
+def transformer_forward(sd, obs: torch.Tensor, num_layers: int, nhead: int, drop_masks=None,
+                        bf16_storage: bool = False, relu_masks=None, relu_inputs: Optional[list] = None):
+    """TransformerModel (transformer.py:37-95) over a state_dict, in the dtype of its weights and on their device:
+    tokens = input_proj(obs as (B, 81, 50)) + row_embed[s // 9] + col_embed[s % 9]; per layer the pre-norm ReLU
+    encoder layer of nn.TransformerEncoderLayer(norm_first=True)
+        x = x + drop1(out_proj(attn(norm1(x))));  x = x + drop2(linear2(drop(relu(linear1(norm2(x))))))
+    then policy = policy_fc(x flattened), value = tanh(value_fc2(relu(value_fc1(mean over squares of x)))).
+
+    drop_masks[i] = (m1, mf, m2): per-element scale tensors (0 or 1 / (1 - p)) of dropout1 (B*81 x d), the FFN
+    dropout (B*81 x 4d) and dropout2 (B*81 x d) of layer i; None = no dropout (eval mode, or p = 0).
+
+    bf16_storage=True rounds to bf16 exactly where the HIP bf16 mode stores bf16 (hip/transformer.py): the tokens, the
+    bf16 copies of the six matrices that run on the matrix cores (input_proj, in_proj, out_proj, linear1, linear2,
+    policy_fc), the input projection and again after the positional add, the LayerNorm outputs h1 / h2, qkv, the
+    attention probabilities (rounded inside the attention kernel before the product with V), the attention output,
+    x_mid, f and x_out.  Biases, LayerNorm statistics and parameters, the embeddings and the value head stay in the
+    working precision, as in the kernels.
+
+    relu_masks (num_layers + 1 tensors: the FFN of each layer (B*81 x 4d), then value_fc1 (B x d)) replaces each ReLU by
+    a product with a given 0 / 1 mask -- the decisions of another implementation, for inputs within its rounding of zero;
+    relu_inputs, a list, receives the ReLU inputs in the same order.  Returns (policy (B, 11259), value (B, 1))."""
+    dt = sd["input_proj.weight"].dtype
+    q = (lambda t: t.to(torch.bfloat16).to(dt)) if bf16_storage else (lambda t: t)
+
+    def relu(a, k):
+        if relu_inputs is not None:
+            relu_inputs.append(a.detach())
+        return torch.relu(a) if relu_masks is None else a * relu_masks[k].reshape(a.shape).to(a.dtype)
+
+    def lin(x, name, bias_name=None):
+        return x @ q(sd[name]).T + sd[bias_name or name[:-len("weight")] + "bias"]
+
+    B = obs.shape[0]
+    d = sd["input_proj.weight"].shape[0]
+    H, dh = nhead, d // nhead
+    tok = q(obs.to(dt).permute(0, 2, 3, 1).reshape(B, 81, -1))
+    pos = (sd["row_embed.weight"][:, None, :] + sd["col_embed.weight"][None, :, :]).reshape(81, d)
+    x = q(q(lin(tok, "input_proj.weight")) + pos)
+    for i in range(num_layers):
+        p = f"encoder.layers.{i}."
+        m1, mf, m2 = drop_masks[i] if drop_masks is not None else (None, None, None)
+        h = q(F.layer_norm(x, (d,), sd[p + "norm1.weight"], sd[p + "norm1.bias"], 1e-5))
+        qkv = q(lin(h, p + "self_attn.in_proj_weight", p + "self_attn.in_proj_bias"))
+        qh, kh, vh = (t.reshape(B, 81, H, dh).transpose(1, 2) for t in qkv.split(d, dim=-1))
+        prob = q(torch.softmax((qh @ kh.transpose(-1, -2)) / math.sqrt(dh), dim=-1))
+        attn = q((prob @ vh).transpose(1, 2).reshape(B, 81, d))
+        y = lin(attn, p + "self_attn.out_proj.weight")
+        if m1 is not None:
+            y = y * m1.reshape(y.shape)
+        x = q(x + y)
+        h = q(F.layer_norm(x, (d,), sd[p + "norm2.weight"], sd[p + "norm2.bias"], 1e-5))
+        f = relu(lin(h, p + "linear1.weight"), i)
+        if mf is not None:
+            f = f * mf.reshape(f.shape)
+        y = lin(q(f), p + "linear2.weight")
+        if m2 is not None:
+            y = y * m2.reshape(y.shape)
+        x = q(x + y)
+    policy = lin(x.reshape(B, 81 * d), "policy_fc.weight")
+    v = relu(x.mean(dim=1) @ sd["value_fc1.weight"].T + sd["value_fc1.bias"], num_layers)
+    value = torch.tanh(v @ sd["value_fc2.weight"].T + sd["value_fc2.bias"])
+    return policy, value
 
 
 # --------------------------------------------------------------------------- losses
