@@ -453,6 +453,30 @@ int ka_arena_referee(int* state, int slots, int envs_per_slot, const float* rewa
                      void* pre_player, void* stream);
 int ka_arena_assign(int* state, const int* jobs, int njobs, int envs_per_slot, const void* players, int* model_of,
                     void* pre_player, void* stream);
+/* Rollout collection inside the ply (concurrent_matches.py:80-163 the per-slot _obs / _masks / _perspective / _actions /
+ * _rewards / _dones lists, :318-327, :366-372, :421-432 the appends).  The store holds `cap` rows per slot (row r of slot s
+ * is store row s * cap + r): st_obs (S*cap, obs_elems) fp32, st_mask_bits (S*cap, mask_words) uint32, st_actions int64,
+ * st_perspective u8, st_rewards / st_dones fp32.  cursors: ka_arena_cursor_words(S) int32 = S x {rows committed, rows written
+ * this ply, rows dropped, unused}; row_of (S*E) int32 = the store row of each env's row of this ply, -1 = none.
+ * side_bits (S) int32: bit 0 = collect side A's rows (pre-step player 0), bit 1 = side B's.
+ * ka_arena_record_pre (after ka_policy_sample_play, before ka_shogi_env_step): for every slot that is seated, not done, has
+ *   side bits and no env with nlegal == 0 (:303-314), appends one row per env whose mover is on a collected side, in env order,
+ *   behind the rows committed so far; rows beyond cap are not written and are counted as dropped.  No atomics: the order
+ *   inside a slot is (ply, env).
+ * ka_arena_record_post (after ka_shogi_env_step, before ka_arena_referee): writes rewards and dones = terminated | truncated
+ *   (fp32 0 / 1, :427-432) into this ply's rows and commits them.
+ * The host reads and zeroes `cursors` at its sync point, outside any captured graph. */
+int ka_arena_cursor_words(int slots);
+int ka_arena_record_pre(const int* state, const int* side_bits, int slots, int envs_per_slot, const float* obs,
+                        const void* mask_bits, const long long* actions, const void* pre_player, const int* nlegal,
+                        int* cursors, int* row_of, float* st_obs, void* st_mask_bits, long long* st_actions,
+                        void* st_perspective, int cap, int obs_elems, int mask_words, void* stream);
+int ka_arena_record_post(int* cursors, const int* row_of, int slots, int envs_per_slot, const float* rewards,
+                         const void* terminated, const void* truncated, float* st_rewards, float* st_dones, int cap,
+                         void* stream);
+/* Dynamic-entry targets (dynamic_trainer.py:310-318, :358): cats[i] = 0 / 1 / 2 (win / draw / loss by the sign of rewards[i])
+ * where dones[i] != 0, else -1; adv[i] = rewards[i] * dones[i]. */
+int ka_dynamic_targets(const float* rewards, const float* dones, long long* cats, float* adv, long long n, void* stream);
 
 /* ---- transformer encoder path (BASELINE config 5; keisei/training/models/transformer.py:37-95: nn.Linear(50, d),
  * row/col nn.Embedding, nn.TransformerEncoder(nn.TransformerEncoderLayer(d, nhead, 4d, batch_first, norm_first), L),

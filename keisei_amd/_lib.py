@@ -105,6 +105,10 @@ _SIGS = {
     "ka_arena_state_words": "i",
     "ka_arena_referee": "p ii ppppp p pp p",
     "ka_arena_assign": "pp ii ppp p",
+    "ka_arena_cursor_words": "i",
+    "ka_arena_record_pre": "pp ii ppppp pp pppp iii p",
+    "ka_arena_record_post": "pp ii ppp pp i p",
+    "ka_dynamic_targets": "pppp q p",
     "ka_tf_gemm_nt": "ppppp iii iii iii f q p",
     "ka_tf_gemm_nt_slabs": "ii",
     "ka_tf_gemm_nt_masked": "pppp iii iii f q p",

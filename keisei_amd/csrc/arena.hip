@@ -127,7 +127,162 @@ __global__ __launch_bounds__(kArenaThreads) void arena_assign_kernel(int* state,
     }
 }
 
+// ---- rollout collection (concurrent_matches.py:80-163, 318-432: the per-slot _obs / _masks / _perspective / _actions /
+// _rewards / _dones lists).  The store is one region of `cap` rows per slot; row r of slot s is store row s * cap + r.
+// cursors: 4 int32 per slot {rows committed, rows written this ply, rows dropped, unused}.  A ply's rows are written by
+// record_pre at rows committed + rank and committed by record_post, so every workgroup of record_pre reads the same
+// cursor and the order inside a slot is (ply, env) whatever the arrival order of the workgroups.
+constexpr int kCursorWords = 4;
+
+struct RecordPreArgs {
+    const int* state; const int* side_bits; int E;
+    const float* obs; const uint32_t* mask; const long long* actions; const uint8_t* pre_player; const int* nlegal;
+    int* cursors; int* row_of;
+    float* st_obs; uint32_t* st_mask; long long* st_actions; uint8_t* st_persp;
+    int cap; int obs_elems; int mask_words;
+};
+
+// grid (slots, Y): every workgroup of a slot repeats the slot's scan over its E envs (E bytes and E words), workgroup y
+// then copies the rows of envs y, y + Y, ...; workgroup 0 alone writes row_of and the slot's counters.
+__global__ __launch_bounds__(kArenaThreads) void arena_record_pre_kernel(RecordPreArgs a) {
+    extern __shared__ int s_rank[];                            // E ints: rank of the env's row this ply, -1 = no row
+    __shared__ int red[kArenaThreads / 64];
+    __shared__ int wsum[kArenaThreads / 64];
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int e0 = s * a.E;
+    const int status = a.state[kHdrWords + s * kSlotWords + 7];
+    const int bits = a.side_bits[s];
+    bool live = (status & kSeated) && !(status & kDone) && (bits & 3);      // uniform over the workgroup
+    if (live) {
+        int stalled = 0;
+        for (int k = tid; k < a.E; k += kArenaThreads) stalled |= a.nlegal[e0 + k] == 0;
+        live = block_sum_int(stalled, red) == 0;               // :303-314: a slot with a zero-legal env appends nothing
+    }
+    if (!live) {
+        if (blockIdx.y == 0) {
+            for (int k = tid; k < a.E; k += kArenaThreads) a.row_of[e0 + k] = -1;
+            if (tid == 0) a.cursors[s * kCursorWords + 1] = 0;
+        }
+        return;
+    }
+    int running = 0;
+    for (int base = 0; base < a.E; base += kArenaThreads) {
+        const int k = base + tid;
+        const bool want = k < a.E && ((bits >> (a.pre_player[e0 + k] & 1)) & 1);
+        const unsigned long long b = __ballot(want);
+        if (lane == 0) wsum[wave] = __popcll(b);
+        __syncthreads();
+        int off = running, tot = 0;
+        for (int w = 0; w < kArenaThreads / 64; ++w) {
+            if (w < wave) off += wsum[w];
+            tot += wsum[w];
+        }
+        if (k < a.E) s_rank[k] = want ? off + __popcll(b & ((1ull << lane) - 1ull)) : -1;
+        running += tot;
+        __syncthreads();
+    }
+    const int first = a.cursors[s * kCursorWords + 0];
+    const int room = max(0, a.cap - first);                    // rows of this ply that still fit
+    if (blockIdx.y == 0) {
+        for (int k = tid; k < a.E; k += kArenaThreads) {
+            const int r = s_rank[k];
+            a.row_of[e0 + k] = (r >= 0 && r < room) ? s * a.cap + first + r : -1;
+        }
+        if (tid == 0) {
+            a.cursors[s * kCursorWords + 1] = min(running, room);
+            a.cursors[s * kCursorWords + 2] += max(0, running - room);
+        }
+    }
+    const int n2 = a.obs_elems >> 1;                           // an observation row is 16 200 bytes: 8-byte vectors
+    for (int k = blockIdx.y; k < a.E; k += gridDim.y) {
+        const int r = s_rank[k];
+        if (r < 0 || r >= room) continue;
+        const size_t row = (size_t)s * a.cap + first + r, e = (size_t)(e0 + k);
+        const float2* src = reinterpret_cast<const float2*>(a.obs + e * a.obs_elems);
+        float2* dst = reinterpret_cast<float2*>(a.st_obs + row * a.obs_elems);
+        for (int i = tid; i < n2; i += kArenaThreads) dst[i] = src[i];
+        const uint32_t* ms = a.mask + e * a.mask_words;
+        uint32_t* md = a.st_mask + row * a.mask_words;
+        for (int i = tid; i < a.mask_words; i += kArenaThreads) md[i] = ms[i];
+        if (tid == 0) {
+            a.st_actions[row] = a.actions[e];
+            a.st_persp[row] = a.pre_player[e];
+        }
+    }
+}
+
+__global__ __launch_bounds__(kArenaThreads) void arena_record_post_kernel(int* cursors, const int* row_of, int E, const float* rewards,
+                                                                         const uint8_t* terminated, const uint8_t* truncated,
+                                                                         float* st_rewards, float* st_dones, int total_rows) {
+    const int s = blockIdx.x, e0 = s * E;
+    for (int k = threadIdx.x; k < E; k += kArenaThreads) {
+        const int r = row_of[e0 + k];
+        if (r < 0 || r >= total_rows) continue;
+        st_rewards[r] = rewards[e0 + k];
+        st_dones[r] = (terminated[e0 + k] || truncated[e0 + k]) ? 1.f : 0.f;
+    }
+    if (threadIdx.x == 0) {                                    // commit the ply's rows
+        cursors[s * kCursorWords + 0] += cursors[s * kCursorWords + 1];
+        cursors[s * kCursorWords + 1] = 0;
+    }
+}
+
+// dynamic_trainer.py:303-318, :358: W/D/L labels of terminal rows (-1 elsewhere) and advantages = rewards x dones
+__global__ void dynamic_targets_kernel(const float* rewards, const float* dones, long long* cats, float* adv, long long n) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float r = rewards[i], d = dones[i];
+    long long c = -1;
+    if (d != 0.f) c = r > 0.f ? 0 : (r == 0.f ? 1 : (r < 0.f ? 2 : -1));
+    cats[i] = c;
+    adv[i] = r * d;
+}
+
 }  // namespace
+
+extern "C" int ka_arena_cursor_words(int slots) { return kCursorWords * slots; }
+
+extern "C" int ka_arena_record_pre(const int* state, const int* side_bits, int slots, int envs_per_slot, const float* obs,
+                                   const void* mask_bits, const long long* actions, const void* pre_player, const int* nlegal,
+                                   int* cursors, int* row_of, float* st_obs, void* st_mask_bits, long long* st_actions,
+                                   void* st_perspective, int cap, int obs_elems, int mask_words, void* stream) {
+    KA_REQUIRE(state && side_bits && obs && mask_bits && actions && pre_player && nlegal && cursors && row_of && st_obs &&
+               st_mask_bits && st_actions && st_perspective, "arena_record_pre: null tensor");
+    KA_REQUIRE(slots > 0 && envs_per_slot > 0 && envs_per_slot <= 8192, "arena_record_pre: slots %d, envs_per_slot %d (1..8192)",
+               slots, envs_per_slot);
+    KA_REQUIRE(cap >= 0 && (long long)slots * cap < (1ll << 31), "arena_record_pre: cap %d x slots %d", cap, slots);
+    KA_REQUIRE(obs_elems > 0 && obs_elems % 2 == 0 && mask_words > 0,
+               "arena_record_pre: obs_elems %d (even: rows are copied as 8-byte vectors), mask_words %d", obs_elems, mask_words);
+    KA_REQUIRE(((uintptr_t)obs | (uintptr_t)st_obs) % 8 == 0, "arena_record_pre: observation buffers must be 8-byte aligned");
+    RecordPreArgs a{state, side_bits, envs_per_slot, obs, static_cast<const uint32_t*>(mask_bits), actions,
+                    static_cast<const uint8_t*>(pre_player), nlegal, cursors, row_of, st_obs,
+                    static_cast<uint32_t*>(st_mask_bits), st_actions, static_cast<uint8_t*>(st_perspective), cap, obs_elems,
+                    mask_words};
+    const int y = envs_per_slot < 64 ? envs_per_slot : 64;
+    hipLaunchKernelGGL(arena_record_pre_kernel, dim3(slots, y), dim3(kArenaThreads), envs_per_slot * sizeof(int),
+                       static_cast<hipStream_t>(stream), a);
+    return ka_check_launch("arena_record_pre");
+}
+
+extern "C" int ka_arena_record_post(int* cursors, const int* row_of, int slots, int envs_per_slot, const float* rewards,
+                                    const void* terminated, const void* truncated, float* st_rewards, float* st_dones,
+                                    int cap, void* stream) {
+    KA_REQUIRE(cursors && row_of && rewards && terminated && truncated && st_rewards && st_dones, "arena_record_post: null tensor");
+    KA_REQUIRE(slots > 0 && envs_per_slot > 0 && cap >= 0 && (long long)slots * cap < (1ll << 31),
+               "arena_record_post: slots %d, envs_per_slot %d, cap %d", slots, envs_per_slot, cap);
+    hipLaunchKernelGGL(arena_record_post_kernel, dim3(slots), dim3(kArenaThreads), 0, static_cast<hipStream_t>(stream), cursors,
+                       row_of, envs_per_slot, rewards, static_cast<const uint8_t*>(terminated),
+                       static_cast<const uint8_t*>(truncated), st_rewards, st_dones, slots * cap);
+    return ka_check_launch("arena_record_post");
+}
+
+extern "C" int ka_dynamic_targets(const float* rewards, const float* dones, long long* cats, float* adv, long long n, void* stream) {
+    KA_REQUIRE(rewards && dones && cats && adv, "dynamic_targets: null tensor");
+    KA_REQUIRE(n > 0, "dynamic_targets: n %lld", n);
+    hipLaunchKernelGGL(dynamic_targets_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       rewards, dones, cats, adv, n);
+    return ka_check_launch("dynamic_targets");
+}
 
 extern "C" int ka_arena_state_words(int slots) { return kHdrWords + kSlotWords * slots; }
 

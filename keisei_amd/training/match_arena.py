@@ -27,7 +27,7 @@ from __future__ import annotations
 
 import time
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, Mapping, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -35,9 +35,12 @@ import torch
 from keisei_amd import _lib
 from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS, VecEnv
 
+from .dynamic_trainer import MatchRollout
 from .model_group import SEResNetGroup
 
 _HDR, _SLOT = 8, 8                      # int32 words of the state header and of one slot (csrc/arena.hip)
+_CUR = 4                                # int32 words of one slot's collection cursors: rows, rows of this ply, dropped, -
+_OBS_ELEMS = 50 * 9 * 9                 # one observation row as the env hands it over (fp32)
 DONE, PARTIAL = 2, 4                   # slot status bits (csrc/arena.hip; 1 = seated, 8 = stalled)
 
 
@@ -51,6 +54,7 @@ class MatchResult:
     draws: int
     plies: int
     partial: bool
+    rollout: Optional[MatchRollout] = None      # collected rows (flat, packed masks, on the arena's device)
 
     @property
     def games(self) -> int:
@@ -67,6 +71,27 @@ class RoundStats:
     round_plies: int = 0                # plies the arena stepped (a multiple of sync_every)
     host_syncs: int = 0                 # reads of the state array
     active_slots: int = 0
+    rollout_rows: int = 0               # rows handed out in rollouts
+    rollouts_dropped: int = 0           # pairings whose rollout was withheld because the store lost rows of it
+
+
+def _side_bits(trainable, pairings: Sequence[Tuple[int, int]]) -> List[int]:
+    """Per pairing: bit 0 = collect side A's rows, bit 1 = side B's.  ``trainable``: None, a callable ``(a, b) -> int``
+    (the reference's trainable_fn, concurrent_matches.py:610-612, with the side in the answer) or a mapping from pairing
+    index to the bits."""
+    if trainable is None:
+        return [0] * len(pairings)
+    if callable(trainable):
+        bits = [int(trainable(a, b)) for a, b in pairings]
+    else:
+        bits = [int(trainable.get(i, 0)) for i in range(len(pairings))]
+        extra = [k for k in trainable if not (isinstance(k, int) and 0 <= k < len(pairings))]
+        if extra:
+            raise ValueError(f"trainable names pairing indices {extra} outside [0, {len(pairings)})")
+    for i, b in enumerate(bits):
+        if not 0 <= b <= 3:
+            raise ValueError(f"trainable gives {b} for pairing {i}: side bits are 0..3 (1 = side A, 2 = side B)")
+    return bits
 
 
 def _check_round(pairings: Sequence[Tuple[int, int]], games_per_match: int, num_models: int) -> List[Tuple[int, int]]:
@@ -86,14 +111,15 @@ def _ceiling(max_ply: int, target: int, envs: int) -> int:
 
 
 def _referee_host(records: Sequence[dict], pairings: Sequence[Tuple[int, int]], *, num_slots: int, envs_per_slot: int,
-                  games_per_match: int, max_ply: int, sync_every: int = 1):
+                  games_per_match: int, max_ply: int, sync_every: int = 1, trace: Optional[list] = None):
     """The reference's per-ply bookkeeping (concurrent_matches.py:254-506) restated in plain Python over per-ply records,
     with the swap-in moved to the sync points (every ``sync_every`` plies) as the arena does it.
 
     Each record holds the env facts of one ply as numpy arrays over all envs: ``pre_players`` (the player to move before
     the step), ``n_legal`` (legal actions before the step; optional), ``rewards``, ``terminated``, ``truncated``.
     Returns ``(results, seating)``: results[i] = (a_wins, b_wins, draws, plies, partial) of pairing i, or None if it never
-    finished within the records; seating[t] = the model index each env plays with at ply t (-1 = unseated)."""
+    finished within the records; seating[t] = the model index each env plays with at ply t (-1 = unseated).  ``trace``
+    (a list) receives per ply the ``{slot index: pairing index}`` of the slots that stepped."""
     P = len(pairings)
     slots = [dict(index=i, start=i * envs_per_slot, end=(i + 1) * envs_per_slot, pairing=None, a_wins=0, b_wins=0,
                   draws=0, target=0, plies=0, finished=False, partial=False) for i in range(min(num_slots, P))]
@@ -128,6 +154,8 @@ def _referee_host(records: Sequence[dict], pairings: Sequence[Tuple[int, int]], 
             pp = np.asarray(rec["pre_players"][lo:hi])
             seat[lo:hi] = np.where(pp == 0, a, b)
         seating.append(seat)
+        if trace is not None:
+            trace.append({s["index"]: s["pairing"] for s in live if s["index"] in stepped})
         for s in live:
             if s["index"] in stepped:
                 lo, hi = s["start"], s["end"]
@@ -155,6 +183,23 @@ def _referee_host(records: Sequence[dict], pairings: Sequence[Tuple[int, int]], 
     return results, seating
 
 
+def _rollout_rows_host(records: Sequence[dict], pairings: Sequence[Tuple[int, int]], bits: Sequence[int], *,
+                       num_slots: int, envs_per_slot: int, games_per_match: int, max_ply: int, sync_every: int = 1):
+    """The record rule of ``ka_arena_record_pre`` restated over ``_referee_host``'s bookkeeping: per pairing, the
+    ``(ply, env)`` pairs of its rollout rows, in order.  A slot that steps at ply t (seated, not finished, no env without
+    a legal action) gives one row per env whose pre-step player p has bit p of the pairing's side bits set."""
+    trace: List[dict] = []
+    _referee_host(records, pairings, num_slots=num_slots, envs_per_slot=envs_per_slot, games_per_match=games_per_match,
+                  max_ply=max_ply, sync_every=sync_every, trace=trace)
+    rows: List[List[Tuple[int, int]]] = [[] for _ in pairings]
+    for t, (rec, stepped) in enumerate(zip(records, trace)):
+        for slot, p in sorted(stepped.items()):
+            for e in range(slot * envs_per_slot, (slot + 1) * envs_per_slot):
+                if (bits[p] >> (int(rec["pre_players"][e]) & 1)) & 1:
+                    rows[p].append((t, e))
+    return rows
+
+
 class MatchArena:
     """Concurrent league matches over one device ``VecEnv`` (see module docstring).
 
@@ -162,10 +207,12 @@ class MatchArena:
     ``results, stats = arena.run_round(pairings, games_per_match)``.  ``seed`` fixes the round's sampling (each round
     draws a fresh one from torch's host generator when it is None).  ``graph=True`` captures ``sync_every`` plies once
     as a CUDA graph and replays it; ``sync_every`` must then be even.  ``record=True`` (no graph) keeps every ply's
-    inputs and outputs in ``self.record`` for tests."""
+    inputs and outputs in ``self.record`` for tests.  ``collect=True`` adds rollout collection to the ply (two launches,
+    ``ka_arena_record_pre`` / ``ka_arena_record_post``, into a store allocated here) for ``run_round(trainable=)``."""
 
     def __init__(self, group: SEResNetGroup, num_envs: int = 512, envs_per_match: int = 64, max_ply: int = 512, *,
-                 sync_every: int = 32, graph: bool = True, seed: Optional[int] = None, record: bool = False) -> None:
+                 sync_every: int = 32, graph: bool = True, seed: Optional[int] = None, record: bool = False,
+                 collect: bool = False) -> None:
         if len(group) == 0:
             raise ValueError("MatchArena needs a group with at least one model")
         if num_envs <= 0 or envs_per_match <= 0 or num_envs % envs_per_match != 0:
@@ -200,6 +247,22 @@ class MatchArena:
             self._nlegal = torch.zeros(N, dtype=torch.int32, device=dev)
             self._jobs = torch.zeros(self.num_slots, 4, dtype=torch.int32, device=dev)
             self._jobs_host = torch.zeros(self.num_slots, 4, dtype=torch.int32).pin_memory()
+            self.collect = bool(collect)
+            if self.collect:
+                # one region of sync_every x envs_per_match rows per slot: a slot's rows of one chunk are a contiguous
+                # slice and cannot overflow between two sync points
+                S, cap = self.num_slots, self.sync_every * self.envs_per_match
+                self._cap = cap
+                self._bits = torch.zeros(S, dtype=torch.int32, device=dev)
+                self._bits_host = torch.zeros(S, dtype=torch.int32).pin_memory()
+                self._cursors = torch.zeros(_lib.query("ka_arena_cursor_words", S), dtype=torch.int32, device=dev)
+                self._cursors_host = torch.zeros(self._cursors.shape, dtype=torch.int32).pin_memory()
+                self._row_of = torch.full((N,), -1, dtype=torch.int32, device=dev)
+                self._store = {"observations": torch.zeros(S * cap, 50, 9, 9, device=dev),
+                               "legal_mask_bits": torch.zeros(S * cap, MASK_WORDS, dtype=torch.int32, device=dev),
+                               "actions": torch.zeros(S * cap, dtype=torch.int64, device=dev),
+                               "perspective": torch.zeros(S * cap, dtype=torch.uint8, device=dev),
+                               "rewards": torch.zeros(S * cap, device=dev), "dones": torch.zeros(S * cap, device=dev)}
         self._graph: Optional[torch.cuda.CUDAGraph] = None
 
     # ------------------------------------------------------------------ one ply
@@ -212,7 +275,16 @@ class MatchArena:
         sp = self._state.data_ptr()
         _lib.call("ka_policy_sample_play", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of,
                   len(self.group), self._actions, self._logp, self._nlegal, sp + 16, N, ACTION_SPACE, st)
+        if self.collect:
+            sto = self._store
+            _lib.call("ka_arena_record_pre", self._state, self._bits, self.num_slots, self.envs_per_match, cur.observations,
+                      cur.legal_mask_bits, self._actions, self._pre, self._nlegal, self._cursors, self._row_of,
+                      sto["observations"], sto["legal_mask_bits"], sto["actions"], sto["perspective"], self._cap,
+                      _OBS_ELEMS, MASK_WORDS, st)
         r = env.step(self._actions)
+        if self.collect:
+            _lib.call("ka_arena_record_post", self._cursors, self._row_of, self.num_slots, self.envs_per_match, r.rewards,
+                      r.terminated, r.truncated, sto["rewards"], sto["dones"], self._cap, st)
         # env._err[1] is the VecEnv's refusal latch: the referee copies it into the state so the host sees a refused
         # step in the same read
         _lib.call("ka_arena_referee", self._state, self.num_slots, self.envs_per_match, r.rewards,
@@ -255,6 +327,8 @@ class MatchArena:
 
     # ------------------------------------------------------------------ host side
     def _read_state(self) -> np.ndarray:
+        if self.collect:                              # same stream: complete when the state copy below returns
+            self._cursors_host.copy_(self._cursors, non_blocking=True)
         self._state_host.copy_(self._state)           # the one device -> host read of a sync point
         st = self._state_host.numpy()
         if st[4]:
@@ -264,21 +338,44 @@ class MatchArena:
             self.env.raise_if_refused()               # a refused step here is a bug: it raises
         return st
 
-    def _assign(self, jobs: List[Tuple[int, int, int, int]]) -> None:
+    def _assign(self, jobs: List[Tuple[int, int, int, int]], bits: Sequence[int] = ()) -> None:
         if not jobs:
             return
+        if self.collect:
+            for (s, _, _, _), b in zip(jobs, bits):
+                self._bits_host[s] = b
+            self._bits.copy_(self._bits_host, non_blocking=True)
         self._jobs_host[:len(jobs)] = torch.tensor(jobs, dtype=torch.int32)
         self._jobs.copy_(self._jobs_host, non_blocking=True)
         env = self.env
         _lib.call("ka_arena_assign", self._state, self._jobs, len(jobs), self.envs_per_match, env._players[env._cur],
                   self._model_of, self._pre, _lib.stream_ptr(self.device))
 
-    def run_round(self, pairings: Sequence[Tuple[int, int]], games_per_match: int = 64, *, max_ply: Optional[int] = None):
+    def _drain(self, slot_pairing: Dict[int, int], chunks: Dict[int, list], lost: set) -> None:
+        """Sync point: move the chunk's rows of every collecting slot out of the store (device to device) and reset the
+        cursors.  The host has read only the cursor array."""
+        cur = self._cursors_host.numpy().reshape(self.num_slots, _CUR)
+        for s, p in slot_pairing.items():
+            n = int(cur[s, 0])
+            if cur[s, 2]:
+                lost.add(p)
+            if n:
+                lo = s * self._cap
+                chunks.setdefault(p, []).append({k: t[lo:lo + n].clone() for k, t in self._store.items()})
+        self._cursors.zero_()
+
+    def run_round(self, pairings: Sequence[Tuple[int, int]], games_per_match: int = 64, *, max_ply: Optional[int] = None,
+                  trainable: Union[None, Callable[[int, int], int], Mapping[int, int]] = None):
         """Play every pairing ``(a, b)`` (model indices into the group, priority order) for ``games_per_match`` games.
         ``max_ply`` sets the ply ceiling ``max_ply * (ceil(games_per_match / envs_per_match) + 1)`` of a pairing, after
         which it ends with a partial result, as the reference's ``run_round(max_ply=)`` does (default: the env's max_ply).
+        ``trainable`` (an arena built with ``collect=True``): a callable ``(a, b) -> bits`` or a mapping pairing index ->
+        bits, bit 0 = collect the rows of side A, bit 1 = of side B; those pairings' results carry a ``MatchRollout``.
         Returns ``(results, stats)``: one MatchResult per pairing, in pairing order, and the round's RoundStats."""
         pairings = _check_round(pairings, games_per_match, len(self.group))
+        if trainable is not None and not self.collect:
+            raise ValueError("run_round(trainable=) needs an arena built with collect=True")
+        bits = _side_bits(trainable, pairings)
         max_ply = self.max_ply if max_ply is None else int(max_ply)
         if max_ply < 1:
             raise ValueError(f"max_ply must be positive, got {max_ply}")
@@ -286,9 +383,9 @@ class MatchArena:
         if not pairings:
             return [], stats
         with torch.cuda.device(self.device), torch.no_grad():
-            return self._run(pairings, int(games_per_match), max_ply, stats)
+            return self._run(pairings, int(games_per_match), max_ply, stats, bits)
 
-    def _run(self, pairings, games_per_match, max_ply, stats):
+    def _run(self, pairings, games_per_match, max_ply, stats, bits):
         if self.graph and self._graph is None:
             self._capture()
         t0 = time.monotonic()
@@ -298,8 +395,13 @@ class MatchArena:
         hdr[3] = max_ply
         self._state.copy_(hdr)
         self._model_of.fill_(-1)
+        if self.collect:
+            self._cursors.zero_()
+            self._bits_host.zero_()
         self.env.reset()
         self.record = []
+        chunks: Dict[int, list] = {}
+        lost: set = set()
         P = len(pairings)
         slot_pairing: Dict[int, int] = {}
         active: List[int] = []
@@ -312,25 +414,37 @@ class MatchArena:
             active.append(s)
             nxt += 1
         stats.active_slots = len(active)
-        self._assign(jobs)
+        self._assign(jobs, [bits[slot_pairing[j[0]]] for j in jobs])
         results: Dict[int, MatchResult] = {}
         while active:
             self._chunk()
             st = self._read_state()
             stats.host_syncs += 1
             slot = st[_HDR:].reshape(self.num_slots, _SLOT)
+            if self.collect:
+                self._drain(slot_pairing, chunks, lost)
             jobs = []
             for i in sorted((i for i, s in enumerate(active) if slot[s, 7] & DONE), reverse=True):
                 s = active.pop(i)
                 ma, mb, _, aw, bw, dr, plies, status = (int(v) for v in slot[s])
-                results[slot_pairing.pop(s)] = MatchResult(ma, mb, aw, bw, dr, plies, bool(status & PARTIAL))
+                p = slot_pairing.pop(s)
+                results[p] = MatchResult(ma, mb, aw, bw, dr, plies, bool(status & PARTIAL))
+                if p in lost:
+                    stats.rollouts_dropped += 1
+                    chunks.pop(p, None)
+                elif p in chunks:                           # to_result: the pairing's chunks become one rollout
+                    parts = chunks.pop(p)
+                    cat = {k: torch.cat([c[k] for c in parts]) for k in parts[0]}
+                    results[p].rollout = MatchRollout(cat["observations"], cat["actions"], cat["rewards"], cat["dones"],
+                                                      None, cat["perspective"], cat["legal_mask_bits"])
+                    stats.rollout_rows += int(cat["actions"].shape[0])
                 if nxt < P:
                     a, b = pairings[nxt]
                     jobs.append((s, a, b, games_per_match))
                     slot_pairing[s] = nxt
                     active.append(s)
                     nxt += 1
-            self._assign(jobs)
+            self._assign(jobs, [bits[slot_pairing[j[0]]] for j in jobs])
         stats.round_plies = int(self._state_host[2])
         stats.round_duration_s = time.monotonic() - t0
         ordered = [results[i] for i in range(P)]

@@ -8,7 +8,10 @@ SEResNetGroup.select_actions with check=True, win / loss / draw tallies in Pytho
 Both run one round after a warm-up round (kernel loading, graph capture) and report plies/s, games/min and host syncs per
 round.  One JSON line per workload.
 
-    python tools/arena_bench.py [--workload a|b|all] [--configs g2,g32,e2,e32,host] [--max-ply 512]
+A config name ending in "c" (g32c, e2c, ...) builds the arena with collect=True and makes every pairing trainable on both
+sides: the worst case of rollout collection, reported with the rows collected.
+
+    python tools/arena_bench.py [--workload a|b|all] [--configs g2,g32,e2,e32,host,g32c] [--max-ply 512] [--repeat 1]
 """
 from __future__ import annotations
 
@@ -121,14 +124,19 @@ def host_loop_round(group, env, pairings, games, max_ply, E):
             "games": games_total, "games_per_min": round(games_total / dt * 60, 1), "host_syncs": syncs}
 
 
-def arena_round(group, N, E, max_ply, graph, sync_every, pairings, games):
-    arena = MatchArena(group, N, E, max_ply, sync_every=sync_every, graph=graph, seed=1234)
-    arena.run_round(pairings[:2], games_per_match=1)          # warm-up: kernel loading and graph capture
+def arena_round(group, N, E, max_ply, graph, sync_every, pairings, games, collect=False, repeat=1):
+    arena = MatchArena(group, N, E, max_ply, sync_every=sync_every, graph=graph, seed=1234, collect=collect)
+    kw = {"trainable": (lambda a, b: 3)} if collect else {}
+    arena.run_round(pairings[:2], games_per_match=1, **kw)    # warm-up: kernel loading and graph capture
     torch.cuda.synchronize()
-    results, st = arena.run_round(pairings, games_per_match=games)
-    torch.cuda.synchronize()
+    rates = []
+    for _ in range(repeat):
+        results, st = arena.run_round(pairings, games_per_match=games, **kw)
+        torch.cuda.synchronize()
+        rates.append(round(st.round_plies / st.round_duration_s, 1))
     dt = st.round_duration_s
-    return {"round_s": round(dt, 3), "round_plies": st.round_plies, "plies_per_s": round(st.round_plies / dt, 1),
+    return {"plies_per_s_runs": rates, "rollout_rows": st.rollout_rows, "rollouts_dropped": st.rollouts_dropped,
+            "round_s": round(dt, 3), "round_plies": st.round_plies, "plies_per_s": round(st.round_plies / dt, 1),
             "games": st.total_games, "games_per_min": round(st.total_games / dt * 60, 1), "host_syncs": st.host_syncs,
             "partial": sum(r.partial for r in results),
             "a_b_d": [sum(r.a_wins for r in results), sum(r.b_wins for r in results), sum(r.draws for r in results)]}
@@ -139,6 +147,7 @@ def main() -> None:
     ap.add_argument("--workload", default="all", choices=["a", "b", "all"])
     ap.add_argument("--configs", default="g2,g32,e2,e32,host")
     ap.add_argument("--max-ply", type=int, default=512)
+    ap.add_argument("--repeat", type=int, default=1, help="timed rounds per arena config")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "arena_bench needs a GPU"
@@ -155,9 +164,12 @@ def main() -> None:
                 host_loop_round(group, env, pairings[:1], 1, args.max_ply, E)          # warm-up
                 row["host_loop"] = host_loop_round(group, env, pairings, 64, args.max_ply, E)
             else:
-                graph, se = CONFIGS[c]
-                row[f"arena_{'graph' if graph else 'eager'}_sync{se}"] = arena_round(group, N, E, args.max_ply, graph, se,
-                                                                                      pairings, 64)
+                collect = c.endswith("c")
+                graph, se = CONFIGS[c[:-1] if collect else c]
+                key = f"arena_{'graph' if graph else 'eager'}_sync{se}{'_collect' if collect else ''}"
+                while key in row:                                # the same config named twice: alternating runs
+                    key += "'"
+                row[key] = arena_round(group, N, E, args.max_ply, graph, se, pairings, 64, collect, args.repeat)
             torch.cuda.synchronize()
         print(json.dumps(row), flush=True)
         lines.append(row)
