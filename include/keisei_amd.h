@@ -474,6 +474,28 @@ int ka_arena_record_pre(const int* state, const int* side_bits, int slots, int e
 int ka_arena_record_post(int* cursors, const int* row_of, int slots, int envs_per_slot, const float* rewards,
                          const void* terminated, const void* truncated, float* st_rewards, float* st_dones, int cap,
                          void* stream);
+/* Per-game style features inside the ply (game_feature_tracker.py:176-356 GameFeatureTracker; concurrent_matches.py:125-130
+ * one tracker per seated pairing, :441-452 record_step on every stepped ply, :46 / :162 MatchResult.feature_tracker).
+ * ka_arena_feature_words(which): int32 words of 0 = one env's accumulator {opening actions kept, num_repetitions, 12 opening
+ *   actions, side A, side B}, 1 = one game record {env, total plies, termination reason, last mover, reward sign, opening
+ *   actions kept, num_repetitions, round ply, 12 opening actions, side A, side B}, 2 = one slot's cursor {records committed,
+ *   records dropped}; -1 for any other `which`.  A side is the ten _SideStats counters in their order (:67-80), -1 for None.
+ * ka_arena_features_step (after ka_shogi_env_step, before ka_arena_referee, which rewrites status and pre_player): for every
+ *   slot that is seated, not done and has no env with nlegal == 0 (concurrent_matches.py:303-314, :410), record_step
+ *   (:204-284) on each env from its action, mover, captured (u8, 255 none), reason (u8), ply (uint16 payload) and, where
+ *   terminated | truncated, _emit_game (:286-356): one record at records[s * cap + committed + rank], rank = the env's place
+ *   among the slot's finished envs of this ply (no atomics: the order inside a slot is (ply, env)), and a fresh accumulator.
+ *   Records beyond cap are not written and are counted as dropped.  acc (S*E x words(0)), records (S*cap x words(1)),
+ *   fcursors (S x words(2)) int32.
+ * ka_arena_features_seat (behind ka_arena_assign, same jobs): a fresh accumulator for every env of each job's slot (a new
+ *   tracker per pairing, concurrent_matches.py:125); rows naming a slot outside [0, slots) are skipped.
+ * The host reads and zeroes `fcursors` at its sync point, outside any captured graph. */
+int ka_arena_feature_words(int which);
+int ka_arena_features_step(const int* state, int slots, int envs_per_slot, const long long* actions, const void* pre_player,
+                           const int* nlegal, const void* captured, const void* reason, const void* ply, const float* rewards,
+                           const void* terminated, const void* truncated, int* acc, int* records, int* fcursors, int cap,
+                           void* stream);
+int ka_arena_features_seat(const int* jobs, int njobs, int slots, int envs_per_slot, int* acc, void* stream);
 /* Dynamic-entry targets (dynamic_trainer.py:310-318, :358): cats[i] = 0 / 1 / 2 (win / draw / loss by the sign of rewards[i])
  * where dones[i] != 0, else -1; adv[i] = rewards[i] * dones[i]. */
 int ka_dynamic_targets(const float* rewards, const float* dones, long long* cats, float* adv, long long n, void* stream);

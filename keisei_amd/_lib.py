@@ -108,6 +108,9 @@ _SIGS = {
     "ka_arena_cursor_words": "i",
     "ka_arena_record_pre": "pp ii ppppp pp pppp iii p",
     "ka_arena_record_post": "pp ii ppp pp i p",
+    "ka_arena_feature_words": "i",
+    "ka_arena_features_step": "p ii ppp ppp ppp ppp i p",
+    "ka_arena_features_seat": "p iii p p",
     "ka_dynamic_targets": "pppp q p",
     "ka_tf_gemm_nt": "ppppp iii iii iii f q p",
     "ka_tf_gemm_nt_slabs": "ii",

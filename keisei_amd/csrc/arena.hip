@@ -33,6 +33,24 @@ __device__ __forceinline__ int block_sum_int(int v, int* red) {
     return r;
 }
 
+// Ranks of the flagged threads of one 256-thread tile, in thread order, behind the `running` flagged threads of the tiles
+// before it: *rank = running + (flagged threads below this one), -1 for a thread that is not flagged.  Returns the tile's
+// count.  One ballot per wave and a sum over the four waves: no atomics, so the order is the thread order.
+__device__ __forceinline__ int tile_rank(bool want, int running, int* wsum, int* rank) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long b = __ballot(want);
+    __syncthreads();                                           // the tile before has read wsum
+    if (lane == 0) wsum[wave] = __popcll(b);
+    __syncthreads();
+    int off = running, tot = 0;
+    for (int w = 0; w < kArenaThreads / 64; ++w) {
+        if (w < wave) off += wsum[w];
+        tot += wsum[w];
+    }
+    *rank = want ? off + __popcll(b & ((1ull << lane) - 1ull)) : -1;
+    return tot;
+}
+
 struct RefereeArgs {
     int* state; int E;
     const float* rewards; const uint8_t* terminated; const uint8_t* truncated; const uint8_t* players;
@@ -148,7 +166,7 @@ __global__ __launch_bounds__(kArenaThreads) void arena_record_pre_kernel(RecordP
     extern __shared__ int s_rank[];                            // E ints: rank of the env's row this ply, -1 = no row
     __shared__ int red[kArenaThreads / 64];
     __shared__ int wsum[kArenaThreads / 64];
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = blockIdx.x, tid = threadIdx.x;
     const int e0 = s * a.E;
     const int status = a.state[kHdrWords + s * kSlotWords + 7];
     const int bits = a.side_bits[s];
@@ -169,18 +187,12 @@ __global__ __launch_bounds__(kArenaThreads) void arena_record_pre_kernel(RecordP
     for (int base = 0; base < a.E; base += kArenaThreads) {
         const int k = base + tid;
         const bool want = k < a.E && ((bits >> (a.pre_player[e0 + k] & 1)) & 1);
-        const unsigned long long b = __ballot(want);
-        if (lane == 0) wsum[wave] = __popcll(b);
-        __syncthreads();
-        int off = running, tot = 0;
-        for (int w = 0; w < kArenaThreads / 64; ++w) {
-            if (w < wave) off += wsum[w];
-            tot += wsum[w];
-        }
-        if (k < a.E) s_rank[k] = want ? off + __popcll(b & ((1ull << lane) - 1ull)) : -1;
+        int rank;
+        const int tot = tile_rank(want, running, wsum, &rank);
+        if (k < a.E) s_rank[k] = rank;
         running += tot;
-        __syncthreads();
     }
+    __syncthreads();
     const int first = a.cursors[s * kCursorWords + 0];
     const int room = max(0, a.cap - first);                    // rows of this ply that still fit
     if (blockIdx.y == 0) {
@@ -225,6 +237,121 @@ __global__ __launch_bounds__(kArenaThreads) void arena_record_post_kernel(int* c
         cursors[s * kCursorWords + 0] += cursors[s * kCursorWords + 1];
         cursors[s * kCursorWords + 1] = 0;
     }
+}
+
+// ---- per-game style features (game_feature_tracker.py:176-356, the GameFeatureTracker every slot gets at seat time,
+// concurrent_matches.py:125-130, and feeds every stepped ply, :441-452).
+// acc: kAccWords int32 per env = {opening actions kept, num_repetitions, 12 opening actions, side A, side B}; a side is
+//   {first_capture_ply, first_drop_ply, num_captures, num_drops, num_promotions, num_early_drops, rook_moved_ply,
+//    rook_moves_in_20, king_displacement_20, king_moves_in_30} (_SideStats order), -1 where the reference holds None.
+// records: `cap` game records per slot, kRecWords int32 each = {env, total plies, termination reason, last mover, reward
+//   sign, opening actions kept, num_repetitions, round ply, 12 opening actions, side A, side B}: one per finished GAME, the
+//   host expands it into the black and the white row.
+// fcursors: kFeatCursorWords int32 per slot = {records committed, records dropped}.
+constexpr int kOpeningKept = 12, kSideWords = 10;
+constexpr int kAccWords = 2 + kOpeningKept + 2 * kSideWords;
+constexpr int kRecHead = 8, kRecWords = kRecHead + kOpeningKept + 2 * kSideWords;
+constexpr int kFeatCursorWords = 2;
+constexpr int kSpatialMoveTypes = 139, kPromotionMin = 64, kPromotionMax = 131, kDropMin = 132, kDropMax = 138;
+constexpr int kNoCapture = 255, kRookSquare = 79, kKingSquare = 76, kReasonRepetition = 2;
+constexpr int kEarlyDropPly = 40, kRookMobilityPly = 20, kKingDisplacementPly = 20, kKingMovementPly = 30;
+
+// word w of a fresh accumulator: the three optional plies of each side are -1, everything else 0
+__device__ __forceinline__ int acc_reset_word(int w) {
+    const int f = w - 2 - kOpeningKept;
+    if (f < 0) return 0;
+    const int k = f % kSideWords;
+    return (k == 0 || k == 1 || k == 6) ? -1 : 0;
+}
+
+struct FeaturesArgs {
+    const int* state; int E;
+    const long long* actions; const uint8_t* pre_player; const int* nlegal;
+    const uint8_t* captured; const uint8_t* reason; const uint16_t* ply;
+    const float* rewards; const uint8_t* terminated; const uint8_t* truncated;
+    int* acc; int* records; int* fcursors; int cap;
+};
+
+__global__ __launch_bounds__(kArenaThreads) void arena_features_kernel(FeaturesArgs a) {
+    __shared__ int red[kArenaThreads / 64];
+    __shared__ int wsum[kArenaThreads / 64];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int e0 = s * a.E;
+    const int status = a.state[kHdrWords + s * kSlotWords + 7];
+    if (!(status & kSeated) || (status & kDone)) return;        // uniform over the workgroup
+    int stalled = 0;
+    for (int k = tid; k < a.E; k += kArenaThreads) stalled |= a.nlegal[e0 + k] == 0;
+    if (block_sum_int(stalled, red) != 0) return;               // concurrent_matches.py:303-314, :410: a skipped slot records nothing
+    const int round_ply = a.state[2];
+    const int first = a.fcursors[s * kFeatCursorWords + 0];
+    const int room = first < 0 ? 0 : max(0, a.cap - first);     // records of this ply that still fit
+    int running = 0;
+    for (int base = 0; base < a.E; base += kArenaThreads) {
+        const int k = base + tid;
+        const bool have = k < a.E;
+        const int e = e0 + (have ? k : 0);
+        int* acc = a.acc + (size_t)e * kAccWords;
+        bool done = false;
+        int ply = 0, mover = 0;
+        if (have) {                                             // game_feature_tracker.py:229-280
+            const int action = (int)a.actions[e];
+            ply = a.ply[e];
+            mover = a.pre_player[e] & 1;
+            done = a.terminated[e] || a.truncated[e];
+            int* side = acc + 2 + kOpeningKept + mover * kSideWords;
+            const int square = action / kSpatialMoveTypes, type = action % kSpatialMoveTypes;
+            const bool drop = type >= kDropMin && type <= kDropMax;
+            const int kept = acc[0];
+            if (kept < kOpeningKept) {                          // :240: the first 12 actions since the reset
+                acc[2 + kept] = action;
+                acc[0] = kept + 1;
+            }
+            if (a.captured[e] != kNoCapture) {
+                side[2] += 1;
+                if (side[0] < 0) side[0] = ply;
+            }
+            if (drop) {
+                side[3] += 1;
+                if (side[1] < 0) side[1] = ply;
+                if (ply <= kEarlyDropPly) side[5] += 1;
+            }
+            if (type >= kPromotionMin && type <= kPromotionMax) side[4] += 1;
+            if (!drop && square == kRookSquare) {               // :264-275: 79 and 76 for both sides, board moves only
+                if (side[6] < 0) side[6] = ply;
+                if (ply <= kRookMobilityPly) side[7] += 1;
+            }
+            if (!drop && square == kKingSquare) {
+                if (ply <= kKingDisplacementPly) side[8] += 1;
+                if (ply <= kKingMovementPly) side[9] += 1;
+            }
+            if (done && a.reason[e] == kReasonRepetition) acc[1] += 1;      // :278-280
+        }
+        int rank;
+        running += tile_rank(done, running, wsum, &rank);
+        if (done) {                                             // :286-356: one record per game, then a fresh accumulator
+            if (rank < room) {
+                int* rec = a.records + ((size_t)s * a.cap + first + rank) * kRecWords;
+                const float r = a.rewards[e];
+                rec[0] = e; rec[1] = ply; rec[2] = a.reason[e]; rec[3] = mover;
+                rec[4] = r > 0.f ? 1 : (r < 0.f ? -1 : 0);      // :298-303 (a NaN is a draw)
+                rec[5] = acc[0]; rec[6] = acc[1]; rec[7] = round_ply;
+                for (int w = 2; w < kAccWords; ++w) rec[kRecHead - 2 + w] = acc[w];
+            }
+            for (int w = 0; w < kAccWords; ++w) acc[w] = acc_reset_word(w);
+        }
+    }
+    if (tid == 0) {                                             // every thread has read `first` before the scan's barriers
+        a.fcursors[s * kFeatCursorWords + 0] = first + min(running, room);
+        a.fcursors[s * kFeatCursorWords + 1] += max(0, running - room);
+    }
+}
+
+// jobs: n rows of {slot, ...} as ka_arena_assign takes them; one workgroup per job
+__global__ __launch_bounds__(kArenaThreads) void arena_features_seat_kernel(const int* jobs, int slots, int E, int* acc) {
+    const int s = jobs[blockIdx.x * 4];
+    if (s < 0 || s >= slots) return;
+    int* base = acc + (size_t)s * E * kAccWords;
+    for (int i = threadIdx.x; i < E * kAccWords; i += kArenaThreads) base[i] = acc_reset_word(i % kAccWords);
 }
 
 // dynamic_trainer.py:303-318, :358: W/D/L labels of terminal rows (-1 elsewhere) and advantages = rewards x dones
@@ -274,6 +401,37 @@ extern "C" int ka_arena_record_post(int* cursors, const int* row_of, int slots, 
                        row_of, envs_per_slot, rewards, static_cast<const uint8_t*>(terminated),
                        static_cast<const uint8_t*>(truncated), st_rewards, st_dones, slots * cap);
     return ka_check_launch("arena_record_post");
+}
+
+extern "C" int ka_arena_feature_words(int which) {
+    return which == 0 ? kAccWords : which == 1 ? kRecWords : which == 2 ? kFeatCursorWords : -1;
+}
+
+extern "C" int ka_arena_features_step(const int* state, int slots, int envs_per_slot, const long long* actions,
+                                      const void* pre_player, const int* nlegal, const void* captured, const void* reason,
+                                      const void* ply, const float* rewards, const void* terminated, const void* truncated,
+                                      int* acc, int* records, int* fcursors, int cap, void* stream) {
+    KA_REQUIRE(state && actions && pre_player && nlegal && captured && reason && ply && rewards && terminated && truncated &&
+               acc && records && fcursors, "arena_features_step: null tensor");
+    KA_REQUIRE(slots > 0 && envs_per_slot > 0 && (long long)slots * envs_per_slot * kAccWords < (1ll << 31),
+               "arena_features_step: slots %d, envs_per_slot %d", slots, envs_per_slot);
+    KA_REQUIRE(cap >= 0 && (long long)slots * cap * kRecWords < (1ll << 31), "arena_features_step: cap %d x slots %d", cap, slots);
+    KA_REQUIRE((uintptr_t)ply % 2 == 0, "arena_features_step: ply must be 2-byte aligned (uint16 payload)");
+    FeaturesArgs a{state, envs_per_slot, actions, static_cast<const uint8_t*>(pre_player), nlegal,
+                   static_cast<const uint8_t*>(captured), static_cast<const uint8_t*>(reason),
+                   static_cast<const uint16_t*>(ply), rewards, static_cast<const uint8_t*>(terminated),
+                   static_cast<const uint8_t*>(truncated), acc, records, fcursors, cap};
+    hipLaunchKernelGGL(arena_features_kernel, dim3(slots), dim3(kArenaThreads), 0, static_cast<hipStream_t>(stream), a);
+    return ka_check_launch("arena_features_step");
+}
+
+extern "C" int ka_arena_features_seat(const int* jobs, int njobs, int slots, int envs_per_slot, int* acc, void* stream) {
+    KA_REQUIRE(jobs && acc, "arena_features_seat: null tensor");
+    KA_REQUIRE(njobs > 0 && slots > 0 && envs_per_slot > 0 && (long long)slots * envs_per_slot * kAccWords < (1ll << 31),
+               "arena_features_seat: njobs %d, slots %d, envs_per_slot %d", njobs, slots, envs_per_slot);
+    hipLaunchKernelGGL(arena_features_seat_kernel, dim3(njobs), dim3(kArenaThreads), 0, static_cast<hipStream_t>(stream), jobs,
+                       slots, envs_per_slot, acc);
+    return ka_check_launch("arena_features_seat");
 }
 
 extern "C" int ka_dynamic_targets(const float* rewards, const float* dones, long long* cats, float* adv, long long n, void* stream) {

@@ -10,6 +10,8 @@ synchronisation:
     ka_policy_sample_play                       (csrc/loss.hip: seed read from the device; unseated rows take their
                                                  first legal action, as the reference does for idle partitions)
     ka_shogi_env_step                           (csrc/shogi_env.hip)
+    ka_arena_features_step                      (csrc/arena.hip, only with features=True: the reference's per-slot
+                                                 GameFeatureTracker, one record per finished game)
     ka_arena_referee                            (csrc/arena.hip: tally by the last-mover rule, close slots, seat the
                                                  next ply, advance the seed)
 
@@ -36,6 +38,7 @@ from keisei_amd import _lib
 from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS, VecEnv
 
 from .dynamic_trainer import MatchRollout
+from .game_feature_tracker import GameFeatureTracker
 from .model_group import SEResNetGroup
 
 _HDR, _SLOT = 8, 8                      # int32 words of the state header and of one slot (csrc/arena.hip)
@@ -55,6 +58,7 @@ class MatchResult:
     plies: int
     partial: bool
     rollout: Optional[MatchRollout] = None      # collected rows (flat, packed masks, on the arena's device)
+    feature_tracker: Optional[GameFeatureTracker] = None     # the pairing's game features (arenas with features=True)
 
     @property
     def games(self) -> int:
@@ -73,6 +77,8 @@ class RoundStats:
     active_slots: int = 0
     rollout_rows: int = 0               # rows handed out in rollouts
     rollouts_dropped: int = 0           # pairings whose rollout was withheld because the store lost rows of it
+    feature_rows: int = 0               # rows handed out in feature trackers (two per finished game)
+    features_dropped: int = 0           # finished games whose record did not fit the feature store
 
 
 def _side_bits(trainable, pairings: Sequence[Tuple[int, int]]) -> List[int]:
@@ -200,6 +206,31 @@ def _rollout_rows_host(records: Sequence[dict], pairings: Sequence[Tuple[int, in
     return rows
 
 
+def _entry_id(entry_ids, model: int) -> int:
+    return model if entry_ids is None else entry_ids[model]
+
+
+def _features_host(records: Sequence[dict], pairings: Sequence[Tuple[int, int]], *, num_slots: int, envs_per_slot: int,
+                   games_per_match: int, max_ply: int, sync_every: int = 1, entry_ids=None,
+                   epoch: int = 0) -> List[GameFeatureTracker]:
+    """The reference's feature tracking (concurrent_matches.py:125-130, :441-452) over ``_referee_host``'s bookkeeping:
+    one host ``GameFeatureTracker`` per pairing, made when the pairing is seated, and ``record_step`` on the envs of
+    every slot that stepped.  The records carry ``actions``, ``captured_piece``, ``termination_reason`` and ``ply_count``
+    beside what ``_referee_host`` reads.  Returns the trackers in pairing order."""
+    trace: List[dict] = []
+    _referee_host(records, pairings, num_slots=num_slots, envs_per_slot=envs_per_slot, games_per_match=games_per_match,
+                  max_ply=max_ply, sync_every=sync_every, trace=trace)
+    trackers = [GameFeatureTracker(envs_per_slot, _entry_id(entry_ids, a), _entry_id(entry_ids, b), epoch)
+                for a, b in pairings]                           # a pairing is seated once: its tracker is new then
+    for rec, stepped in zip(records, trace):
+        for slot, p in sorted(stepped.items()):
+            lo, hi = slot * envs_per_slot, (slot + 1) * envs_per_slot
+            trackers[p].record_step(*(np.asarray(rec[k][lo:hi]) for k in (
+                "actions", "captured_piece", "termination_reason", "ply_count", "pre_players", "terminated", "truncated",
+                "rewards")))
+    return trackers
+
+
 class MatchArena:
     """Concurrent league matches over one device ``VecEnv`` (see module docstring).
 
@@ -208,11 +239,14 @@ class MatchArena:
     draws a fresh one from torch's host generator when it is None).  ``graph=True`` captures ``sync_every`` plies once
     as a CUDA graph and replays it; ``sync_every`` must then be even.  ``record=True`` (no graph) keeps every ply's
     inputs and outputs in ``self.record`` for tests.  ``collect=True`` adds rollout collection to the ply (two launches,
-    ``ka_arena_record_pre`` / ``ka_arena_record_post``, into a store allocated here) for ``run_round(trainable=)``."""
+    ``ka_arena_record_pre`` / ``ka_arena_record_post``, into a store allocated here) for ``run_round(trainable=)``.
+    ``features=True`` adds the reference's per-slot ``GameFeatureTracker`` to the ply (one launch,
+    ``ka_arena_features_step``): every result then carries a ``feature_tracker``.  Without it the ply is launch for
+    launch what it was."""
 
     def __init__(self, group: SEResNetGroup, num_envs: int = 512, envs_per_match: int = 64, max_ply: int = 512, *,
                  sync_every: int = 32, graph: bool = True, seed: Optional[int] = None, record: bool = False,
-                 collect: bool = False) -> None:
+                 collect: bool = False, features: bool = False) -> None:
         if len(group) == 0:
             raise ValueError("MatchArena needs a group with at least one model")
         if num_envs <= 0 or envs_per_match <= 0 or num_envs % envs_per_match != 0:
@@ -263,6 +297,21 @@ class MatchArena:
                                "actions": torch.zeros(S * cap, dtype=torch.int64, device=dev),
                                "perspective": torch.zeros(S * cap, dtype=torch.uint8, device=dev),
                                "rewards": torch.zeros(S * cap, device=dev), "dones": torch.zeros(S * cap, device=dev)}
+            self.features = bool(features)
+            if self.features:
+                # an env finishes at most one game per ply, so sync_every x envs_per_match records per slot cannot
+                # overflow between two sync points
+                S = self.num_slots
+                accw, recw, curw = (_lib.query("ka_arena_feature_words", i) for i in range(3))
+                self._fcap, self._fcurw = self.sync_every * self.envs_per_match, curw
+                self._facc = torch.zeros(N * accw, dtype=torch.int32, device=dev)
+                self._frecords = torch.zeros(S * self._fcap, recw, dtype=torch.int32, device=dev)
+                self._frecords_host = torch.zeros(self._frecords.shape, dtype=torch.int32).pin_memory()
+                self._fcursors = torch.zeros(S * curw, dtype=torch.int32, device=dev)
+                self._fcursors_host = torch.zeros(self._fcursors.shape, dtype=torch.int32).pin_memory()
+                every = torch.zeros(S, 4, dtype=torch.int32)
+                every[:, 0] = torch.arange(S, dtype=torch.int32)
+                self._every_slot = every.to(dev)                  # seat jobs naming every slot: the round-start clear
         self._graph: Optional[torch.cuda.CUDAGraph] = None
 
     # ------------------------------------------------------------------ one ply
@@ -285,6 +334,11 @@ class MatchArena:
         if self.collect:
             _lib.call("ka_arena_record_post", self._cursors, self._row_of, self.num_slots, self.envs_per_match, r.rewards,
                       r.terminated, r.truncated, sto["rewards"], sto["dones"], self._cap, st)
+        if self.features:                                 # before the referee: it rewrites status and pre_player
+            meta = r.step_metadata
+            _lib.call("ka_arena_features_step", self._state, self.num_slots, self.envs_per_match, self._actions, self._pre,
+                      self._nlegal, meta.captured_piece, meta.termination_reason, meta.ply_count, r.rewards, r.terminated,
+                      r.truncated, self._facc, self._frecords, self._fcursors, self._fcap, st)
         # env._err[1] is the VecEnv's refusal latch: the referee copies it into the state so the host sees a refused
         # step in the same read
         _lib.call("ka_arena_referee", self._state, self.num_slots, self.envs_per_match, r.rewards,
@@ -300,6 +354,10 @@ class MatchArena:
         rec.update(actions=self._actions.cpu(), log_probs=self._logp.cpu(), n_legal=self._nlegal.cpu(),
                    rewards=self.env._rewards[self.env._cur].cpu(), terminated=self.env._terminated[self.env._cur].cpu(),
                    truncated=self.env._truncated[self.env._cur].cpu())
+        if self.features:
+            rec.update(captured_piece=self.env._captured[self.env._cur].cpu(),
+                       termination_reason=self.env._reason[self.env._cur].cpu(),
+                       ply_count=self.env._ply[self.env._cur].cpu().to(torch.int32) & 0xFFFF)    # a uint16 payload
         self.record.append(rec)
 
     def _chunk(self) -> None:
@@ -329,6 +387,8 @@ class MatchArena:
     def _read_state(self) -> np.ndarray:
         if self.collect:                              # same stream: complete when the state copy below returns
             self._cursors_host.copy_(self._cursors, non_blocking=True)
+        if self.features:
+            self._fcursors_host.copy_(self._fcursors, non_blocking=True)
         self._state_host.copy_(self._state)           # the one device -> host read of a sync point
         st = self._state_host.numpy()
         if st[4]:
@@ -350,6 +410,9 @@ class MatchArena:
         env = self.env
         _lib.call("ka_arena_assign", self._state, self._jobs, len(jobs), self.envs_per_match, env._players[env._cur],
                   self._model_of, self._pre, _lib.stream_ptr(self.device))
+        if self.features:                                 # a new tracker per pairing (concurrent_matches.py:125)
+            _lib.call("ka_arena_features_seat", self._jobs, len(jobs), self.num_slots, self.envs_per_match, self._facc,
+                      _lib.stream_ptr(self.device))
 
     def _drain(self, slot_pairing: Dict[int, int], chunks: Dict[int, list], lost: set) -> None:
         """Sync point: move the chunk's rows of every collecting slot out of the store (device to device) and reset the
@@ -364,18 +427,46 @@ class MatchArena:
                 chunks.setdefault(p, []).append({k: t[lo:lo + n].clone() for k, t in self._store.items()})
         self._cursors.zero_()
 
+    def _drain_features(self, slot_pairing: Dict[int, int], games: Dict[int, list], stats: RoundStats) -> None:
+        """Sync point: the chunk's game records of every slot that finished games come to the host (exactly the committed
+        ones, one copy per such slot) and join their pairing's list; the cursors are reset."""
+        cur = self._fcursors_host.numpy().reshape(self.num_slots, self._fcurw)
+        stats.features_dropped += int(cur[:, 1].sum())
+        took = []
+        for s, p in slot_pairing.items():
+            n = int(cur[s, 0])
+            if n:
+                lo = s * self._fcap
+                self._frecords_host[lo:lo + n].copy_(self._frecords[lo:lo + n], non_blocking=True)
+                took.append((p, lo, n))
+        if took:
+            torch.cuda.current_stream(self.device).synchronize()
+            host = self._frecords_host.numpy()
+            for p, lo, n in took:
+                games.setdefault(p, []).append(host[lo:lo + n].copy())
+        if cur.any():
+            self._fcursors.zero_()
+
     def run_round(self, pairings: Sequence[Tuple[int, int]], games_per_match: int = 64, *, max_ply: Optional[int] = None,
-                  trainable: Union[None, Callable[[int, int], int], Mapping[int, int]] = None):
+                  trainable: Union[None, Callable[[int, int], int], Mapping[int, int]] = None,
+                  entry_ids: Union[None, Sequence[int], Mapping[int, int]] = None, epoch: int = 0):
         """Play every pairing ``(a, b)`` (model indices into the group, priority order) for ``games_per_match`` games.
         ``max_ply`` sets the ply ceiling ``max_ply * (ceil(games_per_match / envs_per_match) + 1)`` of a pairing, after
         which it ends with a partial result, as the reference's ``run_round(max_ply=)`` does (default: the env's max_ply).
         ``trainable`` (an arena built with ``collect=True``): a callable ``(a, b) -> bits`` or a mapping pairing index ->
         bits, bit 0 = collect the rows of side A, bit 1 = of side B; those pairings' results carry a ``MatchRollout``.
+        ``entry_ids`` (model index -> league entry id; default: the model index) and ``epoch`` name the rows of the
+        results' ``feature_tracker`` (an arena built with ``features=True``), as the reference's ``run_round(epoch=)``.
         Returns ``(results, stats)``: one MatchResult per pairing, in pairing order, and the round's RoundStats."""
         pairings = _check_round(pairings, games_per_match, len(self.group))
         if trainable is not None and not self.collect:
             raise ValueError("run_round(trainable=) needs an arena built with collect=True")
         bits = _side_bits(trainable, pairings)
+        if entry_ids is not None:
+            missing = sorted({m for pair in pairings for m in pair
+                              if (m not in entry_ids if isinstance(entry_ids, Mapping) else m >= len(entry_ids))})
+            if missing:
+                raise ValueError(f"entry_ids names no id for models {missing}")
         max_ply = self.max_ply if max_ply is None else int(max_ply)
         if max_ply < 1:
             raise ValueError(f"max_ply must be positive, got {max_ply}")
@@ -383,9 +474,9 @@ class MatchArena:
         if not pairings:
             return [], stats
         with torch.cuda.device(self.device), torch.no_grad():
-            return self._run(pairings, int(games_per_match), max_ply, stats, bits)
+            return self._run(pairings, int(games_per_match), max_ply, stats, bits, entry_ids, int(epoch))
 
-    def _run(self, pairings, games_per_match, max_ply, stats, bits):
+    def _run(self, pairings, games_per_match, max_ply, stats, bits, entry_ids=None, epoch=0):
         if self.graph and self._graph is None:
             self._capture()
         t0 = time.monotonic()
@@ -398,10 +489,15 @@ class MatchArena:
         if self.collect:
             self._cursors.zero_()
             self._bits_host.zero_()
+        if self.features:
+            self._fcursors.zero_()
+            _lib.call("ka_arena_features_seat", self._every_slot, self.num_slots, self.num_slots, self.envs_per_match,
+                      self._facc, _lib.stream_ptr(self.device))
         self.env.reset()
         self.record = []
         chunks: Dict[int, list] = {}
         lost: set = set()
+        games: Dict[int, list] = {}
         P = len(pairings)
         slot_pairing: Dict[int, int] = {}
         active: List[int] = []
@@ -423,6 +519,8 @@ class MatchArena:
             slot = st[_HDR:].reshape(self.num_slots, _SLOT)
             if self.collect:
                 self._drain(slot_pairing, chunks, lost)
+            if self.features:
+                self._drain_features(slot_pairing, games, stats)
             jobs = []
             for i in sorted((i for i, s in enumerate(active) if slot[s, 7] & DONE), reverse=True):
                 s = active.pop(i)
@@ -438,6 +536,12 @@ class MatchArena:
                     results[p].rollout = MatchRollout(cat["observations"], cat["actions"], cat["rewards"], cat["dones"],
                                                       None, cat["perspective"], cat["legal_mask_bits"])
                     stats.rollout_rows += int(cat["actions"].shape[0])
+                if self.features:
+                    recs = games.pop(p, [])
+                    recs = np.concatenate(recs) if recs else np.zeros((0, self._frecords.shape[1]), np.int32)
+                    results[p].feature_tracker = GameFeatureTracker.from_records(
+                        recs, _entry_id(entry_ids, ma), _entry_id(entry_ids, mb), epoch, self.envs_per_match)
+                    stats.feature_rows += len(results[p].feature_tracker.completed_rows)
                 if nxt < P:
                     a, b = pairings[nxt]
                     jobs.append((s, a, b, games_per_match))

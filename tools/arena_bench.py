@@ -9,9 +9,11 @@ Both run one round after a warm-up round (kernel loading, graph capture) and rep
 round.  One JSON line per workload.
 
 A config name ending in "c" (g32c, e2c, ...) builds the arena with collect=True and makes every pairing trainable on both
-sides: the worst case of rollout collection, reported with the rows collected.
+sides: the worst case of rollout collection, reported with the rows collected.  An "f" (g32f, and
+g32cf with collection) builds it with features=True, reported with the feature rows and the time the
+host spent draining game records.
 
-    python tools/arena_bench.py [--workload a|b|all] [--configs g2,g32,e2,e32,host,g32c] [--max-ply 512] [--repeat 1]
+    python tools/arena_bench.py [--workload a|b|all] [--configs g2,g32,e2,e32,host,g32c,g32f,g32cf] [--max-ply 512] [--repeat 1]
 """
 from __future__ import annotations
 
@@ -124,18 +126,32 @@ def host_loop_round(group, env, pairings, games, max_ply, E):
             "games": games_total, "games_per_min": round(games_total / dt * 60, 1), "host_syncs": syncs}
 
 
-def arena_round(group, N, E, max_ply, graph, sync_every, pairings, games, collect=False, repeat=1):
-    arena = MatchArena(group, N, E, max_ply, sync_every=sync_every, graph=graph, seed=1234, collect=collect)
+def arena_round(group, N, E, max_ply, graph, sync_every, pairings, games, collect=False, repeat=1, features=False):
+    arena = MatchArena(group, N, E, max_ply, sync_every=sync_every, graph=graph, seed=1234, collect=collect, features=features)
+    drain = [0.0, 0]
+    if features:                                             # time the host side of a sync point: the record drain
+        inner = arena._drain_features
+
+        def timed(*a):
+            t0 = time.perf_counter()
+            inner(*a)
+            drain[0] += time.perf_counter() - t0
+            drain[1] += 1
+
+        arena._drain_features = timed
     kw = {"trainable": (lambda a, b: 3)} if collect else {}
     arena.run_round(pairings[:2], games_per_match=1, **kw)    # warm-up: kernel loading and graph capture
     torch.cuda.synchronize()
     rates = []
     for _ in range(repeat):
+        drain[:] = [0.0, 0]
         results, st = arena.run_round(pairings, games_per_match=games, **kw)
         torch.cuda.synchronize()
         rates.append(round(st.round_plies / st.round_duration_s, 1))
     dt = st.round_duration_s
-    return {"plies_per_s_runs": rates, "rollout_rows": st.rollout_rows, "rollouts_dropped": st.rollouts_dropped,
+    extra = {"feature_rows": st.feature_rows, "features_dropped": st.features_dropped,
+             "drain_us_per_sync": round(drain[0] / max(1, drain[1]) * 1e6, 1)} if features else {}
+    return {**extra, "plies_per_s_runs": rates, "rollout_rows": st.rollout_rows, "rollouts_dropped": st.rollouts_dropped,
             "round_s": round(dt, 3), "round_plies": st.round_plies, "plies_per_s": round(st.round_plies / dt, 1),
             "games": st.total_games, "games_per_min": round(st.total_games / dt * 60, 1), "host_syncs": st.host_syncs,
             "partial": sum(r.partial for r in results),
@@ -164,12 +180,14 @@ def main() -> None:
                 host_loop_round(group, env, pairings[:1], 1, args.max_ply, E)          # warm-up
                 row["host_loop"] = host_loop_round(group, env, pairings, 64, args.max_ply, E)
             else:
-                collect = c.endswith("c")
-                graph, se = CONFIGS[c[:-1] if collect else c]
-                key = f"arena_{'graph' if graph else 'eager'}_sync{se}{'_collect' if collect else ''}"
+                features = c.endswith("f")
+                base = c[:-1] if features else c
+                collect = base.endswith("c")
+                graph, se = CONFIGS[base[:-1] if collect else base]
+                key = f"arena_{'graph' if graph else 'eager'}_sync{se}{'_collect' if collect else ''}{'_features' if features else ''}"
                 while key in row:                                # the same config named twice: alternating runs
                     key += "'"
-                row[key] = arena_round(group, N, E, args.max_ply, graph, se, pairings, 64, collect, args.repeat)
+                row[key] = arena_round(group, N, E, args.max_ply, graph, se, pairings, 64, collect, args.repeat, features)
             torch.cuda.synchronize()
         print(json.dumps(row), flush=True)
         lines.append(row)
