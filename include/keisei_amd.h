@@ -59,6 +59,11 @@ int ka_conv3x3_fwd_keep(const void* in, const void* wpack, void* out, const floa
                         const float* in_bias, int relu, float* bsum, float* sqpart, void* x_out, int B, int Cin, int Cout, int dtype,
                         void* stream);
 int ka_conv3x3_sqpart_rows(int B);
+/* launch counts per dispatch form of ka_conv3x3_* and ka_conv3x3_wgrad into a host array of n counts, in this order: generic
+   kernel, producer / consumer kernel, two-board kernel at 128 channels, two-board kernel at 256 channels with square 80 inside,
+   two-board kernel at 256 channels with the corner launch behind it, corner launch, lean weight gradient, tiled weight
+   gradient.  Host-side counters: tests check that a case reached the route it claims to cover. */
+int ka_conv_route_counts(long long* out, int n);
 /* Data-gradient convolution with the surrounding BatchNorm-backward passes fused in (bf16): the input is
  * dy = in*k[0:C] + k[C:2C] + in2*k[2C:3C] (= ka_bn_bwd_apply on the fly, also written to dy_out for the weight-gradient
  * kernel); with ep_y the output is masked by the ReLU of the preceding BatchNorm, out = conv(dy)*[ep_scale*ep_y+ep_shift>0],

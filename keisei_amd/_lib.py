@@ -24,6 +24,7 @@ _SIGS = {
     "ka_conv3x3_dgrad_gated_supported": "iiiii",
     "ka_conv3x3_dgrad_fused_gated": "pppppp pp ppppp pp iii i p",
     "ka_conv3x3_sqpart_rows": "i",
+    "ka_conv_route_counts": "p i",
     "ka_debug_conv_stamps": "p",
     "ka_pack_conv3x3": "pp iiii i i p",
     "ka_pack_conv3x3_multi": "p i q i p",

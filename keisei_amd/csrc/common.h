@@ -80,6 +80,21 @@ inline int ka_opt(KaOpt o, int dflt) { const KaOptVal v = ka_opts()[o]; return v
 // main loop, 3 / 4: s_memrealtime there); null in production -- no stamp executes
 std::atomic<unsigned long long*>& ka_debug_stamps();         // capi.hip
 
+// Launch counts per dispatch form of the 3x3 convolutions and their weight gradient, read by ka_conv_route_counts: the tests see
+// from these which kernel a (shape, batch, switch) combination reached.  Host-side, one relaxed increment per dispatch.
+enum KaConvRoute {
+    KA_RT_CONV,            // conv3x3_kernel (the generic form)
+    KA_RT_PC,              // conv3x3_pc_kernel
+    KA_RT_PC2,             // conv3x3_pc2_kernel, 128 channels (all 81 squares: no corner)
+    KA_RT_PC2_CORNER_IN,   // conv3x3_pc2_kernel, 256 channels, square 80 as a sixth tile inside
+    KA_RT_PC2_CORNER_OUT,  // conv3x3_pc2_kernel, 256 channels, square 80 left to the corner launch behind it
+    KA_RT_CORNER,          // conv3x3_corner_kernel
+    KA_RT_WGRAD_LEAN,      // wgrad_flat_kernel
+    KA_RT_WGRAD_TILED,     // wgrad_kernel
+    KA_RT_COUNT
+};
+void ka_conv_route(int r);                                   // conv3x3.hip
+
 // ---- scalar conversions -----------------------------------------------------
 __device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
 // Plain cast: hipcc emits v_cvt_pk_bf16_f32 (RNE, NaN stays NaN) on gfx950.

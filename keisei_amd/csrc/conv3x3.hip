@@ -33,6 +33,9 @@
 #include <utility>
 #include "common.h"
 
+static std::atomic<long long> g_conv_routes[KA_RT_COUNT];
+void ka_conv_route(int r) { g_conv_routes[r].fetch_add(1, std::memory_order_relaxed); }
+
 namespace {
 
 constexpr int kNB = 2;                       // boards per workgroup in the paired layout
@@ -587,6 +590,7 @@ int launch_conv(const ConvArgs& a, hipStream_t st) {
     const size_t lds = (size_t)((WM == 2 ? kLdsSquares : kImgSquares1) + kZeroSquares) * (a.KC * E::kSize + 32);
     KA_REQUIRE(lds <= 160 * 1024, "conv3x3: LDS tile %zu B exceeds 160 KiB (KC=%d)", lds, a.KC);
     dim3 grid((a.B + WM - 1) / WM, (a.Cout + BN - 1) / BN);
+    ka_conv_route(KA_RT_CONV);
     if constexpr (sizeof(T) == 2 && NTW == 4 && WM == 1) {
         if (a.mt5) {
             static std::atomic<unsigned long long> attr5{0};
@@ -941,6 +945,7 @@ static int launch_conv_pc(ConvArgs a, hipStream_t st) {
     a.tune_stagger = 0; a.tune_prio = 0;                       // diagnostics: KA_CONV_P_ABL 1 no epilogue, 2 no staging after the first unit
     if (const char* e = ka_diag_env("KA_CONV_P_ABL")) a.tune_stagger = atoi(e);
     a.tune_prio = ka_opt(KA_OPT_CONV_P_PRIO, 0);
+    ka_conv_route(KA_RT_PC);
     int grid = 256;
     if (const int v = ka_opt(KA_OPT_CONV_P_WGS, 0); v > 0) grid = v;
     if (grid > a.B) grid = a.B;
@@ -1611,7 +1616,8 @@ static int launch_conv_pc2_form(const ConvArgs& a, hipStream_t st, const char* w
     return ka_check_launch(what);
 }
 static int launch_conv_pc2(const ConvArgs& a, hipStream_t st) {
-    if (a.in2 && a.in_bias) {                                  // conv2's data gradient taking (du, gate, add) for dz: ka_conv3x3_dgrad_fused_gated
+    ka_conv_route(a.Cin == 128 ? KA_RT_PC2 : (a.mt5 == 2 ? KA_RT_PC2_CORNER_IN : KA_RT_PC2_CORNER_OUT));
+    if (a.in2 && a.in_bias) {                                // conv2's data gradient taking (du, gate, add) for dz: ka_conv3x3_dgrad_fused_gated
         KA_REQUIRE(a.in2 && a.ep_y, "conv3x3: the gated input comes with the two-tensor transform and the masked epilogue");
         if (a.Cin == 128) return launch_conv_pc2_form<128, 6, true, true, 4, false, false, true>(a, st, "conv3x3 (two boards per unit, 128 channels, gated two-tensor, masked)");
         return launch_conv_pc2_form<256, 5, true, true, 4, false, false, true>(a, st, "conv3x3 (two boards per unit, gated two-tensor, masked)");
@@ -1798,6 +1804,7 @@ __global__ __launch_bounds__(512) void conv3x3_corner_kernel(ConvArgs a) {
 }
 static int launch_conv_corner(const ConvArgs& a, hipStream_t st) {
     static std::atomic<unsigned long long> done{0};
+    ka_conv_route(KA_RT_CORNER);
     if (int rc = ka_big_lds_once(reinterpret_cast<const void*>(&conv3x3_corner_kernel), done, "conv3x3 (corner)")) return rc;
     hipLaunchKernelGGL(conv3x3_corner_kernel, dim3((a.B + kCornerBoards - 1) / kCornerBoards, 2), dim3(512), kCornerLds, st, a);
     return ka_check_launch("conv3x3 (corner)");
@@ -1981,6 +1988,12 @@ extern "C" int ka_conv3x3_dgrad_fused_gated(const void* du, const float* gate_ad
 extern "C" int ka_debug_conv_stamps(unsigned long long* stamps) { g_stamps.store(stamps); return KA_OK; }
 
 extern "C" int ka_conv3x3_sqpart_rows(int B) { return B; }
+
+extern "C" int ka_conv_route_counts(long long* out, int n) {
+    KA_REQUIRE(out && n >= 0, "conv_route_counts: bad arguments");
+    for (int i = 0; i < n && i < KA_RT_COUNT; ++i) out[i] = g_conv_routes[i].load(std::memory_order_relaxed);
+    return KA_OK;
+}
 
 extern "C" int ka_pack_conv3x3(const float* w, void* dst, int Co, int Ci, int Nout, int Kin, int mode, int dtype,
                                void* stream) {

@@ -738,7 +738,9 @@ extern "C" int ka_conv3x3_wgrad(const void* dy, const void* x, const float* in_s
 #define KA_WG(T_, TN_) (fused ? launch_wgrad<T_, TN_, true>(a, grid, st) : launch_wgrad<T_, TN_, false>(a, grid, st))
     // (the lean kernel addresses a tensor through a 32-bit buffer descriptor with the board as a signed scalar offset)
     const bool fits32 = (unsigned long long)B * KA_BOARD * 2 * (unsigned long long)(Cin > Cout ? Cin : Cout) < 0x7fffffffull;
-    if (dtype == KA_DTYPE_BF16 && tn == 128 && fits32 && ka_opt(KA_OPT_WGRAD_LEAN, 1) != 0)
+    const bool lean = dtype == KA_DTYPE_BF16 && tn == 128 && fits32 && ka_opt(KA_OPT_WGRAD_LEAN, 1) != 0;
+    ka_conv_route(lean ? KA_RT_WGRAD_LEAN : KA_RT_WGRAD_TILED);
+    if (lean)
         rc = fused ? launch_wgrad_flat<true>(a, grid, st) : launch_wgrad_flat<false>(a, grid, st);
     else if (dtype == KA_DTYPE_BF16) rc = tn == 64 ? KA_WG(bf16_t, 64) : KA_WG(bf16_t, 128);
     else if (dtype == KA_DTYPE_F32) rc = tn == 64 ? KA_WG(float, 64) : KA_WG(float, 128);

@@ -232,13 +232,82 @@ def closed_form_fill(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return out
 
 
-def global_pool(x: torch.Tensor) -> torch.Tensor:
+class _Hooks:
+    """Decision hooks of seresnet_forward / block_forward / global_pool (all off by default) and the bf16-storage switch.
+
+    relu_inputs (a list) receives every ReLU input in call order -- stem; per block: bn1, global_fc hidden, se_fc1 hidden,
+    block output; policy_bn1; value_fc1; score_fc1 -- and relu_masks (as many tensors) turns the k-th ReLU into x * mask:
+    the decisions of another implementation, for inputs within its rounding of zero.  pool_inputs receives the (B, C, 81)
+    tensor every global_pool sees (per block, then the heads' pool); pool_winners (as many boolean (B, C, 81) sets) turns
+    the maximum into (flat * w).sum(2) / w.sum(2): amax with its gradient shared equally over the set, torch's own rule
+    for exact ties and the kernels' (board.hip: "ties share the gradient equally")."""
+
+    def __init__(self, relu_inputs=None, relu_masks=None, pool_inputs=None, pool_winners=None, bf16_storage=False, rounding=True):
+        self.relu_inputs, self.relu_masks = relu_inputs, relu_masks
+        self.pool_inputs, self.pool_winners = pool_inputs, pool_winners
+        self.bf16_storage, self.rounding = bf16_storage, rounding
+        self.k_relu = self.k_pool = 0
+
+    def relu(self, x):
+        k = self.k_relu
+        self.k_relu += 1
+        if self.relu_inputs is not None:
+            self.relu_inputs.append(x.detach())
+        if self.relu_masks is not None:
+            return x * self.relu_masks[k].reshape(x.shape).to(x.dtype)
+        return torch.relu(x)
+
+    def q(self, t):
+        """round to bf16 and back where the HIP bf16 mode stores bf16 (identity unless bf16_storage with rounding)"""
+        if self.bf16_storage and self.rounding:
+            return t.to(torch.bfloat16).to(t.dtype)
+        return t
+
+
+def global_pool(x: torch.Tensor, hooks: Optional[_Hooks] = None) -> torch.Tensor:
     """(B,C,H,W) -> (B,3C) = [mean | max | population std].  se_resnet.py:93-98."""
     flat = x.flatten(2)
     mu = flat.mean(dim=2)
-    mx = flat.amax(dim=2)
+    k = -1
+    if hooks is not None:
+        k = hooks.k_pool
+        hooks.k_pool += 1
+        if hooks.pool_inputs is not None:
+            hooks.pool_inputs.append(flat.detach())
+    if hooks is not None and hooks.pool_winners is not None:
+        w = hooks.pool_winners[k].reshape(flat.shape).to(flat.dtype)
+        mx = (flat * w).sum(dim=2) / w.sum(dim=2)
+    else:
+        mx = flat.amax(dim=2)
     sd = flat.std(dim=2, correction=0)
     return torch.cat((mu, mx, sd), dim=1)
+
+
+def _conv(x, w, bias=None, padding=0):
+    """F.conv2d(x, w, bias, padding=padding) for the 3x3 (padding 1) and 1x1 convolutions of the model.  On the CPU it is
+    that call.  On a GPU the same sums are taken as ONE matrix product over the gathered taps: the vendor convolution
+    library has no float64 kernels and compiles its kernels per shape on first use, a plain GEMM has neither problem
+    (under autocast the product is the autocast type's, as the convolution would be)."""
+    if not x.is_cuda:
+        return F.conv2d(x, w, bias, padding=padding)
+    return _conv_gemm(x, w, bias, padding)
+
+
+def _conv_gemm(x, w, bias=None, padding=0):
+    """the GPU form of _conv (device-independent: tests/test_seresnet_oracle_cpu.py holds it to F.conv2d on the CPU)"""
+    O, C, kh, kw = w.shape
+    xn = x.permute(0, 2, 3, 1)                                   # (B, 9, 9, C)
+    if kh == 1:
+        cols, wm = xn, w.reshape(O, C)
+    else:
+        xp = F.pad(xn, (0, 0, padding, padding, padding, padding))
+        H, W = x.shape[2], x.shape[3]
+        cols = torch.cat([xp[:, i:i + H, j:j + W, :] for i in range(kh) for j in range(kw)], dim=3)      # (B, 9, 9, 9 C), taps major
+        wm = w.permute(0, 2, 3, 1).reshape(O, kh * kw * C)
+    out = cols @ wm.T
+    if bias is not None:
+        out = out + bias
+    return out.permute(0, 3, 1, 2)
 
 
 def _bn(x, sd, prefix, train, momentum, update_running):
@@ -252,47 +321,94 @@ def _bn(x, sd, prefix, train, momentum, update_running):
     return y
 
 
+def _bn_storage(y, sd, prefix, train, q):
+    """BatchNorm of the bf16-storage emulation: the statistics come from the unrounded convolution result (the conv
+    epilogue's fp32 sums), the affine map is applied to the stored (rounded) tensor.  Returns (z, scale, shift)."""
+    if train:
+        mu, var = y.mean(dim=(0, 2, 3)), y.var(dim=(0, 2, 3), unbiased=False)
+    else:
+        mu, var = sd[prefix + ".running_mean"], sd[prefix + ".running_var"]
+    sc = sd[prefix + ".weight"] / torch.sqrt(var + BN_EPS)
+    sh = sd[prefix + ".bias"] - mu * sc
+    return q(y) * sc[None, :, None, None] + sh[None, :, None, None], sc, sh
+
+
 def block_forward(sd, prefix: str, x: torch.Tensor, train: bool,
-                  momentum: float = 0.1, update_running: bool = False) -> torch.Tensor:
-    """One GlobalPoolBiasBlock (se_resnet.py:68-90), functional."""
+                  momentum: float = 0.1, update_running: bool = False, hooks: Optional[_Hooks] = None) -> torch.Tensor:
+    """One GlobalPoolBiasBlock (se_resnet.py:68-90), functional.  `hooks`: see _Hooks (None = all off)."""
+    hk = hooks if hooks is not None else _Hooks()
+    q = hk.q
     C = x.shape[1]
-    h = F.conv2d(x, sd[prefix + "conv1.weight"], padding=1)
-    h = torch.relu(_bn(h, sd, prefix + "bn1", train, momentum, update_running))
-    g = global_pool(x)
-    g = torch.relu(F.linear(g, sd[prefix + "global_fc.0.weight"], sd[prefix + "global_fc.0.bias"]))
+    y1 = _conv(x, q(sd[prefix + "conv1.weight"]), padding=1)
+    if hk.bf16_storage:
+        h = hk.relu(_bn_storage(y1, sd, prefix + "bn1", train, q)[0])
+    else:
+        h = hk.relu(_bn(y1, sd, prefix + "bn1", train, momentum, update_running))
+    g = global_pool(x, hooks)
+    g = hk.relu(F.linear(g, sd[prefix + "global_fc.0.weight"], sd[prefix + "global_fc.0.bias"]))
     g = F.linear(g, sd[prefix + "global_fc.2.weight"], sd[prefix + "global_fc.2.bias"])
-    h = h + g[:, :, None, None]
-    z = _bn(F.conv2d(h, sd[prefix + "conv2.weight"], padding=1), sd, prefix + "bn2",
-            train, momentum, update_running)
-    sq = z.flatten(2).mean(dim=2)
-    e = torch.relu(F.linear(sq, sd[prefix + "se_fc1.weight"], sd[prefix + "se_fc1.bias"]))
+    h = q(h + g[:, :, None, None])
+    y2 = _conv(h, q(sd[prefix + "conv2.weight"]), padding=1)
+    if hk.bf16_storage:
+        z, sc2, sh2 = _bn_storage(y2, sd, prefix + "bn2", train, q)
+        sq = sc2 * y2.mean(dim=(2, 3)) + sh2                  # the squeeze comes from the conv epilogue's unrounded board sums
+    else:
+        z = _bn(y2, sd, prefix + "bn2", train, momentum, update_running)
+        sq = z.flatten(2).mean(dim=2)
+    e = hk.relu(F.linear(sq, sd[prefix + "se_fc1.weight"], sd[prefix + "se_fc1.bias"]))
     e = F.linear(e, sd[prefix + "se_fc2.weight"], sd[prefix + "se_fc2.bias"])
     gate, shift = e[:, :C], e[:, C:]
     u = z * torch.sigmoid(gate)[:, :, None, None] + shift[:, :, None, None]
-    return torch.relu(u + x)
+    return q(hk.relu(u + x))
 
 
 def seresnet_forward(sd, obs: torch.Tensor, num_blocks: int, train: bool,
-                     momentum: float = 0.1, update_running: bool = False):
-    """SEResNetModel._forward_impl (se_resnet.py:132-159).
+                     momentum: float = 0.1, update_running: bool = False, *, relu_inputs: Optional[list] = None,
+                     relu_masks=None, pool_inputs: Optional[list] = None, pool_winners=None,
+                     bf16_storage: bool = False, rounding: bool = True):
+    """SEResNetModel._forward_impl (se_resnet.py:132-159), in the dtype of `sd` and on its device.
 
     Returns (policy_logits (B,9,9,139), value_logits (B,3), score_lead (B,1)).
-    """
+
+    relu_inputs / relu_masks / pool_inputs / pool_winners: the decision hooks of _Hooks; with all of them off (the
+    default) the result is bit-identical to the plain forward.
+
+    bf16_storage=True is the emulation of the HIP bf16 mode: the working precision everywhere, with a rounding to bf16
+    exactly where that mode stores bf16 (hip/seresnet.py) -- the observation, the 3x3 convolution weights, the
+    convolution outputs y0 / y1 / y2 as read back by the next kernel, the fused relu(bn1(.)) + g input of conv2 and
+    every block's output; BatchNorm statistics and the squeeze come from the unrounded convolution results, as in the
+    conv epilogue; the FC layers, the policy head's 1x1 convolutions and the pooled statistics stay in the working
+    precision.  rounding=False keeps that code path and switches the roundings off (it then equals the plain forward
+    up to the working precision).  The emulation does not update running statistics."""
     c_in = sd["input_conv.weight"].shape[1]
     if obs.ndim != 4 or tuple(obs.shape[1:]) != (c_in, 9, 9):
         raise ValueError(f"Expected obs shape (batch, {c_in}, 9, 9), got {tuple(obs.shape)}")
-    x = F.conv2d(obs, sd["input_conv.weight"], padding=1)
-    x = torch.relu(_bn(x, sd, "input_bn", train, momentum, update_running))
+    hooked = (relu_inputs is not None or relu_masks is not None or pool_inputs is not None or pool_winners is not None
+              or bf16_storage)
+    hk = _Hooks(relu_inputs, relu_masks, pool_inputs, pool_winners, bf16_storage, rounding)
+    hooks = hk if hooked else None
+    q = hk.q
+    if bf16_storage:
+        if update_running:
+            raise ValueError("the bf16-storage emulation does not update running statistics")
+        y0 = _conv(q(obs), q(sd["input_conv.weight"]), padding=1)
+        x = q(hk.relu(_bn_storage(y0, sd, "input_bn", train, q)[0]))
+    else:
+        x = _conv(obs, sd["input_conv.weight"], padding=1)
+        x = hk.relu(_bn(x, sd, "input_bn", train, momentum, update_running))
     for i in range(num_blocks):
-        x = block_forward(sd, f"blocks.{i}.", x, train, momentum, update_running)
-    p = F.conv2d(x, sd["policy_conv1.weight"])
-    p = torch.relu(_bn(p, sd, "policy_bn1", train, momentum, update_running))
-    p = F.conv2d(p, sd["policy_conv2.weight"], sd["policy_conv2.bias"])
+        x = block_forward(sd, f"blocks.{i}.", x, train, momentum, update_running, hooks)
+    p = _conv(x, sd["policy_conv1.weight"])
+    if bf16_storage:
+        p = hk.relu(_bn_storage(p, sd, "policy_bn1", train, lambda t: t)[0])          # (p1 is an fp32 tensor in the engine)
+    else:
+        p = hk.relu(_bn(p, sd, "policy_bn1", train, momentum, update_running))
+    p = _conv(p, sd["policy_conv2.weight"], sd["policy_conv2.bias"])
     policy = p.permute(0, 2, 3, 1)
-    pool = global_pool(x)
-    v = torch.relu(F.linear(pool, sd["value_fc1.weight"], sd["value_fc1.bias"]))
+    pool = global_pool(x, hooks)
+    v = hk.relu(F.linear(pool, sd["value_fc1.weight"], sd["value_fc1.bias"]))
     v = F.linear(v, sd["value_fc2.weight"], sd["value_fc2.bias"])
-    s = torch.relu(F.linear(pool, sd["score_fc1.weight"], sd["score_fc1.bias"]))
+    s = hk.relu(F.linear(pool, sd["score_fc1.weight"], sd["score_fc1.bias"]))
     s = F.linear(s, sd["score_fc2.weight"], sd["score_fc2.bias"])
     return policy, v, s
 
@@ -301,67 +417,26 @@ def relu_margin(sd, obs: torch.Tensor, num_blocks: int) -> float:
     """Smallest non-zero |ReLU input| of a train-mode fp64 forward: how far the batch is from a ReLU knife edge.  Two
     fp32 implementations agree on every ReLU mask (and hence on gradients to ~1e-6) when this is well above their
     rounding noise (~1e-6 for O(1) activations); fixtures and smoke() pick their batch by it."""
-    seen = {"min": float("inf")}
-    real = torch.relu
-
-    def rec(x):
-        a = x.detach().abs()
+    taps: list = []
+    sd64 = {k: (v.double() if v.dtype.is_floating_point else v.clone()) for k, v in sd.items()}
+    with torch.no_grad():
+        seresnet_forward(sd64, obs.double(), num_blocks, train=True, momentum=0.0, relu_inputs=taps)
+    low = float("inf")
+    for a in taps:
+        a = a.abs()
         a = a[a > 0]
         if a.numel():
-            seen["min"] = min(seen["min"], float(a.min()))
-        return real(x)
-
-    sd64 = {k: (v.double() if v.dtype.is_floating_point else v.clone()) for k, v in sd.items()}
-    torch.relu = rec
-    try:
-        with torch.no_grad():
-            seresnet_forward(sd64, obs.double(), num_blocks, train=True, momentum=0.0)
-    finally:
-        torch.relu = real
-    return seen["min"]
+            low = min(low, float(a.min()))
+    return low
 
 
 def seresnet_policy_bf16_storage(sd, obs: torch.Tensor, num_blocks: int, train: bool) -> torch.Tensor:
-    """fp32 math with bf16 rounding at exactly the points where the HIP bf16 mode stores bf16
-    (conv operands, y1/y2/out activations, the fused relu(bn1)+g conv2 input); BN statistics come
-    from the unrounded conv results, as in the conv epilogue.  This DEFINES the bf16 mode's stated
-    numerics: tests hold the HIP bf16 path to a few bf16 ulps of this emulation, and report the
-    (inherent, input-dependent) distance of both from the fp32 reference side by side."""
-    def q(t):
-        return t.bfloat16().float()
-
-    def coeffs(y, pre):
-        if train:
-            mu, var = y.mean(dim=(0, 2, 3)), y.var(dim=(0, 2, 3), unbiased=False)
-        else:
-            mu, var = sd[pre + ".running_mean"], sd[pre + ".running_var"]
-        sc = sd[pre + ".weight"] / torch.sqrt(var + BN_EPS)
-        return sc, sd[pre + ".bias"] - mu * sc
-
-    def aff(y, sc, sh):
-        return y * sc[None, :, None, None] + sh[None, :, None, None]
-
-    y0 = F.conv2d(q(obs), q(sd["input_conv.weight"]), padding=1)
-    sc, sh = coeffs(y0, "input_bn")
-    x = q(torch.relu(aff(q(y0), sc, sh)))
-    for i in range(num_blocks):
-        pre = f"blocks.{i}."
-        C = x.shape[1]
-        y1 = F.conv2d(x, q(sd[pre + "conv1.weight"]), padding=1)
-        sc1, sh1 = coeffs(y1, pre + "bn1")
-        g = torch.relu(F.linear(global_pool(x), sd[pre + "global_fc.0.weight"], sd[pre + "global_fc.0.bias"]))
-        g = F.linear(g, sd[pre + "global_fc.2.weight"], sd[pre + "global_fc.2.bias"])
-        h = q(torch.relu(aff(q(y1), sc1, sh1)) + g[:, :, None, None])
-        y2 = F.conv2d(h, q(sd[pre + "conv2.weight"]), padding=1)
-        sc2, sh2 = coeffs(y2, pre + "bn2")
-        sqz = sc2 * y2.mean(dim=(2, 3)) + sh2
-        e = torch.relu(F.linear(sqz, sd[pre + "se_fc1.weight"], sd[pre + "se_fc1.bias"]))
-        e = F.linear(e, sd[pre + "se_fc2.weight"], sd[pre + "se_fc2.bias"])
-        x = q(torch.relu(aff(q(y2), sc2, sh2) * torch.sigmoid(e[:, :C])[:, :, None, None] + e[:, C:, None, None] + x))
-    p1 = F.conv2d(x, sd["policy_conv1.weight"])
-    scp, shp = coeffs(p1, "policy_bn1")
-    p = F.conv2d(torch.relu(aff(p1, scp, shp)), sd["policy_conv2.weight"], sd["policy_conv2.bias"])
-    return p.permute(0, 2, 3, 1)
+    """Policy logits of the bf16-storage emulation, seresnet_forward(..., bf16_storage=True): the working precision of
+    `sd` with bf16 rounding at exactly the points where the HIP bf16 mode stores bf16.  This DEFINES the bf16 mode's
+    stated numerics.  tests/test_hip_seresnet_batch.py holds the engine's bf16 forward to it at training batch sizes (the
+    engine must be nearer to the emulation than the emulation is to fp64); tests/test_seresnet_oracle_cpu.py pins the
+    emulation itself (rounding off = the plain forward; rounding on = within the stated bf16 bounds of the fp32 fixture)."""
+    return seresnet_forward(sd, obs, num_blocks, train, momentum=0.0, bf16_storage=True)[0]
 
 
 # --------------------------------------------------------------------------- transformer
