@@ -505,6 +505,49 @@ int ka_arena_features_seat(const int* jobs, int njobs, int slots, int envs_per_s
  * where dones[i] != 0, else -1; adv[i] = rewards[i] * dones[i]. */
 int ka_dynamic_targets(const float* rewards, const float* dones, long long* cats, float* adv, long long n, void* stream);
 
+/* ---- league rollout (csrc/league.hip; katago_loop.py:1162-1437 the opponent branch of the rollout loop, :1537-1563 the
+ * flush at the end of an epoch).  E envs; the learner is model 0 of the group, opponent k (0 <= k < K) model k + 1.
+ * state: ka_league_state_words K int32 = {0-1 sampler seed int64, 2 plies, 3 rows written behind the descriptor's base row,
+ *   4 non-empty blocks (the reference's add() calls), 5 rows dropped, 6-7 sampler flags, 8-9 refusal latch copy int64,
+ *   10-11 draw seed int64, 12 truncation slots used, 13 truncation records dropped, 14-20 wins / losses / draws (learner
+ *   frame) / black wins / white wins / terminated / truncated-only, 21-24 the four guards of ka_rollout_append over the rows
+ *   written, 25 a pending slot opened while taken, 26 zero-legal bits (1 learner row, 2 opponent row), 27-31 unused,
+ *   then K x {wins, losses, draws}}.
+ * ka_league_layout gives the other sizes: which 0 = int32 words of one env's plan, 1 = int64 words of the descriptor,
+ *   2 = int32 columns of the pending scalars {action, log-prob, value, reward, score target, valid} (each E words, column
+ *   major), 3 = int32 words of one truncation record {env, store row, player to move | learner side << 1}, 4 = largest E.
+ * desc: {observations, legal mask bits, actions, log_probs, values, rewards, dones u8, terminated u8, value_categories,
+ *   score_targets, env_ids, next_value_override} column base pointers of the rollout store, the base row and the number of
+ *   rows reserved behind it.  It is read on the device by every launch, so a captured graph survives a store that grows:
+ *   the host rewrites it at its sync points.
+ * ka_league_step, after ka_shogi_env_step, with flush = 0: one ply's bookkeeping in the reference's order --
+ *   (1) learner-frame rewards: the reward of a ply the opponent moved is negated (to_learner_perspective, :111-122), and the
+ *   tallies of :1219-1248; (2) rewards accumulate into the pending slots and the slots with valid & (done | learner to move
+ *   next) settle (:1290-1316) as rows of the store in env order, labelled by _compute_value_cats (:75-92); (3) a slot opens
+ *   where the learner moved (:1319-1341): pre-step observation and packed mask, action, log-prob, value P(W) - P(L) blended
+ *   with clamp(score_lead, -1, 1) by alpha as ka_policy_sample does, reward, score target material / score_norm; (4) where
+ *   that move ended the game it settles at once, a second block of rows behind the first (:1343-1365); (5) terminated games
+ *   count for the opponent that played them (:1384-1407); (6) every done env draws its next opponent and (7), with
+ *   color_rand, its next learner side (:1409-1437); (8) model_of of the next ply.  Rows of truncated, unterminated games
+ *   (:1250-1283) put the env's terminal observation into a truncation slot with a record; the host computes the bootstrap
+ *   override there.  Rows beyond the reserved capacity are not written and are counted.  values[e] = the learner's value
+ *   where it moved, else 0.  stall (E) u8 latches the zero-legal bits per env.  No atomics: rows are ranked by ballot scans.
+ *   flush = 1 (:1537-1563): every pending slot settles with done = terminated = 0, label -1; the step's tensors are unused.
+ * Draws: mix = the splitmix64 finaliser x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;
+ *   x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31.  h(salt, env, n) = mix(draw_seed ^ mix((env << 32 | n) + salt)), n = the
+ *   games that env has finished since the reset, this one included.  opponent = the first k with
+ *   h(0x6F70706F, env, n) >> 33 < cum[k] (K uint32 thresholds of the cumulative weights on a 31-bit scale, the last one
+ *   2^31); side = h(0x73696465, env, n) >> 63. */
+int ka_league_state_words(int opponents);
+int ka_league_layout(int which);
+int ka_league_step(int* state, int envs, int opponents, int flush, const float* obs, const void* mask_bits,
+                   const long long* actions, const float* logp, const float* vlogits, const float* score_lead, float alpha,
+                   const int* nlegal, const void* pre_player, const float* rewards, const void* terminated,
+                   const void* truncated, const void* players, const int* material, float score_norm, const float* term_obs,
+                   const long long* refusal, void* side, int* opp, int* games, const void* cum, int color_rand,
+                   int* model_of, void* stall, float* values, float* p_obs, void* p_bits, int* p_scal, float* t_obs,
+                   int* t_list, const long long* desc, int* plan, int obs_elems, int mask_words, void* stream);
+
 /* ---- transformer encoder path (BASELINE config 5; keisei/training/models/transformer.py:37-95: nn.Linear(50, d),
  * row/col nn.Embedding, nn.TransformerEncoder(nn.TransformerEncoderLayer(d, nhead, 4d, batch_first, norm_first), L),
  * nn.Linear(81 d, 11259), value head).  Tokens are (B*81, d) row-major, bf16 (autocast) or fp32 (parity mode; its linear

@@ -113,6 +113,9 @@ _SIGS = {
     "ka_arena_features_step": "p ii ppp ppp ppp ppp i p",
     "ka_arena_features_seat": "p iii p p",
     "ka_dynamic_targets": "pppp q p",
+    "ka_league_state_words": "i",
+    "ka_league_layout": "i",
+    "ka_league_step": "p iii pppppp f ppppppp f pp pppp i ppp ppp pp pp ii p",
     "ka_tf_gemm_nt": "ppppp iii iii iii f q p",
     "ka_tf_gemm_nt_slabs": "ii",
     "ka_tf_gemm_nt_masked": "pppp iii iii f q p",

@@ -33,24 +33,6 @@ __device__ __forceinline__ int block_sum_int(int v, int* red) {
     return r;
 }
 
-// Ranks of the flagged threads of one 256-thread tile, in thread order, behind the `running` flagged threads of the tiles
-// before it: *rank = running + (flagged threads below this one), -1 for a thread that is not flagged.  Returns the tile's
-// count.  One ballot per wave and a sum over the four waves: no atomics, so the order is the thread order.
-__device__ __forceinline__ int tile_rank(bool want, int running, int* wsum, int* rank) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long b = __ballot(want);
-    __syncthreads();                                           // the tile before has read wsum
-    if (lane == 0) wsum[wave] = __popcll(b);
-    __syncthreads();
-    int off = running, tot = 0;
-    for (int w = 0; w < kArenaThreads / 64; ++w) {
-        if (w < wave) off += wsum[w];
-        tot += wsum[w];
-    }
-    *rank = want ? off + __popcll(b & ((1ull << lane) - 1ull)) : -1;
-    return tot;
-}
-
 struct RefereeArgs {
     int* state; int E;
     const float* rewards; const uint8_t* terminated; const uint8_t* truncated; const uint8_t* players;
@@ -188,7 +170,7 @@ __global__ __launch_bounds__(kArenaThreads) void arena_record_pre_kernel(RecordP
         const int k = base + tid;
         const bool want = k < a.E && ((bits >> (a.pre_player[e0 + k] & 1)) & 1);
         int rank;
-        const int tot = tile_rank(want, running, wsum, &rank);
+        const int tot = ka_tile_rank(want, running, wsum, &rank);
         if (k < a.E) s_rank[k] = rank;
         running += tot;
     }
@@ -327,7 +309,7 @@ __global__ __launch_bounds__(kArenaThreads) void arena_features_kernel(FeaturesA
             if (done && a.reason[e] == kReasonRepetition) acc[1] += 1;      // :278-280
         }
         int rank;
-        running += tile_rank(done, running, wsum, &rank);
+        running += ka_tile_rank(done, running, wsum, &rank);
         if (done) {                                             // :286-356: one record per game, then a fresh accumulator
             if (rank < room) {
                 int* rec = a.records + ((size_t)s * a.cap + first + rank) * kRecWords;

@@ -172,3 +172,22 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 #define KA_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// Ranks of the flagged threads of one 256-thread tile, in thread order, behind the `running` flagged threads of the tiles
+// before it: *rank = running + (flagged threads below this one), -1 for a thread that is not flagged.  Returns the tile's
+// count.  One ballot per wave and a sum over the four waves (wsum: 4 ints of LDS): no atomics, so the order is the thread
+// order.  Every thread of the workgroup calls it.  Shared by the arena's record_pre / features_step and the league's plan.
+__device__ __forceinline__ int ka_tile_rank(bool want, int running, int* wsum, int* rank) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long b = __ballot(want);
+    __syncthreads();                                           // the tile before has read wsum
+    if (lane == 0) wsum[wave] = __popcll(b);
+    __syncthreads();
+    int off = running, tot = 0;
+    for (int w = 0; w < 4; ++w) {
+        if (w < wave) off += wsum[w];
+        tot += wsum[w];
+    }
+    *rank = want ? off + __popcll(b & ((1ull << lane) - 1ull)) : -1;
+    return tot;
+}

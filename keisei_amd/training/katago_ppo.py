@@ -295,6 +295,33 @@ class KataGoRolloutBuffer:
         self._write_offset = hi
         self._step_count += 1
 
+    # ---- rows written by a kernel (LeagueRollout): reserve room, let the kernel write behind _write_offset, commit
+    def reserve(self, rows: int, device: torch.device | str | None = None) -> dict[str, torch.Tensor]:
+        """Make room for ``rows`` more rows behind the ones written so far and return every column of the device store
+        (``env_ids`` and ``next_value_override`` included; the tensors change when the store grows, so ask again after
+        every ``reserve``).  A writer fills rows ``[_write_offset, _write_offset + rows)`` itself and then calls
+        ``commit``; nothing is appended here."""
+        if self._device is None:
+            if device is None:
+                raise ValueError("reserve() on an empty buffer needs the device of its columns")
+            self._device = torch.device(device)
+        if not self.is_device_resident:
+            raise ValueError("reserve() serves the device-resident store (the host store is written by add())")
+        if rows < 0:
+            raise ValueError(f"rows must not be negative, got {rows}")
+        self._has_env_ids = self._has_next_value_override = True
+        self._ensure_capacity(rows)
+        for key in (*_FIELDS, "env_ids", "next_value_override"):
+            self._column(key)
+        return dict(self._storage)
+
+    def commit(self, rows: int, steps: int) -> None:
+        """Count ``rows`` rows written behind ``_write_offset`` (inside the last ``reserve``) as ``steps`` add() calls."""
+        if rows < 0 or steps < 0 or self._write_offset + rows > self._alloc_samples:
+            raise ValueError(f"commit({rows}, {steps}) outside the reserved rows ({self._alloc_samples - self._write_offset})")
+        self._write_offset += rows
+        self._step_count += steps
+
     def fill_alternating_perspective_overrides(self) -> None:
         """Two-player frames alternate every ply: where no override was supplied and the transition is not
         terminal, bootstrap from -V[t+1] (katago_ppo.py:320-362).  No-op for the env_ids (split-merge) layout."""

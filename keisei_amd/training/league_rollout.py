@@ -1,0 +1,564 @@
+"""LeagueRollout: the learner-vs-league rollout epoch on the device (the opponent branch of the reference's
+``KataGoTrainingLoop.run``, katago_loop.py:1162-1437, and the flush and bootstrap behind it, :1537-1580).
+
+The learner and its cohort of opponents sit in one ``SEResNetGroup`` (learner = model 0, opponent k = model k + 1): the
+learner's forward in this loop is an eval-mode, no-grad forward (katago_loop.py:333-343), so it can be seated like any
+opponent.  One ply is four steps on one stream, with no host synchronisation:
+
+    grouped stem / tower / heads on model_of   (csrc/tower.hip, the group's tables)
+    ka_policy_sample_play                       (csrc/loss.hip: actions and log-probs, seed read from the device)
+    ka_shogi_env_step                           (csrc/shogi_env.hip)
+    ka_league_step                              (csrc/league.hip: the reference's whole per-step bookkeeping -- learner-frame
+                                                 rewards and tallies, pending accumulate / settle / open / immediate
+                                                 settle straight into the rollout store's columns, per-opponent results,
+                                                 opponent and colour re-draws, the next model_of)
+
+``sync_every`` plies are captured as one graph; the host reads ONE state array per chunk.  Nothing inside an epoch needs
+a host decision, so a chunk's result does not depend on ``sync_every`` or on graph capture: the re-draws are a stateless
+function of (seed, env, games that env has finished), restated in numpy below (``league_draw``).
+
+Rows go straight into a device-resident ``KataGoRolloutBuffer`` (``reserve`` / ``commit``): the kernel reads the column
+pointers from a small device descriptor the host rewrites at each sync point, so the captured graph survives a store
+that grows.  The bootstrap override of truncated games (:1250-1283) is deferred: the kernel parks the terminal
+observation, the host runs one learner forward over exactly those rows at the sync point.  The learner's weights do
+not change inside ``collect`` and eval mode couples no two boards, so the values are what an in-ply forward gives.
+
+``_league_host`` restates the protocol on the CPU from this package's host pieces (``PendingTransitions``,
+``to_learner_perspective``, ``_compute_value_cats``, a host ``KataGoRolloutBuffer``); the tests hold the kernel to it and
+hold it to the reference (tests/golden/g13_league_rollout.npz).
+"""
+from __future__ import annotations
+
+import gc
+import math
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from keisei_amd import _lib
+from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS, OBS_CHANNELS, VecEnv
+
+from .katago_loop import (_ZERO_LEGAL, PendingTransitions, _compute_value_cats, sign_correct_bootstrap,
+                          to_learner_perspective)
+from .katago_ppo import SCORE_NORMALIZATION, KataGoRolloutBuffer, _check_step_inputs
+from .model_group import SEResNetGroup
+from .value_adapter import MultiHeadValueAdapter
+
+__all__ = ["LeagueRollout", "LeagueRolloutStats", "league_draw", "draw_opponents", "draw_sides", "cum_thresholds"]
+
+_OBS_SHAPE = (OBS_CHANNELS, 9, 9)
+_OBS_ELEMS = OBS_CHANNELS * 81
+# state words (csrc/league.hip)
+_SEED, _PLY, _ROWS, _BLOCKS, _DROPPED, _SAMP, _REFUSAL, _DRAW_SEED, _TRUNC, _TRUNC_DROPPED = 0, 2, 3, 4, 5, 6, 8, 10, 12, 13
+_WINS, _LOSSES, _DRAWS, _BLACK, _WHITE, _TERMINATED, _TRUNCATED, _GUARDS, _CONFLICT, _STALL, _HDR = 14, 15, 16, 17, 18, 19, 20, 21, 25, 26, 32
+SALT_OPPONENT, SALT_SIDE, SALT_EPOCH_SIDE = 0x6F70706F, 0x73696465, 0x65706F63
+
+
+# ---------------------------------------------------------------------------------------------- draws (numpy form)
+def _mix(x: np.ndarray) -> np.ndarray:
+    """splitmix64 finaliser on uint64 arrays (wrapping arithmetic), as ``sample_mix`` of csrc/loss.hip."""
+    with np.errstate(over="ignore"):
+        x = x + np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return x ^ (x >> np.uint64(31))
+
+
+def league_draw(seed: int, salt: int, env, n) -> np.ndarray:
+    """h(salt, env, n) = mix(seed ^ mix((env << 32 | n) + salt)) as uint64: the draw of env ``env`` after its n-th
+    finished game (include/keisei_amd.h, league rollout)."""
+    env = np.asarray(env, dtype=np.uint64)
+    n = np.asarray(n, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    with np.errstate(over="ignore"):
+        key = ((env << np.uint64(32)) | n) + np.uint64(salt)
+    return _mix(np.uint64(seed & (2 ** 64 - 1)) ^ _mix(key))
+
+
+def cum_thresholds(weights: Optional[Sequence[float]], K: int) -> np.ndarray:
+    """K uint32 thresholds of the cumulative opponent weights (uniform when None) on the 31-bit scale of the draw:
+    opponent = first k with u < cum[k], u = h >> 33 < 2^31 = the threshold of the last opponent with a weight."""
+    w = np.ones(K, dtype=np.float64) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.shape[0] != K:
+        raise ValueError(f"opponent_weights holds {w.shape[0]} weights for {K} opponents")
+    if not np.isfinite(w).all() or (w < 0).any() or w.sum() <= 0:
+        raise ValueError("opponent_weights must be finite, non-negative and not all zero")
+    cum = np.minimum(np.floor(np.cumsum(w) / w.sum() * 2.0 ** 31), 2.0 ** 31).astype(np.uint32)
+    cum[int(np.flatnonzero(w > 0)[-1]):] = np.uint32(1 << 31)
+    return cum
+
+
+def draw_opponents(seed: int, env, n, cum: np.ndarray) -> np.ndarray:
+    u = (league_draw(seed, SALT_OPPONENT, env, n) >> np.uint64(33)).astype(np.uint32)
+    k = np.searchsorted(cum, u, side="right")                  # first k with u < cum[k]
+    return np.minimum(k, len(cum) - 1).astype(np.int32)
+
+
+def draw_sides(seed: int, env, n, salt: int = SALT_SIDE) -> np.ndarray:
+    return (league_draw(seed, salt, env, n) >> np.uint64(63)).astype(np.uint8)
+
+
+# ---------------------------------------------------------------------------------------------- stats
+@dataclass
+class LeagueRolloutStats:
+    plies: int = 0
+    rows: int = 0                       # transitions written to the buffer
+    adds: int = 0                       # non-empty blocks: what the reference's sequence of add() calls counts
+    wins: int = 0                       # terminated games, learner's frame
+    losses: int = 0
+    draws: int = 0
+    black_wins: int = 0
+    white_wins: int = 0
+    terminated: int = 0
+    truncated: int = 0                  # truncated and not terminated
+    opponent_results: Dict[int, List[int]] = field(default_factory=dict)      # opponent id -> [wins, losses, draws]
+    host_syncs: int = 0                 # reads of the state array
+    truncation_overrides: int = 0       # rows whose bootstrap override was computed at a sync point
+    flushed: int = 0                    # rows the flush at the end of collect closed (done = 0)
+
+
+def _stats_from_state(st: np.ndarray, opponent_ids: Sequence[int], stats: LeagueRolloutStats) -> None:
+    stats.rows, stats.adds = int(st[_ROWS]), int(st[_BLOCKS])
+    stats.wins, stats.losses, stats.draws = int(st[_WINS]), int(st[_LOSSES]), int(st[_DRAWS])
+    stats.black_wins, stats.white_wins = int(st[_BLACK]), int(st[_WHITE])
+    stats.terminated, stats.truncated = int(st[_TERMINATED]), int(st[_TRUNCATED])
+    stats.opponent_results = {oid: [int(v) for v in st[_HDR + 3 * k:_HDR + 3 * k + 3]] for k, oid in enumerate(opponent_ids)}
+
+
+def _check_args(num_opponents: int, opponent_ids, num_envs: int, max_ply: int, sync_every: int, graph: bool, record: bool,
+                score_norm: float, value_adapter) -> None:
+    if num_opponents == 0:
+        raise ValueError("LeagueRollout needs at least one opponent (the no-opponent branch is select_actions' loop)")
+    if len(opponent_ids) != num_opponents or len(set(opponent_ids)) != num_opponents:
+        raise ValueError(f"opponent_ids must name each of the {num_opponents} opponents once, got {list(opponent_ids)}")
+    if _lib.available():
+        top = _lib.query("ka_league_layout", 4)
+        if not 1 <= num_envs <= top:
+            raise ValueError(f"num_envs must lie in [1, {top}], got {num_envs}")
+    elif num_envs < 1:
+        raise ValueError(f"num_envs must be positive, got {num_envs}")
+    if not 1 <= max_ply <= 65535:
+        raise ValueError(f"max_ply must lie in [1, 65535], got {max_ply}")
+    if sync_every < 1:
+        raise ValueError(f"sync_every must be at least 1, got {sync_every}")
+    if sync_every > max_ply:
+        raise ValueError(f"sync_every ({sync_every}) must not exceed max_ply ({max_ply}): an env may truncate only once "
+                         "between two sync points (one truncation slot per env)")
+    if graph and record:
+        raise ValueError("record=True runs without a graph (graph=False)")
+    if graph and sync_every % 2:
+        raise ValueError(f"graph=True needs an even sync_every (VecEnv alternates two result buffers), got {sync_every}")
+    if not math.isfinite(score_norm) or score_norm == 0:
+        raise ValueError(f"score_norm must be finite and non-zero, got {score_norm}")
+    if value_adapter is not None and type(value_adapter) is not MultiHeadValueAdapter:
+        raise ValueError(f"value_adapter must be None or a MultiHeadValueAdapter (the kernel blends by its "
+                         f"score_blend_alpha), got {type(value_adapter).__name__}")
+
+
+class LeagueRollout:
+    """The learner's rollout against its league cohort, resident on the device (see module docstring).
+
+    ``roll = LeagueRollout(learner, opponents, opponent_ids, num_envs=512, max_ply=500, ...)``;
+    ``stats = roll.collect(buffer, steps)`` steps every env ``steps`` plies and leaves the learner's transitions in
+    ``buffer`` (a device-resident ``KataGoRolloutBuffer``); ``roll.bootstrap_values()`` is the ``next_values`` of
+    ``KataGoPPOAlgorithm.update``; ``roll.refresh()`` after the update brings the learner's new weights into the group;
+    ``roll.set_opponents`` seats a new cohort.  The env is not reset between ``collect`` calls (the reference carries
+    games over epochs); ``reset()`` is explicit.  ``seed`` fixes sampling and re-draws from the last ``reset()`` on.
+    ``record=True`` (no graph) keeps every ply's inputs and outputs in ``self.record`` for tests."""
+
+    def __init__(self, learner, opponents: Sequence, opponent_ids: Sequence[int], *, num_envs: int = 512, max_ply: int = 500,
+                 value_adapter=None, score_norm: float = SCORE_NORMALIZATION, color_randomization: bool = False,
+                 opponent_weights: Optional[Sequence[float]] = None, sync_every: int = 32, graph: bool = True,
+                 seed: Optional[int] = None, record: bool = False) -> None:
+        opponents, opponent_ids = list(opponents), [int(i) for i in opponent_ids]
+        _check_args(len(opponents), opponent_ids, int(num_envs), int(max_ply), int(sync_every), bool(graph), bool(record),
+                    float(score_norm), value_adapter)
+        self._cum_host = cum_thresholds(opponent_weights, len(opponents))
+        self.group = self._make_group(learner, opponents)
+        self.learner, self.opponent_ids = learner, opponent_ids
+        self.device = self.group.device
+        self.num_envs, self.max_ply, self.sync_every = int(num_envs), int(max_ply), int(sync_every)
+        self.graph, self.seed, self.record_enabled = bool(graph), seed, bool(record)
+        self.value_adapter, self.score_norm = value_adapter, float(score_norm)
+        self.alpha = 0.0 if value_adapter is None else float(value_adapter.score_blend_alpha)
+        self.color_randomization = bool(color_randomization)
+        self.record: List[dict] = []
+        N, dev = self.num_envs, self.device
+        q = lambda which: _lib.query("ka_league_layout", which)  # noqa: E731
+        with torch.cuda.device(dev):
+            z = lambda *s, dtype=torch.int32: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731
+            self.env = VecEnv(N, self.max_ply, "katago", "spatial", device=dev, output="torch", check_actions=False)
+            self._actions, self._logp, self._nlegal = z(N, dtype=torch.int64), z(N, dtype=torch.float32), z(N)
+            self._values = z(N, dtype=torch.float32)
+            self._model_of, self._learner_of = z(N), z(N)
+            self._side, self._opp, self._games, self._stall = z(N, dtype=torch.uint8), z(N), z(N), z(N, dtype=torch.uint8)
+            self._p_obs, self._p_bits = z(N, *_OBS_SHAPE, dtype=torch.float32), z(N, MASK_WORDS)
+            self._p_scal = z(q(2), N)
+            self._t_obs, self._t_list = z(N, *_OBS_SHAPE, dtype=torch.float32), z(N, q(3))
+            self._plan = z(N, q(0))
+            self._desc = z(q(1), dtype=torch.int64)
+            self._desc_host = torch.zeros(q(1), dtype=torch.int64).pin_memory()
+            self._side_host = torch.zeros(N, dtype=torch.uint8).pin_memory()
+        self._graphs: Dict[int, torch.cuda.CUDAGraph] = {}
+        self._collects = 0
+        self._seat_cohort()
+        with torch.cuda.device(dev), torch.no_grad():            # load every kernel of the ply before any capture
+            self.reset()
+            self._ply()
+            self._ply()
+        self.reset()
+
+    # ------------------------------------------------------------------ cohort
+    @staticmethod
+    def _make_group(learner, opponents) -> SEResNetGroup:
+        try:
+            group = SEResNetGroup([learner, *opponents])
+        except ValueError as e:
+            raise ValueError(f"LeagueRollout needs the learner and every opponent as SEResNetModels of one shape on one "
+                             f"GPU ({e}); use split_merge_step for this cohort") from e
+        if group.device.type != "cuda" or group._tables is None:
+            raise ValueError(f"LeagueRollout runs on a GPU group; these models are on {group.device}: use "
+                             "split_merge_step for this cohort")
+        return group
+
+    def _seat_cohort(self) -> None:
+        """Buffers whose size follows the number of opponents; the header of an existing state is kept."""
+        K, dev = len(self.opponent_ids), self.device
+        with torch.cuda.device(dev):
+            old = getattr(self, "_state", None)
+            self._state = torch.zeros(_lib.query("ka_league_state_words", K), dtype=torch.int32, device=dev)
+            if old is not None:
+                self._state[:_HDR].copy_(old[:_HDR])
+            self._state_host = torch.zeros(self._state.shape, dtype=torch.int32).pin_memory()
+            self._cum = torch.from_numpy(self._cum_host.view(np.int32).copy()).to(dev)
+            self._ws = self.group._tables.workspace(self.num_envs)
+        self._graphs = {}
+
+    def set_opponents(self, opponents: Sequence, opponent_ids: Sequence[int],
+                      opponent_weights: Optional[Sequence[float]] = None) -> None:
+        """A new cohort (epoch start): every env draws its opponent afresh; games in progress go on."""
+        opponents, opponent_ids = list(opponents), [int(i) for i in opponent_ids]
+        _check_args(len(opponents), opponent_ids, self.num_envs, self.max_ply, self.sync_every, self.graph,
+                    self.record_enabled, self.score_norm, self.value_adapter)
+        cum = cum_thresholds(opponent_weights, len(opponents))
+        same = len(opponents) + 1 == len(self.group) and all(a is b for a, b in zip(opponents, self.group.models[1:]))
+        if not same:
+            self.group = self._make_group(self.learner, opponents)
+        else:
+            self.group.refresh()
+        self.opponent_ids, self._cum_host = opponent_ids, cum
+        self._seat_cohort()
+        with torch.cuda.device(self.device):
+            games = self._games.cpu().numpy()
+            self._opp.copy_(torch.from_numpy(draw_opponents(self._draw_seed, np.arange(self.num_envs), games, cum)))
+            self._seat()
+
+    def refresh(self) -> None:
+        """After ``ppo.update()`` (or any in-place edit of weights): the group's snapshot follows the models."""
+        self.group.refresh()
+
+    # ------------------------------------------------------------------ state
+    def reset(self) -> None:
+        """Every env back to the start position, no pending transition, fresh seed, opponents and sides drawn anew."""
+        N, dev = self.num_envs, self.device
+        seed = self.seed if self.seed is not None else int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        self._draw_seed = int(seed)
+        with torch.cuda.device(dev):
+            hdr = torch.zeros(self._state.shape, dtype=torch.int32)
+            hdr[_SEED:_SEED + 2].view(torch.int64)[0] = seed
+            hdr[_DRAW_SEED:_DRAW_SEED + 2].view(torch.int64)[0] = seed
+            self._state.copy_(hdr)
+            self._desc.zero_()
+            self._p_scal.zero_()
+            self._games.zero_()
+            self._stall.zero_()
+            envs = np.arange(N)
+            self._opp.copy_(torch.from_numpy(draw_opponents(seed, envs, np.zeros(N, np.int64), self._cum_host)))
+            side = draw_sides(seed, envs, np.zeros(N, np.int64)) if self.color_randomization else np.zeros(N, np.uint8)
+            self._side.copy_(torch.from_numpy(side))
+            self.env.reset()
+            self._seat()
+        self._collects = 0
+        self.record = []
+
+    def _seat(self) -> None:
+        """model_of of the ply to come from the current players, sides and opponents."""
+        players = self.env._players[self.env._cur]
+        self._model_of.copy_(torch.where(players == self._side, torch.zeros_like(self._opp), self._opp + 1))
+
+    @property
+    def last_values(self) -> torch.Tensor:
+        """The learner's value of the last ply where it moved, 0 elsewhere (the reference's ``latest_values``)."""
+        return self._values
+
+    # ------------------------------------------------------------------ one ply
+    def _ply(self) -> None:
+        """forward -> sample -> step -> league bookkeeping on the current stream; no host synchronisation."""
+        env, N, K = self.env, self.num_envs, len(self.opponent_ids)
+        st = _lib.stream_ptr(self.device)
+        cur, prev = env.current(), env._cur
+        logits, value, score = self.group._tables.forward(cur.observations, self._model_of, ws=self._ws)
+        sp = self._state.data_ptr()
+        _lib.call("ka_policy_sample_play", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of, K + 1,
+                  self._actions, self._logp, self._nlegal, sp + 4 * _SAMP, N, ACTION_SPACE, st)
+        r = env.step(self._actions)
+        _lib.call("ka_league_step", self._state, N, K, 0, cur.observations, cur.legal_mask_bits, self._actions, self._logp,
+                  value, score if self.alpha != 0.0 else None, self.alpha, self._nlegal, env._players[prev], r.rewards,
+                  r.terminated, r.truncated, r.current_players, r.step_metadata.material_balance, self.score_norm,
+                  r.terminal_observations, env._err.data_ptr() + 8, self._side, self._opp, self._games, self._cum,
+                  int(self.color_randomization), self._model_of, self._stall, self._values, self._p_obs, self._p_bits,
+                  self._p_scal, self._t_obs, self._t_list, self._desc, self._plan, _OBS_ELEMS, MASK_WORDS, st)
+
+    def _ply_recorded(self) -> None:
+        env = self.env
+        cur, prev = env.current(), env._cur
+        rec = {"seed": int(self._state[:2].view(torch.int64).item()), "obs": cur.observations.cpu(),
+               "mask_bits": cur.legal_mask_bits.cpu(), "model_of": self._model_of.cpu().numpy(),
+               "pre_players": env._players[prev].cpu().numpy(), "side": self._side.cpu().numpy(),
+               "opp": self._opp.cpu().numpy()}
+        self._ply()
+        c = env._cur
+        trunc = (env._truncated[c] & ~env._terminated[c]).nonzero(as_tuple=True)[0]
+        rec.update(actions=self._actions.cpu().numpy(), log_probs=self._logp.cpu().numpy(), values=self._values.cpu().numpy(),
+                   n_legal=self._nlegal.cpu().numpy(), rewards=env._rewards[c].cpu().numpy(),
+                   terminated=env._terminated[c].cpu().numpy(), truncated=env._truncated[c].cpu().numpy(),
+                   current_players=env._players[c].cpu().numpy(), material=env._material[c].cpu().numpy(),
+                   terminal_envs=trunc.cpu().numpy(), terminal_obs=env._terminal_obs[trunc].cpu())
+        self.record.append(rec)
+
+    def _capture(self, parity: int) -> torch.cuda.CUDAGraph:
+        """Capture sync_every plies for the env's current buffer parity (an even count: the parity is the same afterwards)."""
+        g = torch.cuda.CUDAGraph()
+        # torch.cuda.graph does not collect garbage on entry.  Observed: a dead rollout object (captured graphs, pinned
+        # buffers) still waiting in a reference cycle was collected inside a later capture, and the process aborted in its
+        # destructor.  After a collection here, what the capture itself allocates holds no such object.
+        gc.collect()
+        with torch.cuda.graph(g):
+            for _ in range(self.sync_every):
+                self._ply()
+        self._graphs[parity] = g
+        return g
+
+    def _chunk(self, plies: int) -> None:
+        if self.graph and plies == self.sync_every:
+            (self._graphs.get(self.env._cur) or self._capture(self.env._cur)).replay()
+            return
+        for _ in range(plies):
+            self._ply_recorded() if self.record_enabled else self._ply()
+
+    # ------------------------------------------------------------------ host side
+    def _describe(self, buffer: KataGoRolloutBuffer, base: int, rows: int) -> dict:
+        """Reserve ``rows`` rows behind the ones committed and point the kernel at the columns."""
+        cols = buffer.reserve(rows, self.device)
+        d = self._desc_host
+        for i, key in enumerate(("observations", "legal_masks", "actions", "log_probs", "values", "rewards", "dones",
+                                 "terminated", "value_categories", "score_targets", "env_ids", "next_value_override")):
+            d[i] = cols[key].data_ptr()
+        d[12], d[13] = base, buffer._write_offset - base + rows
+        self._desc.copy_(d, non_blocking=True)
+        return cols
+
+    def _read_state(self, stats: LeagueRolloutStats) -> np.ndarray:
+        self._state_host.copy_(self._state)           # the one device -> host read of a sync point
+        stats.host_syncs += 1
+        st = self._state_host.numpy()
+        if st[_STALL]:
+            stall = self._stall.cpu().numpy()
+            for bit, who in ((1, "Learner"), (2, "Opponent")):
+                if st[_STALL] & bit:
+                    raise RuntimeError(_ZERO_LEGAL.format(who=who, envs=np.flatnonzero(stall & bit).tolist()))
+        if st[_SAMP]:
+            raise RuntimeError("NaN in raw policy logits in LeagueRollout — probability tensor contains nan "
+                               "(a model has diverged)")
+        if st[_REFUSAL] or st[_REFUSAL + 1]:
+            self.env.raise_if_refused()
+        if st[_CONFLICT]:
+            PendingTransitions._conflict()
+        g = st[_GUARDS:_GUARDS + 4]
+        peak = float(g[3:4].view(np.float32)[0])
+        if g[:3].any() or peak > 3.5:                  # the rollout store's input guards, with the reference's messages
+            _check_step_inputs(torch.tensor([not g[0]]), torch.tensor([True]), torch.tensor([5 if g[1] else 0]),
+                               torch.tensor([float("nan") if g[2] else peak]))
+        if st[_DROPPED] or st[_TRUNC_DROPPED]:
+            raise RuntimeError(f"LeagueRollout: {int(st[_DROPPED])} rows did not fit the rows reserved in the rollout "
+                               f"buffer, {int(st[_TRUNC_DROPPED])} truncations found no slot")
+        return st
+
+    def _overrides(self, cols: dict, n: int) -> None:
+        """The deferred truncation bootstrap (:1250-1283): one learner forward over the n parked terminal observations,
+        sign-corrected to the learner's frame, scattered into the rows' next_value_override."""
+        tl = self._t_list[:n]
+        v = self._learner_values(self._t_obs[:n], n, None)
+        who = tl[:, 2]
+        v = torch.where((who & 1) != (who >> 1), -v, v)          # sign_correct_bootstrap(term_v, 1 - pre_players, side)
+        cols["next_value_override"].index_copy_(0, tl[:, 1].long(), v)
+        self._state[_TRUNC:_TRUNC + 1].zero_()
+
+    def _learner_values(self, obs: torch.Tensor, n: int, ws: Optional[dict]) -> torch.Tensor:
+        _, vl, sc = self.group._tables.forward(obs, self._learner_of[:n], ws=ws)
+        v = torch.empty(n, device=self.device)
+        _lib.call("ka_scalar_value", vl, sc if self.alpha != 0.0 else None, self.alpha, v, n, _lib.stream_ptr(self.device))
+        return v
+
+    def collect(self, buffer: KataGoRolloutBuffer, steps: int) -> LeagueRolloutStats:
+        """Step every env ``steps`` plies; the learner's transitions land in ``buffer`` in the reference's order."""
+        if steps < 1:
+            raise ValueError(f"steps must be positive, got {steps}")
+        if not isinstance(buffer, KataGoRolloutBuffer):
+            raise ValueError(f"collect() writes a KataGoRolloutBuffer, got {type(buffer).__name__}")
+        if tuple(buffer.obs_shape) != _OBS_SHAPE or buffer.action_space != ACTION_SPACE:
+            raise ValueError(f"buffer holds obs {tuple(buffer.obs_shape)} / {buffer.action_space} actions, the env gives "
+                             f"{_OBS_SHAPE} / {ACTION_SPACE}")
+        bd = buffer._device
+        if bd is not None and (bd.type != "cuda" or (bd.index is not None and bd.index != self.device.index)):
+            raise ValueError(f"buffer lives on {buffer._device}, the rollout on {self.device} (a device-resident buffer)")
+        stats = LeagueRolloutStats()
+        with torch.cuda.device(self.device), torch.no_grad():
+            self._collect(buffer, int(steps), stats)
+        return stats
+
+    def _collect(self, buffer, steps, stats) -> None:
+        N = self.num_envs
+        self.record = []
+        self._state[_ROWS:_SAMP + 2].zero_()
+        self._state[_TRUNC:].zero_()
+        self._stall.zero_()
+        if self.color_randomization:                              # katago_loop.py:1134-1137: all sides anew every epoch
+            self._side_host.copy_(torch.from_numpy(draw_sides(self._draw_seed, np.arange(N), np.full(N, self._collects),
+                                                              SALT_EPOCH_SIDE)))
+            self._side.copy_(self._side_host, non_blocking=True)
+            self._seat()
+        self._collects += 1
+        base, rows, adds, done = buffer._write_offset, 0, 0, 0
+
+        def sync(cols):
+            nonlocal rows, adds
+            st = self._read_state(stats)
+            buffer.commit(int(st[_ROWS]) - rows, int(st[_BLOCKS]) - adds)
+            rows, adds = int(st[_ROWS]), int(st[_BLOCKS])
+            n = int(st[_TRUNC])
+            if n:
+                self._overrides(cols, n)
+                stats.truncation_overrides += n
+            return st
+
+        while done < steps:
+            plies = min(self.sync_every, steps - done)
+            cols = self._describe(buffer, base, plies * N)
+            self._chunk(plies)
+            sync(cols)
+            done += plies
+        cols = self._describe(buffer, base, N)                   # :1537-1563: what is still pending leaves with done = 0
+        _lib.call("ka_league_step", self._state, N, len(self.opponent_ids), 1, *([None] * 6), 0.0, *([None] * 7), 1.0,
+                  *([None] * 6), 0, None, None, None, self._p_obs, self._p_bits, self._p_scal, None, None, self._desc,
+                  self._plan, _OBS_ELEMS, MASK_WORDS, _lib.stream_ptr(self.device))
+        before = rows
+        st = sync(cols)
+        stats.plies, stats.flushed = steps, rows - before
+        _stats_from_state(st, self.opponent_ids, stats)
+
+    def bootstrap_values(self) -> torch.Tensor:
+        """V(observation now) by the learner, in the learner's frame (katago_loop.py:1565-1580): ``update``'s next_values."""
+        with torch.cuda.device(self.device), torch.no_grad():
+            env = self.env
+            v = self._learner_values(env.current().observations, self.num_envs, self._ws)
+            return torch.where(env._players[env._cur] != self._side, -v, v)
+
+
+# ---------------------------------------------------------------------------------------------- host restatement
+def _league_host(records: Sequence[dict], *, num_envs: int, obs_shape: tuple, action_space: int, opponent_ids: Sequence[int],
+                 seed: int, cum: np.ndarray, color_randomization: bool, score_norm: float, side: np.ndarray,
+                 opp: np.ndarray, games: Optional[np.ndarray] = None, trace: Optional[list] = None):
+    """The reference's rollout protocol (katago_loop.py:1219-1437, :1537-1563) over per-ply records, on the CPU, from
+    this package's host pieces.  A record holds one ply as arrays over all envs: ``obs``, ``mask_bits`` (packed int32
+    rows) or ``legal_masks`` (bool), ``pre_players``, ``actions``, ``log_probs``, ``values``, ``rewards``, ``terminated``,
+    ``truncated``, ``current_players``, ``material`` and, for plies with truncations, ``term_values`` (the learner's value
+    of every env's terminal observation, before the sign correction; NaN where there is none).  ``side`` / ``opp`` /
+    ``games``: the per-env learner side, opponent index and finished-game count before the first record.
+    Returns ``(columns, stats)``: the host buffer's ``flatten()`` plus ``size``, and the tallies as a dict.  ``trace`` (a
+    list) receives per ply the state after it: side, opp, games, model_of and the pending slots' valid flags."""
+    t = lambda x, dt=None: torch.as_tensor(np.asarray(x), dtype=dt)  # noqa: E731
+    dev = torch.device("cpu")
+    K = len(opponent_ids)
+    side, opp = np.array(side, dtype=np.uint8), np.array(opp, dtype=np.int32)
+    games = np.zeros(num_envs, np.int64) if games is None else np.array(games, dtype=np.int64)
+    pending = PendingTransitions(num_envs, tuple(obs_shape), action_space, dev)
+    buffer = KataGoRolloutBuffer(num_envs, tuple(obs_shape), action_space)
+    tally = dict(wins=0, losses=0, draws=0, black_wins=0, white_wins=0, terminated=0, truncated=0, truncation_overrides=0)
+    results = {oid: [0, 0, 0] for oid in opponent_ids}
+    envs = np.arange(num_envs)
+
+    def add(fin, cats, override):
+        buffer.add(fin["obs"], fin["actions"], fin["log_probs"], fin["values"], fin["rewards"], fin["dones"],
+                   fin["terminated"], fin["legal_masks"], cats, fin["score_targets"], env_ids=fin["env_ids"],
+                   next_value_override=override)
+
+    for rec in records:
+        pre, cur = np.asarray(rec["pre_players"]).astype(np.uint8), np.asarray(rec["current_players"]).astype(np.uint8)
+        learner_moved, learner_next = t(pre == side), t(cur == side)
+        rewards = t(rec["rewards"], torch.float32)
+        terminated, truncated = t(rec["terminated"]).bool(), t(rec["truncated"]).bool()
+        dones = terminated | truncated
+        tally["terminated"] += int(terminated.sum())
+        tally["truncated"] += int((truncated & ~terminated).sum())
+        learner_rewards = to_learner_perspective(rewards, pre, side)
+        if terminated.any():                                     # :1226-1248
+            tr = learner_rewards[terminated]
+            tally["wins"] += int((tr > 0).sum()); tally["losses"] += int((tr < 0).sum()); tally["draws"] += int((tr == 0).sum())
+            raw, who = rewards[terminated], t(pre)[terminated]
+            tally["black_wins"] += int((((raw > 0) & (who == 0)) | ((raw < 0) & (who == 1))).sum())
+            tally["white_wins"] += int((((raw > 0) & (who == 1)) | ((raw < 0) & (who == 0))).sum())
+        truncated_only = truncated & ~terminated
+        override_full = None
+        if bool(truncated_only.any()):                           # :1258-1283
+            term_v = sign_correct_bootstrap(t(rec["term_values"], torch.float32), 1 - pre, side)
+            override_full = torch.full_like(term_v, float("nan"))
+            override_full[truncated_only] = term_v[truncated_only]
+        pending.accumulate_reward(learner_rewards)               # :1290-1316
+        fin = pending.finalize(pending.valid & (dones | learner_next), dones, terminated)
+        if fin is not None:
+            ov = override_full[fin["env_ids"]] if override_full is not None else None
+            tally["truncation_overrides"] += 0 if ov is None else int((~torch.isnan(ov)).sum())
+            add(fin, _compute_value_cats(fin["rewards"], fin["terminated"].bool(), dev), ov)
+        if learner_moved.any():                                  # :1319-1365
+            masks = t(rec["mask_bits"], torch.int32) if "mask_bits" in rec else t(rec["legal_masks"]).bool()
+            zero = torch.zeros(num_envs)
+            pending.create(learner_moved, t(rec["obs"], torch.float32), t(rec["actions"], torch.long),
+                           torch.where(learner_moved, t(rec["log_probs"], torch.float32), zero),
+                           torch.where(learner_moved, t(rec["values"], torch.float32), zero), masks, learner_rewards,
+                           t(rec["material"]).to(torch.float32) / score_norm)
+            imm = learner_moved & dones
+            if imm.any():
+                fin = pending.finalize(imm, dones, terminated)
+                if fin is not None:
+                    ov = override_full[fin["env_ids"]] if override_full is not None else None
+                    tally["truncation_overrides"] += 0 if ov is None else int((~torch.isnan(ov)).sum())
+                    add(fin, _compute_value_cats(fin["rewards"], fin["terminated"].bool(), dev), ov)
+        done_np = dones.numpy()
+        for e in np.flatnonzero(done_np):                        # :1384-1407: by the opponent that played the game
+            if terminated[e]:
+                lr = float(learner_rewards[e])
+                results[opponent_ids[opp[e]]][0 if lr > 0 else (1 if lr < 0 else 2)] += 1
+        if done_np.any():                                        # :1409-1437: the next game's opponent and side
+            games[done_np] += 1
+            opp[done_np] = draw_opponents(seed, envs[done_np], games[done_np], cum)
+            if color_randomization:
+                side[done_np] = draw_sides(seed, envs[done_np], games[done_np])
+        if trace is not None:
+            trace.append(dict(side=side.copy(), opp=opp.copy(), games=games.copy(),
+                              model_of=np.where(cur == side, 0, opp + 1).astype(np.int32),
+                              valid=pending.valid.numpy().copy(), rewards=pending.rewards.numpy().copy(),
+                              obs=pending.obs.numpy().copy(), mask_bits=pending.legal_mask_bits.numpy().copy(),
+                              actions=pending.actions.numpy().copy(), log_probs=pending.log_probs.numpy().copy(),
+                              values=pending.values.numpy().copy(), score_targets=pending.score_targets.numpy().copy()))
+    if bool(pending.valid.any()):                                # :1537-1563
+        zero = torch.zeros(num_envs)
+        fin = pending.finalize(pending.valid.clone(), zero, zero)
+        if fin is not None:
+            add(fin, torch.full((fin["env_ids"].numel(),), -1, dtype=torch.long), None)
+    cols = dict(buffer.flatten()) if buffer.size else {}
+    cols["size"] = buffer.size
+    stats = dict(tally, plies=len(records), rows=buffer._write_offset, adds=buffer.size,
+                 opponent_results={k: list(v) for k, v in results.items()})
+    return cols, stats
