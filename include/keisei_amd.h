@@ -548,6 +548,40 @@ int ka_league_step(int* state, int envs, int opponents, int flush, const float* 
                    int* model_of, void* stall, float* values, float* p_obs, void* p_bits, int* p_scal, float* t_obs,
                    int* t_list, const long long* desc, int* plan, int obs_elems, int mask_words, void* stream);
 
+/* ---- self-play rollout (csrc/selfplay.hip; katago_loop.py:1438-1527, the no-opponent branch of the rollout loop: every
+ * env is the learner, every ply gives one transition per env).  E envs, one model.
+ * state: ka_selfplay_state_words() int32 = {0-1 sampler seed int64, 2 ply of the epoch, 3 rows written behind the
+ *   descriptor's base row, 4 plies since the reset, 5 rows dropped, 6-7 sampler flags, 8-9 refusal latch copy int64, 10-11
+ *   unused, 12 truncation slots used, 13 truncations without a slot, 14-20 wins / losses / draws (the mover's frame) / black
+ *   wins / white wins / terminated / truncated-only, 21-24 the four guards of ka_rollout_append over the rows written, 25 an
+ *   env without a legal action, 26-31 unused}.
+ * ka_selfplay_layout gives the other sizes: which 0 = int32 words of one env's plan {store row, truncation slot}, 1 = int64
+ *   words of the descriptor, 2 = int32 words of one truncation record {env, store row}, 3 = largest E.
+ * desc: the league rollout's descriptor; the env_ids pointer is not read (the dense (T, N) layout has no such column).
+ * ka_selfplay_step, after ka_shogi_env_step: env e at ply p = state[2] owns store row base + p * E + e; a row beyond the
+ *   reserved capacity is not written and is counted.  Statement by statement:
+ *     :1446       values[e] = the learner's value this ply (latest_values)
+ *     :1455-1458  rewards in the mover's frame, done = terminated | truncated
+ *     :1460-1461  terminated and truncated-only counts
+ *     :1463-1485  wins / losses / draws by the sign of the reward over terminated envs, black / white wins by pre_player
+ *     :1487       label {-1, 0, 1, 2} (_compute_value_cats, :75-92)
+ *     :1491-1494  score target material / score_norm
+ *     :1502-1521  a truncated, unterminated env parks terminal_observations[e] in a truncation slot with {env, store row},
+ *                 slots in (ply, env) order; the host computes -V there at its sync point.  next_value_override = NaN
+ *     :1523-1527  the row: pre-step observation and packed mask row, action, log-prob, value P(W) - P(L) blended with
+ *                 clamp(score_lead, -1, 1) by alpha (the arithmetic of ka_policy_sample), reward, done, terminated, label,
+ *                 score target; the add() guards become state words 21-24
+ *   stall (E) u8 latches the envs without a legal action.  The seed advances by the Weyl step 0x9E3779B97F4A7C15 and
+ *   state[2] by one per call, so a captured graph replays.  No atomics: truncation slots are ranked by ballot scans. */
+int ka_selfplay_state_words(void);
+int ka_selfplay_layout(int which);
+int ka_selfplay_step(int* state, int envs, const float* obs, const void* mask_bits, const long long* actions,
+                     const float* logp, const float* vlogits, const float* score_lead, float alpha, const int* nlegal,
+                     const void* pre_player, const float* rewards, const void* terminated, const void* truncated,
+                     const int* material, float score_norm, const float* term_obs, const long long* refusal, void* stall,
+                     float* values, float* t_obs, int* t_list, const long long* desc, int* plan, int obs_elems,
+                     int mask_words, void* stream);
+
 /* ---- transformer encoder path (BASELINE config 5; keisei/training/models/transformer.py:37-95: nn.Linear(50, d),
  * row/col nn.Embedding, nn.TransformerEncoder(nn.TransformerEncoderLayer(d, nhead, 4d, batch_first, norm_first), L),
  * nn.Linear(81 d, 11259), value head).  Tokens are (B*81, d) row-major, bf16 (autocast) or fp32 (parity mode; its linear

@@ -116,6 +116,9 @@ _SIGS = {
     "ka_league_state_words": "i",
     "ka_league_layout": "i",
     "ka_league_step": "p iii pppppp f ppppppp f pp pppp i ppp ppp pp pp ii p",
+    "ka_selfplay_state_words": "",
+    "ka_selfplay_layout": "i",
+    "ka_selfplay_step": "p i pppppp f pppppp f pp pp pp pp ii p",
     "ka_tf_gemm_nt": "ppppp iii iii iii f q p",
     "ka_tf_gemm_nt_slabs": "ii",
     "ka_tf_gemm_nt_masked": "pppp iii iii f q p",

@@ -173,6 +173,18 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// The rollout's scalar value (katago_ppo.py:536-541 / value_adapter.py:56-65): P(W) - P(L) of the three value logits at
+// vl, blended with clamp(score_lead, -1, 1) by alpha when there is a score.  ONE body for ka_policy_sample,
+// ka_scalar_value, ka_league_step and ka_selfplay_step: the rows of a rollout and the sampler's values agree bit for bit.
+__device__ __forceinline__ float ka_blended_value(const float* vl, const float* score, float alpha) {
+    const float l0 = vl[0], l1 = vl[1], l2 = vl[2];
+    const float m = fmaxf(l0, fmaxf(l1, l2));
+    const float e0 = expf(l0 - m), e1 = expf(l1 - m), e2 = expf(l2 - m);
+    float v = (e0 - e2) / (e0 + e1 + e2);
+    if (score && alpha != 0.f) v = (1.f - alpha) * v + alpha * fminf(fmaxf(*score, -1.f), 1.f);
+    return v;
+}
+
 // Ranks of the flagged threads of one 256-thread tile, in thread order, behind the `running` flagged threads of the tiles
 // before it: *rank = running + (flagged threads below this one), -1 for a thread that is not flagged.  Returns the tile's
 // count.  One ballot per wave and a sum over the four waves (wsum: 4 ints of LDS): no atomics, so the order is the thread

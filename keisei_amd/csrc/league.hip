@@ -226,13 +226,8 @@ __global__ __launch_bounds__(kLgThreads) void league_plan_kernel(LeagueArgs a) {
         }
         // 3. open a slot where the learner just moved (:1319-1341); 4. settle it at once if that ended the game (:1343-1365)
         float value = 0.f;
-        if (step && lm) {                                       // katago_ppo.py:536-541 / value_adapter.py:56-65, as ka_policy_sample
-            const float l0 = a.vlogits[k * 3], l1 = a.vlogits[k * 3 + 1], l2 = a.vlogits[k * 3 + 2];
-            const float m = fmaxf(l0, fmaxf(l1, l2));
-            const float e0 = expf(l0 - m), e1 = expf(l1 - m), e2 = expf(l2 - m);
-            value = (e0 - e2) / (e0 + e1 + e2);
-            if (a.score_lead && a.alpha != 0.f) value = (1.f - a.alpha) * value + a.alpha * fminf(fmaxf(a.score_lead[k], -1.f), 1.f);
-        }
+        if (step && lm)                                         // katago_ppo.py:536-541 / value_adapter.py:56-65, as ka_policy_sample
+            value = ka_blended_value(a.vlogits + k * 3, a.score_lead ? a.score_lead + k : nullptr, a.alpha);
         if (step) a.values[k] = value;
         bool keep = false;
         if (open) {

@@ -304,12 +304,7 @@ __global__ void scalar_value_kernel(const float* __restrict__ vl, const float* _
                                     float* __restrict__ out, int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const float l0 = vl[b * 3], l1 = vl[b * 3 + 1], l2 = vl[b * 3 + 2];
-    const float m = fmaxf(l0, fmaxf(l1, l2));
-    const float e0 = expf(l0 - m), e1 = expf(l1 - m), e2 = expf(l2 - m);
-    float v = (e0 - e2) / (e0 + e1 + e2);
-    if (score && alpha != 0.f) v = (1.f - alpha) * v + alpha * fminf(fmaxf(score[b], -1.f), 1.f);
-    out[b] = v;
+    out[b] = ka_blended_value(vl + b * 3, score ? score + b : nullptr, alpha);
 }
 
 // Rollout side, one launch per select_actions call (katago_ppo.py:567-612: masked_fill(-inf) -> softmax -> Categorical.sample()
@@ -410,14 +405,8 @@ __global__ __launch_bounds__(kPolThreads) void policy_sample_kernel(SampleArgs a
         if (nanf_ > 0.f) atomicOr(&a.flags[0], 1);
         if (nlegal == 0.f) { atomicOr(&a.flags[1], 1); a.actions[b] = 0; a.logp[b] = 0.f; }
         a.nlegal[b] = (int)nlegal;
-        if (a.values) {                                        // katago_ppo.py:536-541 / value_adapter.py:56-65
-            const float l0 = a.vlogits[b * 3], l1 = a.vlogits[b * 3 + 1], l2 = a.vlogits[b * 3 + 2];
-            const float m = fmaxf(l0, fmaxf(l1, l2));
-            const float e0 = expf(l0 - m), e1 = expf(l1 - m), e2 = expf(l2 - m);
-            float v = (e0 - e2) / (e0 + e1 + e2);
-            if (a.score && a.alpha != 0.f) v = (1.f - a.alpha) * v + a.alpha * fminf(fmaxf(a.score[b], -1.f), 1.f);
-            a.values[b] = v;
-        }
+        if (a.values)                                          // katago_ppo.py:536-541 / value_adapter.py:56-65
+            a.values[b] = ka_blended_value(a.vlogits + b * 3, a.score ? a.score + b : nullptr, a.alpha);
     }
     if (tid == winner) {
         float run = incl - local;

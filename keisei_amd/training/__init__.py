@@ -4,3 +4,4 @@ from .dynamic_trainer import DynamicTrainer, MatchRollout  # noqa: F401
 from .game_feature_tracker import GameFeatureAccumulator, GameFeatureRow, GameFeatureTracker, classify_action  # noqa: F401
 from .league_rollout import LeagueRollout, LeagueRolloutStats  # noqa: F401
 from .match_arena import MatchArena, MatchResult, RoundStats  # noqa: F401
+from .selfplay_rollout import SelfPlayRollout, SelfPlayStats  # noqa: F401

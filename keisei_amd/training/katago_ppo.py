@@ -296,11 +296,18 @@ class KataGoRolloutBuffer:
         self._step_count += 1
 
     # ---- rows written by a kernel (LeagueRollout): reserve room, let the kernel write behind _write_offset, commit
-    def reserve(self, rows: int, device: torch.device | str | None = None) -> dict[str, torch.Tensor]:
+    def reserve(self, rows: int, device: torch.device | str | None = None, *, env_ids: bool = True) -> dict[str, torch.Tensor]:
         """Make room for ``rows`` more rows behind the ones written so far and return every column of the device store
         (``env_ids`` and ``next_value_override`` included; the tensors change when the store grows, so ask again after
         every ``reserve``).  A writer fills rows ``[_write_offset, _write_offset + rows)`` itself and then calls
-        ``commit``; nothing is appended here."""
+        ``commit``; nothing is appended here.
+
+        ``env_ids=False`` (SelfPlayRollout) reserves the dense (T, N) layout of ``add()`` calls without ``env_ids``: the
+        flag is not set and the column is not created, so ``flatten()`` has no ``env_ids``,
+        ``fill_alternating_perspective_overrides()`` acts and ``update()`` takes the (T, N) GAE.  An empty buffer takes
+        the layout of its first writer.  ``reserve(env_ids=False)`` refuses a buffer that holds ``env_ids`` rows; the
+        default ``reserve()`` keeps its earlier behaviour and does not check for dense rows (it marks the whole buffer
+        as ``env_ids`` rows), so a caller of the default form answers for the buffer it is handed."""
         if self._device is None:
             if device is None:
                 raise ValueError("reserve() on an empty buffer needs the device of its columns")
@@ -309,6 +316,16 @@ class KataGoRolloutBuffer:
             raise ValueError("reserve() serves the device-resident store (the host store is written by add())")
         if rows < 0:
             raise ValueError(f"rows must not be negative, got {rows}")
+        if not env_ids:
+            if self._has_env_ids and self._write_offset:
+                raise ValueError("reserve(env_ids=False) on a buffer that holds rows in the env_ids layout: the dense "
+                                 "(T, N) layout and the env_ids layout do not mix")
+            self._has_env_ids = False
+            self._has_next_value_override = True
+            self._ensure_capacity(rows)
+            for key in (*_FIELDS, "next_value_override"):
+                self._column(key)
+            return {k: v for k, v in self._storage.items() if k != "env_ids"}
         self._has_env_ids = self._has_next_value_override = True
         self._ensure_capacity(rows)
         for key in (*_FIELDS, "env_ids", "next_value_override"):
