@@ -582,6 +582,31 @@ int ka_selfplay_step(int* state, int envs, const float* obs, const void* mask_bi
                      float* values, float* t_obs, int* t_list, const long long* desc, int* plan, int obs_elems,
                      int mask_words, void* stream);
 
+/* ---- SL shard preparation (csrc/sl_prepare.hip; the replay keisei/sl/prepare.py:151-161 leaves out).  A batch of E game
+ * records, game g in env g, stepped in lockstep from ka_shogi_env_reset.  One ply = ka_sl_replay_plan, ka_shogi_env_step
+ * (unchanged), ka_sl_replay_record on one stream.
+ * state: int32, ka_sl_replay_state_words(0) header words {0 plies, 1 records written, 2 filler steps, 3 games cut at an
+ *   illegal move, 4 games the rules ended before the record did, 5 envs without a legal action, 6-7 copy of the VecEnv
+ *   refusal latch int64}, then cursor[E], valid_len[E], reason[E] (0 none, 1 illegal move, 2 ended by the rules).  The host
+ *   zeroes the header and the cursors and sets valid_len = the record's length before the first ply (the kernels
+ *   take no length of their own).  which: 0 = header words, 1 = arrays
+ *   of E words behind it, 2 = largest E, 3 = bytes of a shard record (16 220).
+ * plan: the move actions[offset[g] + cursor] against the packed mask row of the position to move.  Live and legal:
+ *   act = the move, write = 1.  Otherwise act = the lowest legal action (a filler: the env step refuses a batch with any
+ *   illegal action), write = 0; a live game with an illegal move is cut there (valid_len = cursor, reason 1).
+ * record: if write, shard row row_of[g] + cursor = {f32 obs[4050] of the position BEFORE the move (the env's previous
+ *   buffer), i64 policy = act, i64 value 0 / 1 / 2 = W / D / L for the mover players[e] under outcome[g] (0 black wins,
+ *   1 white wins, 2 draw), f32 score = material[e] / 76} in 4-byte stores (a row is 4-byte aligned only); rows outside
+ *   [0, rows) are not written.  A game whose step reported terminated | truncated with moves left is cut (valid_len =
+ *   cursor + 1, reason 2); the cursor advances. */
+int ka_sl_replay_state_words(int which);
+int ka_sl_replay_plan(int* state, int envs, const int* actions, int total, const int* offset, const void* mask_bits,
+                      int mask_words, long long* act, int* write, void* stream);
+int ka_sl_replay_record(int* state, int envs, const int* outcome, const int* row_of, const float* obs, int obs_elems,
+                        const void* players, const long long* act, const int* write, const int* material,
+                        const void* terminated, const void* truncated, const long long* refusal, void* shard, int rows,
+                        void* stream);
+
 /* ---- transformer encoder path (BASELINE config 5; keisei/training/models/transformer.py:37-95: nn.Linear(50, d),
  * row/col nn.Embedding, nn.TransformerEncoder(nn.TransformerEncoderLayer(d, nhead, 4d, batch_first, norm_first), L),
  * nn.Linear(81 d, 11259), value head).  Tokens are (B*81, d) row-major, bf16 (autocast) or fp32 (parity mode; its linear

@@ -119,6 +119,9 @@ _SIGS = {
     "ka_selfplay_state_words": "",
     "ka_selfplay_layout": "i",
     "ka_selfplay_step": "p i pppppp f pppppp f pp pp pp pp ii p",
+    "ka_sl_replay_state_words": "i",
+    "ka_sl_replay_plan": "p i p i p p i pp p",
+    "ka_sl_replay_record": "p i ppp i ppppppp p i p",
     "ka_tf_gemm_nt": "ppppp iii iii iii f q p",
     "ka_tf_gemm_nt_slabs": "ii",
     "ka_tf_gemm_nt_masked": "pppp iii iii f q p",
