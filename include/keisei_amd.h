@@ -607,6 +607,28 @@ int ka_sl_replay_record(int* state, int envs, const int* outcome, const int* row
                         const void* terminated, const void* truncated, const long long* refusal, void* shard, int rows,
                         void* stream);
 
+/* ---- packed, device-resident SL dataset (csrc/sl_data.hip; keisei_amd/sl/device_dataset.py).  Every channel of a shard
+ * record's observation is a 0/1 piece plane or a spatially constant plane, so a mask and one value per channel hold it bit
+ * for bit.  Packed record = KA_SL_PACKED_WORDS dwords (816 bytes, rows 16-byte aligned):
+ *   [3c, 3c+3)  c in 0..49: occupancy of channel c.  Bit p of the 96-bit little-endian field is set iff the 32-bit PATTERN
+ *               of obs[c*81 + p] is non-zero (-0.0 is non-zero); bits 81..95 are zero.
+ *   150 + c     the pattern shared by the non-zero squares of channel c; 0 when the mask is empty.
+ *   200         policy as int32;  201 value as int32;  202 the score's bits;  203 zero.
+ * A record is packable iff in every channel all non-zero patterns are equal; its targets are valid iff policy lies in
+ * [0, 11259) and value in {0, 1, 2} (the score is not inspected).
+ * pack: packed row i from the 16 220-byte record src_rows[i] (int64, device), or record i when src_rows is null; all loads
+ *   are 4-byte loads (a record is 4-byte aligned only).  flags: int32[4] {unpackable records, lowest unpackable i, records
+ *   with an invalid target, lowest such i}; the counts are added to, the indices taken as minima (the host sets them to
+ *   INT_MAX).  A flagged record's packed row is written but is not a faithful copy: the caller raises.
+ * gather: batch row b < B = packed row idx[b] (int64, device) decoded into obs_out[b] (fp32 NCHW (50, 9, 9), 8-byte
+ *   aligned), policy_out[b] / value_out[b] (int64), score_out[b] (fp32).  An idx[b] outside [0, n) adds 1 to flags[0] and
+ *   gives a row of zeros with targets 0; nothing outside the n packed rows is read. */
+#define KA_SL_PACKED_WORDS 204
+int ka_sl_packed_words(void);
+int ka_sl_pack(const void* records, const long long* src_rows, int n, void* packed_out, int* flags, void* stream);
+int ka_sl_gather(const void* packed, long long n, const long long* idx, int B, float* obs_out, long long* policy_out,
+                 long long* value_out, float* score_out, int* flags, void* stream);
+
 /* ---- transformer encoder path (BASELINE config 5; keisei/training/models/transformer.py:37-95: nn.Linear(50, d),
  * row/col nn.Embedding, nn.TransformerEncoder(nn.TransformerEncoderLayer(d, nhead, 4d, batch_first, norm_first), L),
  * nn.Linear(81 d, 11259), value head).  Tokens are (B*81, d) row-major, bf16 (autocast) or fp32 (parity mode; its linear

@@ -122,6 +122,9 @@ _SIGS = {
     "ka_sl_replay_state_words": "i",
     "ka_sl_replay_plan": "p i p i p p i pp p",
     "ka_sl_replay_record": "p i ppp i ppppppp p i p",
+    "ka_sl_packed_words": "",
+    "ka_sl_pack": "pp i pp p",
+    "ka_sl_gather": "p q p i ppppp p",
     "ka_tf_gemm_nt": "ppppp iii iii iii f q p",
     "ka_tf_gemm_nt_slabs": "ii",
     "ka_tf_gemm_nt_masked": "pppp iii iii f q p",

@@ -1,0 +1,146 @@
+// The packed, device-resident SL dataset (keisei_amd/sl/device_dataset.py).  A shard record is 4050 floats of observation, but
+// each of its 50 channels is a 0/1 piece plane or a spatially constant plane: the non-zero squares of a plane share one
+// 32-bit pattern.  Three mask words and one value word per channel reproduce the observation bit for bit -- 816 bytes
+// instead of 16 220 -- so a whole corpus stays in HBM and a minibatch is one launch with no host work.
+//
+// Packed record, KA_SL_PACKED_WORDS = 204 dwords (include/keisei_amd.h is the contract):
+//   [3c, 3c+3)  occupancy of channel c: bit p of the 96-bit little-endian field is set iff the PATTERN of obs[c*81 + p] is
+//               non-zero (-0.0 is non-zero); bits 81..95 are zero
+//   150 + c     the pattern the non-zero squares of channel c share, 0 for an empty mask
+//   200, 201    policy, value (int32);  202 the score's bits;  203 zero
+//
+//   sl_pack_kernel    one workgroup per record, wave w takes channels w, w+4, ...: lanes load squares 0..63 and 64..80, two
+//                     ballots are the mask, the value is the pattern of the lowest set lane, a third ballot (non-zero and
+//                     not the value) says whether the record can be held packed at all.  The 204 words go through LDS and
+//                     out in one coalesced store.  A source row starts at 16 220 * r bytes, 8-byte aligned only for even r:
+//                     every load is a 4-byte load, the int64 targets as two dwords each.
+//   sl_gather_kernel  one workgroup per batch row: the 816 bytes of row idx[b] into LDS, then the 16 200-byte NCHW fp32
+//                     observation as coalesced 8-byte stores (a row of obs_out starts at 16 200 * b bytes: 8-byte aligned
+//                     only) and the three targets.  An index outside [0, n) counts in the flag word and gives a zero row:
+//                     nothing outside the dataset is read.
+// Both are memory-bound copies; nothing in them is tuned further.
+#include "common.h"
+
+#include <limits.h>
+
+namespace {
+
+constexpr int kPkThreads = 256;
+constexpr int kPkWaves = kPkThreads / 64;
+constexpr int kPkChannels = 50;
+constexpr int kPkSquares = 81;
+constexpr int kPkObsWords = kPkChannels * kPkSquares;         // 4050
+constexpr int kPkRowWords = kPkObsWords + 5;                   // 16 220 B: obs, i64 policy, i64 value, f32 score
+constexpr int kPkValueAt = 3 * kPkChannels;                    // 150
+constexpr int kPkPolicyAt = kPkValueAt + kPkChannels;          // 200
+constexpr int kPkWords = kPkPolicyAt + 4;                      // 204
+constexpr uint32_t kPkActions = 81 * 139;
+static_assert(kPkWords * 4 % 16 == 0, "packed rows are 16-byte aligned");
+static_assert(kPkObsWords % 2 == 0, "the gather stores pairs");
+
+__global__ __launch_bounds__(kPkThreads) void sl_pack_kernel(const uint32_t* __restrict__ records,
+                                                             const long long* __restrict__ src_rows, int n,
+                                                             uint32_t* __restrict__ packed, int* __restrict__ flags) {
+    __shared__ uint32_t s_row[kPkWords];
+    __shared__ int s_bad[kPkWaves];
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (i >= n) return;
+    const long long r = src_rows ? src_rows[i] : (long long)i;
+    const uint32_t* src = records + (size_t)r * kPkRowWords;
+    bool bad = false;
+    for (int c = wave; c < kPkChannels; c += kPkWaves) {         // wave-uniform bounds: all 64 lanes reach every ballot
+        const uint32_t* plane = src + c * kPkSquares;
+        const uint32_t x0 = plane[lane];
+        const uint32_t x1 = lane < kPkSquares - 64 ? plane[64 + lane] : 0u;
+        const unsigned long long m0 = __ballot(x0 != 0u), m1 = __ballot(x1 != 0u);
+        const uint32_t v0 = __shfl(x0, m0 ? __ffsll(m0) - 1 : 0);
+        const uint32_t v1 = __shfl(x1, m1 ? __ffsll(m1) - 1 : 0);
+        const uint32_t value = m0 ? v0 : v1;                      // (no set lane at all: x1 of lane 0, which is 0)
+        bad |= __ballot((x0 != 0u && x0 != value) || (x1 != 0u && x1 != value)) != 0ull;
+        if (lane == 0) {
+            s_row[3 * c + 0] = (uint32_t)m0;
+            s_row[3 * c + 1] = (uint32_t)(m0 >> 32);
+            s_row[3 * c + 2] = (uint32_t)m1;
+            s_row[kPkValueAt + c] = value;
+        }
+    }
+    if (lane == 0) s_bad[wave] = bad;
+    bool bad_target = false;
+    if (tid == 0) {
+        const uint32_t* t = src + kPkObsWords;
+        const uint32_t pol_lo = t[0], pol_hi = t[1], val_lo = t[2], val_hi = t[3];
+        bad_target = pol_hi != 0u || pol_lo >= kPkActions || val_hi != 0u || val_lo > 2u;
+        s_row[kPkPolicyAt + 0] = pol_lo;
+        s_row[kPkPolicyAt + 1] = val_lo;
+        s_row[kPkPolicyAt + 2] = t[4];
+        s_row[kPkPolicyAt + 3] = 0u;
+    }
+    __syncthreads();
+    if (tid < kPkWords) packed[(size_t)i * kPkWords + tid] = s_row[tid];
+    if (tid == 0) {
+        bool unpackable = false;
+        for (int w = 0; w < kPkWaves; ++w) unpackable |= s_bad[w] != 0;
+        if (unpackable) { atomicAdd(flags + 0, 1); atomicMin(flags + 1, i); }
+        if (bad_target) { atomicAdd(flags + 2, 1); atomicMin(flags + 3, i); }
+    }
+}
+
+__global__ __launch_bounds__(kPkThreads) void sl_gather_kernel(const uint32_t* __restrict__ packed, long long n,
+                                                               const long long* __restrict__ idx, int B,
+                                                               uint32_t* __restrict__ obs_out, long long* __restrict__ policy_out,
+                                                               long long* __restrict__ value_out, uint32_t* __restrict__ score_out,
+                                                               int* __restrict__ flags) {
+    __shared__ uint32_t s_row[kPkWords];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (b >= B) return;
+    const long long r = idx[b];
+    const bool inside = r >= 0 && r < n;                           // uniform over the workgroup
+    if (tid < kPkWords) s_row[tid] = inside ? packed[(size_t)r * kPkWords + tid] : 0u;
+    __syncthreads();
+    uint2* dst = reinterpret_cast<uint2*>(obs_out + (size_t)b * kPkObsWords);
+    for (int j = tid; j < kPkObsWords / 2; j += kPkThreads) {
+        uint2 out;
+        {
+            const int e = 2 * j, c = e / kPkSquares, p = e - c * kPkSquares;
+            out.x = (s_row[3 * c + (p >> 5)] >> (p & 31)) & 1u ? s_row[kPkValueAt + c] : 0u;
+        }
+        {
+            const int e = 2 * j + 1, c = e / kPkSquares, p = e - c * kPkSquares;
+            out.y = (s_row[3 * c + (p >> 5)] >> (p & 31)) & 1u ? s_row[kPkValueAt + c] : 0u;
+        }
+        dst[j] = out;
+    }
+    if (tid == 0) {
+        policy_out[b] = (long long)(int)s_row[kPkPolicyAt + 0];
+        value_out[b] = (long long)(int)s_row[kPkPolicyAt + 1];
+        score_out[b] = s_row[kPkPolicyAt + 2];
+        if (!inside) atomicAdd(flags, 1);
+    }
+}
+
+}  // namespace
+
+extern "C" int ka_sl_packed_words(void) { return kPkWords; }
+
+extern "C" int ka_sl_pack(const void* records, const long long* src_rows, int n, void* packed_out, int* flags, void* stream) {
+    KA_REQUIRE(records && packed_out && flags, "sl_pack: null tensor");
+    KA_REQUIRE(n > 0, "sl_pack: n %d", n);
+    KA_REQUIRE((reinterpret_cast<uintptr_t>(records) & 3) == 0 && (reinterpret_cast<uintptr_t>(packed_out) & 3) == 0,
+               "sl_pack: the records and the packed rows must be 4-byte aligned");
+    hipLaunchKernelGGL(sl_pack_kernel, dim3(n), dim3(kPkThreads), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint32_t*>(records), src_rows, n, static_cast<uint32_t*>(packed_out), flags);
+    return ka_check_launch("sl_pack");
+}
+
+extern "C" int ka_sl_gather(const void* packed, long long n, const long long* idx, int B, float* obs_out,
+                            long long* policy_out, long long* value_out, float* score_out, int* flags, void* stream) {
+    KA_REQUIRE(idx && obs_out && policy_out && value_out && score_out && flags, "sl_gather: null tensor");
+    KA_REQUIRE(n >= 0 && (packed || n == 0), "sl_gather: n %lld without a dataset", n);
+    KA_REQUIRE(B > 0, "sl_gather: B %d", B);
+    KA_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 3) == 0 && (reinterpret_cast<uintptr_t>(obs_out) & 7) == 0,
+               "sl_gather: the packed rows must be 4-byte aligned and the observations 8-byte aligned");
+    hipLaunchKernelGGL(sl_gather_kernel, dim3(B), dim3(kPkThreads), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint32_t*>(packed), n, idx, B, reinterpret_cast<uint32_t*>(obs_out), policy_out,
+                       value_out, reinterpret_cast<uint32_t*>(score_out), flags);
+    return ka_check_launch("sl_gather");
+}

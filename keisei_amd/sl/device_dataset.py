@@ -1,0 +1,298 @@
+"""The SL position dataset held packed in device memory (csrc/sl_data.hip; an addition the reference does not have).
+
+Every channel of a shard record's observation is a 0/1 piece plane or a spatially constant plane, so three mask words and
+one value word per channel reproduce its 4050 floats bit for bit: a packed record is 204 dwords (816 bytes, the layout is
+in include/keisei_amd.h) instead of 16 220 bytes.  ``DeviceSLDataset`` keeps the whole dataset that way in ONE device
+allocation; a minibatch is one ``ka_sl_gather`` launch that decodes the rows of an index tensor into the fp32 NCHW
+observations and the targets ``SLDataset.read_batch`` would give -- no memory map, no pinned copy, no upload per batch.
+
+It is filled from a shard directory (``from_shards``: the files stream through two pinned staging buffers and are packed
+on arrival) or from records that are already on the device (``append_raw``: the growth path of
+``keisei_amd.sl.prepare.prepare_sl_dataset``, which never touches the disk).  A record that cannot be held packed, or whose
+targets ``SLDataset`` would refuse, is never stored in altered form: the load raises.
+
+``pack_records`` / ``unpack_records`` are the two kernels in numpy: the yardstick the GPU tests hold them to, byte for byte.
+"""
+from __future__ import annotations
+
+from pathlib import Path
+from typing import Callable, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from keisei_amd import _lib
+from keisei_amd.sl.dataset import NUM_ACTIONS, OBS_SIZE, RECORD_SIZE, SLDataset, _RECORD
+
+__all__ = ["DeviceSLDataset", "pack_records", "unpack_records", "PACKED_WORDS", "PACKED_BYTES"]
+
+PACKED_WORDS = 204                       # KA_SL_PACKED_WORDS
+PACKED_BYTES = 4 * PACKED_WORDS
+_CHANNELS, _SQUARES = 50, 81
+_VALUE_AT, _POLICY_AT = 3 * _CHANNELS, 4 * _CHANNELS
+_INT_MAX = 2 ** 31 - 1
+_UNPACKABLE = "channel values are not one-valued planes; this dataset cannot be held packed"
+
+
+# ---------------------------------------------------------------------------------------------- host restatement
+def _as_records(records) -> np.ndarray:
+    rec = np.asarray(records)
+    if rec.dtype != _RECORD:
+        raise TypeError(f"records must have the shard record dtype, got {rec.dtype}")
+    return rec.reshape(-1)
+
+
+def _obs_bits(rec: np.ndarray) -> np.ndarray:
+    return np.ascontiguousarray(rec["obs"]).view(np.uint32).reshape(len(rec), _CHANNELS, _SQUARES)
+
+
+def record_faults(records) -> Tuple[np.ndarray, np.ndarray]:
+    """``(unpackable, bad_target)``, one bool per record: some channel holds two different non-zero patterns; the policy
+    lies outside [0, 11259) or the value outside {0, 1, 2} (the rule of ``SLDataset._check_targets``)."""
+    rec = _as_records(records)
+    bits = _obs_bits(rec)
+    nonzero = bits != 0
+    value = np.take_along_axis(bits, nonzero.argmax(axis=2)[..., None], axis=2)      # the lowest non-zero square's pattern
+    unpackable = (nonzero & (bits != value)).any(axis=(1, 2))
+    policy, val = rec["policy"], rec["value"]
+    bad_target = (policy < 0) | (policy >= NUM_ACTIONS) | (val < 0) | (val > 2)
+    return unpackable, bad_target
+
+
+def pack_records(records) -> Tuple[np.ndarray, Optional[int]]:
+    """``ka_sl_pack`` in numpy: ``(uint32[n, 204], first_bad)``.  ``first_bad`` is the lowest index of a record that is not
+    packable or has an invalid target (``record_faults`` says which), None when there is none; such a record's packed row
+    is what the kernel writes for it, not a faithful copy."""
+    rec = _as_records(records)
+    n = len(rec)
+    bits = _obs_bits(rec)
+    nonzero = bits != 0
+    out = np.zeros((n, PACKED_WORDS), dtype=np.uint32)
+    field = np.zeros((n, _CHANNELS, 96), dtype=np.uint32)
+    field[:, :, :_SQUARES] = nonzero
+    weights = np.uint32(1) << np.arange(32, dtype=np.uint32)
+    out[:, :_VALUE_AT] = (field.reshape(n, _CHANNELS, 3, 32) * weights).sum(axis=3, dtype=np.uint32).reshape(n, _VALUE_AT)
+    value = np.take_along_axis(bits, nonzero.argmax(axis=2)[..., None], axis=2)[..., 0]
+    out[:, _VALUE_AT:_POLICY_AT] = np.where(nonzero.any(axis=2), value, 0)
+    out[:, _POLICY_AT + 0] = rec["policy"].astype(np.int64).view(np.uint64).astype(np.uint32)      # the low dword
+    out[:, _POLICY_AT + 1] = rec["value"].astype(np.int64).view(np.uint64).astype(np.uint32)
+    out[:, _POLICY_AT + 2] = np.ascontiguousarray(rec["score"]).view(np.uint32)
+    unpackable, bad_target = record_faults(rec)
+    bad = np.nonzero(unpackable | bad_target)[0]
+    return out, (int(bad[0]) if bad.size else None)
+
+
+def unpack_records(packed) -> np.ndarray:
+    """``ka_sl_gather`` in numpy: the shard records of packed rows ``uint32[n, 204]``."""
+    pk = np.ascontiguousarray(packed, dtype=np.uint32).reshape(-1, PACKED_WORDS)
+    n = len(pk)
+    squares = np.arange(_SQUARES)
+    words = pk[:, :_VALUE_AT].reshape(n, _CHANNELS, 3)[:, :, squares >> 5]            # (n, 50, 81): the word of square p
+    mask = ((words >> (squares & 31).astype(np.uint32)) & np.uint32(1)).astype(bool)
+    bits = np.where(mask, pk[:, _VALUE_AT:_POLICY_AT, None], np.uint32(0)).astype(np.uint32)
+    rec = np.zeros(n, dtype=_RECORD)
+    rec["obs"] = bits.reshape(n, OBS_SIZE).view(np.float32)
+    rec["policy"] = pk[:, _POLICY_AT + 0].view(np.int32).astype(np.int64)
+    rec["value"] = pk[:, _POLICY_AT + 1].view(np.int32).astype(np.int64)
+    rec["score"] = pk[:, _POLICY_AT + 2].view(np.float32)
+    return rec
+
+
+# ---------------------------------------------------------------------------------------------- the device dataset
+def _require_library() -> None:
+    words = _lib.query("ka_sl_packed_words")                    # raises KeiseiHipError without the library
+    if words != PACKED_WORDS:
+        raise _lib.KeiseiHipError(f"libkeisei_amd.so packs a position into {words} words, keisei_amd.sl.device_dataset "
+                                  f"into {PACKED_WORDS}: rebuild the library")
+
+
+def _fresh_flags(rows: int, device) -> torch.Tensor:
+    return torch.tensor([0, _INT_MAX, 0, _INT_MAX], dtype=torch.int32).repeat(rows, 1).to(device)
+
+
+class DeviceSLDataset:
+    """Positions packed in device memory, in the order they were added.  ``read_batch`` / ``gather`` decode rows."""
+
+    def __init__(self, device=None) -> None:
+        _require_library()
+        if not torch.cuda.is_available():
+            raise _lib.KeiseiHipError("DeviceSLDataset needs a GPU: the dataset lives in device memory")
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise ValueError(f"DeviceSLDataset lives on a GPU, got device {dev}")
+        self._device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+        self._packed = torch.empty(0, PACKED_WORDS, dtype=torch.int32, device=self._device)
+        self._n = 0
+        # flags of the pack launches not read yet: (index of the launch's first position, int32[4] on the device)
+        self._unread: List[Tuple[int, torch.Tensor]] = []
+
+    # ------------------------------------------------------------------ properties
+    def __len__(self) -> int:
+        return self._n
+
+    @property
+    def device(self) -> torch.device:
+        return self._device
+
+    @property
+    def nbytes(self) -> int:
+        """Device bytes the positions occupy (the allocation may be larger while the dataset grows)."""
+        return self._n * PACKED_BYTES
+
+    @property
+    def packed(self) -> torch.Tensor:
+        """The packed rows, int32 ``(len, 204)``: a view of the dataset's memory."""
+        return self._packed[:self._n]
+
+    # ------------------------------------------------------------------ filling
+    def _reserve(self, total: int) -> None:
+        """Room for ``total`` positions; growth doubles, the rows keep their order."""
+        cap = self._packed.shape[0]
+        if total <= cap:
+            return
+        with torch.cuda.device(self._device):
+            grown = torch.empty(max(total, 2 * cap, 1024), PACKED_WORDS, dtype=torch.int32, device=self._device)
+            grown[:self._n].copy_(self._packed[:self._n])
+        self._packed = grown
+
+    def _pack(self, raw: torch.Tensor, src_rows: Optional[torch.Tensor], count: int, flags: torch.Tensor) -> None:
+        """Queue ``ka_sl_pack`` of ``count`` records onto the end (room reserved by the caller)."""
+        with torch.cuda.device(self._device):
+            _lib.call("ka_sl_pack", raw, src_rows, count, self._packed[self._n:], flags, _lib.stream_ptr(self._device))
+        self._unread.append((self._n, flags))
+        self._n += count
+
+    def append_raw(self, raw_device_bytes: torch.Tensor, src_rows) -> None:
+        """Pack the records ``src_rows`` (row numbers, in the order they are to be appended) of a device buffer of
+        16 220-byte records onto the end.  Nothing is read back: ``check()`` reports what could not be packed."""
+        raw = raw_device_bytes
+        if raw.dtype != torch.uint8 or not raw.is_contiguous() or raw.device != self._device or raw.numel() % RECORD_SIZE:
+            raise ValueError(f"raw_device_bytes must be a contiguous uint8 tensor of whole {RECORD_SIZE}-byte records "
+                             f"on {self._device}")
+        rows = np.ascontiguousarray(src_rows.cpu().numpy() if isinstance(src_rows, torch.Tensor) else src_rows,
+                                    dtype=np.int64).reshape(-1)
+        total = raw.numel() // RECORD_SIZE
+        if rows.size and (rows.min() < 0 or rows.max() >= total):
+            bad = int(rows[(rows < 0) | (rows >= total)][0])
+            raise IndexError(f"source row {bad} out of range for a buffer of {total} records")
+        if rows.size == 0:
+            return
+        self._reserve(self._n + rows.size)
+        self._pack(raw, torch.from_numpy(rows).to(self._device), int(rows.size), _fresh_flags(1, self._device)[0])
+
+    def check(self, describe: Optional[Callable[[int, bool], None]] = None) -> None:
+        """Read the flags of every pack launch since the last check -- one read -- and raise ``ValueError`` for the
+        lowest position that has an invalid target or cannot be held packed.  ``describe(index, bad_target)`` may raise a
+        message of its own first (``from_shards`` names the shard)."""
+        if not self._unread:
+            return
+        starts = [s for s, _ in self._unread]
+        host = torch.stack([f for _, f in self._unread]).cpu().numpy()
+        self._unread = []
+        faults = []                                              # (index, 0 for a bad target / 1 for unpackable)
+        for start, (unpackable, at_u, bad_target, at_t) in zip(starts, host.tolist()):
+            if bad_target:
+                faults.append((start + at_t, 0))
+            if unpackable:
+                faults.append((start + at_u, 1))
+        if not faults:
+            return
+        index, kind = min(faults)
+        if describe is not None:
+            describe(index, kind == 0)
+        if kind == 0:
+            policy, value = self._packed[index, _POLICY_AT:_POLICY_AT + 2].cpu().tolist()
+            raise ValueError(f"Invalid targets (policy_target={policy}, value_target={value} as stored) at index {index}: "
+                             f"policy must be in [0, {NUM_ACTIONS}), value 0 (W), 1 (D), or 2 (L)")
+        raise ValueError(f"Unpackable observation at index {index}: {_UNPACKABLE}")
+
+    @classmethod
+    def from_shards(cls, data_dir, *, device=None, chunk_records: int = 8192,
+                    allow_placeholder: bool = False) -> "DeviceSLDataset":
+        """The positions of a shard directory, in ``SLDataset``'s order (which also refuses placeholder data and warns
+        about the files).  The maps stream in chunks of ``chunk_records`` -- a chunk may straddle files -- through two pinned
+        staging buffers and a copy stream; each chunk is packed on arrival into its place in one device allocation."""
+        if chunk_records < 1:
+            raise ValueError(f"chunk_records must be >= 1, got {chunk_records}")
+        source = SLDataset(Path(data_dir), allow_placeholder=allow_placeholder)
+        self = cls(device)
+        dev, n = self._device, len(source)
+        if n == 0:
+            return self
+        if n > _INT_MAX:
+            raise ValueError(f"{n} positions: a device dataset holds at most {_INT_MAX}")
+        chunk = min(int(chunk_records), n)
+        chunks = (n + chunk - 1) // chunk
+        needed = n * PACKED_BYTES + 2 * chunk * RECORD_SIZE
+        free = torch.cuda.mem_get_info(dev)[0]
+        if needed > free:
+            raise ValueError(f"The dataset in {data_dir} does not fit on {dev}: {n} positions need {needed} bytes "
+                             f"({n * PACKED_BYTES} packed + {2 * chunk * RECORD_SIZE} staging), {free} bytes are free")
+        with torch.cuda.device(dev):
+            self._packed = torch.empty(n, PACKED_WORDS, dtype=torch.int32, device=dev)
+            flags = _fresh_flags(chunks, dev)
+            pinned = [torch.empty(chunk * RECORD_SIZE, dtype=torch.uint8).pin_memory() for _ in range(2)]
+            staged = [torch.empty(chunk * RECORD_SIZE, dtype=torch.uint8, device=dev) for _ in range(2)]
+            packed_ev: List[Optional[torch.cuda.Event]] = [None, None]
+            main, copy_stream = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+            shard, local = 0, 0
+            for k in range(chunks):
+                slot, count = k & 1, min(chunk, n - k * chunk)
+                if packed_ev[slot] is not None:
+                    packed_ev[slot].synchronize()                # chunk k - 2 has left both buffers of this slot
+                host = pinned[slot].numpy()[:count * RECORD_SIZE].view(_RECORD)
+                filled = 0
+                while filled < count:
+                    take = min(count - filled, source.shards[shard][1] - local)
+                    host[filled:filled + take] = source._records(shard)[local:local + take]
+                    filled, local = filled + take, local + take
+                    if local == source.shards[shard][1]:
+                        shard, local = shard + 1, 0
+                with torch.cuda.stream(copy_stream):
+                    staged[slot][:count * RECORD_SIZE].copy_(pinned[slot][:count * RECORD_SIZE], non_blocking=True)
+                    arrived = torch.cuda.Event()
+                    arrived.record(copy_stream)
+                main.wait_event(arrived)
+                self._pack(staged[slot], None, count, flags[k])
+                packed_ev[slot] = torch.cuda.Event()
+                packed_ev[slot].record(main)
+
+        def describe(index: int, bad_target: bool) -> None:
+            at, where = source._locate(index)
+            rec = source._records(at)[where]
+            if bad_target:
+                source._check_targets(int(rec["policy"]), int(rec["value"]), index, at, where)
+            raise ValueError(f"Unpackable observation at index {index} (shard={source.shards[at][0].name}, local={where}): "
+                             f"{_UNPACKABLE}")
+
+        self.check(describe)                                     # the one read of the flags (it also ends the copies)
+        source.clear_cache()
+        return self
+
+    # ------------------------------------------------------------------ reading
+    def gather(self, idx: torch.Tensor, flag: torch.Tensor) -> dict:
+        """The batch of the int64 device tensor ``idx`` as fresh device tensors, keys / dtypes / shapes of
+        ``SLDataset.read_batch``: one launch, no host work.  An index outside the dataset adds 1 to ``flag`` (int32[1] on
+        the device) and gives a zero row."""
+        if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != self._device or not idx.is_contiguous():
+            raise ValueError(f"idx must be a contiguous 1-d int64 tensor on {self._device}")
+        B, dev = idx.shape[0], self._device
+        with torch.cuda.device(dev):
+            out = {"observation": torch.empty(B, _CHANNELS, 9, 9, dtype=torch.float32, device=dev),
+                   "policy_target": torch.empty(B, dtype=torch.int64, device=dev),
+                   "value_target": torch.empty(B, dtype=torch.int64, device=dev),
+                   "score_target": torch.empty(B, dtype=torch.float32, device=dev)}
+            if B:
+                _lib.call("ka_sl_gather", self._packed, self._n, idx, B, out["observation"], out["policy_target"],
+                          out["value_target"], out["score_target"], flag, _lib.stream_ptr(dev))
+        return out
+
+    def read_batch(self, indices) -> dict:
+        """``SLDataset.read_batch(indices)`` as device tensors.  (The range check on the host is this convenience
+        method's; the training epoch reads the kernel's flag once instead.)"""
+        idx = np.asarray(indices.cpu() if isinstance(indices, torch.Tensor) else indices, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= self._n):
+            bad = int(idx[(idx < 0) | (idx >= self._n)][0])
+            raise IndexError(f"index {bad} out of range for dataset with {self._n} positions")
+        return self.gather(torch.from_numpy(np.ascontiguousarray(idx)).to(self._device),
+                           torch.zeros(1, dtype=torch.int32, device=self._device))

@@ -19,6 +19,10 @@ fall inside a game.  What differs is where a position comes from:
 A game is cut, keeping the positions before the cut, at a move that has no spatial encoding or is not legal, where the
 rules end it before the record does, and at ``max_moves``.  Only games from the standard start position are replayed.
 
+``prepare_sl_dataset`` is the same preparation without the disk (not in the reference): the same games, batches, cuts and
+counters, but the kept records of every batch are packed from the replay's device buffer straight onto a
+``keisei_amd.sl.device_dataset.DeviceSLDataset``; no shard file, no pinned copy, no ``shard_meta.json``.
+
 ``_replay_host`` is the same bookkeeping in numpy over any VecEnv-shaped object (the CPU oracle in the tests): the
 yardstick the kernels are held to.
 """
@@ -43,7 +47,7 @@ from keisei_amd.sl.parsers import (CSAParser, GameFilter, GameOutcome, GameParse
 
 logger = logging.getLogger(__name__)
 
-__all__ = ["prepare_sl_data", "usi_to_action", "ReplayBatch", "main"]
+__all__ = ["prepare_sl_data", "prepare_sl_dataset", "usi_to_action", "ReplayBatch", "main"]
 
 # why a game's record was not used to its end
 REASON_NONE, REASON_ILLEGAL, REASON_RULES, REASON_LONG, REASON_NO_ENCODING = 0, 1, 2, 3, 4
@@ -426,35 +430,18 @@ def prepare_sl_data(game_sources: List[str], output_dir: str, min_ply: int = 40,
                     batch_envs=batch_envs, max_moves=max_moves, max_batch_positions=max_batch_positions)
 
 
-def _prepare(game_sources: Sequence[str], output_dir: str, game_filter: GameFilter, shard_size: int, replay, *,
-             batch_envs: int, max_moves: int, max_batch_positions: int) -> dict:
-    """Everything of ``prepare_sl_data`` around the replay; ``replay(batch)`` is ``_DeviceReplay.replay`` (or, in the CPU
-    tests, ``_replay_host`` over the oracle)."""
-    out = Path(output_dir)
-    out.mkdir(parents=True, exist_ok=True)
-    meta_path = out / "shard_meta.json"
-    # what an earlier run left goes first: SLDataset reads every shard_*.bin it finds, and this run may write fewer
-    for old in [*out.glob("shard_*.bin"), meta_path]:
-        old.unlink(missing_ok=True)
+def _new_counters() -> dict:
+    return dict(games=0, skipped=0, parse_errors=0, illegal=0, rules=0, long=0, nonstandard=0, filler=0, steps=0)
 
+
+def _game_batches(game_sources: Sequence[str], game_filter: GameFilter, count: dict, *, batch_envs: int, max_moves: int,
+                  max_batch_positions: int) -> Iterator[List[tuple]]:
+    """The game iteration of ``prepare_sl_data`` and ``prepare_sl_dataset``: discover the files, parse and filter the
+    records, encode the accepted games as ``(actions, outcome, host reason)`` and hand them out in replay batches.
+    ``count`` is counted into while the batches are drawn."""
     parsers = _parsers_by_extension()
     game_files = _discover(game_sources, parsers)
     logger.info("%d game files in %d sources", len(game_files), len(game_sources))
-
-    writer = _ShardWriter(out, shard_size)
-    count = dict(games=0, skipped=0, parse_errors=0, illegal=0, rules=0, long=0, nonstandard=0, filler=0, steps=0)
-
-    def run(games) -> None:
-        batch = ReplayBatch.build(games)
-        buf, valid_len, reason, hdr = replay(batch)
-        host_reason = np.asarray([g[2] for g in games], np.int32)[batch.order]
-        final = np.where(reason[:len(games)] != REASON_NONE, reason[:len(games)], host_reason)
-        count["illegal"] += int(((final == REASON_ILLEGAL) | (final == REASON_NO_ENCODING)).sum())
-        count["rules"] += int((final == REASON_RULES).sum())
-        count["filler"] += int(hdr[_FILLER])
-        count["steps"] += int(hdr[_FILLER] + hdr[_WRITTEN])
-        if batch.rows:
-            writer.append(buf[_kept_rows(batch, valid_len)])
 
     def accepted() -> Iterator[tuple]:
         for game_file in game_files:
@@ -475,23 +462,106 @@ def _prepare(game_sources: Sequence[str], output_dir: str, game_filter: GameFilt
                     count["long"] += int(why == REASON_LONG)
                     yield actions, _OUTCOME[record.outcome], why
 
-    for games in _batches(accepted(), batch_envs, max_batch_positions):
-        run(games)
-    writer.close()
+    return _batches(accepted(), batch_envs, max_batch_positions)
 
-    meta = {"placeholder": False, "num_shards": writer.num_shards, "num_games": count["games"],
-            "num_positions": writer.num_positions, "games_cut_illegal": count["illegal"],
+
+def _count_replay(count: dict, games: List[tuple], batch: ReplayBatch, reason: np.ndarray, hdr: np.ndarray) -> None:
+    """What one replayed batch adds to the counters: the cuts (the device's reason, else the host's) and the fillers."""
+    host_reason = np.asarray([g[2] for g in games], np.int32)[batch.order]
+    final = np.where(reason[:len(games)] != REASON_NONE, reason[:len(games)], host_reason)
+    count["illegal"] += int(((final == REASON_ILLEGAL) | (final == REASON_NO_ENCODING)).sum())
+    count["rules"] += int((final == REASON_RULES).sum())
+    count["filler"] += int(hdr[_FILLER])
+    count["steps"] += int(hdr[_FILLER] + hdr[_WRITTEN])
+
+
+def _meta_of(count: dict, num_positions: int, num_shards: Optional[int] = None) -> dict:
+    meta = {"placeholder": False, "num_shards": num_shards, "num_games": count["games"],
+            "num_positions": num_positions, "games_cut_illegal": count["illegal"],
             "games_cut_by_rules": count["rules"], "games_cut_long": count["long"],
             "games_nonstandard_start": count["nonstandard"]}
+    if num_shards is None:
+        del meta["num_shards"]
+    return meta
+
+
+def _log_summary(what: str, num_positions: int, count: dict) -> None:
+    logger.info("Prepared %s (%d positions) from %d games: %d skipped by filter, %d parse errors, %d not from the "
+                "standard start; cut: %d illegal, %d by the rules, %d long; %d of %d env steps were fillers",
+                what, num_positions, count["games"], count["skipped"], count["parse_errors"],
+                count["nonstandard"], count["illegal"], count["rules"], count["long"], count["filler"], count["steps"])
+
+
+def _prepare(game_sources: Sequence[str], output_dir: str, game_filter: GameFilter, shard_size: int, replay, *,
+             batch_envs: int, max_moves: int, max_batch_positions: int) -> dict:
+    """Everything of ``prepare_sl_data`` around the replay; ``replay(batch)`` is ``_DeviceReplay.replay`` (or, in the CPU
+    tests, ``_replay_host`` over the oracle)."""
+    out = Path(output_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    meta_path = out / "shard_meta.json"
+    # what an earlier run left goes first: SLDataset reads every shard_*.bin it finds, and this run may write fewer
+    for old in [*out.glob("shard_*.bin"), meta_path]:
+        old.unlink(missing_ok=True)
+
+    writer = _ShardWriter(out, shard_size)
+    count = _new_counters()
+    for games in _game_batches(game_sources, game_filter, count, batch_envs=batch_envs, max_moves=max_moves,
+                               max_batch_positions=max_batch_positions):
+        batch = ReplayBatch.build(games)
+        buf, valid_len, reason, hdr = replay(batch)
+        _count_replay(count, games, batch, reason, hdr)
+        if batch.rows:
+            writer.append(buf[_kept_rows(batch, valid_len)])
+    writer.close()
+
+    meta = _meta_of(count, writer.num_positions, writer.num_shards)
     # written beside the target and moved over it: a reader sees the old metadata, none, or all of the new
     partial = out / "shard_meta.json.tmp"
     partial.write_text(json.dumps(meta, indent=2) + "\n")
     partial.replace(meta_path)
-    logger.info("Prepared %d shards (%d positions) from %d games: %d skipped by filter, %d parse errors, %d not from the "
-                "standard start; cut: %d illegal, %d by the rules, %d long; %d of %d env steps were fillers",
-                writer.num_shards, writer.num_positions, count["games"], count["skipped"], count["parse_errors"],
-                count["nonstandard"], count["illegal"], count["rules"], count["long"], count["filler"], count["steps"])
+    _log_summary(f"{writer.num_shards} shards", writer.num_positions, count)
     return meta
+
+
+def _replay_onto(dataset, replay: _DeviceReplay, batch: ReplayBatch, raw: Optional[torch.Tensor]):
+    """Replay one batch into the reused device buffer ``raw`` (grown when the batch needs more) and pack its kept records
+    onto ``dataset``; the records never leave the device.  Returns ``(raw, reason, header)``."""
+    if batch.rows == 0:
+        return raw, np.zeros(batch.num_envs, np.int32), np.zeros(8, np.int64)
+    nbytes = batch.rows * RECORD_SIZE
+    if raw is None or raw.numel() < nbytes:
+        raw = None
+        with torch.cuda.device(replay.device):
+            raw = torch.empty(nbytes, dtype=torch.uint8, device=replay.device)
+    _, valid_len, reason, hdr = replay.replay(batch, out=raw[:nbytes])         # valid_len: the one read of the state
+    dataset.append_raw(raw[:nbytes], np.nonzero(_kept_rows(batch, valid_len))[0])
+    return raw, reason, hdr
+
+
+def prepare_sl_dataset(game_sources: Sequence[str], min_ply: int = 40, min_rating: Optional[int] = None, *, device=None,
+                       batch_envs: int = 512, max_moves: int = 512, max_batch_positions: int = 65536):
+    """``prepare_sl_data`` without the disk: the same games, filters, batches, cuts and counters, but every replayed batch
+    stays on the device and its kept records are packed straight onto a ``DeviceSLDataset``.  Returns ``(dataset, meta)``;
+    ``meta`` holds the keys of ``shard_meta.json`` except ``num_shards``."""
+    from keisei_amd.sl.device_dataset import DeviceSLDataset
+
+    if not 1 <= max_moves <= 65535:
+        raise ValueError(f"max_moves must lie in [1, 65535] (the env's ply counter), got {max_moves}")
+    if max_batch_positions < max_moves:
+        raise ValueError(f"max_batch_positions ({max_batch_positions}) must hold one game of max_moves ({max_moves})")
+    replay = _DeviceReplay(batch_envs, max_moves, device)
+    dataset = DeviceSLDataset(replay.device)
+    raw: Optional[torch.Tensor] = None                          # the reused record buffer of a batch
+    count = _new_counters()
+    for games in _game_batches(game_sources, GameFilter(min_ply=min_ply, min_rating=min_rating), count,
+                               batch_envs=batch_envs, max_moves=max_moves, max_batch_positions=max_batch_positions):
+        batch = ReplayBatch.build(games)
+        raw, reason, hdr = _replay_onto(dataset, replay, batch, raw)
+        _count_replay(count, games, batch, reason, hdr)
+    dataset.check()
+    meta = _meta_of(count, len(dataset))
+    _log_summary("a device dataset", len(dataset), count)
+    return dataset, meta
 
 
 def main(argv: Optional[Sequence[str]] = None) -> None:

@@ -10,6 +10,10 @@ trained on data).  Two execution paths:
   loss ops and their autograd, and the fused GradScaler/clip/Adam launch.  Batches are gathered from the shard maps
   by ``SLDataset.read_batch`` on a helper thread one batch ahead and uploaded from pinned memory; nothing in the
   loop waits for the GPU -- the epoch's sums are read back once at the end.
+* **device-resident fused path** (``SLConfig.device_resident`` or a ``DeviceSLDataset`` handed to the constructor; not in
+  the reference): the positions stay packed in device memory, one permutation per epoch is uploaded once, and a
+  minibatch is one ``ka_sl_gather`` launch in front of the same per-batch body -- no thread, no pinned copy, no upload
+  per batch.  Asked for where the fused path cannot run, it raises instead of falling back.
 * **generic path** (CPU tensors, other models): the reference's loop in ordinary tensor ops.
 
 The shuffling is the reference's: the batch order comes from a ``DataLoader`` (``shuffle=True``) -- over the items on
@@ -22,6 +26,7 @@ import math
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
 from pathlib import Path
+from typing import Optional
 
 import torch
 import torch.nn.functional as F
@@ -30,6 +35,7 @@ from torch.utils.data import DataLoader, Dataset, get_worker_info
 
 from keisei_amd import _lib
 from keisei_amd.sl.dataset import SLDataset
+from keisei_amd.sl.device_dataset import DeviceSLDataset
 from keisei_amd.training.fused_optim import FusedAdamMixin
 from keisei_amd.training.models.katago_base import KataGoBaseModel
 from keisei_amd.training.models.se_resnet import SEResNetModel
@@ -50,6 +56,7 @@ class SLConfig:
     grad_clip: float = 0.5
     use_amp: bool = False
     allow_placeholder: bool = False
+    device_resident: bool = False          # hold the dataset packed in device memory (DeviceSLDataset); not in the reference
 
     def __post_init__(self) -> None:
         checks = (("grad_clip", self.grad_clip > 0, "> 0"), ("total_epochs", self.total_epochs >= 0, ">= 0"),
@@ -95,7 +102,7 @@ class _Indices(Dataset):
 class SLTrainer(FusedAdamMixin):
     """Trains one epoch per ``train_epoch()`` call; checkpointing is the caller's business."""
 
-    def __init__(self, model: KataGoBaseModel, config: SLConfig) -> None:
+    def __init__(self, model: KataGoBaseModel, config: SLConfig, dataset: Optional[DeviceSLDataset] = None) -> None:
         self.model = model
         self.config = config
         self.device = next(model.parameters()).device
@@ -110,6 +117,23 @@ class SLTrainer(FusedAdamMixin):
             self._amp_dtype = torch.float16          # unused placeholder when AMP is off
         self._amp_device_type = self.device.type
         model.configure_amp(enabled=config.use_amp, dtype=self._amp_dtype, device_type=self._amp_device_type)
+        self._hip_state: dict = {}
+        self._order_override: Optional[torch.Tensor] = None     # tests: the next device epoch's order instead of randperm
+        self.device_dataset: Optional[DeviceSLDataset] = None
+        if dataset is not None or config.device_resident:
+            # the positions stay packed on the device and config.data_dir is read at most once, here; there is no other
+            # way to run this than the fused path, and no falling back to the shard path
+            if not self._fused_path_available():
+                raise ValueError("a device-resident dataset needs the fused HIP path: an SEResNetModel on a GPU, fp32 or "
+                                 f"bf16 AMP, plain Adam (got {type(model).__name__} on {self.device}, use_amp={config.use_amp})")
+            if dataset is None:
+                dataset = DeviceSLDataset.from_shards(Path(config.data_dir), device=self.device,
+                                                      allow_placeholder=config.allow_placeholder)
+            if dataset.device != self.device:
+                raise ValueError(f"the dataset lives on {dataset.device}, the model on {self.device}")
+            self.device_dataset = dataset
+            self.dataset = self.dataloader = self._index_loader = None
+            return
         self.dataset = SLDataset(Path(config.data_dir), allow_placeholder=config.allow_placeholder)
         has_data = len(self.dataset) > 0
         workers = config.num_workers if has_data else 0
@@ -117,7 +141,6 @@ class SLTrainer(FusedAdamMixin):
                                      pin_memory=on_gpu and workers > 0, persistent_workers=workers > 0,
                                      worker_init_fn=_sl_worker_init if workers > 0 else None)
         self._index_loader = DataLoader(_Indices(len(self.dataset)), batch_size=config.batch_size, shuffle=has_data)
-        self._hip_state: dict = {}
 
     # ------------------------------------------------------------------ dispatch
     def _fused_path_available(self) -> bool:
@@ -129,7 +152,9 @@ class SLTrainer(FusedAdamMixin):
 
     def train_epoch(self) -> dict[str, float]:
         self.model.train()
-        if self._fused_path_available():
+        if self.device_dataset is not None:
+            sums, batches = self._epoch_device()
+        elif self._fused_path_available():
             sums, batches = self._epoch_fused()
         else:
             sums, batches = self._epoch_generic()
@@ -170,22 +195,70 @@ class SLTrainer(FusedAdamMixin):
         return sums, batches
 
     # ------------------------------------------------------------------ fused HIP path
-    def _epoch_fused(self):
-        cfg, dev = self.config, self.device
-        call, sp = _lib.call, _lib.stream_ptr(dev)
+    def _fused_begin(self) -> dict:
+        """The state of one fused epoch: the Adam tables, the GradScaler's words, the sums and the flags."""
+        dev = self.device
         st = self._adam_tables(dev)
         scaler_t = None
         if self.scaler.is_enabled():
             if self.scaler._scale is None:
                 self.scaler._lazy_init_scale_growth_tracker(dev)
             scaler_t = torch.stack([self.scaler._scale.float().reshape(()), self.scaler._growth_tracker.float().reshape(())])
-        gscale = scaler_t[0:1] if scaler_t is not None else None
-        acc = torch.zeros(5, device=dev)               # sums of policy / value / score / (entropy, unused) / grad norm
-        flags = torch.zeros(2, dtype=torch.int32, device=dev)
-        out_m = torch.zeros(16, device=dev)
+        return dict(st=st, sp=_lib.stream_ptr(dev), scaler_t=scaler_t, gscale=scaler_t[0:1] if scaler_t is not None else None,
+                    acc=torch.zeros(5, device=dev),            # sums of policy / value / score / (entropy, unused) / grad norm
+                    flags=torch.zeros(3, dtype=torch.int32, device=dev),   # non-finite logits, bad policy target, bad gather index
+                    out_m=torch.zeros(16, device=dev), A=None)
+
+    def _fused_batch(self, ep: dict, batch: dict) -> None:
+        """One minibatch of device tensors: forward, ``ka_policy_ce``, ``ka_value_loss``, backward, ``ka_clip_adam_step``.
+        The ONE body of the shard epoch and the device-resident epoch."""
+        cfg, dev, call = self.config, self.device, _lib.call
+        st, sp, scaler_t, gscale, acc, flags = ep["st"], ep["sp"], ep["scaler_t"], ep["gscale"], ep["acc"], ep["flags"]
         group = self.optimizer.param_groups[0]
         beta1, beta2 = group["betas"]
-        A = None
+        obs = batch["observation"]
+        B = obs.shape[0]
+        out = self.model(obs)
+        logits = out.policy_logits.reshape(B, -1)
+        A = ep["A"] = logits.shape[1]
+        dlogits = torch.empty_like(logits)
+        rowloss = torch.empty(B, device=dev)
+        rowent = torch.zeros(B, device=dev)
+        dv, ds = torch.empty(B, 3, device=dev), torch.empty(B, 1, device=dev)
+        call("ka_policy_ce", logits, batch["policy_target"], None, dlogits, rowloss, flags, gscale,
+             float(cfg.lambda_policy) / B, B, A, sp)
+        call("ka_value_loss", out.value_logits, out.score_lead, batch["value_target"], batch["score_target"], None,
+             rowloss, rowent, dv, ds, ep["out_m"], acc, gscale, float(cfg.lambda_policy), float(cfg.lambda_value),
+             float(cfg.lambda_score), 0.0, 0, B, sp)
+        self.optimizer.zero_grad(set_to_none=True)
+        torch.autograd.backward([out.policy_logits, out.value_logits, out.score_lead],
+                                [dlogits.view_as(out.policy_logits), dv, ds])
+        tab = self._upload_table(st, dev)
+        call("ka_clip_adam_step", tab, st["blk_t"], st["blk_o"], st["nblocks"], st["partial"], st["ctl"],
+             st["step_dev"], scaler_t, flags, acc[4:5], float(cfg.grad_clip), float(group["lr"]), float(beta1),
+             float(beta2), float(group["eps"]), sp)
+        self.model._hip_engine.notify_weights_updated()
+        self.optimizer._opt_called = True          # the scheduler's "step() before optimizer.step()" check
+
+    def _fused_end(self, ep: dict, batches: int):
+        if batches == 0:
+            return [0.0, 0.0, 0.0], 0
+        st, scaler_t = ep["st"], ep["scaler_t"]
+        host = torch.cat([ep["acc"], st["step_dev"], ep["flags"].float()]).cpu().tolist()       # the epoch's one read-back
+        for q in st["params"]:
+            self.optimizer.state[q]["step"].fill_(host[5])
+        if scaler_t is not None:
+            self.scaler._scale.copy_(scaler_t[0])
+            self.scaler._growth_tracker.copy_(scaler_t[1].to(torch.int32))
+        if host[8]:
+            raise IndexError(f"{int(host[8])} indices outside the dataset reached the gather kernel")
+        if host[7]:
+            raise ValueError(f"policy_target outside [0, {ep['A']}) reached the loss kernel")
+        return host[:3], batches
+
+    def _epoch_fused(self):
+        dev = self.device
+        ep = self._fused_begin()
         batches = 0
         copy_stream = torch.cuda.Stream(dev)
         main = torch.cuda.current_stream(dev)
@@ -209,39 +282,29 @@ class SLTrainer(FusedAdamMixin):
                 main.wait_event(ready)
                 for t in batch.values():
                     t.record_stream(main)
-                obs = batch["observation"]
-                B = obs.shape[0]
-                out = self.model(obs)
-                logits = out.policy_logits.reshape(B, -1)
-                A = logits.shape[1]
-                dlogits = torch.empty_like(logits)
-                rowloss = torch.empty(B, device=dev)
-                rowent = torch.zeros(B, device=dev)
-                dv, ds = torch.empty(B, 3, device=dev), torch.empty(B, 1, device=dev)
-                call("ka_policy_ce", logits, batch["policy_target"], None, dlogits, rowloss, flags, gscale,
-                     float(cfg.lambda_policy) / B, B, A, sp)
-                call("ka_value_loss", out.value_logits, out.score_lead, batch["value_target"], batch["score_target"], None,
-                     rowloss, rowent, dv, ds, out_m, acc, gscale, float(cfg.lambda_policy), float(cfg.lambda_value),
-                     float(cfg.lambda_score), 0.0, 0, B, sp)
-                self.optimizer.zero_grad(set_to_none=True)
-                torch.autograd.backward([out.policy_logits, out.value_logits, out.score_lead],
-                                        [dlogits.view_as(out.policy_logits), dv, ds])
-                tab = self._upload_table(st, dev)
-                call("ka_clip_adam_step", tab, st["blk_t"], st["blk_o"], st["nblocks"], st["partial"], st["ctl"],
-                     st["step_dev"], scaler_t, flags, acc[4:5], float(cfg.grad_clip), float(group["lr"]), float(beta1),
-                     float(beta2), float(group["eps"]), sp)
-                self.model._hip_engine.notify_weights_updated()
-                self.optimizer._opt_called = True          # the scheduler's "step() before optimizer.step()" check
+                self._fused_batch(ep, batch)
                 batches += 1
                 del host
-        if batches == 0:
+        return self._fused_end(ep, batches)
+
+    # ------------------------------------------------------------------ device-resident epoch
+    def _epoch_device(self):
+        """The fused epoch over a ``DeviceSLDataset``: one permutation drawn on the host and uploaded once, then per
+        ``batch_size`` slice (the last one partial) one gather launch and the fused batch body."""
+        ds, dev = self.device_dataset, self.device
+        n = len(ds)
+        if n == 0:
             return [0.0, 0.0, 0.0], 0
-        host = torch.cat([acc, st["step_dev"], flags.float()]).cpu().tolist()       # the epoch's one read-back
-        for q in st["params"]:
-            self.optimizer.state[q]["step"].fill_(host[5])
-        if scaler_t is not None:
-            self.scaler._scale.copy_(scaler_t[0])
-            self.scaler._growth_tracker.copy_(scaler_t[1].to(torch.int32))
-        if host[7]:
-            raise ValueError(f"policy_target outside [0, {A}) reached the loss kernel")
-        return host[:3], batches
+        order, self._order_override = self._order_override, None
+        if order is None:
+            order = torch.randperm(n)
+        elif order.dtype != torch.int64 or order.dim() != 1:
+            raise ValueError("_order_override must be a 1-d int64 tensor")
+        order = order.to(dev)
+        ep = self._fused_begin()
+        gather_flag = ep["flags"][2:3]
+        batches = 0
+        for lo in range(0, order.shape[0], self.config.batch_size):
+            self._fused_batch(ep, ds.gather(order[lo:lo + self.config.batch_size], gather_flag))
+            batches += 1
+        return self._fused_end(ep, batches)
