@@ -416,7 +416,7 @@ int ka_heads_eval_grouped(const void* x, const float* pool, const int* model_of,
  * VecEnv(num_envs, max_ply, "katago", "spatial"), with the rules of shogi-core/src/{movegen,attack,rules,game}.rs, the
  * observation planes of shogi-gym/src/katago_observation.rs:41-92 + observation.rs:81-153 and the action indices of
  * spatial_action_mapper.rs:138-279).  One wave per game; all buffers are device memory owned by the caller:
- *   state  n x ka_shogi_env_state_bytes() bytes: board[81] (piece.rs:10-19 bytes) hands[2][7] side in_check - ply key reps
+ *   state  n x ka_shogi_env_state_bytes() bytes: board[81] (piece.rs:10-19 bytes) hands[2][7] side in_check - ply key reps games
  *   keys   n x max(max_ply,1) u64, checks n x max(max_ply,1) u8: position key / "mover stood in check" of every ply
  *   obs_mode 1 = "katago" 50 planes, 0 = "default" 46 planes (observation.rs:1-15); action_mode 1 = "spatial" A = 11 259,
  *   0 = "default" A = 81*80*2 + 81*7 = 13 527 (action_mapper.rs:17-110); ka_shogi_env_action_space(mode) = A.
@@ -432,7 +432,17 @@ int ka_heads_eval_grouped(const void* x, const float* pool, const int* model_of,
  *   limit, fourfold repetition / perpetual check, 24-point impasse, no legal move), rewards for the mover
  *   (vec_env.rs:98-124), captured hand-type (255 none), TerminationReason, ply, material balance, episode counters
  *   stats[4] u64 {completed, drawn, truncated, total ply}; finished games write terminal_obs (other rows are left as they
- *   were) and restart from the start position; then observation and masks of every game's position to move. */
+ *   were) and restart from the start position; then observation and masks of every game's position to move.
+ * ka_shogi_env_reset_pool / ka_shogi_env_step_pool: the same calls with a pool of start positions, replacing the standard
+ *   start of reset and of every restart (the reference has no counterpart: VecEnv always starts at position.rs:45-93).
+ *   pool = capacity rows of 96 bytes board[81] hands[2][7] side (the first 96 bytes of a state row), pool_hdr = int32[4]
+ *   {count, 0, seed lo, seed hi}, both device memory.  Every launch reads count (<= capacity, the caller's promise) and the
+ *   seed from the header, so new contents apply from the next ply of a captured graph.  A game starting in env e draws
+ *     h = mix(seed ^ mix(((u64)e << 32 | g) + 0x706F6F6C)),  idx = ((h >> 32) * count) >> 32,  mix = the splitmix64 finaliser,
+ *   with g = games started in e since the last reset (u32 at byte 116 of the state row: reset writes 0, a restart adds 1,
+ *   refresh leaves it), and starts from row idx with ply 0, an empty history, repetition count 1, in_check and key derived.
+ *   The rows must be playable positions (keisei_amd.shogi_gym validates them).  count <= 0 or pool = pool_hdr = NULL is
+ *   the standard start: exactly ka_shogi_env_reset / ka_shogi_env_step, which never touch byte 116. */
 int ka_shogi_env_state_bytes(void);
 int ka_shogi_env_action_space(int action_mode);
 int ka_shogi_env_reset(void* state, void* keys, void* checks, int n, int max_ply, int obs_mode, int action_mode, float* obs,
@@ -441,6 +451,14 @@ int ka_shogi_env_step(void* state, void* keys, void* checks, const long long* ac
                       int action_mode, const void* prev_mask, const void* prev_mask_bits, int* err, float* obs, void* mask, void* mask_bits,
                       float* rewards, void* terminated, void* truncated, float* terminal_obs, void* current_players,
                       void* captured, void* term_reason, void* ply_count, int* material, void* stats, void* stream);
+int ka_shogi_env_reset_pool(void* state, void* keys, void* checks, int n, int max_ply, int obs_mode, int action_mode, float* obs,
+                            void* mask, void* mask_bits, void* current_players, int refresh, const void* pool,
+                            const void* pool_hdr, void* stream);
+int ka_shogi_env_step_pool(void* state, void* keys, void* checks, const long long* actions, int n, int max_ply, int obs_mode,
+                           int action_mode, const void* prev_mask, const void* prev_mask_bits, int* err, float* obs, void* mask,
+                           void* mask_bits, float* rewards, void* terminated, void* truncated, float* terminal_obs,
+                           void* current_players, void* captured, void* term_reason, void* ply_count, int* material,
+                           void* stats, const void* pool, const void* pool_hdr, void* stream);
 
 /* ---- match arena (csrc/arena.hip; concurrent_matches.py:196-545 run_round): S slots of E contiguous envs, slot s playing
  * model_a (player 0) against model_b (player 1).  state: ka_arena_state_words(S) int32 = header {seed int64, round ply,

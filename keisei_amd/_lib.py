@@ -103,6 +103,8 @@ _SIGS = {
     "ka_shogi_env_action_space": "i",
     "ka_shogi_env_reset": "ppp ii ii pppp i p",
     "ka_shogi_env_step": "pppp ii ii ppp ppp ppp pp ppp pp p",
+    "ka_shogi_env_reset_pool": "ppp ii ii pppp i pp p",
+    "ka_shogi_env_step_pool": "pppp ii ii ppp ppp ppp pp ppp pp pp p",
     "ka_arena_state_words": "i",
     "ka_arena_referee": "p ii ppppp p pp p",
     "ka_arena_assign": "pp ii ppp p",

@@ -22,7 +22,9 @@ constexpr int kTypes = 139, kBoardMoves = 81 * 80 * 2;
 // observation planes: katago 50 (katago_observation.rs), default 46 (observation.rs: planes 44-45 reserved)
 constexpr int kMaxWords = (13527 + 31) / 32, kMaxCand = 1024;
 __host__ __device__ constexpr int action_space(int amode) { return amode ? 81 * kTypes : kBoardMoves + 81 * 7; }
-constexpr int kStateBytes = 128;      // board[81] hands[14] side in_check pad[3] | ply u32 @100 | key u64 @104 | reps u32 @112
+constexpr int kStateBytes = 128;      // board[81] hands[14] side in_check pad[3] | ply u32 @100 | key u64 @104 | reps u32 @112 | games u32 @116
+constexpr int kPoolRowBytes = 96;     // a start-pool row: board[81] hands[14] side, the first 96 bytes of a state row
+constexpr unsigned long long kSaltPool = 0x706F6F6Cull;
 enum { PAWN = 1, LANCE, KNIGHT, SILVER, GOLD, BISHOP, ROOK, KING };
 constexpr int WHITE_BIT = 0x10, PROM_BIT = 0x20;
 enum { R_PROGRESS = 0, R_CHECKMATE, R_REPETITION, R_PERPETUAL, R_IMPASSE, R_MAXMOVES };   // step_result.rs:9-16
@@ -63,6 +65,7 @@ struct EnvArgs {
     uint8_t* captured; uint8_t* term_reason; uint16_t* ply_out; int* material; unsigned long long* stats;
     int amode, obs_ch;               // action mode 1 spatial / 0 default; observation planes 50 (katago) / 46 (default)
     int n, max_ply, mode;            // mode 0 reset, 1 step, 2 refresh (derive everything from board / hands / side as placed)
+    const uint8_t* pool; const int* pool_hdr;     // start positions (kPool kernels only): rows of kPoolRowBytes, header {count, 0, seed lo, seed hi}
 };
 
 // the board in LDS (explicit address space: these helpers are not always inlined) with up to two squares replaced
@@ -94,6 +97,8 @@ __device__ __forceinline__ bool attacked_from(const View& v, int sq, int by, int
     const int kr = by ? r - 2 : r + 2, kc = c + (d == 8 ? -1 : 1);
     return (unsigned)kr < 9u && (unsigned)kc < 9u && at(v, kr * 9 + kc) == (KNIGHT | (by ? WHITE_BIT : 0));
 }
+// (kPool on the helpers that are not inlined by force: each kernel form owns its copies, as the one kernel did before)
+template <bool kPool>
 __device__ bool attacked(const View& v, int sq, int by) {
 #pragma unroll 1
     for (int d = 0; d < 10; ++d) if (attacked_from(v, sq, by, d)) return true;
@@ -101,6 +106,7 @@ __device__ bool attacked(const View& v, int sq, int by) {
 }
 
 // does the piece `pc` standing on `from` attack `target`? (rules.rs:136-176)
+template <bool kPool>
 __device__ bool attacks(const View& v, int from, int pc, int target) {
     const int fr = from / 9, fc = from % 9, tr = target / 9, tc = target % 9;
     const int dr = tr - fr, dc = tc - fc;
@@ -119,11 +125,12 @@ __device__ bool attacks(const View& v, int from, int pc, int target) {
 }
 
 // rules.rs:18-131: would a pawn of `me` dropped on `to` leave the other king attacked with no way out?
+template <bool kPool>
 __device__ bool pawn_drop_mates(lds_board board, lds_dirs dirs, int to, int me, int opp_king) {
     if (opp_king < 0) return false;
     const int opp = me ^ 1, pawn = PAWN | (me ? WHITE_BIT : 0);
     const View v{board, dirs, to, pawn, -1, 0};
-    if (!attacked(v, opp_king, me)) return false;
+    if (!attacked<kPool>(v, opp_king, me)) return false;
     const int kr = opp_king / 9, kc = opp_king % 9;
     for (int dr = -1; dr <= 1; ++dr) for (int dc = -1; dc <= 1; ++dc) {          // the king steps aside or takes
         if (!dr && !dc) continue;
@@ -131,15 +138,15 @@ __device__ bool pawn_drop_mates(lds_board board, lds_dirs dirs, int to, int me, 
         if ((unsigned)r >= 9u || (unsigned)c >= 9u) continue;
         const int q = at(v, r * 9 + c);
         if (q && ((q >> 4) & 1) == opp) continue;
-        if (attacked(v, r * 9 + c, me)) continue;
+        if (attacked<kPool>(v, r * 9 + c, me)) continue;
         return false;
     }
     for (int sq = 0; sq < 81; ++sq) {                                             // another piece takes the pawn
         const int pc = at(v, sq);
         if (!pc || ((pc >> 4) & 1) != opp || (pc & 15) == KING) continue;
-        if (!attacks(v, sq, pc, to)) continue;
+        if (!attacks<kPool>(v, sq, pc, to)) continue;
         const View w{board, dirs, sq, 0, to, pc};
-        if (!attacked(w, opp_king, me)) return false;
+        if (!attacked<kPool>(w, opp_king, me)) return false;
     }
     return true;
 }
@@ -184,6 +191,9 @@ __device__ __forceinline__ int piece_value(int t, bool pr) {  // rules.rs:333-35
     return pr ? prom[t] : plain[t];
 }
 
+// kPool: games start from rows of a.pool drawn per (seed, env, game number) instead of the standard position.  A compile-time
+// form, so that the kernel without a pool is the code it was.
+template <bool kPool>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void shogi_env_kernel(EnvArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t s_board[96];
     __shared__ uint8_t s_hands[16];
@@ -244,9 +254,35 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
         return (int)(__ballot(hit) != 0);
     };
 
+    // a new game: the standard start, or row idx of the pool with
+    //   h = mix(seed ^ mix((env << 32 | games) + 0x706F6F6C)),  idx = ((h >> 32) * count) >> 32
+    // (the draw of csrc/league.hip: a function of (seed, env, games) alone); count and seed are read from the header by
+    // every launch, so an upload takes effect on the next ply of a captured graph
+    unsigned games = 0;                                        // games started in this env since the last reset
+    auto begin_game = [&]() {
+        if constexpr (!kPool) {                                // the statements the kernel had before there was a pool
+            set_start(); side = 0; ply = 0; reps = 1; in_check = 0; key = position_key();
+            return;
+        }
+        const int count = a.pool_hdr[0];
+        if (count > 0) {
+            const unsigned long long seed = (unsigned long long)(unsigned)a.pool_hdr[2] | ((unsigned long long)(unsigned)a.pool_hdr[3] << 32);
+            const unsigned long long h = mix64(seed ^ mix64((((unsigned long long)(unsigned)env << 32) | games) + kSaltPool));
+            const uint8_t* row = a.pool + (size_t)(((h >> 32) * (unsigned long long)count) >> 32) * kPoolRowBytes;
+            for (int i = lane; i < 81; i += 64) s_board[i] = row[i];
+            if (lane < 14) s_hands[lane] = row[81 + lane];
+            __syncthreads();
+            side = row[95] & 1; in_check = side_in_check(side);
+        } else {
+            set_start(); side = 0; in_check = 0;
+        }
+        ply = 0; reps = 1; key = position_key();
+    };
+    if constexpr (kPool) if (a.mode != 0) games = *reinterpret_cast<const uint32_t*>(st + 116);
+
     int terminal = R_PROGRESS, winner = -1, last_mover = 0, cap = 0;
     if (a.mode == 0) {
-        set_start(); side = 0; ply = 0; reps = 1; in_check = 0; key = position_key();
+        begin_game();
     } else if (a.mode == 2) {
         load_board(); side = st[95]; ply = 0; reps = 1; in_check = side_in_check(side); key = position_key();
     } else if (hold) {
@@ -467,8 +503,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
                 const int from = c & 127, to = (c >> 7) & 127, promote = (c >> 14) & 1, drop = (c >> 15) & 7, act = c >> 18;
                 bool ok = my_king >= 0;
                 if (drop) {
-                    if (ok && in_check) { const View v{brd, drs, to, drop | mine, -1, 0}; ok = !attacked(v, my_king, me ^ 1); }
-                    if (ok && drop == PAWN) ok = !pawn_drop_mates(brd, drs, to, me, opp_king);
+                    if (ok && in_check) { const View v{brd, drs, to, drop | mine, -1, 0}; ok = !attacked<kPool>(v, my_king, me ^ 1); }
+                    if (ok && drop == PAWN) ok = !pawn_drop_mates<kPool>(brd, drs, to, me, opp_king);
                 } else if (ok) {
                     const int pc = s_board[from];
                     const bool king = (pc & 15) == KING;
@@ -476,7 +512,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
                     const bool aligned = dr == 0 || dc == 0 || dr == dc || dr == -dc;
                     if (king || in_check || aligned) {
                         const View v{brd, drs, from, 0, to, promote ? pc | PROM_BIT : pc};
-                        ok = !attacked(v, king ? to : my_king, me ^ 1);
+                        ok = !attacked<kPool>(v, king ? to : my_king, me ^ 1);
                     }
                 }
                 if (ok) atomicOr(&s_bits[act >> 5], 1u << (act & 31));
@@ -498,7 +534,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
             if (terminal == R_MAXMOVES) atomicAdd(&a.stats[2], 1ull);
         }
         write_obs(a.terminal_obs + (size_t)env * kObs);        // the finished game, seen by its side to move
-        set_start(); side = 0; ply = 0; reps = 1; in_check = 0; key = position_key();
+        ++games;
+        begin_game();
         terminal = R_PROGRESS;
     }
 
@@ -520,6 +557,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
         *reinterpret_cast<uint32_t*>(st + 100) = (uint32_t)ply;
         *reinterpret_cast<unsigned long long*>(st + 104) = key;
         *reinterpret_cast<uint32_t*>(st + 112) = (uint32_t)reps;
+        if constexpr (kPool) *reinterpret_cast<uint32_t*>(st + 116) = games;
         if (a.current_players) a.current_players[env] = (uint8_t)side;
     }
     for (int i = lane; i < 81; i += 64) st[i] = s_board[i];
@@ -576,14 +614,16 @@ __global__ void shogi_validate_kernel(const long long* actions, const uint8_t* m
 extern "C" int ka_shogi_env_state_bytes(void) { return kStateBytes; }
 
 static int launch_env(EnvArgs a, hipStream_t st) {
-    hipLaunchKernelGGL(shogi_env_kernel, dim3(a.n), dim3(64), 0, st, a);
+    if (a.pool) hipLaunchKernelGGL(shogi_env_kernel<true>, dim3(a.n), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(shogi_env_kernel<false>, dim3(a.n), dim3(64), 0, st, a);
     return ka_check_launch("shogi_env");
 }
 
 extern "C" int ka_shogi_env_action_space(int action_mode) { return action_space(action_mode); }
 
-extern "C" int ka_shogi_env_reset(void* state, void* keys, void* checks, int n, int max_ply, int obs_mode, int action_mode,
-                                  float* obs, void* mask, void* mask_bits, void* current_players, int refresh, void* stream) {
+static int env_reset(void* state, void* keys, void* checks, int n, int max_ply, int obs_mode, int action_mode, float* obs,
+                     void* mask, void* mask_bits, void* current_players, int refresh, const void* pool, const void* pool_hdr,
+                     void* stream) {
     KA_REQUIRE(state && keys && checks && obs && n > 0 && max_ply >= 0 && (mask || mask_bits), "shogi_env_reset: bad arguments");
     KA_REQUIRE((obs_mode == 0 || obs_mode == 1) && (action_mode == 0 || action_mode == 1), "shogi_env_reset: modes are 0 (default) or 1 (katago / spatial)");
     EnvArgs a{};
@@ -592,14 +632,29 @@ extern "C" int ka_shogi_env_reset(void* state, void* keys, void* checks, int n, 
     a.current_players = static_cast<uint8_t*>(current_players);
     a.amode = action_mode; a.obs_ch = obs_mode ? 50 : 46;
     a.n = n; a.max_ply = max_ply; a.mode = refresh ? 2 : 0;
+    a.pool = static_cast<const uint8_t*>(pool); a.pool_hdr = static_cast<const int*>(pool_hdr);
     return launch_env(a, static_cast<hipStream_t>(stream));
 }
 
-extern "C" int ka_shogi_env_step(void* state, void* keys, void* checks, const long long* actions, int n, int max_ply,
-                                 int obs_mode, int action_mode, const void* prev_mask, const void* prev_mask_bits, int* err,
-                                 float* obs, void* mask, void* mask_bits, float* rewards, void* terminated, void* truncated,
-                                 float* terminal_obs, void* current_players, void* captured, void* term_reason,
-                                 void* ply_count, int* material, void* stats, void* stream) {
+extern "C" int ka_shogi_env_reset(void* state, void* keys, void* checks, int n, int max_ply, int obs_mode, int action_mode,
+                                  float* obs, void* mask, void* mask_bits, void* current_players, int refresh, void* stream) {
+    return env_reset(state, keys, checks, n, max_ply, obs_mode, action_mode, obs, mask, mask_bits, current_players, refresh,
+                     nullptr, nullptr, stream);
+}
+
+extern "C" int ka_shogi_env_reset_pool(void* state, void* keys, void* checks, int n, int max_ply, int obs_mode, int action_mode,
+                                       float* obs, void* mask, void* mask_bits, void* current_players, int refresh,
+                                       const void* pool, const void* pool_hdr, void* stream) {
+    KA_REQUIRE((pool == nullptr) == (pool_hdr == nullptr), "shogi_env_reset_pool: pool and pool_hdr are both given or both NULL");
+    return env_reset(state, keys, checks, n, max_ply, obs_mode, action_mode, obs, mask, mask_bits, current_players, refresh,
+                     pool, pool_hdr, stream);
+}
+
+static int env_step(void* state, void* keys, void* checks, const long long* actions, int n, int max_ply, int obs_mode,
+                    int action_mode, const void* prev_mask, const void* prev_mask_bits, int* err, float* obs, void* mask,
+                    void* mask_bits, float* rewards, void* terminated, void* truncated, float* terminal_obs,
+                    void* current_players, void* captured, void* term_reason, void* ply_count, int* material, void* stats,
+                    const void* pool, const void* pool_hdr, void* stream) {
     KA_REQUIRE(state && keys && checks && actions && err && obs && rewards && terminated && truncated && terminal_obs &&
                current_players && captured && term_reason && ply_count && material && stats && n > 0 && max_ply >= 0,
                "shogi_env_step: bad arguments");
@@ -619,5 +674,28 @@ extern "C" int ka_shogi_env_step(void* state, void* keys, void* checks, const lo
     a.ply_out = static_cast<uint16_t*>(ply_count); a.material = material; a.stats = static_cast<unsigned long long*>(stats);
     a.amode = action_mode; a.obs_ch = obs_mode ? 50 : 46;
     a.n = n; a.max_ply = max_ply; a.mode = 1;
+    a.pool = static_cast<const uint8_t*>(pool); a.pool_hdr = static_cast<const int*>(pool_hdr);
     return launch_env(a, st);
+}
+
+extern "C" int ka_shogi_env_step(void* state, void* keys, void* checks, const long long* actions, int n, int max_ply,
+                                 int obs_mode, int action_mode, const void* prev_mask, const void* prev_mask_bits, int* err,
+                                 float* obs, void* mask, void* mask_bits, float* rewards, void* terminated, void* truncated,
+                                 float* terminal_obs, void* current_players, void* captured, void* term_reason,
+                                 void* ply_count, int* material, void* stats, void* stream) {
+    return env_step(state, keys, checks, actions, n, max_ply, obs_mode, action_mode, prev_mask, prev_mask_bits, err, obs, mask,
+                    mask_bits, rewards, terminated, truncated, terminal_obs, current_players, captured, term_reason, ply_count,
+                    material, stats, nullptr, nullptr, stream);
+}
+
+extern "C" int ka_shogi_env_step_pool(void* state, void* keys, void* checks, const long long* actions, int n, int max_ply,
+                                      int obs_mode, int action_mode, const void* prev_mask, const void* prev_mask_bits, int* err,
+                                      float* obs, void* mask, void* mask_bits, float* rewards, void* terminated, void* truncated,
+                                      float* terminal_obs, void* current_players, void* captured, void* term_reason,
+                                      void* ply_count, int* material, void* stats, const void* pool, const void* pool_hdr,
+                                      void* stream) {
+    KA_REQUIRE((pool == nullptr) == (pool_hdr == nullptr), "shogi_env_step_pool: pool and pool_hdr are both given or both NULL");
+    return env_step(state, keys, checks, actions, n, max_ply, obs_mode, action_mode, prev_mask, prev_mask_bits, err, obs, mask,
+                    mask_bits, rewards, terminated, truncated, terminal_obs, current_players, captured, term_reason, ply_count,
+                    material, stats, pool, pool_hdr, stream);
 }

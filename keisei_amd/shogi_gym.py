@@ -15,6 +15,11 @@ stays until that game ends again.  This is the form `select_actions` and the dev
 A refused step (an illegal action anywhere) moves nothing: the kernel then writes the unchanged positions' observations
 and masks (zero rewards, no flags) into the buffers the caller flips to, so a caller that runs with `check_actions=False`
 and reads the flag late (`raise_if_refused()`) has still stepped against the right masks.
+`VecEnv(..., start_pool_capacity=K)` (not in the reference) keeps a pool of up to K start positions in device memory:
+after `set_start_positions` / `set_start_sfens` the games of `reset()` and every game the kernel restarts begin at a pool
+row drawn per (seed, env, game number) -- `start_pool_index` is the same draw on the host -- instead of the standard
+position; `clear_start_positions()` returns to it.  Uploads are validated here, because the kernel assumes playable
+positions.  `parse_sfen` / `format_sfen` are the text form of a position.
 There is no CPU fallback: without the HIP library or a GPU the constructor raises.
 """
 from __future__ import annotations
@@ -117,6 +122,176 @@ class DefaultActionMapper:
         return {"type": "board", "from_sq": flip(f), "to_sq": flip(off + 1 if off >= f else off), "promote": bool(rem & 1)}
 
 _SFEN = {1: "P", 2: "L", 3: "N", 4: "S", 5: "G", 6: "B", 7: "R", 8: "K"}
+_SFEN_TYPE = {v: k for k, v in _SFEN.items()}
+_PROMOTABLE = (1, 2, 3, 4, 6, 7)
+_SET_MAX = (18, 4, 4, 4, 4, 2, 2)                             # P L N S G B R of a standard set, board and hands together
+POOL_ROW_BYTES = 96                                           # a start-pool row: board[81] hands[14] side
+
+
+def format_sfen(board, hands, side: int) -> str:
+    """sfen.rs:93-171: board rows from rank a, side to move, hands (R B G S N L P, black first), move number 1."""
+    board = np.asarray(board, np.uint8).reshape(81)
+    hands = np.asarray(hands, np.uint8).reshape(2, 7)
+    rows = []
+    for r in range(9):
+        s, empty = "", 0
+        for c in range(9):
+            p = int(board[r * 9 + c])
+            if not p:
+                empty += 1
+                continue
+            if empty:
+                s, empty = s + str(empty), 0
+            ch = _SFEN[p & 15]
+            s += ("+" if p & 0x20 else "") + (ch.lower() if p & 0x10 else ch)
+        rows.append(s + (str(empty) if empty else ""))
+    hs = ""
+    for color in (0, 1):
+        for h in (6, 5, 4, 3, 2, 1, 0):                       # R B G S N L P
+            cnt = int(hands[color, h])
+            if cnt:
+                ch = _SFEN[h + 1]
+                hs += (str(cnt) if cnt > 1 else "") + (ch.lower() if color else ch)
+    return f"{'/'.join(rows)} {'w' if side else 'b'} {hs or '-'} 1"
+
+
+def parse_sfen(sfen: str):
+    """The inverse of `format_sfen` (sfen.rs:17-91): `(board uint8[81], hands uint8[2, 7], side)`; the move number is
+    optional and ignored.  A malformed string raises `ValueError` naming the string and the field."""
+    def bad(field: str, why: str):
+        return ValueError(f"invalid SFEN {sfen!r}: {field} field: {why}")
+
+    if not isinstance(sfen, str):
+        raise ValueError(f"invalid SFEN {sfen!r}: not a string")
+    parts = sfen.split()
+    if len(parts) not in (3, 4):
+        raise ValueError(f"invalid SFEN {sfen!r}: expected 'board side hands [move number]', got {len(parts)} fields")
+    board, hands = np.zeros(81, np.uint8), np.zeros((2, 7), np.uint8)
+    rows = parts[0].split("/")
+    if len(rows) != 9:
+        raise bad("board", f"{len(rows)} ranks, expected 9")
+    for r, row in enumerate(rows):
+        c, prom = 0, False
+        for ch in row:
+            if ch == "+":
+                if prom:
+                    raise bad("board", f"'++' in rank {r + 1}")
+                prom = True
+                continue
+            if ch.isdigit():
+                if prom or ch == "0":
+                    raise bad("board", f"'{ch}' cannot stand there in rank {r + 1}")
+                c += int(ch)
+            else:
+                t = _SFEN_TYPE.get(ch.upper()) if ch.isascii() and ch.isalpha() else None
+                if t is None:
+                    raise bad("board", f"unknown piece letter '{ch}' in rank {r + 1}")
+                if prom and t not in _PROMOTABLE:
+                    raise bad("board", f"'+{ch}' does not exist (rank {r + 1})")
+                if c < 9:
+                    board[r * 9 + c] = t | (0x10 if ch.islower() else 0) | (0x20 if prom else 0)
+                c, prom = c + 1, False
+            if c > 9:
+                raise bad("board", f"rank {r + 1} holds more than 9 files")
+        if prom:
+            raise bad("board", f"'+' ends rank {r + 1}")
+        if c != 9:
+            raise bad("board", f"rank {r + 1} holds {c} files, expected 9")
+    if parts[1] not in ("b", "w"):
+        raise bad("side", f"'{parts[1]}' is neither 'b' nor 'w'")
+    if parts[2] != "-":
+        num = ""
+        for ch in parts[2]:
+            if ch.isdigit():
+                num += ch
+                continue
+            t = _SFEN_TYPE.get(ch.upper()) if ch.isascii() and ch.isalpha() else None
+            if t is None or t == 8:
+                raise bad("hands", f"'{ch}' is no piece a hand can hold")
+            cnt = int(num) if num else 1
+            if cnt < 1 or cnt + int(hands[int(ch.islower()), t - 1]) > 255:
+                raise bad("hands", f"count '{num}' before '{ch}'")
+            hands[int(ch.islower()), t - 1] += cnt
+            num = ""
+        if num:
+            raise bad("hands", f"count '{num}' without a piece")
+    if len(parts) == 4 and not parts[3].isdigit():
+        raise bad("move number", f"'{parts[3]}' is no number")
+    return board, hands, int(parts[1] == "w")
+
+
+_M64 = (1 << 64) - 1
+
+
+def _mix64(x: np.ndarray) -> np.ndarray:
+    """The splitmix64 finaliser of csrc/shogi_env.hip (mix64) over uint64 arrays."""
+    x = x + np.uint64(0x9E3779B97F4A7C15)
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def start_pool_index(seed: int, envs, games, count: int) -> np.ndarray:
+    """Which pool row the game number `games` (0 = the one `reset()` starts) of env `envs` starts from, as the kernel
+    draws it (include/keisei_amd.h): h = mix(seed ^ mix((env << 32 | g) + 0x706F6F6C)), idx = ((h >> 32) * count) >> 32.
+    `envs` and `games` broadcast; returns int64."""
+    if not 1 <= count < (1 << 31):
+        raise ValueError(f"count must lie in [1, 2^31), got {count}")
+    with np.errstate(over="ignore"):
+        e = np.asarray(envs).astype(np.uint64) & np.uint64(0xFFFFFFFF)
+        g = np.asarray(games).astype(np.uint64) & np.uint64(0xFFFFFFFF)
+        h = _mix64(np.uint64(int(seed) & _M64) ^ _mix64(((e << np.uint64(32)) | g) + np.uint64(0x706F6F6C)))
+        return (((h >> np.uint64(32)) * np.uint64(count)) >> np.uint64(32)).astype(np.int64)
+
+
+def _valid_piece_table() -> np.ndarray:
+    ok = np.zeros(256, bool)
+    ok[0] = True
+    for t in range(1, 9):
+        for col in (0, 0x10):
+            ok[t | col] = True
+            if t in _PROMOTABLE:
+                ok[t | col | 0x20] = True
+    return ok
+
+
+_VALID_PIECE = _valid_piece_table()
+
+
+def _static_position_errors(boards: np.ndarray, hands: np.ndarray, sides: np.ndarray):
+    """The checks of a start position that need no move generation, vectorised over K positions.  Returns (bad, why):
+    `bad[k]` and the first failed check of position k."""
+    K = boards.shape[0]
+    why = np.full(K, "", dtype=object)
+    bad = np.zeros(K, bool)
+
+    def mark(cond: np.ndarray, text: str) -> None:
+        new = cond & ~bad
+        why[new] = text
+        bad[:] |= cond
+
+    mark(~_VALID_PIECE[boards].all(axis=1), "a board byte is no piece")
+    mark(sides > 1, "side is neither 0 (black) nor 1 (white)")
+    b = np.where(bad[:, None], 0, boards).astype(np.int64)     # rows already refused are not looked at further
+    typ, white, prom = b & 15, (b & 0x10) != 0, (b & 0x20) != 0
+    for col, name in ((0, "black"), (1, "white")):
+        kings = ((typ == 8) & (white == bool(col))).sum(axis=1)
+        mark(~bad & (kings != 1), f"{name} needs exactly one king")
+    h = hands.reshape(K, 2, 7).astype(np.int64)
+    for t in range(1, 8):
+        total = (typ == t).sum(axis=1) + h[:, 0, t - 1] + h[:, 1, t - 1]
+        mark(~bad & (total > _SET_MAX[t - 1]), f"more than {_SET_MAX[t - 1]} {_SFEN[t]} on the board and in the hands")
+    rows = np.arange(81) // 9
+    for col in (0, 1):
+        last, last2 = (8, 7) if col else (0, 1)
+        mine = (white == bool(col)) & ~prom
+        dead = (mine & ((typ == 1) | (typ == 2)) & (rows == last)[None, :]).any(axis=1)
+        mark(~bad & dead, "an unpromoted pawn or lance stands on its last rank")
+        dead = (mine & (typ == 3) & ((rows == last) | (rows == last2))[None, :]).any(axis=1)
+        mark(~bad & dead, "an unpromoted knight stands on its last two ranks")
+        pawns = (mine & (typ == 1)).reshape(K, 9, 9).sum(axis=1)
+        mark(~bad & (pawns > 1).any(axis=1), "two unpromoted pawns of one colour on a file")
+    return bad, why
 
 
 @dataclass
@@ -150,7 +325,7 @@ class ResetResult:           # step_result.rs:86-97
 class VecEnv:
     def __init__(self, num_envs: int = 512, max_ply: int = 500, observation_mode: str = "default",
                  action_mode: str = "default", *, device: Optional[torch.device] = None, output: str = "numpy",
-                 check_actions: bool = True):
+                 check_actions: bool = True, start_pool_capacity: int = 0):
         if observation_mode not in ("default", "katago"):
             raise ValueError(f"Unknown observation_mode '{observation_mode}'. Valid: 'default', 'katago'")
         if action_mode not in ("default", "spatial"):
@@ -162,6 +337,8 @@ class VecEnv:
             raise ValueError("output must be 'numpy' or 'torch'")
         if num_envs <= 0 or max_ply < 0 or max_ply > 65535:
             raise ValueError("num_envs must be positive and 0 <= max_ply <= 65535")
+        if start_pool_capacity < 0 or start_pool_capacity >= (1 << 31):
+            raise ValueError(f"start_pool_capacity must lie in [0, 2^31), got {start_pool_capacity}")
         _lib._load()                                          # raises KeiseiHipError when the library is missing
         if not torch.cuda.is_available():
             raise _lib.KeiseiHipError("keisei_amd.shogi_gym.VecEnv needs a GPU (there is no CPU fallback)")
@@ -191,6 +368,13 @@ class VecEnv:
         self._stats = z(4, dtype=torch.int64)
         self._err = z(2, dtype=torch.int64)                   # [this step's refusal, the latch raise_if_refused reads and clears]
         self._actions = z(n, dtype=torch.int64)
+        # start positions (set_start_positions): allocated once, so that a captured graph keeps valid pointers; the
+        # header {count, 0, seed lo, seed hi} is read by every launch.  Capacity 0: no pool, the entry points without one.
+        self._pool_capacity = int(start_pool_capacity)
+        self._pool = self._pool_hdr = None
+        if self._pool_capacity:
+            self._pool = z(self._pool_capacity, POOL_ROW_BYTES, dtype=torch.uint8)
+            self._pool_hdr = z(4, dtype=torch.int32)
         # as in the reference's constructor (vec_env.rs:574-612): the games stand at the start position, the mask buffer
         # is still all-false -- a step() before reset() is refused ("action index ... is not legal")
         self.reset()
@@ -205,8 +389,7 @@ class VecEnv:
         with torch.cuda.device(self.device):
             self._cur = 0
             self._err.zero_()                                 # (a refusal nobody asked about ends with the games it belonged to)
-            _lib.call("ka_shogi_env_reset", self._state, self._keys, self._checks, self._n, self._max_ply, self._omode,
-                      self._amode, self._obs[0], self._mask[0], self._bits[0], self._players[0], 0, _lib.stream_ptr())
+            self._call_reset(self._obs[0], self._mask[0], self._bits[0], self._players[0], 0)
         return ResetResult(self._out(self._obs[0]), self._out(self._mask[0]),
                            self._bits[0] if self._output == "torch" else None)
 
@@ -233,10 +416,14 @@ class VecEnv:
             raise RuntimeError(f"env 0: action index {a0} is not legal")
         prev, nxt = self._cur, self._cur ^ 1
         with torch.cuda.device(self.device):
-            _lib.call("ka_shogi_env_step", self._state, self._keys, self._checks, act, n, self._max_ply, self._omode, self._amode,
-                      self._mask[prev], self._bits[prev], self._err, self._obs[nxt], self._mask[nxt], self._bits[nxt],
-                      self._rewards[nxt], self._terminated[nxt], self._truncated[nxt], self._terminal_obs, self._players[nxt],
-                      self._captured[nxt], self._reason[nxt], self._ply[nxt], self._material[nxt], self._stats, _lib.stream_ptr())
+            args = (self._state, self._keys, self._checks, act, n, self._max_ply, self._omode, self._amode,
+                    self._mask[prev], self._bits[prev], self._err, self._obs[nxt], self._mask[nxt], self._bits[nxt],
+                    self._rewards[nxt], self._terminated[nxt], self._truncated[nxt], self._terminal_obs, self._players[nxt],
+                    self._captured[nxt], self._reason[nxt], self._ply[nxt], self._material[nxt], self._stats)
+            if self._pool is None:
+                _lib.call("ka_shogi_env_step", *args, _lib.stream_ptr())
+            else:
+                _lib.call("ka_shogi_env_step_pool", *args, self._pool, self._pool_hdr, _lib.stream_ptr())
         self._cur = nxt                                       # (a refused step has re-written the unchanged positions there)
         if self._check:
             self.raise_if_refused(act)
@@ -267,6 +454,14 @@ class VecEnv:
 
     def _out(self, t: torch.Tensor):
         return t if self._output == "torch" else t.cpu().numpy()
+
+    def _call_reset(self, obs, mask, bits, players, refresh: int) -> None:
+        args = (self._state, self._keys, self._checks, self._n, self._max_ply, self._omode, self._amode, obs, mask, bits,
+                players, refresh)
+        if self._pool is None:
+            _lib.call("ka_shogi_env_reset", *args, _lib.stream_ptr())
+        else:
+            _lib.call("ka_shogi_env_reset_pool", *args, self._pool, self._pool_hdr, _lib.stream_ptr())
 
     # ------------------------------------------------------------------ properties (vec_env.rs:793-870)
     @property
@@ -337,6 +532,8 @@ class VecEnv:
     def set_states(self, boards, hands, sides) -> None:
         """All games at once: boards (N,81), hands (N,2,7) or (N,14), sides (N,); ply and history restart at 0."""
         raw = np.zeros(tuple(self._state.shape), np.uint8)
+        if self._pool is not None:                            # the count of games started is not a part of the position
+            raw[:, 116:120] = self._state[:, 116:120].cpu().numpy()
         raw[:, :81] = np.asarray(boards, np.uint8).reshape(self._n, 81)
         raw[:, 81:95] = np.asarray(hands, np.uint8).reshape(self._n, 14)
         raw[:, 95] = np.asarray(sides, np.uint8).reshape(self._n)
@@ -346,9 +543,99 @@ class VecEnv:
         self._armed = True
         self._state.copy_(torch.from_numpy(raw))
         with torch.cuda.device(self.device):
-            _lib.call("ka_shogi_env_reset", self._state, self._keys, self._checks, self._n, self._max_ply, self._omode,
-                      self._amode, self._obs[self._cur], self._mask[self._cur], self._bits[self._cur], self._players[self._cur], 1,
-                      _lib.stream_ptr())
+            self._call_reset(self._obs[self._cur], self._mask[self._cur], self._bits[self._cur], self._players[self._cur], 1)
+
+    # ------------------------------------------------------------------ start positions
+    @property
+    def start_pool_capacity(self) -> int:
+        return self._pool_capacity
+
+    @property
+    def start_pool_count(self) -> int:
+        """How many start positions are in use (0: every game starts at the standard position)."""
+        return 0 if self._pool_hdr is None else int(self._pool_hdr[0].item())
+
+    def _probe_positions(self, boards: np.ndarray, hands: np.ndarray, sides: np.ndarray):
+        """(side to move is in check, it has a legal move) of K positions, by refresh launches over scratch rows."""
+        K = boards.shape[0]
+        in_check, movable = np.zeros(K, bool), np.zeros(K, bool)
+        dev, chunk = self.device, 1024
+        words = (self._A + 31) // 32
+        with torch.cuda.device(dev):
+            m = min(K, chunk)
+            state = torch.zeros(m, self._state.shape[1], dtype=torch.uint8, device=dev)
+            keys = torch.zeros(m, max(self._max_ply, 1), dtype=torch.int64, device=dev)
+            checks = torch.zeros(m, max(self._max_ply, 1), dtype=torch.uint8, device=dev)
+            obs = torch.zeros(m, self._C, 9, 9, dtype=torch.float32, device=dev)
+            bits = torch.zeros(m, words, dtype=torch.int32, device=dev)
+            for lo in range(0, K, chunk):
+                k = min(chunk, K - lo)
+                raw = np.zeros((k, state.shape[1]), np.uint8)
+                raw[:, :81], raw[:, 81:95], raw[:, 95] = boards[lo:lo + k], hands[lo:lo + k], sides[lo:lo + k]
+                state[:k].copy_(torch.from_numpy(raw))
+                _lib.call("ka_shogi_env_reset", state, keys, checks, k, self._max_ply, self._omode, self._amode, obs, None,
+                          bits, None, 1, _lib.stream_ptr())
+                in_check[lo:lo + k] = state[:k, 96].cpu().numpy() != 0
+                movable[lo:lo + k] = (bits[:k] != 0).any(dim=1).cpu().numpy()
+        return in_check, movable
+
+    def set_start_positions(self, boards, hands, sides, *, seed: int = 0) -> None:
+        """Start every later game -- the restarts inside `step` and the games of `reset()` -- from one of these K
+        positions: boards (K,81) piece bytes, hands (K,2,7) or (K,14), sides (K,), host arrays or tensors.  The game
+        number g (0 at `reset()`) of env e starts from row `start_pool_index(seed, e, g, K)`, with ply 0 and an empty
+        history.  Games in progress go on; a captured graph needs no new capture.  The positions are validated first
+        (a `ValueError` names the first bad index and nothing is uploaded): the kernel assumes playable positions."""
+        to_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)  # noqa: E731
+        b, h, s = to_np(boards), to_np(hands), to_np(sides)
+        if b.ndim != 2 or b.shape[1] != 81:
+            raise ValueError(f"boards must have shape (K, 81), got {tuple(b.shape)}")
+        K = b.shape[0]
+        if tuple(h.shape) not in ((K, 2, 7), (K, 14)) or s.reshape(-1).shape[0] != K or s.ndim > 1:
+            raise ValueError(f"hands must have shape ({K}, 2, 7) or ({K}, 14) and sides ({K},), got {tuple(h.shape)} "
+                             f"and {tuple(s.shape)}")
+        if self._pool_capacity == 0:
+            raise ValueError("this VecEnv has no start pool: construct it with start_pool_capacity > 0")
+        if K > self._pool_capacity:
+            raise ValueError(f"{K} start positions do not fit start_pool_capacity={self._pool_capacity}")
+        if K == 0:
+            raise ValueError("no start positions given (clear_start_positions() returns to the standard start)")
+        for name, x in (("boards", b), ("hands", h), ("sides", s)):
+            if x.dtype.kind not in "iub" or (x.size and (int(x.min()) < 0 or int(x.max()) > 255)):
+                raise ValueError(f"{name} must hold integers in [0, 255]")
+        b, h, s = (np.ascontiguousarray(x, dtype=np.uint8) for x in (b, h.reshape(K, 14), s.reshape(K)))
+        bad, why = _static_position_errors(b, h, s)
+        first = int(np.argmax(bad)) if bad.any() else K
+        if first:                                             # the rows before the first refused one go to the device
+            mover_checked, movable = self._probe_positions(b[:first], h[:first], s[:first])
+            other_checked, _ = self._probe_positions(b[:first], h[:first], s[:first] ^ 1)
+            dyn = other_checked | ~movable
+            if dyn.any():
+                first = int(np.argmax(dyn))
+                reason = "the side not to move is in check" if other_checked[first] else "the side to move has no legal move"
+                raise ValueError(f"start position {first} is not playable: {reason}")
+        if first < K:
+            raise ValueError(f"start position {first} is not playable: {why[first]}")
+        rows = np.concatenate([b, h, s[:, None]], axis=1)
+        sd = int(seed) & _M64
+        hdr = np.array([K, 0, sd & 0xFFFFFFFF, sd >> 32], dtype=np.uint32).view(np.int32)
+        with torch.cuda.device(self.device):
+            # in stream order behind the launches queued so far: rows and seed first, the count that exposes them last
+            self._pool[:K].copy_(torch.from_numpy(rows))
+            self._pool_hdr.copy_(torch.from_numpy(hdr))
+
+    def set_start_sfens(self, sfens, *, seed: int = 0) -> None:
+        """`set_start_positions` of SFEN strings (`parse_sfen`)."""
+        parsed = [parse_sfen(x) for x in sfens]
+        if not parsed:
+            raise ValueError("no start positions given (clear_start_positions() returns to the standard start)")
+        self.set_start_positions(np.stack([p[0] for p in parsed]), np.stack([p[1] for p in parsed]),
+                                 np.asarray([p[2] for p in parsed], np.uint8), seed=seed)
+
+    def clear_start_positions(self) -> None:
+        """Later games start at the standard position again (count 0); games in progress go on."""
+        if self._pool_hdr is not None:
+            with torch.cuda.device(self.device):
+                self._pool_hdr.zero_()
 
     def current(self) -> ResetResult:
         """Observation and masks of the positions to move (what the last reset / step / set_state wrote)."""
@@ -358,27 +645,7 @@ class VecEnv:
     def get_sfen(self, game_id: int) -> str:
         """vec_env.rs:873-882 / sfen.rs:93-171."""
         board, hands, side, _ = self.get_state(game_id)
-        rows = []
-        for r in range(9):
-            s, empty = "", 0
-            for c in range(9):
-                p = int(board[r * 9 + c])
-                if not p:
-                    empty += 1
-                    continue
-                if empty:
-                    s, empty = s + str(empty), 0
-                ch = _SFEN[p & 15]
-                s += ("+" if p & 0x20 else "") + (ch.lower() if p & 0x10 else ch)
-            rows.append(s + (str(empty) if empty else ""))
-        hs = ""
-        for color in (0, 1):
-            for h in (6, 5, 4, 3, 2, 1, 0):                   # R B G S N L P
-                cnt = int(hands[color, h])
-                if cnt:
-                    ch = _SFEN[h + 1]
-                    hs += (str(cnt) if cnt > 1 else "") + (ch.lower() if color else ch)
-        return f"{'/'.join(rows)} {'w' if side else 'b'} {hs or '-'} 1"
+        return format_sfen(board, hands, side)
 
     def get_sfens(self) -> List[str]:
         return [self.get_sfen(i) for i in range(self._n)]

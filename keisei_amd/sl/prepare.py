@@ -47,7 +47,7 @@ from keisei_amd.sl.parsers import (CSAParser, GameFilter, GameOutcome, GameParse
 
 logger = logging.getLogger(__name__)
 
-__all__ = ["prepare_sl_data", "prepare_sl_dataset", "usi_to_action", "ReplayBatch", "main"]
+__all__ = ["prepare_sl_data", "prepare_sl_dataset", "opening_positions", "usi_to_action", "ReplayBatch", "main"]
 
 # why a game's record was not used to its end
 REASON_NONE, REASON_ILLEGAL, REASON_RULES, REASON_LONG, REASON_NO_ENCODING = 0, 1, 2, 3, 4
@@ -562,6 +562,61 @@ def prepare_sl_dataset(game_sources: Sequence[str], min_ply: int = 40, min_ratin
     meta = _meta_of(count, len(dataset))
     _log_summary("a device dataset", len(dataset), count)
     return dataset, meta
+
+
+def opening_positions(game_sources: Sequence[str], ply: int, min_ply: int = 40, min_rating: Optional[int] = None, *,
+                      max_positions: Optional[int] = None, device=None, batch_envs: int = 512):
+    """Start positions for ``VecEnv.set_start_positions`` from game records (not in the reference): the position after
+    ``ply`` moves of every game that ``prepare_sl_data`` would replay (same discovery, parsing and filter; standard start
+    only), as ``(boards (K, 81), hands (K, 2, 7), sides (K,))`` uint8 arrays.  The games are replayed in lockstep on the
+    device env; a game counts when its record has at least ``ply`` moves, all of them encodable and legal, and the rules
+    have not ended it by then.  Duplicates are dropped by exact bytes, the first seen is kept, in record order;
+    ``max_positions`` stops the replay once that many are found."""
+    from keisei_amd.shogi_gym import POOL_ROW_BYTES, VecEnv
+
+    if not 0 <= ply < 65535:
+        raise ValueError(f"ply must lie in [0, 65535), got {ply}")
+    if batch_envs < 1:
+        raise ValueError(f"batch_envs must be positive, got {batch_envs}")
+    if max_positions is not None and max_positions < 1:
+        raise ValueError(f"max_positions must be positive, got {max_positions}")
+    env = VecEnv(batch_envs, ply + 1, "katago", "spatial", device=device, output="torch", check_actions=False)
+    dev, E = env.device, int(batch_envs)
+    count = _new_counters()
+    seen, rows = set(), []
+    full = lambda: max_positions is not None and len(rows) >= max_positions  # noqa: E731
+    for games in _game_batches(game_sources, GameFilter(min_ply=min_ply, min_rating=min_rating), count, batch_envs=E,
+                               max_moves=max(ply, 1), max_batch_positions=E * max(ply, 1)):
+        acts = np.zeros((E, max(ply, 1)), np.int64)
+        alive = np.zeros(E, bool)
+        for e, (a, _, _) in enumerate(games):
+            if len(a) >= ply:
+                acts[e, :ply], alive[e] = a[:ply], True
+        with torch.cuda.device(dev):
+            acts_d, alive_d = torch.from_numpy(acts).to(dev), torch.from_numpy(alive).to(dev)
+            env.reset()
+            ar = torch.arange(E, device=dev)
+            for i in range(ply):
+                cur = env.current()
+                a = acts_d[:, i]
+                legal = ((cur.legal_mask_bits[ar, a >> 5] >> (a & 31)) & 1).bool()
+                alive_d &= legal
+                filler = cur.legal_masks.to(torch.uint8).argmax(dim=1)       # a dead env plays on: the lowest legal action
+                r = env.step(torch.where(alive_d, a, filler))
+                alive_d &= ~(r.terminated | r.truncated)
+            state = env._state[:, :POOL_ROW_BYTES].cpu().numpy()
+            keep = alive_d.cpu().numpy()
+            env.raise_if_refused()
+        for e in np.nonzero(keep)[0]:
+            key = state[e].tobytes()
+            if key not in seen and not full():
+                seen.add(key)
+                rows.append(state[e].copy())
+        if full():
+            break
+    out = np.stack(rows) if rows else np.zeros((0, POOL_ROW_BYTES), np.uint8)
+    logger.info("%d opening positions at ply %d from %d games", len(rows), ply, count["games"])
+    return out[:, :81].copy(), out[:, 81:95].reshape(-1, 2, 7).copy(), out[:, 95].copy()
 
 
 def main(argv: Optional[Sequence[str]] = None) -> None:

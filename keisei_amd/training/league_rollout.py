@@ -165,15 +165,19 @@ class LeagueRollout:
     ``KataGoPPOAlgorithm.update``; ``roll.refresh()`` after the update brings the learner's new weights into the group;
     ``roll.set_opponents`` seats a new cohort.  The env is not reset between ``collect`` calls (the reference carries
     games over epochs); ``reset()`` is explicit.  ``seed`` fixes sampling and re-draws from the last ``reset()`` on.
-    ``record=True`` (no graph) keeps every ply's inputs and outputs in ``self.record`` for tests."""
+    ``record=True`` (no graph) keeps every ply's inputs and outputs in ``self.record`` for tests.  ``start_pool_capacity > 0`` gives the env a pool of
+    start positions of that size: ``roll.env.set_start_positions(...)`` / ``set_start_sfens(...)`` between ``collect`` calls make later
+    games start from them (no re-capture; see ``VecEnv``)."""
 
     def __init__(self, learner, opponents: Sequence, opponent_ids: Sequence[int], *, num_envs: int = 512, max_ply: int = 500,
                  value_adapter=None, score_norm: float = SCORE_NORMALIZATION, color_randomization: bool = False,
                  opponent_weights: Optional[Sequence[float]] = None, sync_every: int = 32, graph: bool = True,
-                 seed: Optional[int] = None, record: bool = False) -> None:
+                 seed: Optional[int] = None, record: bool = False, start_pool_capacity: int = 0) -> None:
         opponents, opponent_ids = list(opponents), [int(i) for i in opponent_ids]
         _check_args(len(opponents), opponent_ids, int(num_envs), int(max_ply), int(sync_every), bool(graph), bool(record),
                     float(score_norm), value_adapter)
+        if start_pool_capacity < 0:
+            raise ValueError(f"start_pool_capacity must not be negative, got {start_pool_capacity}")
         self._cum_host = cum_thresholds(opponent_weights, len(opponents))
         self.group = self._make_group(learner, opponents)
         self.learner, self.opponent_ids = learner, opponent_ids
@@ -188,7 +192,8 @@ class LeagueRollout:
         q = lambda which: _lib.query("ka_league_layout", which)  # noqa: E731
         with torch.cuda.device(dev):
             z = lambda *s, dtype=torch.int32: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731
-            self.env = VecEnv(N, self.max_ply, "katago", "spatial", device=dev, output="torch", check_actions=False)
+            self.env = VecEnv(N, self.max_ply, "katago", "spatial", device=dev, output="torch", check_actions=False,
+                              start_pool_capacity=int(start_pool_capacity))
             self._actions, self._logp, self._nlegal = z(N, dtype=torch.int64), z(N, dtype=torch.float32), z(N)
             self._values = z(N, dtype=torch.float32)
             self._model_of, self._learner_of = z(N), z(N)

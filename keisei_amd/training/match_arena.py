@@ -242,11 +242,13 @@ class MatchArena:
     ``ka_arena_record_pre`` / ``ka_arena_record_post``, into a store allocated here) for ``run_round(trainable=)``.
     ``features=True`` adds the reference's per-slot ``GameFeatureTracker`` to the ply (one launch,
     ``ka_arena_features_step``): every result then carries a ``feature_tracker``.  Without it the ply is launch for
-    launch what it was."""
+    launch what it was.  ``start_pool_capacity > 0`` gives the env a pool of
+    start positions of that size: ``arena.env.set_start_positions(...)`` / ``set_start_sfens(...)`` between rounds make later
+    games start from them (no re-capture; see ``VecEnv``).  Not with ``features=True``."""
 
     def __init__(self, group: SEResNetGroup, num_envs: int = 512, envs_per_match: int = 64, max_ply: int = 512, *,
                  sync_every: int = 32, graph: bool = True, seed: Optional[int] = None, record: bool = False,
-                 collect: bool = False, features: bool = False) -> None:
+                 collect: bool = False, features: bool = False, start_pool_capacity: int = 0) -> None:
         if len(group) == 0:
             raise ValueError("MatchArena needs a group with at least one model")
         if num_envs <= 0 or envs_per_match <= 0 or num_envs % envs_per_match != 0:
@@ -259,6 +261,11 @@ class MatchArena:
             raise ValueError(f"graph=True needs an even sync_every (VecEnv alternates two result buffers), got {sync_every}")
         if graph and record:
             raise ValueError("record=True runs without a graph (graph=False)")
+        if start_pool_capacity < 0:
+            raise ValueError(f"start_pool_capacity must not be negative, got {start_pool_capacity}")
+        if features and start_pool_capacity > 0:
+            raise ValueError("features=True cannot be combined with start_pool_capacity > 0: the opening and rook-square "
+                             "style features are defined from the standard start position")
         if group.device.type != "cuda" or group._tables is None:
             raise ValueError(f"MatchArena runs on a GPU group; this group is on {group.device} (VecEnv has no CPU path)")
         self.group = group
@@ -270,7 +277,8 @@ class MatchArena:
         self.record: List[dict] = []
         N, dev = self.num_envs, self.device
         with torch.cuda.device(dev):
-            self.env = VecEnv(N, self.max_ply, "katago", "spatial", device=dev, output="torch", check_actions=False)
+            self.env = VecEnv(N, self.max_ply, "katago", "spatial", device=dev, output="torch", check_actions=False,
+                              start_pool_capacity=int(start_pool_capacity))
             self._ws = group._tables.workspace(N)
             self._state = torch.zeros(_lib.query("ka_arena_state_words", self.num_slots), dtype=torch.int32, device=dev)
             self._state_host = torch.zeros(self._state.shape, dtype=torch.int32).pin_memory()
