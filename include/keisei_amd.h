@@ -310,6 +310,21 @@ int ka_value_loss(const float* vlogits, const float* score, const long long* cat
                   const long long* idx, const float* rowloss, const float* rowent, float* dvlogits, float* dscore,
                   float* out, float* acc, const float* gscale, float lambda_policy, float lambda_value, float lambda_score,
                   float entropy_coeff, int combined_value_metric, int B, void* stream);
+/* Held-out evaluation of one batch of the supervised heads: no gradient.  logits (B, A), vlogits (B, 3), score (B) and the
+ * targets policy_t / value_t (int64) and score_t (fp32), row b of each.  The batch is ADDED into acc, 64 bytes, 8-byte aligned,
+ * zeroed by the caller before the first batch:
+ *   int64   [positions, top1, topk, value_correct]
+ *   float64 [sum of policy CE, sum of value CE, sum of squared score error, 0]
+ * sums over positions, so batches of different sizes weigh what they should.  Per row: policy CE = logsumexp(z) - z_t in
+ * fp32 as ka_policy_ce forms it; rank = #{j : z_j > z_t} + #{j < t : z_j == z_t}, the target's place in a stable descending
+ * sort, top1 = (rank == 0), topk = (rank < k), 1 <= k <= A; value CE and the predicted class by ka_value_loss's rule
+ * (l0 >= l1 && l0 >= l2 ? 0 : l1 >= l2 ? 1 : 2).  A policy target outside [0, A) adds nothing to the policy terms, a value
+ * target outside {0, 1, 2} nothing to the value terms; either sets flags[1].  flags[0] |= NaN in the logits, the value logits
+ * or the score.  rowloss (fp32[B]) and rank (int32[B]) are workspace.  All reductions run in a fixed order: the same input
+ * gives the same bits. */
+int ka_sl_eval(const float* logits, const float* vlogits, const float* score, const long long* policy_t,
+               const long long* value_t, const float* score_t, int B, int A, int k, float* rowloss, int* rank, void* acc,
+               int* flags, void* stream);
 /* P(W) - P(L), optionally blended with clamp(score,-1,1) (katago_ppo.py:533-541, value_adapter.py:76-96) */
 int ka_scalar_value(const float* vlogits, const float* score, float alpha, float* out, int B, void* stream);
 
@@ -646,6 +661,22 @@ int ka_sl_packed_words(void);
 int ka_sl_pack(const void* records, const long long* src_rows, int n, void* packed_out, int* flags, void* stream);
 int ka_sl_gather(const void* packed, long long n, const long long* idx, int B, float* obs_out, long long* policy_out,
                  long long* value_out, float* score_out, int* flags, void* stream);
+/* gather with the left-right reflection of the board (files reversed, ranks kept; shogi's rules are symmetric under it):
+ *   mode 0  ka_sl_gather.
+ *   mode 1  every row is reflected.
+ *   mode 2  row b is reflected iff h >> 63, h = mix(seed ^ mix((((u64)epoch << 32) | (u32)i) + 0x6D6972726F72)), i = idx[b],
+ *           mix = the splitmix64 finaliser (x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;
+ *           x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31): a function of (seed, epoch, position) alone, whatever the
+ *           batch, its order or the launch geometry.  epoch >= 0.
+ * A reflected row is the plain row with obs[c][r][f] taken from obs[c][r][8 - f] (mask bit r * 9 + (8 - f) of the packed
+ * record) and the policy target a = square * 139 + slot, if it lies in [0, 11259), replaced by mirror(a):
+ *   square (r, f) -> (r, 8 - f);
+ *   slot < 128 (promote = slot & 64, dir = (slot & 63) >> 3 clockwise from north, dist = slot & 7): dir -> (8 - dir) % 8;
+ *   slot 128 + 2 * side + promote (knight): side -> 1 - side;   slots 132..138 (drops) unchanged.
+ * mirror is an involution on [0, 11259); the white perspective (80 - q) commutes with it.  Value and score are unchanged.  An
+ * idx[b] outside [0, n) gives a zero row with targets 0 and adds 1 to flags[0] in every mode. */
+int ka_sl_gather_aug(const void* packed, long long n, const long long* idx, int B, float* obs_out, long long* policy_out,
+                     long long* value_out, float* score_out, int* flags, int mode, long long seed, int epoch, void* stream);
 
 /* ---- transformer encoder path (BASELINE config 5; keisei/training/models/transformer.py:37-95: nn.Linear(50, d),
  * row/col nn.Embedding, nn.TransformerEncoder(nn.TransformerEncoderLayer(d, nhead, 4d, batch_first, norm_first), L),

@@ -127,6 +127,8 @@ _SIGS = {
     "ka_sl_packed_words": "",
     "ka_sl_pack": "pp i pp p",
     "ka_sl_gather": "p q p i ppppp p",
+    "ka_sl_gather_aug": "p q p i ppppp i q i p",
+    "ka_sl_eval": "pppppp iii pp p p p",
     "ka_tf_gemm_nt": "ppppp iii iii iii f q p",
     "ka_tf_gemm_nt_slabs": "ii",
     "ka_tf_gemm_nt_masked": "pppp iii iii f q p",

@@ -299,6 +299,114 @@ __global__ __launch_bounds__(1024) void value_loss_kernel(ValueArgs a) {
     }
 }
 
+// Held-out evaluation of the supervised heads (SLTrainer.evaluate): no gradient, sums over positions instead of batch means.
+// sl_eval_rows_kernel is policy_ce_kernel's row pass -- one workgroup per sample, the logit row staged in LDS, rowloss[b] =
+// logsumexp(row) - row[t] -- and, from the same staged row, the target's place in a stable descending sort:
+//   rank[b] = #{j : z_j > z_t} + #{j < t : z_j == z_t}
+// (an integer count, whatever the order of the threads).  A target outside [0, A) gives rowloss 0, rank A and flags[1].
+// sl_eval_reduce_kernel is one workgroup, as value_loss_kernel: per row the W/D/L cross-entropy and the argmax by its rule,
+// the squared score error, top-1 = rank 0, top-k = rank < k; per-thread sums in double over b, b + 1024, ..., a wave
+// reduction, the 16 waves added in order by thread 0, and thread 0 alone adds the batch into the accumulator -- launches
+// are ordered by the stream, so two runs give the same bits and nothing needs a float atomic.
+struct SlEvalArgs {
+    const float* logits; const float* vlogits; const float* score;
+    const long long* policy_t; const long long* value_t; const float* score_t;
+    float* rowloss; int* rank; long long* acc_i; double* acc_f; int* flags; int B, A, k;
+};
+
+__global__ __launch_bounds__(kPolThreads) void sl_eval_rows_kernel(SlEvalArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* row = reinterpret_cast<float*>(smem);
+    __shared__ float red[kPolThreads / 64];
+    __shared__ int redi[kPolThreads / 64];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* lg = a.logits + (size_t)b * a.A;
+    float mx = -INFINITY;
+    int nan_seen = 0;
+    for (int j = tid; j < a.A; j += kPolThreads) {
+        const float v = lg[j];
+        row[j] = v;
+        nan_seen |= (v != v);
+        mx = fmaxf(mx, v);
+    }
+    mx = block_reduce(mx, red, true);
+    const float nanf_ = block_reduce((float)nan_seen, red, false);
+    float s = 0.f;
+    for (int j = tid; j < a.A; j += kPolThreads) s += expf(row[j] - mx);
+    s = block_reduce(s, red, false);
+    const float lse = mx + logf(s);
+    const long long tgt = a.policy_t[b];
+    const bool ok = tgt >= 0 && tgt < a.A;
+    const float zt = ok ? row[tgt] : 0.f;
+    int above = 0;
+    if (ok)
+        for (int j = tid; j < a.A; j += kPolThreads) {
+            const float v = row[j];
+            above += (v > zt) || (v == zt && j < tgt);
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) above += __shfl_xor(above, o);
+    if ((tid & 63) == 0) redi[tid >> 6] = above;
+    __syncthreads();
+    if (tid == 0) {
+        int rank = 0;
+        for (int w = 0; w < kPolThreads / 64; ++w) rank += redi[w];
+        if (nanf_ > 0.f) atomicOr(&a.flags[0], 1);
+        if (!ok) atomicOr(&a.flags[1], 1);
+        a.rowloss[b] = ok ? lse - zt : 0.f;
+        a.rank[b] = ok ? rank : a.A;
+    }
+}
+
+__global__ __launch_bounds__(1024) void sl_eval_reduce_kernel(SlEvalArgs a) {
+    __shared__ double redd[3][16];
+    __shared__ int redi[3][16];
+    const int tid = threadIdx.x;
+    double sum[3] = {0, 0, 0};                  // policy CE, value CE, squared score error
+    int cnt[3] = {0, 0, 0};                     // top-1, top-k, value prediction right
+    int nan_seen = 0, bad = 0;
+    for (int b = tid; b < a.B; b += 1024) {
+        const float l0 = a.vlogits[b * 3], l1 = a.vlogits[b * 3 + 1], l2 = a.vlogits[b * 3 + 2], sc = a.score[b];
+        nan_seen |= (l0 != l0) | (l1 != l1) | (l2 != l2) | (sc != sc);
+        const long long cat = a.value_t[b];
+        if (cat >= 0 && cat <= 2) {
+            const float m = fmaxf(l0, fmaxf(l1, l2));
+            const float lse = m + logf(expf(l0 - m) + expf(l1 - m) + expf(l2 - m));
+            sum[1] += (double)(lse - (cat == 0 ? l0 : (cat == 1 ? l1 : l2)));
+            const int pred = (l0 >= l1 && l0 >= l2) ? 0 : (l1 >= l2 ? 1 : 2);
+            cnt[2] += pred == cat;
+        } else {
+            bad = 1;
+        }
+        const float d = sc - a.score_t[b];
+        sum[2] += (double)(d * d);
+        sum[0] += (double)a.rowloss[b];
+        const int rank = a.rank[b];
+        cnt[0] += rank == 0;
+        cnt[1] += rank < a.k;
+    }
+    if (nan_seen) atomicOr(&a.flags[0], 1);
+    if (bad) atomicOr(&a.flags[1], 1);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        sum[q] = wave_sum_d(sum[q]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt[q] += __shfl_xor(cnt[q], o);
+        if ((tid & 63) == 0) { redd[q][tid >> 6] = sum[q]; redi[q][tid >> 6] = cnt[q]; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        a.acc_i[0] += a.B;
+        for (int q = 0; q < 3; ++q) {
+            double t = 0;
+            long long c = 0;
+            for (int w = 0; w < 16; ++w) { t += redd[q][w]; c += redi[q][w]; }
+            a.acc_i[1 + q] += c;
+            a.acc_f[q] += t;
+        }
+    }
+}
+
 // rollout side: scalar value P(W)-P(L) (+ optional blend with clamp(score,-1,1))
 __global__ void scalar_value_kernel(const float* __restrict__ vl, const float* __restrict__ score, float alpha,
                                     float* __restrict__ out, int B) {
@@ -504,6 +612,23 @@ extern "C" int ka_value_loss(const float* vlogits, const float* score, const lon
                 lambda_policy, lambda_value, lambda_score, entropy_coeff, B, combined_value_metric};
     hipLaunchKernelGGL(value_loss_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), a);
     return ka_check_launch("value_loss");
+}
+
+extern "C" int ka_sl_eval(const float* logits, const float* vlogits, const float* score, const long long* policy_t,
+                          const long long* value_t, const float* score_t, int B, int A, int k, float* rowloss, int* rank,
+                          void* acc, int* flags, void* stream) {
+    KA_REQUIRE(logits && vlogits && score && policy_t && value_t && score_t && rowloss && rank && acc && flags,
+               "sl_eval: null tensor");
+    KA_REQUIRE(B > 0 && A > 0, "sl_eval: B %d, A %d", B, A);
+    KA_REQUIRE(k >= 1 && k <= A, "sl_eval: k %d outside [1, %d]", k, A);
+    KA_REQUIRE((reinterpret_cast<uintptr_t>(acc) & 7) == 0, "sl_eval: the accumulator must be 8-byte aligned");
+    const size_t lds = ((size_t)A * 4 + 15) / 16 * 16;
+    KA_REQUIRE(lds <= 64 * 1024, "sl_eval: action space %d too large for the LDS row", A);
+    SlEvalArgs a{logits, vlogits, score, policy_t, value_t, score_t, rowloss, rank, static_cast<long long*>(acc),
+                 reinterpret_cast<double*>(static_cast<char*>(acc) + 32), flags, B, A, k};
+    hipLaunchKernelGGL(sl_eval_rows_kernel, dim3(B), dim3(kPolThreads), lds, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(sl_eval_reduce_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), a);
+    return ka_check_launch("sl_eval");
 }
 
 extern "C" int ka_scalar_value(const float* vlogits, const float* score, float alpha, float* out, int B, void* stream) {

@@ -18,7 +18,14 @@
 //                     observation as coalesced 8-byte stores (a row of obs_out starts at 16 200 * b bytes: 8-byte aligned
 //                     only) and the three targets.  An index outside [0, n) counts in the flag word and gives a zero row:
 //                     nothing outside the dataset is read.
-// Both are memory-bound copies; nothing in them is tuned further.
+//   sl_gather_kernel<true> (ka_sl_gather_aug) is the same kernel with the left-right reflection of the board decided per row:
+//                     shogi's rules are symmetric under (rank, file) -> (rank, 8 - file), so a reflected row reads mask bit
+//                     r * 9 + (8 - c) where the plain one reads r * 9 + c, and its policy target goes through
+//                     sl_mirror_action (square reflected, E<->W / NE<->NW / SE<->SW, the two knight jumps swapped, drops
+//                     kept).  Value and score do not change.  mode 1 reflects every row, mode 2 the rows whose draw
+//                     h(seed, epoch, idx[b]) has its top bit set (include/keisei_amd.h states the draw).  The <false>
+//                     instance, which ka_sl_gather launches, contains none of this.
+// All are memory-bound copies; nothing in them is tuned further.
 #include "common.h"
 
 #include <limits.h>
@@ -85,32 +92,66 @@ __global__ __launch_bounds__(kPkThreads) void sl_pack_kernel(const uint32_t* __r
     }
 }
 
+__device__ __forceinline__ unsigned long long sl_mix(unsigned long long x) {      // the splitmix64 finaliser
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+constexpr unsigned long long kSaltMirror = 0x6D6972726F72ull;     // "mirror"
+
+// The reflected action of a spatial action index square * 139 + slot (keisei_amd/shogi_gym.py, _DIRS clockwise from north):
+// slots 0..127 = promote * 64 + dir * 8 + (dist - 1), 128..131 = 128 + 2 * side + promote (knight), 132..138 = drops.
+__device__ __forceinline__ uint32_t sl_mirror_action(uint32_t a) {
+    const uint32_t sq = a / 139u, slot = a - sq * 139u;
+    const uint32_t msq = sq + 8u - 2u * (sq % 9u);
+    uint32_t mslot = slot;
+    if (slot < 128u) mslot = (slot & 64u) | (((8u - ((slot & 63u) >> 3)) & 7u) << 3) | (slot & 7u);
+    else if (slot < 132u) mslot = slot ^ 2u;
+    return msq * 139u + mslot;
+}
+
+template <bool kAug>
 __global__ __launch_bounds__(kPkThreads) void sl_gather_kernel(const uint32_t* __restrict__ packed, long long n,
                                                                const long long* __restrict__ idx, int B,
                                                                uint32_t* __restrict__ obs_out, long long* __restrict__ policy_out,
                                                                long long* __restrict__ value_out, uint32_t* __restrict__ score_out,
-                                                               int* __restrict__ flags) {
+                                                               int* __restrict__ flags, int mode, unsigned long long seed,
+                                                               unsigned epoch) {
     __shared__ uint32_t s_row[kPkWords];
     const int b = blockIdx.x, tid = threadIdx.x;
     if (b >= B) return;
     const long long r = idx[b];
     const bool inside = r >= 0 && r < n;                           // uniform over the workgroup
+    bool reflect = false;                                          // uniform too; a row outside the dataset stays all zero
+    if constexpr (kAug) {
+        if (inside && mode == 1) reflect = true;
+        if (inside && mode == 2)
+            reflect = (sl_mix(seed ^ sl_mix((((unsigned long long)epoch << 32) | (uint32_t)r) + kSaltMirror)) >> 63) != 0ull;
+    }
     if (tid < kPkWords) s_row[tid] = inside ? packed[(size_t)r * kPkWords + tid] : 0u;
     __syncthreads();
     uint2* dst = reinterpret_cast<uint2*>(obs_out + (size_t)b * kPkObsWords);
     for (int j = tid; j < kPkObsWords / 2; j += kPkThreads) {
         uint2 out;
         {
-            const int e = 2 * j, c = e / kPkSquares, p = e - c * kPkSquares;
+            const int e = 2 * j, c = e / kPkSquares;
+            int p = e - c * kPkSquares;
+            if constexpr (kAug) { if (reflect) p += 8 - 2 * (p % 9); }
             out.x = (s_row[3 * c + (p >> 5)] >> (p & 31)) & 1u ? s_row[kPkValueAt + c] : 0u;
         }
         {
-            const int e = 2 * j + 1, c = e / kPkSquares, p = e - c * kPkSquares;
+            const int e = 2 * j + 1, c = e / kPkSquares;
+            int p = e - c * kPkSquares;
+            if constexpr (kAug) { if (reflect) p += 8 - 2 * (p % 9); }
             out.y = (s_row[3 * c + (p >> 5)] >> (p & 31)) & 1u ? s_row[kPkValueAt + c] : 0u;
         }
         dst[j] = out;
     }
     if (tid == 0) {
+        if constexpr (kAug) {                                      // (a policy outside the action space is left as stored)
+            if (reflect && s_row[kPkPolicyAt + 0] < kPkActions) s_row[kPkPolicyAt + 0] = sl_mirror_action(s_row[kPkPolicyAt + 0]);
+        }
         policy_out[b] = (long long)(int)s_row[kPkPolicyAt + 0];
         value_out[b] = (long long)(int)s_row[kPkPolicyAt + 1];
         score_out[b] = s_row[kPkPolicyAt + 2];
@@ -139,8 +180,26 @@ extern "C" int ka_sl_gather(const void* packed, long long n, const long long* id
     KA_REQUIRE(B > 0, "sl_gather: B %d", B);
     KA_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 3) == 0 && (reinterpret_cast<uintptr_t>(obs_out) & 7) == 0,
                "sl_gather: the packed rows must be 4-byte aligned and the observations 8-byte aligned");
-    hipLaunchKernelGGL(sl_gather_kernel, dim3(B), dim3(kPkThreads), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(sl_gather_kernel<false>, dim3(B), dim3(kPkThreads), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint32_t*>(packed), n, idx, B, reinterpret_cast<uint32_t*>(obs_out), policy_out,
-                       value_out, reinterpret_cast<uint32_t*>(score_out), flags);
+                       value_out, reinterpret_cast<uint32_t*>(score_out), flags, 0, 0ull, 0u);
     return ka_check_launch("sl_gather");
+}
+
+extern "C" int ka_sl_gather_aug(const void* packed, long long n, const long long* idx, int B, float* obs_out,
+                                long long* policy_out, long long* value_out, float* score_out, int* flags, int mode,
+                                long long seed, int epoch, void* stream) {
+    KA_REQUIRE(mode >= 0 && mode <= 2, "sl_gather_aug: mode %d (0 plain, 1 every row reflected, 2 drawn per row)", mode);
+    KA_REQUIRE(epoch >= 0, "sl_gather_aug: epoch %d", epoch);
+    if (mode == 0) return ka_sl_gather(packed, n, idx, B, obs_out, policy_out, value_out, score_out, flags, stream);
+    KA_REQUIRE(idx && obs_out && policy_out && value_out && score_out && flags, "sl_gather_aug: null tensor");
+    KA_REQUIRE(n >= 0 && (packed || n == 0), "sl_gather_aug: n %lld without a dataset", n);
+    KA_REQUIRE(B > 0, "sl_gather_aug: B %d", B);
+    KA_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 3) == 0 && (reinterpret_cast<uintptr_t>(obs_out) & 7) == 0,
+               "sl_gather_aug: the packed rows must be 4-byte aligned and the observations 8-byte aligned");
+    hipLaunchKernelGGL(sl_gather_kernel<true>, dim3(B), dim3(kPkThreads), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint32_t*>(packed), n, idx, B, reinterpret_cast<uint32_t*>(obs_out), policy_out,
+                       value_out, reinterpret_cast<uint32_t*>(score_out), flags, mode, (unsigned long long)seed,
+                       (unsigned)epoch);
+    return ka_check_launch("sl_gather_aug");
 }

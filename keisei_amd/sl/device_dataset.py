@@ -12,6 +12,12 @@ on arrival) or from records that are already on the device (``append_raw``: the 
 targets ``SLDataset`` would refuse, is never stored in altered form: the load raises.
 
 ``pack_records`` / ``unpack_records`` are the two kernels in numpy: the yardstick the GPU tests hold them to, byte for byte.
+
+Shogi's rules are symmetric under the left-right reflection of the board (files reversed, ranks kept), so a reflected
+position with the reflected move is as valid a sample as the original.  ``gather(..., mirror=)`` decodes rows reflected
+(``ka_sl_gather_aug``: another mask bit per square and a closed form on the policy target; no second copy of the corpus);
+``mirror_action`` / ``mirror_records`` / ``sl_mirror_draw`` restate it in numpy.  ``view(start, stop)`` is a read-only
+dataset over a range of the same memory: shards keep game order, so a tail range is a held-out set of whole games.
 """
 from __future__ import annotations
 
@@ -24,13 +30,17 @@ import torch
 from keisei_amd import _lib
 from keisei_amd.sl.dataset import NUM_ACTIONS, OBS_SIZE, RECORD_SIZE, SLDataset, _RECORD
 
-__all__ = ["DeviceSLDataset", "pack_records", "unpack_records", "PACKED_WORDS", "PACKED_BYTES"]
+__all__ = ["DeviceSLDataset", "pack_records", "unpack_records", "mirror_action", "mirror_records", "sl_mirror_draw",
+           "PACKED_WORDS", "PACKED_BYTES"]
 
 PACKED_WORDS = 204                       # KA_SL_PACKED_WORDS
 PACKED_BYTES = 4 * PACKED_WORDS
 _CHANNELS, _SQUARES = 50, 81
 _VALUE_AT, _POLICY_AT = 3 * _CHANNELS, 4 * _CHANNELS
 _INT_MAX = 2 ** 31 - 1
+_M64 = 2 ** 64 - 1
+_MIRROR_SALT = 0x6D6972726F72            # "mirror": the salt of ka_sl_gather_aug's draw
+MIRROR_NONE, MIRROR_ALL, MIRROR_DRAWN = 0, 1, 2      # the modes of ka_sl_gather_aug
 _UNPACKABLE = "channel values are not one-valued planes; this dataset cannot be held packed"
 
 
@@ -98,6 +108,51 @@ def unpack_records(packed) -> np.ndarray:
     return rec
 
 
+def mirror_action(a) -> np.ndarray:
+    """The spatial action index ``square * 139 + slot`` of the left-right reflected move (int64, any shape): the square's
+    file reversed; sliding slots (``promote * 64 + dir * 8 + dist - 1``, ``dir`` clockwise from north) ``dir -> (8 - dir) % 8``;
+    knight slots ``128 + 2 * side + promote`` with the side swapped; drop slots 132..138 unchanged.  An involution."""
+    a = np.asarray(a, dtype=np.int64)
+    if a.size and (a.min() < 0 or a.max() >= NUM_ACTIONS):
+        raise ValueError(f"action indices must lie in [0, {NUM_ACTIONS})")
+    square, slot = np.divmod(a, 139)
+    square = square + 8 - 2 * (square % 9)
+    sliding = (slot & 64) | (((8 - ((slot & 63) >> 3)) & 7) << 3) | (slot & 7)
+    slot = np.where(slot < 128, sliding, np.where(slot < 132, slot ^ 2, slot))
+    return square * 139 + slot
+
+
+def mirror_records(records) -> np.ndarray:
+    """Shard records of the reflected positions: every plane with its file axis reversed, the policy through
+    ``mirror_action``, value and score as they are (``ka_sl_gather_aug`` mode 1 in numpy)."""
+    rec = _as_records(records)
+    out = rec.copy()
+    out["obs"] = rec["obs"].reshape(len(rec), _CHANNELS, 9, 9)[:, :, :, ::-1].reshape(len(rec), OBS_SIZE)
+    out["policy"] = mirror_action(rec["policy"])
+    return out
+
+
+def _mix64(x: np.ndarray) -> np.ndarray:
+    """The splitmix64 finaliser over uint64 arrays (wrapping arithmetic), ``sl_mix`` of csrc/sl_data.hip."""
+    x = x + np.uint64(0x9E3779B97F4A7C15)
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def sl_mirror_draw(seed: int, epoch: int, indices) -> np.ndarray:
+    """Which positions ``ka_sl_gather_aug`` reflects in mode 2 (bool, the shape of ``indices``): the top bit of
+    ``h = mix(seed ^ mix(((epoch << 32) | index) + 0x6D6972726F72))`` (include/keisei_amd.h), a function of
+    (seed, epoch, position) alone."""
+    if not 0 <= int(epoch) <= _INT_MAX:
+        raise ValueError(f"epoch must lie in [0, 2^31), got {epoch}")
+    with np.errstate(over="ignore"):
+        i = np.asarray(indices).astype(np.int64).astype(np.uint64) & np.uint64(0xFFFFFFFF)
+        key = ((np.uint64(int(epoch)) << np.uint64(32)) | i) + np.uint64(_MIRROR_SALT)
+        h = _mix64(np.uint64(int(seed) & _M64) ^ _mix64(key))
+    return (h >> np.uint64(63)).astype(bool)
+
+
 # ---------------------------------------------------------------------------------------------- the device dataset
 def _require_library() -> None:
     words = _lib.query("ka_sl_packed_words")                    # raises KeiseiHipError without the library
@@ -123,6 +178,7 @@ class DeviceSLDataset:
         self._device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
         self._packed = torch.empty(0, PACKED_WORDS, dtype=torch.int32, device=self._device)
         self._n = 0
+        self._read_only = False                                  # a view(): rows of another dataset's memory
         # flags of the pack launches not read yet: (index of the launch's first position, int32[4] on the device)
         self._unread: List[Tuple[int, torch.Tensor]] = []
 
@@ -165,6 +221,8 @@ class DeviceSLDataset:
     def append_raw(self, raw_device_bytes: torch.Tensor, src_rows) -> None:
         """Pack the records ``src_rows`` (row numbers, in the order they are to be appended) of a device buffer of
         16 220-byte records onto the end.  Nothing is read back: ``check()`` reports what could not be packed."""
+        if self._read_only:
+            raise ValueError("this dataset is a view of another one's memory and cannot grow: append to its parent")
         raw = raw_device_bytes
         if raw.dtype != torch.uint8 or not raw.is_contiguous() or raw.device != self._device or raw.numel() % RECORD_SIZE:
             raise ValueError(f"raw_device_bytes must be a contiguous uint8 tensor of whole {RECORD_SIZE}-byte records "
@@ -269,22 +327,45 @@ class DeviceSLDataset:
         source.clear_cache()
         return self
 
+    def view(self, start: int, stop: int) -> "DeviceSLDataset":
+        """The positions ``[start, stop)`` as a dataset over the SAME device memory: no copy, read-only (``append_raw``
+        raises).  It covers the rows as they lie when it is taken: a parent that grows past its allocation afterwards
+        moves on to new memory and the view keeps the old.  Positions not checked yet stay the parent's to ``check()``."""
+        start, stop = int(start), int(stop)
+        if not 0 <= start <= stop <= self._n:
+            raise IndexError(f"view [{start}, {stop}) out of range for dataset with {self._n} positions")
+        part = DeviceSLDataset(self._device)
+        part._packed = self._packed[start:stop]
+        part._n = stop - start
+        part._read_only = True
+        return part
+
     # ------------------------------------------------------------------ reading
-    def gather(self, idx: torch.Tensor, flag: torch.Tensor) -> dict:
+    def gather(self, idx: torch.Tensor, flag: torch.Tensor, *, mirror: int = MIRROR_NONE, seed: int = 0, epoch: int = 0) -> dict:
         """The batch of the int64 device tensor ``idx`` as fresh device tensors, keys / dtypes / shapes of
         ``SLDataset.read_batch``: one launch, no host work.  An index outside the dataset adds 1 to ``flag`` (int32[1] on
-        the device) and gives a zero row."""
+        the device) and gives a zero row.  ``mirror``: 0 the rows as stored, 1 every row reflected left to right, 2 the rows
+        ``sl_mirror_draw(seed, epoch, idx)`` names."""
         if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != self._device or not idx.is_contiguous():
             raise ValueError(f"idx must be a contiguous 1-d int64 tensor on {self._device}")
+        if mirror not in (MIRROR_NONE, MIRROR_ALL, MIRROR_DRAWN):
+            raise ValueError(f"mirror must be 0 (off), 1 (every row) or 2 (drawn per row), got {mirror!r}")
+        if not 0 <= int(epoch) <= _INT_MAX:
+            raise ValueError(f"epoch must lie in [0, 2^31), got {epoch}")
         B, dev = idx.shape[0], self._device
         with torch.cuda.device(dev):
             out = {"observation": torch.empty(B, _CHANNELS, 9, 9, dtype=torch.float32, device=dev),
                    "policy_target": torch.empty(B, dtype=torch.int64, device=dev),
                    "value_target": torch.empty(B, dtype=torch.int64, device=dev),
                    "score_target": torch.empty(B, dtype=torch.float32, device=dev)}
-            if B:
+            if B and mirror == MIRROR_NONE:
                 _lib.call("ka_sl_gather", self._packed, self._n, idx, B, out["observation"], out["policy_target"],
                           out["value_target"], out["score_target"], flag, _lib.stream_ptr(dev))
+            elif B:
+                seed64 = int(seed) & _M64                        # the C ABI takes the 64 bits as a signed long long
+                _lib.call("ka_sl_gather_aug", self._packed, self._n, idx, B, out["observation"], out["policy_target"],
+                          out["value_target"], out["score_target"], flag, int(mirror),
+                          seed64 - (1 << 64) if seed64 >> 63 else seed64, int(epoch), _lib.stream_ptr(dev))
         return out
 
     def read_batch(self, indices) -> dict:

@@ -13,7 +13,12 @@ trained on data).  Two execution paths:
 * **device-resident fused path** (``SLConfig.device_resident`` or a ``DeviceSLDataset`` handed to the constructor; not in
   the reference): the positions stay packed in device memory, one permutation per epoch is uploaded once, and a
   minibatch is one ``ka_sl_gather`` launch in front of the same per-batch body -- no thread, no pinned copy, no upload
-  per batch.  Asked for where the fused path cannot run, it raises instead of falling back.
+  per batch.  Asked for where the fused path cannot run, it raises instead of falling back.  ``SLConfig.mirror_augment``
+  has that gather reflect, left to right, the positions a draw of (``mirror_seed``, epoch, position) names.
+* **held-out evaluation** (``evaluate()``, not in the reference; the fused path only): eval-mode forwards under ``no_grad``
+  over a ``DeviceSLDataset`` -- ``eval_dataset``, typically a tail ``view()`` of the corpus -- one gather and one
+  ``ka_sl_eval`` per chunk, the losses as sums over positions and the top-1 / top-k / value hit counts in a 64-byte
+  device accumulator that is read once at the end.  Nothing of the training state changes.
 * **generic path** (CPU tensors, other models): the reference's loop in ordinary tensor ops.
 
 The shuffling is the reference's: the batch order comes from a ``DataLoader`` (``shuffle=True``) -- over the items on
@@ -24,7 +29,7 @@ from __future__ import annotations
 import logging
 import math
 from concurrent.futures import ThreadPoolExecutor
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from pathlib import Path
 from typing import Optional
 
@@ -35,7 +40,7 @@ from torch.utils.data import DataLoader, Dataset, get_worker_info
 
 from keisei_amd import _lib
 from keisei_amd.sl.dataset import SLDataset
-from keisei_amd.sl.device_dataset import DeviceSLDataset
+from keisei_amd.sl.device_dataset import MIRROR_ALL, MIRROR_DRAWN, MIRROR_NONE, DeviceSLDataset
 from keisei_amd.training.fused_optim import FusedAdamMixin
 from keisei_amd.training.models.katago_base import KataGoBaseModel
 from keisei_amd.training.models.se_resnet import SEResNetModel
@@ -56,6 +61,10 @@ class SLConfig:
     grad_clip: float = 0.5
     use_amp: bool = False
     allow_placeholder: bool = False
+    # the device-resident epoch reflects the drawn positions left to right (keyword-only: device_resident stays the last
+    # field and the last positional argument); not in the reference
+    mirror_augment: bool = field(default=False, kw_only=True)
+    mirror_seed: int = field(default=0, kw_only=True)
     device_resident: bool = False          # hold the dataset packed in device memory (DeviceSLDataset); not in the reference
 
     def __post_init__(self) -> None:
@@ -72,6 +81,8 @@ class SLConfig:
                 raise ValueError(f"{name} must be finite, got {value!r}")
             if value < 0:
                 raise ValueError(f"{name} must be >= 0, got {value!r}")
+        if not -2 ** 63 <= self.mirror_seed < 2 ** 64:
+            raise ValueError(f"mirror_seed must fit 64 bits, got {self.mirror_seed!r}")
 
 
 def _sl_worker_init(worker_id: int) -> None:
@@ -102,7 +113,8 @@ class _Indices(Dataset):
 class SLTrainer(FusedAdamMixin):
     """Trains one epoch per ``train_epoch()`` call; checkpointing is the caller's business."""
 
-    def __init__(self, model: KataGoBaseModel, config: SLConfig, dataset: Optional[DeviceSLDataset] = None) -> None:
+    def __init__(self, model: KataGoBaseModel, config: SLConfig, dataset: Optional[DeviceSLDataset] = None,
+                 eval_dataset: Optional[DeviceSLDataset] = None) -> None:
         self.model = model
         self.config = config
         self.device = next(model.parameters()).device
@@ -120,6 +132,11 @@ class SLTrainer(FusedAdamMixin):
         self._hip_state: dict = {}
         self._order_override: Optional[torch.Tensor] = None     # tests: the next device epoch's order instead of randperm
         self.device_dataset: Optional[DeviceSLDataset] = None
+        self.eval_dataset = eval_dataset                        # what evaluate() reads when it is given no dataset
+        self.epochs_done = 0                                    # train_epoch() calls so far: the epoch of the mirror draw
+        if config.mirror_augment and dataset is None and not config.device_resident:
+            raise ValueError("mirror_augment reflects positions inside the device-resident gather: it needs "
+                             "device_resident=True or a DeviceSLDataset, there is no reflection on the shard path")
         if dataset is not None or config.device_resident:
             # the positions stay packed on the device and config.data_dir is read at most once, here; there is no other
             # way to run this than the fused path, and no falling back to the shard path
@@ -158,6 +175,7 @@ class SLTrainer(FusedAdamMixin):
             sums, batches = self._epoch_fused()
         else:
             sums, batches = self._epoch_generic()
+        self.epochs_done += 1
         if batches > 0:                       # an empty dataset must not burn annealing ticks (trainer.py:176-179)
             self.scheduler.step()
         d = max(batches, 1)
@@ -304,7 +322,76 @@ class SLTrainer(FusedAdamMixin):
         ep = self._fused_begin()
         gather_flag = ep["flags"][2:3]
         batches = 0
+        how = {}
+        if self.config.mirror_augment:                           # the draw of (mirror_seed, this epoch, position)
+            how = dict(mirror=MIRROR_DRAWN, seed=self.config.mirror_seed, epoch=self.epochs_done)
         for lo in range(0, order.shape[0], self.config.batch_size):
-            self._fused_batch(ep, ds.gather(order[lo:lo + self.config.batch_size], gather_flag))
+            self._fused_batch(ep, ds.gather(order[lo:lo + self.config.batch_size], gather_flag, **how))
             batches += 1
         return self._fused_end(ep, batches)
+
+    # ------------------------------------------------------------------ held-out evaluation
+    def evaluate(self, dataset: Optional[DeviceSLDataset] = None, *, batch_size: Optional[int] = None, topk: int = 5,
+                 mirror: bool = False) -> dict:
+        """Losses and hit rates over ``dataset`` (default ``eval_dataset``) without an update: eval-mode forwards under
+        ``no_grad`` in ``batch_size`` chunks (default ``config.batch_size``, the last one partial), each one gather and one
+        ``ka_sl_eval``; the accumulator and the flags are read once, at the end.  ``mirror=True`` evaluates the reflected
+        positions.  Losses are means over positions (not means of batch means), ``policy_top1`` / ``policy_topk`` the
+        fraction of positions whose target move ranks first / among the first ``topk`` logits (ties by the lower index).
+        Parameters, BatchNorm buffers, optimiser, scaler, scheduler and every module's train / eval mode are left as found."""
+        ds = self.eval_dataset if dataset is None else dataset
+        if ds is None:
+            raise ValueError("evaluate() needs a dataset: pass one or construct the trainer with eval_dataset=")
+        if not self._fused_path_available():
+            raise ValueError("evaluate() runs on the fused HIP path only: an SEResNetModel on a GPU, fp32 or bf16 AMP "
+                             f"(got {type(self.model).__name__} on {self.device}, use_amp={self.config.use_amp})")
+        if ds.device != self.device:
+            raise ValueError(f"the dataset lives on {ds.device}, the model on {self.device}")
+        chunk = self.config.batch_size if batch_size is None else int(batch_size)
+        if chunk < 1:
+            raise ValueError(f"batch_size must be > 0, got {batch_size}")
+        if topk < 1:
+            raise ValueError(f"topk must be >= 1, got {topk}")
+        dev, n = self.device, len(ds)
+        acc = torch.zeros(8, dtype=torch.int64, device=dev)      # int64[4] counts, then float64[4] sums (ka_sl_eval)
+        flags = torch.zeros(3, dtype=torch.int32, device=dev)    # non-finite outputs, bad target, bad gather index
+        modes = [(m, m.training) for m in self.model.modules()]
+        A = None
+        self.model.eval()
+        try:
+            with torch.no_grad(), torch.cuda.device(dev):
+                order = torch.arange(n, device=dev)
+                rowloss = torch.empty(min(chunk, n), device=dev)
+                rank = torch.empty(min(chunk, n), dtype=torch.int32, device=dev)
+                sp = _lib.stream_ptr(dev)
+                for lo in range(0, n, chunk):
+                    batch = ds.gather(order[lo:lo + chunk], flags[2:3], mirror=MIRROR_ALL if mirror else MIRROR_NONE)
+                    B = batch["observation"].shape[0]
+                    out = self.model(batch["observation"])
+                    logits = out.policy_logits.reshape(B, -1)
+                    if A is None:
+                        A = logits.shape[1]
+                        if topk > A:
+                            raise ValueError(f"topk must be <= the {A} actions, got {topk}")
+                    if any(t.dtype != torch.float32 for t in (logits, out.value_logits, out.score_lead)):
+                        raise _lib.KeiseiHipError("evaluate(): the model's outputs must be fp32")
+                    _lib.call("ka_sl_eval", logits.contiguous(), out.value_logits.contiguous(),
+                              out.score_lead.reshape(B).contiguous(), batch["policy_target"], batch["value_target"],
+                              batch["score_target"], B, A, int(topk), rowloss, rank, acc, flags, sp)
+        finally:
+            for m, was in modes:
+                m.training = was
+        host = torch.cat([acc, flags.to(torch.int64)]).cpu()     # the one read-back
+        counts, sums = host[:4].tolist(), host[4:8].view(torch.float64).tolist()
+        nan, bad_target, bad_index = host[8:].tolist()
+        if bad_index:
+            raise IndexError(f"{bad_index} indices outside the dataset reached the gather kernel")
+        if nan:
+            raise ValueError("non-finite model outputs reached the evaluation kernel")
+        if bad_target:
+            raise ValueError(f"a policy target outside [0, {A}) or a value target outside {{0, 1, 2}} reached the "
+                             "evaluation kernel")
+        d = max(counts[0], 1)
+        return {"policy_loss": sums[0] / d, "value_loss": sums[1] / d, "score_loss": sums[2] / d,
+                "policy_top1": counts[1] / d, "policy_topk": counts[2] / d, "value_accuracy": counts[3] / d,
+                "positions": int(counts[0])}

@@ -6,12 +6,16 @@ Data: the positions of tests/golden/g15_games.{sfen,csa} (prepared on the device
 as shards of 8192 into a temporary directory -- about 1 GB at the default, the page cache warm after the write and the
 warm-up epoch.  Workloads: se_resnet 6x128 at B = 2048 and 40x256 at B = 4096, bf16.  Per workload and path: one warm-up
 epoch, then the best of --repeat epochs; the shard path and the device path alternate model by model in one job, so the
-ratio is not a job-to-job comparison.  Also reported: the ``DeviceSLDataset.from_shards`` load time (best of --repeat,
+ratio is not a job-to-job comparison.  Two more legs run on the device-resident dataset: ``mirror``, the device epoch with
+``SLConfig.mirror_augment`` (the gather reflects the drawn half of the positions), and ``evaluate``, ``SLTrainer.evaluate``
+over the same positions (eval-mode forwards and ``ka_sl_eval``; --eval-batch rows per chunk, 0 = the training batch), timed
+the same way.  --legs chooses among shard, device, mirror, evaluate.  Also reported: the ``DeviceSLDataset.from_shards`` load time (best of --repeat,
 after a warm-up load) and the positions/s of the replay-and-pack step of ``prepare_sl_dataset`` on the synthetic games of
 tools/sl_prepare_bench.py (as there, the games go in as action indices: parsing is not in the timing).
 Clocks are not pinned.  One JSON line.
 
     python tools/sl_epoch_bench.py [--positions 65536] [--repeat 3] [--games 512] [--workloads 6x128,40x256]
+                                   [--legs shard,device,mirror,evaluate] [--eval-batch 0]
 """
 from __future__ import annotations
 
@@ -88,7 +92,13 @@ def main() -> None:
     ap.add_argument("--games", type=int, default=512, help="synthetic games of the prepare_sl_dataset timing; 0 skips it")
     ap.add_argument("--moves", type=int, default=120)
     ap.add_argument("--workloads", default="6x128,40x256")
+    ap.add_argument("--legs", default="shard,device,mirror,evaluate")
+    ap.add_argument("--eval-batch", type=int, default=0, help="rows per evaluate() chunk; 0 = the workload's training batch")
     args = ap.parse_args()
+    legs = args.legs.split(",")
+    unknown = set(legs) - {"shard", "device", "mirror", "evaluate"}
+    if unknown:
+        ap.error(f"unknown legs {sorted(unknown)}")
     out = {"metric": "sl_epoch_positions_per_s", "positions": args.positions, "repeat": args.repeat, "dtype": "bf16"}
     with tempfile.TemporaryDirectory() as tmp:
         out["distinct_positions"] = write_shards(Path(tmp), args.positions)
@@ -101,19 +111,29 @@ def main() -> None:
         for name in args.workloads.split(","):
             params, batch = WORKLOADS[name]
             row = {"batch": batch}
-            for path in ("shard", "device"):
+            for path in legs:
                 torch.manual_seed(0)
                 model = build_model("se_resnet", params).to("cuda")
-                cfg = SLConfig(data_dir=tmp, batch_size=batch, use_amp=True)
-                trainer = SLTrainer(model, cfg, dataset=dataset if path == "device" else None)
-                assert trainer._fused_path_available() and (trainer.device_dataset is not None) == (path == "device")
-                seconds, metrics = best_epoch(trainer, args.repeat)
+                cfg = SLConfig(data_dir=tmp, batch_size=batch, use_amp=True, mirror_augment=path == "mirror")
+                trainer = SLTrainer(model, cfg, dataset=None if path == "shard" else dataset)
+                assert trainer._fused_path_available() and (trainer.device_dataset is not None) == (path != "shard")
+                if path == "evaluate":
+                    held = {}
+                    chunk = args.eval_batch or batch
+                    seconds = timed(lambda: held.update(m=trainer.evaluate(dataset, batch_size=chunk)), args.repeat)
+                    metrics = held["m"]
+                    row["evaluate_batch"] = chunk
+                    row["evaluate_policy_top1"] = round(metrics["policy_top1"], 4)
+                else:
+                    seconds, metrics = best_epoch(trainer, args.repeat)
                 row[f"{path}_s"] = round(seconds, 4)
                 row[f"{path}_positions_per_s"] = round(args.positions / seconds)
                 row[f"{path}_policy_loss"] = round(metrics["policy_loss"], 4)
                 del trainer, model
                 torch.cuda.empty_cache()
-            row["device_over_shard"] = round(row["shard_s"] / row["device_s"], 3)
+            for a, b in (("device", "shard"), ("mirror", "device"), ("evaluate", "device")):
+                if f"{a}_s" in row and f"{b}_s" in row:
+                    row[f"{a}_over_{b}"] = round(row[f"{b}_s"] / row[f"{a}_s"], 3)
             out[name] = row
         del dataset, held
     if args.games:
