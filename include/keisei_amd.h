@@ -615,6 +615,56 @@ int ka_selfplay_step(int* state, int envs, const float* obs, const void* mask_bi
                      float* values, float* t_obs, int* t_list, const long long* desc, int* plan, int obs_elems,
                      int mask_words, void* stream);
 
+/* ---- game log (csrc/gamelog.hip; the per-env move_history of the reference's VecEnv, vec_env.rs:259, cleared on
+ * auto-reset): the moves of the games played on the device, kept inside the ply and handed over as whole finished games.
+ * E envs (at most ka_gamelog_words(6, 0)); every buffer is device memory owned by the caller:
+ *   rows     E x row_stride uint16, 4-byte aligned, row_stride even and >= max_ply: the moves of the game in progress
+ *   meta     E x ka_gamelog_words(2, 0) int32 {moves in the row, carried (0 / 1), games finished since begin, unused}
+ *   starts   E x 24 int32: the first 96 bytes of the env's state row (board[81] hands[2][7] side, a pool row) as they were
+ *            when the game in progress began
+ *   records  game_cap x ka_gamelog_words(0, max_ply) int32, one finished game each: 12 header words {env, plies, winner
+ *            0 black / 1 white / 2 draw, termination reason, flags (bit 0 truncated and not terminated, bit 1 carried),
+ *            black id, white id, the owner's ply counter, number of the game within its env since begin, 3 zero words},
+ *            the 24 start words, then the moves two per word, low half first.  The unused half of the last move word is
+ *            zero; the words behind it are not written.
+ *   cursor   ka_gamelog_words(1, 0) int32 {records committed, records dropped, plies logged, unused}.  The host reads and
+ *            zeroes it at its sync point, outside any captured graph.
+ * ka_gamelog_words(which, max_ply): int32 words of 0 = one record, 1 = the cursor, 2 = one env's meta, 3 = the move words
+ *   of a record ((max_ply + 1) / 2), 4 = a record's header, 5 = a start position; 6 = the largest E; -1 for any other which.
+ * ka_gamelog_begin (after ka_shogi_env_reset / ka_shogi_env_reset_pool): for every env an empty row, carried 0, game
+ *   number 0, and the start slot copied from the state row (state_bytes = ka_shogi_env_state_bytes(), a multiple of 4).
+ * ka_gamelog_step (after ka_shogi_env_step / ka_shogi_env_step_pool, BEFORE the owner's bookkeeping launch --
+ *   ka_selfplay_step, ka_arena_referee -- because the referee rewrites model_of and pre_player).  For every env e, in
+ *   this order:
+ *     1. actions[e] is appended to the row as uint16 unless the row already holds max_ply moves (it then stays as it is).
+ *     2. live (E int32, may be NULL = every env is live; the arena's pre-step model_of): where live[e] < 0 the env's carried
+ *        flag is set -- a ply of this game was not played by a seated model.
+ *     3. where terminated[e] | truncated[e], the env is live, and no env of its group had nlegal == 0 (nlegal may be
+ *        NULL; the group of e is the envs_per_pair envs of pair e / envs_per_pair when pairs is given, else e alone:
+ *        the rule by which ka_arena_referee leaves a stalled slot untallied), the game is committed as one record:
+ *        plies = the moves in the row, winner from the sign of rewards[e] (the mover's reward) and pre_player[e] (u8, the
+ *        mover): positive -> the mover, negative -> the other side, zero or NaN -> draw (the outcome of
+ *        ka_sl_replay_record); reason = term_reason[e] (u8); black / white = pairs[(e / envs_per_pair) * pair_stride + 0 / 1]
+ *        (the arena passes its slot table: model_a plays black, model_b white) or -1 when pairs is NULL; the owner's
+ *        ply counter = *ply_counter as this launch finds it (0 when NULL).
+ *     4. for every env that finished, live or not: the row is emptied, carried cleared, the game number advanced and the
+ *        start slot reloaded from the state row, where the env kernel has already restarted the game (from the standard
+ *        start or the pool row it drew).
+ *   Records are written behind the committed ones in (ply, env) order: the rank of a committed env is its place among the
+ *   committed envs of this ply in env order (ballot scans in one workgroup that walks the envs in tiles of 256; no
+ *   atomics, nothing waits on another workgroup), so the order does not depend on the launch geometry.  A game that does
+ *   not fit game_cap is dropped whole and counted; nothing is written outside the buffers named above.
+ * ka_gamelog_seat (behind ka_arena_assign, same jobs = njobs rows of 4 int32 {slot, ...}): every env of a job's slot whose
+ *   row holds a move gets carried = 1 (the new pairing inherits that game); a slot outside [0, slots) is skipped. */
+int ka_gamelog_words(int which, int max_ply);
+int ka_gamelog_begin(const void* env_state, int state_bytes, int envs, int* meta, int* starts, void* stream);
+int ka_gamelog_step(const void* env_state, int state_bytes, int envs, int max_ply, const long long* actions,
+                    const float* rewards, const void* terminated, const void* truncated, const void* pre_player,
+                    const void* term_reason, const int* nlegal, const int* live, const int* pairs, int pair_stride,
+                    int envs_per_pair, const int* ply_counter, void* rows, int row_stride, int* meta, int* starts,
+                    int* records, int game_cap, int* cursor, void* stream);
+int ka_gamelog_seat(const int* jobs, int njobs, int slots, int envs_per_slot, int* meta, void* stream);
+
 /* ---- SL shard preparation (csrc/sl_prepare.hip; the replay keisei/sl/prepare.py:151-161 leaves out).  A batch of E game
  * records, game g in env g, stepped in lockstep from ka_shogi_env_reset.  One ply = ka_sl_replay_plan, ka_shogi_env_step
  * (unchanged), ka_sl_replay_record on one stream.

@@ -121,6 +121,10 @@ _SIGS = {
     "ka_selfplay_state_words": "",
     "ka_selfplay_layout": "i",
     "ka_selfplay_step": "p i pppppp f pppppp f pp pp pp pp ii p",
+    "ka_gamelog_words": "ii",
+    "ka_gamelog_begin": "p ii pp p",
+    "ka_gamelog_step": "p iii pppppp ppp ii p p i ppp i p p",
+    "ka_gamelog_seat": "p iii p p",
     "ka_sl_replay_state_words": "i",
     "ka_sl_replay_plan": "p i p i p p i pp p",
     "ka_sl_replay_record": "p i ppp i ppppppp p i p",

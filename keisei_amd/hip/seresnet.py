@@ -19,6 +19,7 @@ from __future__ import annotations
 
 from typing import Dict, List, Optional
 
+import gc
 import os
 import threading
 
@@ -545,8 +546,19 @@ class SEResNetEngine:
                     self.forward(static_in, False, False, T, None)            # warm-up: one-time kernel attributes etc.
                     torch.cuda.synchronize(dev)
                     graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph):
-                        out = self.forward(static_in, False, False, T, None)[:3]
+                    # torch.cuda.graph does not collect garbage on entry: dead objects still waiting in a reference cycle
+                    # (captured graphs, pinned buffers kept by an exception's traceback) must not be released inside the
+                    # capture, where the collector may otherwise run at an allocation of its choosing (see
+                    # LeagueRollout._capture); a graph captured around such a release has crashed at its first replay
+                    gc.collect()
+                    collecting = gc.isenabled()
+                    gc.disable()                                 # and none while the capture runs
+                    try:
+                        with torch.cuda.graph(graph):
+                            out = self.forward(static_in, False, False, T, None)[:3]
+                    finally:
+                        if collecting:
+                            gc.enable()
                 finally:
                     self.fork_fc = saved_overlap
                 ent = (graph, static_in, out)

@@ -47,7 +47,7 @@ from keisei_amd.sl.parsers import (CSAParser, GameFilter, GameOutcome, GameParse
 
 logger = logging.getLogger(__name__)
 
-__all__ = ["prepare_sl_data", "prepare_sl_dataset", "opening_positions", "usi_to_action", "ReplayBatch", "main"]
+__all__ = ["prepare_sl_data", "prepare_sl_dataset", "dataset_from_recorded_games", "opening_positions", "usi_to_action", "ReplayBatch", "main"]
 
 # why a game's record was not used to its end
 REASON_NONE, REASON_ILLEGAL, REASON_RULES, REASON_LONG, REASON_NO_ENCODING = 0, 1, 2, 3, 4
@@ -561,6 +561,47 @@ def prepare_sl_dataset(game_sources: Sequence[str], min_ply: int = 40, min_ratin
     dataset.check()
     meta = _meta_of(count, len(dataset))
     _log_summary("a device dataset", len(dataset), count)
+    return dataset, meta
+
+
+def dataset_from_recorded_games(games, *, device=None, batch_envs: int = 512, max_moves: int = 512,
+                                max_batch_positions: int = 65536):
+    """A ``DeviceSLDataset`` straight from games a ``GameLog`` recorded (``keisei_amd.training.game_log.RecordedGame``:
+    ``actions``, ``winner``, ``is_standard_start``): the replay of ``prepare_sl_dataset`` without the text -- no USI, no
+    file, no new kernel.  The recorded action indices are the replay's action stream as they are.  Only games from the
+    standard start are replayed; the others are counted in ``games_nonstandard_start``, a game without a move is passed
+    over.  ``max_moves`` is the replay env's ``max_ply`` as in ``prepare_sl_dataset`` (a longer game is cut there and
+    counted): the observation's ply plane is ply / max_ply, so pass the ``max_ply`` the games were played with to get the
+    observations their players saw.  Positions are in the order of ``games``.  Returns ``(dataset, meta)`` with the keys
+    of ``prepare_sl_dataset``."""
+    from keisei_amd.sl.device_dataset import DeviceSLDataset
+
+    if batch_envs < 1:
+        raise ValueError(f"batch_envs must be positive, got {batch_envs}")
+    if not 1 <= max_moves <= 65535:
+        raise ValueError(f"max_moves must lie in [1, 65535] (the env's ply counter), got {max_moves}")
+    if max_batch_positions < max_moves:
+        raise ValueError(f"max_batch_positions ({max_batch_positions}) must hold one game of max_moves ({max_moves})")
+    count = _new_counters()
+    kept: List[tuple] = []
+    for g in games:
+        if not g.is_standard_start:
+            count["nonstandard"] += 1
+        elif len(g.actions):
+            count["games"] += 1
+            actions = np.asarray(g.actions).astype(np.int32)
+            count["long"] += int(len(actions) > max_moves)
+            kept.append((actions[:max_moves], int(g.winner), REASON_LONG if len(actions) > max_moves else REASON_NONE))
+    replay = _DeviceReplay(min(int(batch_envs), max(len(kept), 1)), max_moves, device)
+    dataset = DeviceSLDataset(replay.device)
+    raw: Optional[torch.Tensor] = None
+    for batch_games in _batches(iter(kept), replay.num_envs, max_batch_positions):
+        batch = ReplayBatch.build(batch_games)
+        raw, reason, hdr = _replay_onto(dataset, replay, batch, raw)
+        _count_replay(count, batch_games, batch, reason, hdr)
+    dataset.check()
+    meta = _meta_of(count, len(dataset))
+    _log_summary("a device dataset from recorded games", len(dataset), count)
     return dataset, meta
 
 

@@ -1,6 +1,7 @@
 """Host-side mirror of the reference's ``keisei.training`` hot-path API (same names, arguments,
 error behaviour), backed by hand-written HIP kernels for GPU tensors."""
 from .dynamic_trainer import DynamicTrainer, MatchRollout  # noqa: F401
+from .game_log import GameLog, RecordedGame, game_log_host, write_sfen_games  # noqa: F401
 from .game_feature_tracker import GameFeatureAccumulator, GameFeatureRow, GameFeatureTracker, classify_action  # noqa: F401
 from .league_rollout import LeagueRollout, LeagueRolloutStats  # noqa: F401
 from .match_arena import MatchArena, MatchResult, RoundStats  # noqa: F401

@@ -12,6 +12,8 @@ synchronisation:
     ka_shogi_env_step                           (csrc/shogi_env.hip)
     ka_arena_features_step                      (csrc/arena.hip, only with features=True: the reference's per-slot
                                                  GameFeatureTracker, one record per finished game)
+    ka_gamelog_step                             (csrc/gamelog.hip, only with game_log > 0: the finished games, move
+                                                 by move, one record per game the referee tallies)
     ka_arena_referee                            (csrc/arena.hip: tally by the last-mover rule, close slots, seat the
                                                  next ply, advance the seed)
 
@@ -39,6 +41,7 @@ from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS, VecEnv
 
 from .dynamic_trainer import MatchRollout
 from .game_feature_tracker import GameFeatureTracker
+from .game_log import GameLog, RecordedGame
 from .model_group import SEResNetGroup
 
 _HDR, _SLOT = 8, 8                      # int32 words of the state header and of one slot (csrc/arena.hip)
@@ -59,6 +62,9 @@ class MatchResult:
     partial: bool
     rollout: Optional[MatchRollout] = None      # collected rows (flat, packed masks, on the arena's device)
     feature_tracker: Optional[GameFeatureTracker] = None     # the pairing's game features (arenas with features=True)
+    # the pairing's finished games, move by move, in (ply, env) order (arenas with game_log > 0, else None).  The name
+    # `games` is taken by the count below.
+    recorded_games: Optional[List[RecordedGame]] = None
 
     @property
     def games(self) -> int:
@@ -79,6 +85,7 @@ class RoundStats:
     rollouts_dropped: int = 0           # pairings whose rollout was withheld because the store lost rows of it
     feature_rows: int = 0               # rows handed out in feature trackers (two per finished game)
     features_dropped: int = 0           # finished games whose record did not fit the feature store
+    games_dropped: int = 0              # finished games that did not fit the game log between two sync points
 
 
 def _side_bits(trainable, pairings: Sequence[Tuple[int, int]]) -> List[int]:
@@ -244,11 +251,19 @@ class MatchArena:
     ``ka_arena_features_step``): every result then carries a ``feature_tracker``.  Without it the ply is launch for
     launch what it was.  ``start_pool_capacity > 0`` gives the env a pool of
     start positions of that size: ``arena.env.set_start_positions(...)`` / ``set_start_sfens(...)`` between rounds make later
-    games start from them (no re-capture; see ``VecEnv``).  Not with ``features=True``."""
+    games start from them (no re-capture; see ``VecEnv``).  Not with ``features=True``.
+    ``game_log=K > 0`` adds a device-resident ``GameLog`` of K records to the ply (one launch, ``ka_gamelog_step``, before
+    the referee): every result then carries its pairing's finished games, move by move, in ``recorded_games`` -- one per
+    game the referee tallied, as long as ``RoundStats.games_dropped`` is 0.  A game is ``carried`` when the pairing
+    inherited it from the slot's previous pairing or the slot sat idle during it (there is no per-slot reset).
+    ``collect``, ``features`` and ``game_log`` are independent."""
 
     def __init__(self, group: SEResNetGroup, num_envs: int = 512, envs_per_match: int = 64, max_ply: int = 512, *,
                  sync_every: int = 32, graph: bool = True, seed: Optional[int] = None, record: bool = False,
-                 collect: bool = False, features: bool = False, start_pool_capacity: int = 0) -> None:
+                 collect: bool = False, features: bool = False, start_pool_capacity: int = 0,
+                 game_log: int = 0) -> None:
+        if game_log < 0:
+            raise ValueError(f"game_log must not be negative, got {game_log}")
         if len(group) == 0:
             raise ValueError("MatchArena needs a group with at least one model")
         if num_envs <= 0 or envs_per_match <= 0 or num_envs % envs_per_match != 0:
@@ -320,6 +335,9 @@ class MatchArena:
                 every = torch.zeros(S, 4, dtype=torch.int32)
                 every[:, 0] = torch.arange(S, dtype=torch.int32)
                 self._every_slot = every.to(dev)                  # seat jobs naming every slot: the round-start clear
+            self.game_log: Optional[GameLog] = None
+            if game_log:
+                self.game_log = GameLog(self.env, capacity=int(game_log), envs_per_slot=self.envs_per_match)
         self._graph: Optional[torch.cuda.CUDAGraph] = None
 
     # ------------------------------------------------------------------ one ply
@@ -327,7 +345,7 @@ class MatchArena:
         """forward -> sample -> step -> referee on the current stream; no host synchronisation."""
         env, N = self.env, self.num_envs
         st = _lib.stream_ptr(self.device)
-        cur = env.current()
+        cur, prev = env.current(), env._cur
         logits, _, _ = self.group._tables.forward(cur.observations, self._model_of, ws=self._ws)
         sp = self._state.data_ptr()
         _lib.call("ka_policy_sample_play", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of,
@@ -347,6 +365,11 @@ class MatchArena:
             _lib.call("ka_arena_features_step", self._state, self.num_slots, self.envs_per_match, self._actions, self._pre,
                       self._nlegal, meta.captured_piece, meta.termination_reason, meta.ply_count, r.rewards, r.terminated,
                       r.truncated, self._facc, self._frecords, self._fcursors, self._fcap, st)
+        if self.game_log is not None:                     # before the referee: it rewrites model_of and the round ply
+            self.game_log.step(self._actions, r.rewards, r.terminated, r.truncated, env._players[prev],
+                               r.step_metadata.termination_reason, nlegal=self._nlegal, live=self._model_of,
+                               pairs=sp + 4 * _HDR, pair_stride=_SLOT, envs_per_pair=self.envs_per_match,
+                               ply_counter=sp + 8)
         # env._err[1] is the VecEnv's refusal latch: the referee copies it into the state so the host sees a refused
         # step in the same read
         _lib.call("ka_arena_referee", self._state, self.num_slots, self.envs_per_match, r.rewards,
@@ -421,6 +444,8 @@ class MatchArena:
         if self.features:                                 # a new tracker per pairing (concurrent_matches.py:125)
             _lib.call("ka_arena_features_seat", self._jobs, len(jobs), self.num_slots, self.envs_per_match, self._facc,
                       _lib.stream_ptr(self.device))
+        if self.game_log is not None:                     # the new pairing inherits the games in progress
+            self.game_log.seat(self._jobs, len(jobs))
 
     def _drain(self, slot_pairing: Dict[int, int], chunks: Dict[int, list], lost: set) -> None:
         """Sync point: move the chunk's rows of every collecting slot out of the store (device to device) and reset the
@@ -502,6 +527,9 @@ class MatchArena:
             _lib.call("ka_arena_features_seat", self._every_slot, self.num_slots, self.num_slots, self.envs_per_match,
                       self._facc, _lib.stream_ptr(self.device))
         self.env.reset()
+        if self.game_log is not None:
+            self.game_log.begin()
+        logged: Dict[int, List[RecordedGame]] = {}
         self.record = []
         chunks: Dict[int, list] = {}
         lost: set = set()
@@ -529,6 +557,10 @@ class MatchArena:
                 self._drain(slot_pairing, chunks, lost)
             if self.features:
                 self._drain_features(slot_pairing, games, stats)
+            if self.game_log is not None:                 # a slot's games of this chunk are its seated pairing's
+                for g in self.game_log.drain():
+                    logged.setdefault(slot_pairing[g.env // self.envs_per_match], []).append(g)
+                stats.games_dropped = self.game_log.dropped
             jobs = []
             for i in sorted((i for i, s in enumerate(active) if slot[s, 7] & DONE), reverse=True):
                 s = active.pop(i)
@@ -550,6 +582,8 @@ class MatchArena:
                     results[p].feature_tracker = GameFeatureTracker.from_records(
                         recs, _entry_id(entry_ids, ma), _entry_id(entry_ids, mb), epoch, self.envs_per_match)
                     stats.feature_rows += len(results[p].feature_tracker.completed_rows)
+                if self.game_log is not None:
+                    results[p].recorded_games = logged.pop(p, [])
                 if nxt < P:
                     a, b = pairings[nxt]
                     jobs.append((s, a, b, games_per_match))

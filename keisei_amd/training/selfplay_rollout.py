@@ -8,6 +8,7 @@ four steps on one stream, with no host synchronisation:
     grouped stem / tower / heads, every row model 0   (csrc/tower.hip, the group's tables)
     ka_policy_sample_play, K = 1                        (csrc/loss.hip: actions and log-probs, seed read from the device)
     ka_shogi_env_step                                   (csrc/shogi_env.hip)
+    ka_gamelog_step                                     (csrc/gamelog.hip, only with game_log > 0: the finished games, move by move)
     ka_selfplay_step                                    (csrc/selfplay.hip: tallies, the env's row straight into the rollout
                                                          store's columns, input guards, truncation slots)
 
@@ -28,7 +29,7 @@ from __future__ import annotations
 
 import gc
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -37,6 +38,7 @@ import torch
 from keisei_amd import _lib
 from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS, OBS_CHANNELS, VecEnv
 
+from .game_log import GameLog, RecordedGame
 from .katago_loop import _compute_value_cats
 from .katago_ppo import SCORE_NORMALIZATION, KataGoRolloutBuffer, _check_step_inputs
 from .model_group import SEResNetGroup
@@ -67,6 +69,8 @@ class SelfPlayStats:
     truncated: int = 0                  # truncated and not terminated
     host_syncs: int = 0                 # reads of the state array
     truncation_overrides: int = 0       # rows whose bootstrap override was computed at a sync point
+    games: List[RecordedGame] = field(default_factory=list)     # the finished games (a rollout built with game_log > 0)
+    games_dropped: int = 0              # finished games that did not fit the log between two sync points
 
 
 def _check_args(num_envs: int, max_ply: int, sync_every: int, graph: bool, record: bool, score_norm: float,
@@ -106,14 +110,19 @@ class SelfPlayRollout:
     ``reset()`` is explicit.  ``seed`` fixes sampling from the last ``reset()`` on.  ``record=True`` (no graph) keeps every
     ply's inputs and outputs in ``self.record`` for tests.  ``start_pool_capacity > 0`` gives the env a pool of
     start positions of that size: ``roll.env.set_start_positions(...)`` / ``set_start_sfens(...)`` between ``collect`` calls make later
-    games start from them (no re-capture; see ``VecEnv``)."""
+    games start from them (no re-capture; see ``VecEnv``).  ``game_log=K > 0`` adds a device-resident ``GameLog`` of K
+    records to the ply (one launch, ``ka_gamelog_step``, between the env step and ``ka_selfplay_step``): ``collect``
+    drains it at every sync point onto ``SelfPlayStats.games``.  Without it the ply is launch for launch what it was."""
 
     def __init__(self, learner, *, num_envs: int = 512, max_ply: int = 500, value_adapter=None,
                  score_norm: float = SCORE_NORMALIZATION, sync_every: int = 32, graph: bool = True,
-                 seed: Optional[int] = None, record: bool = False, start_pool_capacity: int = 0) -> None:
+                 seed: Optional[int] = None, record: bool = False, start_pool_capacity: int = 0,
+                 game_log: int = 0) -> None:
         _check_args(int(num_envs), int(max_ply), int(sync_every), bool(graph), bool(record), float(score_norm), value_adapter)
         if start_pool_capacity < 0:
             raise ValueError(f"start_pool_capacity must not be negative, got {start_pool_capacity}")
+        if game_log < 0:
+            raise ValueError(f"game_log must not be negative, got {game_log}")
         self.group = self._make_group(learner)
         self.learner = learner
         self.device = self.group.device
@@ -139,6 +148,7 @@ class SelfPlayRollout:
             self._state = z(_lib.query("ka_selfplay_state_words"))
             self._state_host = torch.zeros(self._state.shape, dtype=torch.int32).pin_memory()
             self._ws = self.group._tables.workspace(N)
+            self.game_log: Optional[GameLog] = GameLog(self.env, capacity=int(game_log)) if game_log else None
         self._graphs: Dict[int, torch.cuda.CUDAGraph] = {}
         with torch.cuda.device(dev), torch.no_grad():            # load every kernel of the ply before any capture
             self.reset()                                         # (a zeroed descriptor reserves no row: nothing is written)
@@ -174,6 +184,8 @@ class SelfPlayRollout:
             self._stall.zero_()
             self._values.zero_()
             self.env.reset()
+            if self.game_log is not None:
+                self.game_log.begin()
         self.record = []
 
     @property
@@ -192,6 +204,9 @@ class SelfPlayRollout:
         _lib.call("ka_policy_sample_play", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of, 1,
                   self._actions, self._logp, self._nlegal, sp + 4 * _SAMP, N, ACTION_SPACE, st)
         r = env.step(self._actions)
+        if self.game_log is not None:                     # before ka_selfplay_step advances the ply counter it stamps
+            self.game_log.step(self._actions, r.rewards, r.terminated, r.truncated, env._players[prev],
+                               r.step_metadata.termination_reason, nlegal=self._nlegal, ply_counter=sp + 4 * _PLIES)
         _lib.call("ka_selfplay_step", self._state, N, cur.observations, cur.legal_mask_bits, self._actions, self._logp,
                   value, score if self.alpha != 0.0 else None, self.alpha, self._nlegal, env._players[prev], r.rewards,
                   r.terminated, r.truncated, r.step_metadata.material_balance, self.score_norm, r.terminal_observations,
@@ -308,12 +323,16 @@ class SelfPlayRollout:
         self._state[_TRUNC:].zero_()
         self._stall.zero_()
         base, done, st = buffer._write_offset, 0, None
+        dropped_before = self.game_log.dropped if self.game_log is not None else 0
         while done < steps:
             plies = min(self.sync_every, steps - done)
             cols = self._describe(buffer, base, plies * N)
             self._chunk(plies)
             st = self._read_state(stats)               # raises before the commit: a chunk with a guard fired is not kept
             buffer.commit(plies * N, plies)
+            if self.game_log is not None:
+                stats.games += self.game_log.drain()
+                stats.games_dropped = self.game_log.dropped - dropped_before
             n = int(st[_TRUNC])
             if n:
                 self._overrides(cols, n)
