@@ -619,12 +619,14 @@ int ka_selfplay_step(int* state, int envs, const float* obs, const void* mask_bi
  * auto-reset): the moves of the games played on the device, kept inside the ply and handed over as whole finished games.
  * E envs (at most ka_gamelog_words(6, 0)); every buffer is device memory owned by the caller:
  *   rows     E x row_stride uint16, 4-byte aligned, row_stride even and >= max_ply: the moves of the game in progress
- *   meta     E x ka_gamelog_words(2, 0) int32 {moves in the row, carried (0 / 1), games finished since begin, unused}
+ *   meta     E x ka_gamelog_words(2, 0) int32 {moves in the row, carried (0 / 1), games finished since begin, player tag
+ *            (ka_gamelog_step_env only: 0 for an empty row, else the tag of the players who made the row's last move)}
  *   starts   E x 24 int32: the first 96 bytes of the env's state row (board[81] hands[2][7] side, a pool row) as they were
  *            when the game in progress began
  *   records  game_cap x ka_gamelog_words(0, max_ply) int32, one finished game each: 12 header words {env, plies, winner
  *            0 black / 1 white / 2 draw, termination reason, flags (bit 0 truncated and not terminated, bit 1 carried),
- *            black id, white id, the owner's ply counter, number of the game within its env since begin, 3 zero words},
+ *            black id, white id, the owner's ply counter, number of the game within its env since begin, the learner's
+ *            colour + 1 (1 black, 2 white; 0 = no learner, what ka_gamelog_step writes), 2 zero words},
  *            the 24 start words, then the moves two per word, low half first.  The unused half of the last move word is
  *            zero; the words behind it are not written.
  *   cursor   ka_gamelog_words(1, 0) int32 {records committed, records dropped, plies logged, unused}.  The host reads and
@@ -632,7 +634,8 @@ int ka_selfplay_step(int* state, int envs, const float* obs, const void* mask_bi
  * ka_gamelog_words(which, max_ply): int32 words of 0 = one record, 1 = the cursor, 2 = one env's meta, 3 = the move words
  *   of a record ((max_ply + 1) / 2), 4 = a record's header, 5 = a start position; 6 = the largest E; -1 for any other which.
  * ka_gamelog_begin (after ka_shogi_env_reset / ka_shogi_env_reset_pool): for every env an empty row, carried 0, game
- *   number 0, and the start slot copied from the state row (state_bytes = ka_shogi_env_state_bytes(), a multiple of 4).
+ *   number 0, player tag 0, and the start slot copied from the state row (state_bytes = ka_shogi_env_state_bytes(), a
+ *   multiple of 4).
  * ka_gamelog_step (after ka_shogi_env_step / ka_shogi_env_step_pool, BEFORE the owner's bookkeeping launch --
  *   ka_selfplay_step, ka_arena_referee -- because the referee rewrites model_of and pre_player).  For every env e, in
  *   this order:
@@ -654,6 +657,28 @@ int ka_selfplay_step(int* state, int envs, const float* obs, const void* mask_bi
  *   committed envs of this ply in env order (ballot scans in one workgroup that walks the envs in tiles of 256; no
  *   atomics, nothing waits on another workgroup), so the order does not depend on the launch geometry.  A game that does
  *   not fit game_cap is dropped whole and counted; nothing is written outside the buffers named above.
+ *   ka_gamelog_step neither reads nor writes the fourth meta word.
+ * ka_gamelog_step_env (the league rollout: after ka_shogi_env_step, BEFORE ka_league_step, which re-draws side and opp of
+ *   the envs that finished -- so it reads the players who played the ply): ka_gamelog_step with per-env players in place
+ *   of the pair table.  The group of an env is the env itself.  side (E u8): the learner's colour in env e, 0 black (bit
+ *   0 is read); opp (E int32): the opponent index k of env e; ids (opponents + 1 int32, device memory): ids[0] the
+ *   learner's id, ids[k + 1] opponent k's.  Steps 1-4 as above, the same kernel body, with these differences:
+ *     - black / white of a record = ids[0] on the learner's side, ids[opp[e] + 1] on the other; an opp[e] outside
+ *       [0, opponents) gives -1 and reads nothing outside ids.  Header word 9 = side[e] + 1.
+ *     - tag = ((opp[e] << 1) | side[e]) + 1 in 32-bit wrapping arithmetic.  Where the row was empty before step 1 the
+ *       fourth meta word becomes tag; where it held a move and the word differs from tag, the carried flag is set (before
+ *       step 3, so a record carries it) and the word becomes tag: a side or an opponent re-drawn on the host or on the
+ *       device in the middle of a game needs no call here, and the record names the players who ended the game, the ones
+ *       ka_league_step tallies it for.  A change between two games sets nothing.  Where the game finished the word becomes 0.
+ * ka_gamelog_peek (at a sync point; not meant for capture): the games in progress.  Writes n record-shaped rows of
+ *   ka_gamelog_words(0, max_ply) words into out, row j for env envs_list[j] (n int32, device memory), or env j when
+ *   envs_list is NULL (then n <= envs); one wave per row.  Header {env, moves in the row, -1, 0, flags = the carried bit
+ *   alone, black, white, *ply_counter (0 when NULL), game number, learner's colour + 1, 0, 0}, the 24 start words, the moves
+ *   two per word with the unused half of the last word zero; the words behind are not written.  Players: from pairs
+ *   (pair_stride, envs_per_pair) as ka_gamelog_step names them; or from side / opp / ids / opponents as
+ *   ka_gamelog_step_env names them (word 9 = side + 1); giving both is an error; with neither black = white = -1 and
+ *   word 9 = 0.  An index outside [0, envs) gives env -1, 0 moves, players -1, zero start words and reads no env buffer.
+ *   rows, meta and starts are only read; records and cursor are not touched.
  * ka_gamelog_seat (behind ka_arena_assign, same jobs = njobs rows of 4 int32 {slot, ...}): every env of a job's slot whose
  *   row holds a move gets carried = 1 (the new pairing inherits that game); a slot outside [0, slots) is skipped. */
 int ka_gamelog_words(int which, int max_ply);
@@ -663,6 +688,14 @@ int ka_gamelog_step(const void* env_state, int state_bytes, int envs, int max_pl
                     const void* term_reason, const int* nlegal, const int* live, const int* pairs, int pair_stride,
                     int envs_per_pair, const int* ply_counter, void* rows, int row_stride, int* meta, int* starts,
                     int* records, int game_cap, int* cursor, void* stream);
+int ka_gamelog_step_env(const void* env_state, int state_bytes, int envs, int max_ply, const long long* actions,
+                        const float* rewards, const void* terminated, const void* truncated, const void* pre_player,
+                        const void* term_reason, const int* nlegal, const int* live, const void* side, const int* opp,
+                        const int* ids, int opponents, const int* ply_counter, void* rows, int row_stride, int* meta,
+                        int* starts, int* records, int game_cap, int* cursor, void* stream);
+int ka_gamelog_peek(const int* envs_list, int n, int envs, int max_ply, const int* pairs, int pair_stride, int envs_per_pair,
+                    const void* side, const int* opp, const int* ids, int opponents, const int* ply_counter,
+                    const void* rows, int row_stride, const int* meta, const int* starts, int* out, void* stream);
 int ka_gamelog_seat(const int* jobs, int njobs, int slots, int envs_per_slot, int* meta, void* stream);
 
 /* ---- SL shard preparation (csrc/sl_prepare.hip; the replay keisei/sl/prepare.py:151-161 leaves out).  A batch of E game

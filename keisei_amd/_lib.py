@@ -124,6 +124,8 @@ _SIGS = {
     "ka_gamelog_words": "ii",
     "ka_gamelog_begin": "p ii pp p",
     "ka_gamelog_step": "p iii pppppp ppp ii p p i ppp i p p",
+    "ka_gamelog_step_env": "p iii pppppp pp ppp i p p i ppp i p p",
+    "ka_gamelog_peek": "p iii p ii ppp i p p i pp p p",
     "ka_gamelog_seat": "p iii p p",
     "ka_sl_replay_state_words": "i",
     "ka_sl_replay_plan": "p i p i p p i pp p",

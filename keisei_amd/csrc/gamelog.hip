@@ -16,6 +16,16 @@
 // the tiles before plus a ballot scan in thread order, so records follow the committed ones in (ply, env) order whatever
 // the geometry.  Per tile the four waves then copy the tile's committed games, a wave per game.  It is the only writer of
 // the cursor: no atomics.
+//
+// The kernel has two forms of one body (the template parameter kEnv).  kEnv = false names the players of a game through a
+// pair table indexed by env / envs_per_pair (the arena).  kEnv = true takes them per env (the league: side[e] the learner's
+// colour, opp[e] its opponent's index, ids the learner's and the opponents' ids); header word 9 is then the learner's colour
+// + 1, and the fourth meta word holds tag = ((opp << 1) | side) + 1 of the players who made the row's last move: a later move
+// under another tag sets the carried flag, so a re-draw of side or opponent in the middle of a game needs no call of its
+// own.  kEnv = false neither reads nor writes that word.
+//
+// gamelog_peek_kernel writes the games in progress as record-shaped rows into a caller's buffer, a wave per game as in the
+// copy phase above; it reads the log's buffers and writes nothing but those rows.
 #include "common.h"
 
 namespace {
@@ -31,6 +41,7 @@ struct GameLogArgs {
     const long long* actions; const float* rewards; const uint8_t* terminated; const uint8_t* truncated;
     const uint8_t* pre_player; const uint8_t* reason; const int* nlegal; const int* live;
     const int* pairs; int pair_stride; int group; const int* ply_counter;
+    const uint8_t* side; const int* opp; const int* ids; int K;      // kEnv only
     uint16_t* rows; int* meta; int* starts; int* records; int* cursor;
 };
 
@@ -43,6 +54,17 @@ __global__ __launch_bounds__(kGlThreads) void gamelog_begin_kernel(int E, const 
     if (w < kGlMeta) meta[e * kGlMeta + w] = 0;
 }
 
+// the ids of env e's players from its learner side and opponent index: an index outside [0, K) names nobody (-1) and reads
+// ids[0] in its place
+__device__ __forceinline__ void gamelog_env_players(const int* ids, int K, int s, int k, int* black, int* white) {
+    const bool ok = (unsigned)k < (unsigned)K;
+    const int other = ids[ok ? k + 1 : 0], me = ids[0];
+    const int oid = ok ? other : -1;
+    *black = s ? oid : me;
+    *white = s ? me : oid;
+}
+
+template <bool kEnv>
 __global__ __launch_bounds__(kGlThreads) void gamelog_step_kernel(GameLogArgs a) {
     __shared__ int wsum[kGlThreads / 64];
     __shared__ int s_env[kGlThreads];                          // the tile's committed games: env and record index
@@ -75,13 +97,22 @@ __global__ __launch_bounds__(kGlThreads) void gamelog_step_kernel(GameLogArgs a)
         const int why = a.reason[e];
         const int game = m[2];
         const bool done = have && (tm || tr);
-        const int carried = (m[1] | (is_live ? 0 : 1)) & 1;
+        int carried = (m[1] | (is_live ? 0 : 1)) & 1;
+        int s = 0, tag = 0, black = -1, white = -1;
+        if constexpr (kEnv) {
+            s = a.side[e] & 1;
+            const int ko = a.opp[e], last = m[3];
+            tag = (int)((((unsigned)ko << 1) | (unsigned)s) + 1u);
+            if (count > 0 && last != tag) carried = 1;         // the players changed since the row's last move
+            gamelog_env_players(a.ids, a.K, s, ko, &black, &white);
+        }
         const int plies = min(count + 1, a.max_ply);
         if (have) {
             if ((unsigned)count < (unsigned)a.max_ply) a.rows[(size_t)e * a.row_stride + count] = (uint16_t)action;
             m[0] = done ? 0 : plies;
             m[1] = done ? 0 : carried;
             m[2] = game + (done ? 1 : 0);
+            if constexpr (kEnv) m[3] = done ? 0 : tag;
         }
         const bool commit = done && is_live && !s_stall[e / G];
         int rank;
@@ -93,17 +124,18 @@ __global__ __launch_bounds__(kGlThreads) void gamelog_step_kernel(GameLogArgs a)
             s_rec[slot] = first + rank;
             s_n[slot] = plies;
             int* rec = a.records + (size_t)(first + rank) * a.rec_words;
-            int black = -1, white = -1;
-            if (a.pairs) {
-                const int* p = a.pairs + (size_t)(e / G) * a.pair_stride;
-                black = p[0]; white = p[1];
+            if constexpr (!kEnv) {
+                if (a.pairs) {
+                    const int* p = a.pairs + (size_t)(e / G) * a.pair_stride;
+                    black = p[0]; white = p[1];
+                }
             }
             rec[0] = e; rec[1] = plies;
             rec[2] = r > 0.f ? pre : (r < 0.f ? 1 - pre : 2);   // the mover's reward; a NaN is a draw
             rec[3] = why;
             rec[4] = ((tr && !tm) ? kGlTruncOnly : 0) | (carried ? kGlCarried : 0);
             rec[5] = black; rec[6] = white; rec[7] = owner_ply; rec[8] = game;
-            rec[9] = 0; rec[10] = 0; rec[11] = 0;
+            rec[9] = kEnv ? s + 1 : 0; rec[10] = 0; rec[11] = 0;
         }
         const int kept = max(0, min(tot, room - running));     // the tile's games that fit: its first `kept` by rank
         running += tot;
@@ -146,6 +178,56 @@ __global__ __launch_bounds__(kGlThreads) void gamelog_seat_kernel(const int* job
     }
 }
 
+struct GamePeekArgs {
+    const int* list; int n; int E, max_ply, row_stride, rec_words;
+    const int* pairs; int pair_stride; int group;
+    const uint8_t* side; const int* opp; const int* ids; int K;
+    const int* ply_counter;
+    const uint16_t* rows; const int* meta; const int* starts; int* out;
+};
+
+// a wave per game in progress; every branch on the game is uniform over its wave
+__global__ __launch_bounds__(kGlThreads) void gamelog_peek_kernel(GamePeekArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int j = blockIdx.x * (kGlThreads / 64) + (threadIdx.x >> 6);
+    if (j >= a.n) return;
+    int* rec = a.out + (size_t)j * a.rec_words;
+    const int idx = a.list ? a.list[j] : j;
+    const int owner_ply = a.ply_counter ? *a.ply_counter : 0;
+    if ((unsigned)idx >= (unsigned)a.E) {                      // no such env: an empty row, no env buffer is read
+        if (lane < kGlHead) rec[lane] = (lane == 0 || lane == 2 || lane == 5 || lane == 6) ? -1 : (lane == 7 ? owner_ply : 0);
+        if (lane < kGlStart) rec[kGlHead + lane] = 0;
+        return;
+    }
+    const int e = idx;
+    const int* m = a.meta + (size_t)e * kGlMeta;
+    const int n = max(0, min(m[0], a.max_ply));
+    if (lane == 0) {
+        int black = -1, white = -1, colour = 0;
+        if (a.pairs) {
+            const int* p = a.pairs + (size_t)(e / a.group) * a.pair_stride;
+            black = p[0]; white = p[1];
+        } else if (a.side) {
+            const int s = a.side[e] & 1;
+            gamelog_env_players(a.ids, a.K, s, a.opp[e], &black, &white);
+            colour = s + 1;
+        }
+        rec[0] = e; rec[1] = n; rec[2] = -1; rec[3] = 0;
+        rec[4] = (m[1] & 1) ? kGlCarried : 0;
+        rec[5] = black; rec[6] = white; rec[7] = owner_ply; rec[8] = m[2];
+        rec[9] = colour; rec[10] = 0; rec[11] = 0;
+    }
+    const int* start = a.starts + (size_t)e * kGlStart;
+    if (lane < kGlStart) rec[kGlHead + lane] = start[lane];
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(a.rows + (size_t)e * a.row_stride);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(rec + kGlHead + kGlStart);
+    const int words = (n + 1) >> 1;
+    for (int i = lane; i < words; i += 64) {
+        const uint32_t v = row[i];
+        dst[i] = (2 * i + 1 < n) ? v : (v & 0xffffu);
+    }
+}
+
 }  // namespace
 
 extern "C" int ka_gamelog_words(int which, int max_ply) {
@@ -164,31 +246,91 @@ extern "C" int ka_gamelog_begin(const void* env_state, int state_bytes, int envs
     return ka_check_launch("gamelog_begin");
 }
 
+namespace {
+
+int gamelog_step_check(const char* who, const void* env_state, int state_bytes, int envs, int max_ply, const void* actions,
+                       const void* rewards, const void* terminated, const void* truncated, const void* pre_player,
+                       const void* term_reason, const void* rows, int row_stride, const void* meta, const void* starts,
+                       const void* records, int game_cap, const void* cursor) {
+    KA_REQUIRE(env_state && actions && rewards && terminated && truncated && pre_player && term_reason && rows && meta &&
+               starts && records && cursor, "%s: null tensor", who);
+    KA_REQUIRE(envs > 0 && envs <= kGlMaxEnvs, "%s: envs %d (1..%d)", who, envs, kGlMaxEnvs);
+    KA_REQUIRE(max_ply >= 1 && max_ply <= 65535, "%s: max_ply %d (1..65535)", who, max_ply);
+    KA_REQUIRE(state_bytes >= 4 * kGlStart && state_bytes % 4 == 0 && (uintptr_t)env_state % 4 == 0,
+               "%s: state rows of %d bytes (at least 96, 4-byte aligned)", who, state_bytes);
+    KA_REQUIRE((uintptr_t)rows % 4 == 0 && row_stride % 2 == 0 && row_stride >= max_ply,
+               "%s: move rows of %d uint16 (even, at least max_ply %d, 4-byte aligned)", who, row_stride, max_ply);
+    const int rec_words = kGlHead + kGlStart + (max_ply + 1) / 2;
+    KA_REQUIRE(game_cap >= 0 && (long long)game_cap * rec_words < (1ll << 31), "%s: game_cap %d x %d words", who, game_cap,
+               rec_words);
+    return 0;
+}
+
+}  // namespace
+
 extern "C" int ka_gamelog_step(const void* env_state, int state_bytes, int envs, int max_ply, const long long* actions,
                                const float* rewards, const void* terminated, const void* truncated, const void* pre_player,
                                const void* term_reason, const int* nlegal, const int* live, const int* pairs, int pair_stride,
                                int envs_per_pair, const int* ply_counter, void* rows, int row_stride, int* meta, int* starts,
                                int* records, int game_cap, int* cursor, void* stream) {
-    KA_REQUIRE(env_state && actions && rewards && terminated && truncated && pre_player && term_reason && rows && meta &&
-               starts && records && cursor, "gamelog_step: null tensor");
-    KA_REQUIRE(envs > 0 && envs <= kGlMaxEnvs, "gamelog_step: envs %d (1..%d)", envs, kGlMaxEnvs);
-    KA_REQUIRE(max_ply >= 1 && max_ply <= 65535, "gamelog_step: max_ply %d (1..65535)", max_ply);
-    KA_REQUIRE(state_bytes >= 4 * kGlStart && state_bytes % 4 == 0 && (uintptr_t)env_state % 4 == 0,
-               "gamelog_step: state rows of %d bytes (at least 96, 4-byte aligned)", state_bytes);
-    KA_REQUIRE((uintptr_t)rows % 4 == 0 && row_stride % 2 == 0 && row_stride >= max_ply,
-               "gamelog_step: move rows of %d uint16 (even, at least max_ply %d, 4-byte aligned)", row_stride, max_ply);
-    const int row_words = (max_ply + 1) / 2, rec_words = kGlHead + kGlStart + row_words;
-    KA_REQUIRE(game_cap >= 0 && (long long)game_cap * rec_words < (1ll << 31), "gamelog_step: game_cap %d x %d words",
-               game_cap, rec_words);
+    if (int rc = gamelog_step_check("gamelog_step", env_state, state_bytes, envs, max_ply, actions, rewards, terminated,
+                                    truncated, pre_player, term_reason, rows, row_stride, meta, starts, records, game_cap, cursor))
+        return rc;
     KA_REQUIRE(!pairs || (pair_stride >= 2 && envs_per_pair > 0), "gamelog_step: pair_stride %d (>= 2), envs_per_pair %d (> 0)",
                pair_stride, envs_per_pair);
-    GameLogArgs a{envs, max_ply, game_cap, row_stride, rec_words, static_cast<const uint8_t*>(env_state), state_bytes, actions,
+    GameLogArgs a{envs, max_ply, game_cap, row_stride, kGlHead + kGlStart + (max_ply + 1) / 2,
+                  static_cast<const uint8_t*>(env_state), state_bytes, actions,
                   rewards, static_cast<const uint8_t*>(terminated), static_cast<const uint8_t*>(truncated),
                   static_cast<const uint8_t*>(pre_player), static_cast<const uint8_t*>(term_reason), nlegal, live, pairs,
-                  pair_stride, pairs ? envs_per_pair : 1, ply_counter, static_cast<uint16_t*>(rows), meta, starts, records,
-                  cursor};
-    hipLaunchKernelGGL(gamelog_step_kernel, dim3(1), dim3(kGlThreads), 0, static_cast<hipStream_t>(stream), a);
+                  pair_stride, pairs ? envs_per_pair : 1, ply_counter, nullptr, nullptr, nullptr, 0,
+                  static_cast<uint16_t*>(rows), meta, starts, records, cursor};
+    hipLaunchKernelGGL(gamelog_step_kernel<false>, dim3(1), dim3(kGlThreads), 0, static_cast<hipStream_t>(stream), a);
     return ka_check_launch("gamelog_step");
+}
+
+extern "C" int ka_gamelog_step_env(const void* env_state, int state_bytes, int envs, int max_ply, const long long* actions,
+                                   const float* rewards, const void* terminated, const void* truncated,
+                                   const void* pre_player, const void* term_reason, const int* nlegal, const int* live,
+                                   const void* side, const int* opp, const int* ids, int opponents, const int* ply_counter,
+                                   void* rows, int row_stride, int* meta, int* starts, int* records, int game_cap, int* cursor,
+                                   void* stream) {
+    if (int rc = gamelog_step_check("gamelog_step_env", env_state, state_bytes, envs, max_ply, actions, rewards, terminated,
+                                    truncated, pre_player, term_reason, rows, row_stride, meta, starts, records, game_cap, cursor))
+        return rc;
+    KA_REQUIRE(side && opp && ids, "gamelog_step_env: null side / opp / ids");
+    KA_REQUIRE(opponents >= 0, "gamelog_step_env: opponents %d (>= 0)", opponents);
+    GameLogArgs a{envs, max_ply, game_cap, row_stride, kGlHead + kGlStart + (max_ply + 1) / 2,
+                  static_cast<const uint8_t*>(env_state), state_bytes, actions,
+                  rewards, static_cast<const uint8_t*>(terminated), static_cast<const uint8_t*>(truncated),
+                  static_cast<const uint8_t*>(pre_player), static_cast<const uint8_t*>(term_reason), nlegal, live, nullptr,
+                  0, 1, ply_counter, static_cast<const uint8_t*>(side), opp, ids, opponents,
+                  static_cast<uint16_t*>(rows), meta, starts, records, cursor};
+    hipLaunchKernelGGL(gamelog_step_kernel<true>, dim3(1), dim3(kGlThreads), 0, static_cast<hipStream_t>(stream), a);
+    return ka_check_launch("gamelog_step_env");
+}
+
+extern "C" int ka_gamelog_peek(const int* envs_list, int n, int envs, int max_ply, const int* pairs, int pair_stride,
+                               int envs_per_pair, const void* side, const int* opp, const int* ids, int opponents,
+                               const int* ply_counter, const void* rows, int row_stride, const int* meta, const int* starts,
+                               int* out, void* stream) {
+    KA_REQUIRE(rows && meta && starts && out, "gamelog_peek: null tensor");
+    KA_REQUIRE(envs > 0 && envs <= kGlMaxEnvs, "gamelog_peek: envs %d (1..%d)", envs, kGlMaxEnvs);
+    KA_REQUIRE(max_ply >= 1 && max_ply <= 65535, "gamelog_peek: max_ply %d (1..65535)", max_ply);
+    KA_REQUIRE((uintptr_t)rows % 4 == 0 && row_stride % 2 == 0 && row_stride >= max_ply,
+               "gamelog_peek: move rows of %d uint16 (even, at least max_ply %d, 4-byte aligned)", row_stride, max_ply);
+    const int rec_words = kGlHead + kGlStart + (max_ply + 1) / 2;
+    KA_REQUIRE(n > 0 && (long long)n * rec_words < (1ll << 31), "gamelog_peek: %d rows x %d words", n, rec_words);
+    KA_REQUIRE(envs_list || n <= envs, "gamelog_peek: %d rows of %d envs without a list", n, envs);
+    KA_REQUIRE(!(pairs && side), "gamelog_peek: players from pairs or from side / opp / ids, not both");
+    KA_REQUIRE(!pairs || (pair_stride >= 2 && envs_per_pair > 0), "gamelog_peek: pair_stride %d (>= 2), envs_per_pair %d (> 0)",
+               pair_stride, envs_per_pair);
+    KA_REQUIRE(!side || (opp && ids && opponents >= 0), "gamelog_peek: side needs opp, ids and opponents %d (>= 0)", opponents);
+    GamePeekArgs a{envs_list, n, envs, max_ply, row_stride, rec_words, pairs, pair_stride, pairs ? envs_per_pair : 1,
+                   static_cast<const uint8_t*>(side), opp, ids, opponents, ply_counter, static_cast<const uint16_t*>(rows),
+                   meta, starts, out};
+    const int per = kGlThreads / 64;
+    hipLaunchKernelGGL(gamelog_peek_kernel, dim3((n + per - 1) / per), dim3(kGlThreads), 0, static_cast<hipStream_t>(stream), a);
+    return ka_check_launch("gamelog_peek");
 }
 
 extern "C" int ka_gamelog_seat(const int* jobs, int njobs, int slots, int envs_per_slot, int* meta, void* stream) {

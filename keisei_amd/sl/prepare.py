@@ -570,7 +570,8 @@ def dataset_from_recorded_games(games, *, device=None, batch_envs: int = 512, ma
     ``actions``, ``winner``, ``is_standard_start``): the replay of ``prepare_sl_dataset`` without the text -- no USI, no
     file, no new kernel.  The recorded action indices are the replay's action stream as they are.  Only games from the
     standard start are replayed; the others are counted in ``games_nonstandard_start``, a game without a move is passed
-    over.  ``max_moves`` is the replay env's ``max_ply`` as in ``prepare_sl_dataset`` (a longer game is cut there and
+    over, a game still in progress (``live_games()``: no winner yet) raises ``ValueError``.  ``max_moves`` is the replay
+    env's ``max_ply`` as in ``prepare_sl_dataset`` (a longer game is cut there and
     counted): the observation's ply plane is ply / max_ply, so pass the ``max_ply`` the games were played with to get the
     observations their players saw.  Positions are in the order of ``games``.  Returns ``(dataset, meta)`` with the keys
     of ``prepare_sl_dataset``."""
@@ -584,6 +585,11 @@ def dataset_from_recorded_games(games, *, device=None, batch_envs: int = 512, ma
         raise ValueError(f"max_batch_positions ({max_batch_positions}) must hold one game of max_moves ({max_moves})")
     count = _new_counters()
     kept: List[tuple] = []
+    games = list(games)
+    for g in games:
+        if not getattr(g, "finished", True):
+            raise ValueError(f"the game in progress in env {g.env} (game {g.game_number}) has no winner yet: a dataset's value "
+                             "targets need one; pass finished games (drained ones, not live_games())")
     for g in games:
         if not g.is_standard_start:
             count["nonstandard"] += 1

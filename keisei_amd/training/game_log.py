@@ -3,15 +3,16 @@ on auto-reset, and the move lists it stores with showcase games).
 
 The loops that play on the device never hand a move to the host, so a game can only be kept by a kernel inside the ply.
 ``GameLog`` owns the buffers of csrc/gamelog.hip (include/keisei_amd.h, "game log"): per env a move row, a start slot and
-three counters; a store of ``capacity`` finished games; a four-word cursor.  One launch per ply (``step``), no host
-synchronisation, capturable in the rollout graphs; ``drain()`` at the owner's sync point reads the cursor, copies exactly
-the committed records and zeroes the cursor.
+four meta words; a store of ``capacity`` finished games; a four-word cursor.  One launch per ply (``step``, or ``step_env``
+where the players are per env, as in the league rollout), no host synchronisation, capturable in the rollout graphs;
+``drain()`` at the owner's sync point reads the cursor, copies exactly the committed records and zeroes the cursor;
+``live()`` at a sync point hands out the games still in progress (the reference's ``move_history`` can be read at any time).
 
 Three uses of a drained ``RecordedGame``: ``write_sfen_games`` writes ``.sfen`` files this package's ``SFENParser`` reads
 back; ``keisei_amd.sl.prepare.dataset_from_recorded_games`` builds a ``DeviceSLDataset`` from them; ``actions`` and the
 start position replay on the CPU oracle.
 
-``HostGameLog`` restates the three kernels in numpy over the same buffers, word for word; ``game_log_host`` runs a whole
+``HostGameLog`` restates the kernels in numpy over the same buffers, word for word; ``game_log_host`` runs a whole
 script of plies through it.  The tests hold the kernels to it.
 """
 from __future__ import annotations
@@ -31,7 +32,7 @@ __all__ = ["GameLog", "RecordedGame", "HostGameLog", "game_log_host", "games_fro
 # layout of csrc/gamelog.hip
 HEAD_WORDS, START_WORDS, CURSOR_WORDS, META_WORDS = 12, POOL_ROW_BYTES // 4, 4, 4
 TRUNCATED_ONLY, CARRIED = 1, 2                                   # flag bits of a record
-_ENV, _PLIES, _WINNER, _REASON, _FLAGS, _BLACK, _WHITE, _END_PLY, _GAME = range(9)
+_ENV, _PLIES, _WINNER, _REASON, _FLAGS, _BLACK, _WHITE, _END_PLY, _GAME, _LEARNER = range(10)
 _HAND = "PLNSGBR"
 _MAPPER = SpatialActionMapper()
 _RESULT = ("win_black", "win_white", "draw")
@@ -71,12 +72,12 @@ def _standard_start_row() -> np.ndarray:
 
 @dataclass
 class RecordedGame:
-    """One finished game as the device logged it."""
+    """One game as the device logged it: finished (a drained record) or still in progress (a peeked row)."""
     start_board: np.ndarray             # uint8 (81,), the piece bytes of the env's state row
     start_hands: np.ndarray             # uint8 (2, 7)
     start_side: int                     # the side to move at the start: 0 black, 1 white
     actions: np.ndarray                 # uint16 (plies,), spatial action indices in the mover's perspective
-    winner: int                         # 0 black, 1 white, 2 draw
+    winner: int                         # 0 black, 1 white, 2 draw; -1 for a game in progress
     reason: int                         # the env's TerminationReason of the last ply
     truncated: bool                     # cut at max_ply, not decided
     carried: bool                       # a ply of it was not played by the pairing named here (idle or inherited)
@@ -85,6 +86,8 @@ class RecordedGame:
     white: int
     end_ply: int                        # the owner's ply counter at the game's last ply
     game_number: int                    # games the env had finished before this one, since begin()
+    finished: bool = True               # False: a game in progress as ``live()`` peeked it (winner -1, end_ply = now)
+    learner_side: Optional[int] = None  # 0 black, 1 white where the owner has a learner (the league rollout), else None
 
     def start_sfen(self) -> str:
         return format_sfen(self.start_board, self.start_hands, int(self.start_side))
@@ -102,11 +105,23 @@ class RecordedGame:
     def outcome(self):
         from keisei_amd.sl.parsers import GameOutcome
 
+        if not self.finished:
+            raise ValueError(f"the game in progress in env {self.env} has no outcome yet")
         return (GameOutcome.WIN_BLACK, GameOutcome.WIN_WHITE, GameOutcome.DRAW)[int(self.winner)]
+
+    @property
+    def learner_result(self) -> Optional[str]:
+        """``"win"`` / ``"loss"`` / ``"draw"`` in the learner's frame; None without a learner or for a game in progress."""
+        if self.learner_side is None or not self.finished:
+            return None
+        if int(self.winner) == 2:
+            return "draw"
+        return "win" if int(self.winner) == int(self.learner_side) else "loss"
 
 
 def games_from_records(records: np.ndarray) -> List[RecordedGame]:
-    """Decode committed records (int32 rows of ``record_words(max_ply)`` words) into games, in their order."""
+    """Decode records (int32 rows of ``record_words(max_ply)`` words) into games, in their order.  A row with winner -1
+    is a game in progress (``ka_gamelog_peek``); header word 9 is the learner's colour + 1, 0 where there is no learner."""
     out = []
     records = np.ascontiguousarray(records, dtype=np.int32)
     for rec in records:
@@ -116,7 +131,8 @@ def games_from_records(records: np.ndarray) -> List[RecordedGame]:
         flags = int(rec[_FLAGS])
         out.append(RecordedGame(start[:81].copy(), start[81:95].reshape(2, 7).copy(), int(start[95]), moves,
                                 int(rec[_WINNER]), int(rec[_REASON]), bool(flags & TRUNCATED_ONLY), bool(flags & CARRIED),
-                                int(rec[_ENV]), int(rec[_BLACK]), int(rec[_WHITE]), int(rec[_END_PLY]), int(rec[_GAME])))
+                                int(rec[_ENV]), int(rec[_BLACK]), int(rec[_WHITE]), int(rec[_END_PLY]), int(rec[_GAME]),
+                                int(rec[_WINNER]) >= 0, int(rec[_LEARNER]) - 1 if int(rec[_LEARNER]) in (1, 2) else None))
     return out
 
 
@@ -126,8 +142,13 @@ def write_sfen_games(path, games: Iterable[RecordedGame], *,
     ``key:value`` metadata lines (``black``, ``white`` when the game names its players, ``reason``, and ``metadata`` --
     one mapping for every game or one per game; a key may hold no digit and no colon), the position line (``startpos`` or
     the SFEN), one USI move per line; a blank line between games.  A game without a move is not written (the parser
-    would drop the block).  Returns the number of games written."""
+    would drop the block).  A game in progress raises ``ValueError``: the format needs a result.  Returns the number of
+    games written."""
     games = list(games)
+    for g in games:
+        if not g.finished:
+            raise ValueError(f"the game in progress in env {g.env} (game {g.game_number}) has no result yet: a .sfen block "
+                             "needs one; write finished games")
     if metadata is not None and not isinstance(metadata, Mapping):
         metadata = list(metadata)
         if len(metadata) != len(games):
@@ -158,7 +179,8 @@ def write_sfen_games(path, games: Iterable[RecordedGame], *,
 
 # ---------------------------------------------------------------------------------------------- host restatement
 class HostGameLog:
-    """``ka_gamelog_begin`` / ``ka_gamelog_step`` / ``ka_gamelog_seat`` in numpy, over buffers of the device's layout:
+    """``ka_gamelog_begin`` / ``ka_gamelog_step`` / ``ka_gamelog_step_env`` / ``ka_gamelog_peek`` / ``ka_gamelog_seat``
+    in numpy, over buffers of the device's layout:
     ``rows`` uint16 (E, row_stride), ``meta`` int32 (E, 4), ``starts`` int32 (E, 24), ``records`` int32 (capacity,
     record_words(max_ply)), ``cursor`` int32 (4,).  Words the kernel does not write keep what they held."""
 
@@ -191,9 +213,16 @@ class HostGameLog:
                 m[m[:, 0] > 0, 1] = 1
 
     def step(self, state_rows, actions, rewards, terminated, truncated, pre_player, reason, *, nlegal=None, live=None,
-             pairs=None, pair_stride: int = 0, envs_per_pair: int = 1, ply_counter: int = 0) -> None:
-        """One ply; ``state_rows`` is the env state AFTER the env step (finished games already restarted)."""
+             pairs=None, pair_stride: int = 0, envs_per_pair: int = 1, ply_counter: int = 0, side=None, opp=None,
+             ids=None) -> None:
+        """One ply; ``state_rows`` is the env state AFTER the env step (finished games already restarted).  With ``side``
+        / ``opp`` / ``ids`` (the per-env players) it is ``ka_gamelog_step_env``, else ``ka_gamelog_step``."""
         E = self.num_envs
+        per_env = side is not None or opp is not None or ids is not None
+        if per_env and pairs is not None:
+            raise ValueError("the players come from pairs or from side / opp / ids, not both")
+        if per_env and (side is None or opp is None or ids is None):
+            raise ValueError("per-env players need side, opp and ids together")
         starts_now = self._start_words(state_rows)
         tm, tr = np.asarray(terminated).astype(bool), np.asarray(truncated).astype(bool)
         rewards = np.asarray(rewards, np.float32)
@@ -213,6 +242,10 @@ class HostGameLog:
             is_live = True if live is None else int(live[e]) >= 0
             carried = (int(self.meta[e, 1]) | (0 if is_live else 1)) & 1
             done = bool(tm[e] or tr[e])
+            if per_env:
+                s, tag = int(side[e]) & 1, _player_tag(side[e], opp[e])
+                if count > 0 and int(self.meta[e, 3]) != tag:
+                    carried = 1
             if done and is_live and not stalled[e // G]:
                 if rank < room:
                     rec = self.records[first + rank]
@@ -221,9 +254,11 @@ class HostGameLog:
                     if pairs is not None:
                         p = np.asarray(pairs).reshape(-1)[(e // G) * pair_stride:]
                         black, white = int(p[0]), int(p[1])
+                    if per_env:
+                        black, white = _env_players(ids, s, opp[e])
                     rec[:HEAD_WORDS] = [e, plies, pre if r > 0 else (1 - pre if r < 0 else 2), int(reason[e]),
                                         (TRUNCATED_ONLY if tr[e] and not tm[e] else 0) | (CARRIED if carried else 0),
-                                        black, white, int(ply_counter), int(self.meta[e, 2]), 0, 0, 0]
+                                        black, white, int(ply_counter), int(self.meta[e, 2]), s + 1 if per_env else 0, 0, 0]
                     rec[HEAD_WORDS:HEAD_WORDS + START_WORDS] = self.starts[e]
                     words = (plies + 1) // 2
                     mv = np.zeros(2 * words, np.uint16)
@@ -235,21 +270,77 @@ class HostGameLog:
                 self.starts[e] = starts_now[e]
             else:
                 self.meta[e, 0], self.meta[e, 1] = plies, carried
+            if per_env:
+                self.meta[e, 3] = 0 if done else tag
         self.cursor[0] = first + min(rank, room)
         self.cursor[1] += max(0, rank - room)
         self.cursor[2] += 1
+
+    def peek(self, envs=None, *, pairs=None, pair_stride: int = 0, envs_per_pair: int = 1, side=None, opp=None, ids=None,
+             ply_counter: int = 0, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """``ka_gamelog_peek``: the games in progress of ``envs`` (default: every env) as record-shaped rows, written into
+        ``out`` (n, record_words(max_ply)) int32 where given -- words the kernel does not write keep what they held."""
+        per_env = side is not None or opp is not None or ids is not None
+        if per_env and pairs is not None:
+            raise ValueError("the players come from pairs or from side / opp / ids, not both")
+        if per_env and (side is None or opp is None or ids is None):
+            raise ValueError("per-env players need side, opp and ids together")
+        envs = np.arange(self.num_envs) if envs is None else np.asarray(envs, np.int64).reshape(-1)
+        if out is None:
+            out = np.zeros((len(envs), record_words(self.max_ply)), np.int32)
+        G = int(envs_per_pair) if pairs is not None else 1
+        for j, e in enumerate(int(v) for v in envs):
+            rec = out[j]
+            if not 0 <= e < self.num_envs:
+                rec[:HEAD_WORDS] = [-1, 0, -1, 0, 0, -1, -1, int(ply_counter), 0, 0, 0, 0]
+                rec[HEAD_WORDS:HEAD_WORDS + START_WORDS] = 0
+                continue
+            n = max(0, min(int(self.meta[e, 0]), self.max_ply))
+            black = white = -1
+            colour = 0
+            if pairs is not None:
+                p = np.asarray(pairs).reshape(-1)[(e // G) * pair_stride:]
+                black, white = int(p[0]), int(p[1])
+            elif per_env:
+                s = int(side[e]) & 1
+                black, white = _env_players(ids, s, opp[e])
+                colour = s + 1
+            rec[:HEAD_WORDS] = [e, n, -1, 0, CARRIED if int(self.meta[e, 1]) & 1 else 0, black, white, int(ply_counter),
+                                int(self.meta[e, 2]), colour, 0, 0]
+            rec[HEAD_WORDS:HEAD_WORDS + START_WORDS] = self.starts[e]
+            words = (n + 1) // 2
+            mv = np.zeros(2 * words, np.uint16)
+            mv[:n] = self.rows[e, :n]
+            rec[HEAD_WORDS + START_WORDS:HEAD_WORDS + START_WORDS + words] = mv.view(np.int32)
+        return out
 
     def games(self) -> List[RecordedGame]:
         return games_from_records(self.records[:int(self.cursor[0])])
 
 
+def _player_tag(side, opp) -> int:
+    """((opp << 1) | side) + 1 in the kernel's 32-bit wrapping arithmetic, as an int32 value."""
+    t = ((((int(opp) & 0xFFFFFFFF) << 1) & 0xFFFFFFFF) | (int(side) & 1)) + 1 & 0xFFFFFFFF
+    return t - (1 << 32) if t >= 1 << 31 else t
+
+
+def _env_players(ids, s: int, opp):
+    """(black, white) of an env whose learner plays colour ``s`` against opponent index ``opp``: ids[0] is the learner."""
+    ids = np.asarray(ids).reshape(-1)
+    k = int(opp)
+    oid = int(ids[k + 1]) if 0 <= k < len(ids) - 1 else -1
+    return (oid, int(ids[0])) if s else (int(ids[0]), oid)
+
+
 def game_log_host(plies: Sequence[Mapping], *, num_envs: int, max_ply: int, capacity: int, start_state=None, pairs=None,
-                  pair_stride: int = 0, envs_per_pair: int = 1) -> HostGameLog:
+                  pair_stride: int = 0, envs_per_pair: int = 1, ids=None) -> HostGameLog:
     """Run a script of plies through ``HostGameLog`` from ``begin``.  A ply is a mapping with ``actions``, ``rewards``,
     ``terminated``, ``truncated``, ``pre_players`` and optionally ``reason``, ``n_legal``, ``live``, ``state`` (the env
     state rows after the step; default ``start_state``), ``ply_counter`` (default: the ply's index) and ``seat`` =
     ``(jobs, slots, envs_per_slot)``, applied before the ply as the arena seats at a sync point.  ``start_state``: the
-    (E, >= 96) uint8 rows games start from (default: the standard start)."""
+    (E, >= 96) uint8 rows games start from (default: the standard start).  Per-env players (``ka_gamelog_step_env``):
+    ``ids`` here, or ``ids`` in a ply from which on they hold (a new cohort), and ``side`` / ``opp`` in every ply, the
+    players who play it."""
     E = int(num_envs)
     if start_state is None:
         start_state = np.tile(_standard_start_row(), (E, 1))
@@ -258,10 +349,13 @@ def game_log_host(plies: Sequence[Mapping], *, num_envs: int, max_ply: int, capa
     for t, ply in enumerate(plies):
         if ply.get("seat") is not None:
             log.seat(*ply["seat"])
+        if ply.get("ids") is not None:
+            ids = ply["ids"]
+        per_env = {} if ids is None else dict(side=ply["side"], opp=ply["opp"], ids=ids)
         log.step(ply.get("state", start_state), ply["actions"], ply["rewards"], ply["terminated"], ply["truncated"],
                  ply["pre_players"], ply.get("reason", np.zeros(E, np.uint8)), nlegal=ply.get("n_legal"),
                  live=ply.get("live"), pairs=pairs, pair_stride=pair_stride, envs_per_pair=envs_per_pair,
-                 ply_counter=ply.get("ply_counter", t))
+                 ply_counter=ply.get("ply_counter", t), **per_env)
     return log
 
 
@@ -270,8 +364,10 @@ class GameLog:
     """The device-resident log of one ``VecEnv`` (see the module docstring).  ``capacity`` finished games fit between two
     ``drain()`` calls; a game beyond that is dropped whole and counted in ``dropped``.
 
-    ``begin()`` follows ``env.reset()``; ``step(...)`` follows ``env.step(...)`` and precedes the owner's bookkeeping
-    launch; ``seat(jobs, n)`` follows ``ka_arena_assign`` (the arena's slots are ``envs_per_slot`` envs each); ``drain()`` runs at a sync point, outside any captured graph."""
+    ``begin()`` follows ``env.reset()``; ``step(...)`` (or ``step_env(...)``, per-env players) follows ``env.step(...)``
+    and precedes the owner's bookkeeping launch; ``live(...)`` reads the games in progress at a sync point;
+    ``seat(jobs, n)`` follows ``ka_arena_assign`` (the arena's slots are ``envs_per_slot`` envs each); ``drain()`` runs at
+    a sync point, outside any captured graph."""
 
     def __init__(self, env, *, capacity: int, device=None, envs_per_slot: Optional[int] = None) -> None:
         if capacity < 1:
@@ -330,6 +426,44 @@ class GameLog:
                   terminated, truncated, pre_player, reason, nlegal, live, pairs, int(pair_stride), int(envs_per_pair),
                   ply_counter, self._rows, self.row_stride, self._meta, self._starts, self._records, self.capacity,
                   self._cursor, _lib.stream_ptr(self.device))
+
+    def step_env(self, actions, rewards, terminated, truncated, pre_player, reason, *, side, opp, ids, opponents: int,
+                 nlegal=None, live=None, ply_counter=None) -> None:
+        """One launch on the current stream with the players per env: ``side`` (E u8, the learner's colour), ``opp`` (E
+        int32, the opponent's index), ``ids`` (``opponents`` + 1 int32 on the device: the learner's id, then the
+        opponents').  See ``ka_gamelog_step_env`` in the header."""
+        _lib.call("ka_gamelog_step_env", self.env._state, self._state_bytes, self.num_envs, self.max_ply, actions, rewards,
+                  terminated, truncated, pre_player, reason, nlegal, live, side, opp, ids, int(opponents), ply_counter,
+                  self._rows, self.row_stride, self._meta, self._starts, self._records, self.capacity, self._cursor,
+                  _lib.stream_ptr(self.device))
+
+    def live(self, envs=None, *, pairs=None, pair_stride: int = 0, envs_per_pair: int = 1, side=None, opp=None, ids=None,
+             opponents: Optional[int] = None, ply_counter=None) -> List[RecordedGame]:
+        """Sync point: the games in progress of ``envs`` (default: every env, in env order) as ``RecordedGame`` with
+        ``finished=False``, ``winner=-1`` and ``end_ply`` = the owner's ply counter now.  One launch (``ka_gamelog_peek``)
+        and one copy of exactly the rows asked for; the log is not changed.  The players as ``step`` (``pairs``) or
+        ``step_env`` (``side`` / ``opp`` / ``ids``) takes them, or neither."""
+        if pairs is not None and side is not None:
+            raise ValueError("the players come from pairs or from side / opp / ids, not both")
+        if side is not None:
+            if opp is None or ids is None:
+                raise ValueError("per-env players need side, opp and ids together")
+            opponents = int(ids.numel()) - 1 if opponents is None else int(opponents)
+        with torch.cuda.device(self.device):
+            lst, n = None, self.num_envs
+            if envs is not None:
+                host = np.asarray(envs, dtype=np.int64).reshape(-1)
+                if host.size and (host.min() < 0 or host.max() >= self.num_envs):
+                    raise ValueError(f"envs must lie in [0, {self.num_envs}), got {host.tolist()}")
+                lst, n = torch.from_numpy(host.astype(np.int32)).to(self.device), int(host.size)
+            if n == 0:
+                return []
+            words = record_words(self.max_ply)
+            out = torch.empty(n, words, dtype=torch.int32, device=self.device)
+            _lib.call("ka_gamelog_peek", lst, n, self.num_envs, self.max_ply, pairs, int(pair_stride), int(envs_per_pair),
+                      side, opp, ids, int(opponents or 0), ply_counter, self._rows, self.row_stride, self._meta, self._starts,
+                      out, _lib.stream_ptr(self.device))
+            return games_from_records(out.cpu().numpy())
 
     def seat(self, jobs, n: int) -> None:
         """Behind ``ka_arena_assign`` with the same ``n`` jobs (a log built with ``envs_per_slot``): the games in progress

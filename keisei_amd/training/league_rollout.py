@@ -3,11 +3,13 @@
 
 The learner and its cohort of opponents sit in one ``SEResNetGroup`` (learner = model 0, opponent k = model k + 1): the
 learner's forward in this loop is an eval-mode, no-grad forward (katago_loop.py:333-343), so it can be seated like any
-opponent.  One ply is four steps on one stream, with no host synchronisation:
+opponent.  One ply is four steps (five with a game log) on one stream, with no host synchronisation:
 
     grouped stem / tower / heads on model_of   (csrc/tower.hip, the group's tables)
     ka_policy_sample_play                       (csrc/loss.hip: actions and log-probs, seed read from the device)
     ka_shogi_env_step                           (csrc/shogi_env.hip)
+    ka_gamelog_step_env                         (csrc/gamelog.hip, only with game_log > 0: the finished games, move by
+                                                 move, with the learner's colour and the players' ids)
     ka_league_step                              (csrc/league.hip: the reference's whole per-step bookkeeping -- learner-frame
                                                  rewards and tallies, pending accumulate / settle / open / immediate
                                                  settle straight into the rollout store's columns, per-opponent results,
@@ -38,8 +40,9 @@ import numpy as np
 import torch
 
 from keisei_amd import _lib
-from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS, OBS_CHANNELS, VecEnv
+from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS, OBS_CHANNELS, POOL_ROW_BYTES, VecEnv
 
+from .game_log import GameLog, RecordedGame
 from .katago_loop import (_ZERO_LEGAL, PendingTransitions, _compute_value_cats, sign_correct_bootstrap,
                           to_learner_perspective)
 from .katago_ppo import SCORE_NORMALIZATION, KataGoRolloutBuffer, _check_step_inputs
@@ -116,6 +119,8 @@ class LeagueRolloutStats:
     host_syncs: int = 0                 # reads of the state array
     truncation_overrides: int = 0       # rows whose bootstrap override was computed at a sync point
     flushed: int = 0                    # rows the flush at the end of collect closed (done = 0)
+    games: List[RecordedGame] = field(default_factory=list)     # the finished games (a rollout built with game_log > 0)
+    games_dropped: int = 0              # finished games that did not fit the log between two sync points
 
 
 def _stats_from_state(st: np.ndarray, opponent_ids: Sequence[int], stats: LeagueRolloutStats) -> None:
@@ -167,17 +172,28 @@ class LeagueRollout:
     games over epochs); ``reset()`` is explicit.  ``seed`` fixes sampling and re-draws from the last ``reset()`` on.
     ``record=True`` (no graph) keeps every ply's inputs and outputs in ``self.record`` for tests.  ``start_pool_capacity > 0`` gives the env a pool of
     start positions of that size: ``roll.env.set_start_positions(...)`` / ``set_start_sfens(...)`` between ``collect`` calls make later
-    games start from them (no re-capture; see ``VecEnv``)."""
+    games start from them (no re-capture; see ``VecEnv``).  ``game_log=K > 0`` adds a device-resident ``GameLog`` of K
+    records to the ply (one launch, ``ka_gamelog_step_env``, between the env step and ``ka_league_step``): ``collect``
+    drains it at every sync point onto ``LeagueRolloutStats.games``.  A game names its players by id (``learner_id`` and
+    ``opponent_ids``: the players who ended it, the ones its result is tallied for) and the learner's colour; it is
+    ``carried`` where its side or its opponent changed in the middle of it (the epoch's side re-draw) and where it spans a
+    ``set_opponents``.
+    ``live_games()`` between two ``collect`` calls gives the games still in progress.  Without ``game_log`` the ply is
+    launch for launch what it was."""
 
     def __init__(self, learner, opponents: Sequence, opponent_ids: Sequence[int], *, num_envs: int = 512, max_ply: int = 500,
                  value_adapter=None, score_norm: float = SCORE_NORMALIZATION, color_randomization: bool = False,
                  opponent_weights: Optional[Sequence[float]] = None, sync_every: int = 32, graph: bool = True,
-                 seed: Optional[int] = None, record: bool = False, start_pool_capacity: int = 0) -> None:
+                 seed: Optional[int] = None, record: bool = False, start_pool_capacity: int = 0, game_log: int = 0,
+                 learner_id: int = -1) -> None:
         opponents, opponent_ids = list(opponents), [int(i) for i in opponent_ids]
         _check_args(len(opponents), opponent_ids, int(num_envs), int(max_ply), int(sync_every), bool(graph), bool(record),
                     float(score_norm), value_adapter)
         if start_pool_capacity < 0:
             raise ValueError(f"start_pool_capacity must not be negative, got {start_pool_capacity}")
+        if game_log < 0:
+            raise ValueError(f"game_log must not be negative, got {game_log}")
+        self.learner_id = int(learner_id)
         self._cum_host = cum_thresholds(opponent_weights, len(opponents))
         self.group = self._make_group(learner, opponents)
         self.learner, self.opponent_ids = learner, opponent_ids
@@ -205,6 +221,9 @@ class LeagueRollout:
             self._desc = z(q(1), dtype=torch.int64)
             self._desc_host = torch.zeros(q(1), dtype=torch.int64).pin_memory()
             self._side_host = torch.zeros(N, dtype=torch.uint8).pin_memory()
+            self.game_log: Optional[GameLog] = GameLog(self.env, capacity=int(game_log), envs_per_slot=N) if game_log else None
+            self._every_env = z(1, 4)                             # a seat job naming the one slot of all envs
+            self._ids: Optional[torch.Tensor] = None
         self._graphs: Dict[int, torch.cuda.CUDAGraph] = {}
         self._collects = 0
         self._seat_cohort()
@@ -238,6 +257,12 @@ class LeagueRollout:
             self._state_host = torch.zeros(self._state.shape, dtype=torch.int32).pin_memory()
             self._cum = torch.from_numpy(self._cum_host.view(np.int32).copy()).to(dev)
             self._ws = self.group._tables.workspace(self.num_envs)
+            if self.game_log is not None:                         # the ids the log names the players by: the same words
+                ids = torch.tensor([self.learner_id, *self.opponent_ids], dtype=torch.int32)       # where K is unchanged
+                if self._ids is None or self._ids.numel() != K + 1:
+                    self._ids = ids.to(dev)
+                else:
+                    self._ids.copy_(ids)
         self._graphs = {}
 
     def set_opponents(self, opponents: Sequence, opponent_ids: Sequence[int],
@@ -255,6 +280,8 @@ class LeagueRollout:
         self.opponent_ids, self._cum_host = opponent_ids, cum
         self._seat_cohort()
         with torch.cuda.device(self.device):
+            if self.game_log is not None:                         # an unchanged index may name another model now: every game
+                self.game_log.seat(self._every_env, 1)            # in progress is carried, whatever its env draws below
             games = self._games.cpu().numpy()
             self._opp.copy_(torch.from_numpy(draw_opponents(self._draw_seed, np.arange(self.num_envs), games, cum)))
             self._seat()
@@ -283,6 +310,8 @@ class LeagueRollout:
             side = draw_sides(seed, envs, np.zeros(N, np.int64)) if self.color_randomization else np.zeros(N, np.uint8)
             self._side.copy_(torch.from_numpy(side))
             self.env.reset()
+            if self.game_log is not None:
+                self.game_log.begin()
             self._seat()
         self._collects = 0
         self.record = []
@@ -308,6 +337,10 @@ class LeagueRollout:
         _lib.call("ka_policy_sample_play", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of, K + 1,
                   self._actions, self._logp, self._nlegal, sp + 4 * _SAMP, N, ACTION_SPACE, st)
         r = env.step(self._actions)
+        if self.game_log is not None:                     # before ka_league_step re-draws side and opp of finished envs
+            self.game_log.step_env(self._actions, r.rewards, r.terminated, r.truncated, env._players[prev],
+                                   r.step_metadata.termination_reason, side=self._side, opp=self._opp, ids=self._ids,
+                                   opponents=K, nlegal=self._nlegal, ply_counter=sp + 4 * _PLY)
         _lib.call("ka_league_step", self._state, N, K, 0, cur.observations, cur.legal_mask_bits, self._actions, self._logp,
                   value, score if self.alpha != 0.0 else None, self.alpha, self._nlegal, env._players[prev], r.rewards,
                   r.terminated, r.truncated, r.current_players, r.step_metadata.material_balance, self.score_norm,
@@ -329,7 +362,8 @@ class LeagueRollout:
                    n_legal=self._nlegal.cpu().numpy(), rewards=env._rewards[c].cpu().numpy(),
                    terminated=env._terminated[c].cpu().numpy(), truncated=env._truncated[c].cpu().numpy(),
                    current_players=env._players[c].cpu().numpy(), material=env._material[c].cpu().numpy(),
-                   terminal_envs=trunc.cpu().numpy(), terminal_obs=env._terminal_obs[trunc].cpu())
+                   terminal_envs=trunc.cpu().numpy(), terminal_obs=env._terminal_obs[trunc].cpu(),
+                   reason=env._reason[c].cpu().numpy(), state=env._state[:, :POOL_ROW_BYTES].cpu().numpy())
         self.record.append(rec)
 
     def _capture(self, parity: int) -> torch.cuda.CUDAGraph:
@@ -436,12 +470,16 @@ class LeagueRollout:
             self._seat()
         self._collects += 1
         base, rows, adds, done = buffer._write_offset, 0, 0, 0
+        dropped_before = self.game_log.dropped if self.game_log is not None else 0
 
         def sync(cols):
             nonlocal rows, adds
             st = self._read_state(stats)
             buffer.commit(int(st[_ROWS]) - rows, int(st[_BLOCKS]) - adds)
             rows, adds = int(st[_ROWS]), int(st[_BLOCKS])
+            if self.game_log is not None:
+                stats.games += self.game_log.drain()
+                stats.games_dropped = self.game_log.dropped - dropped_before
             n = int(st[_TRUNC])
             if n:
                 self._overrides(cols, n)
@@ -462,6 +500,15 @@ class LeagueRollout:
         st = sync(cols)
         stats.plies, stats.flushed = steps, rows - before
         _stats_from_state(st, self.opponent_ids, stats)
+
+    def live_games(self, envs: Optional[Sequence[int]] = None) -> List[RecordedGame]:
+        """The games in progress (every env, or ``envs``) between two ``collect`` calls: ``RecordedGame`` with
+        ``finished=False``, named by the players seated now."""
+        if self.game_log is None:
+            raise ValueError("live_games() needs a rollout built with game_log > 0")
+        with torch.cuda.device(self.device):
+            return self.game_log.live(envs, side=self._side, opp=self._opp, ids=self._ids, opponents=len(self.opponent_ids),
+                                      ply_counter=self._state.data_ptr() + 4 * _PLY)
 
     def bootstrap_values(self) -> torch.Tensor:
         """V(observation now) by the learner, in the learner's frame (katago_loop.py:1565-1580): ``update``'s next_values."""

@@ -480,6 +480,16 @@ class MatchArena:
         if cur.any():
             self._fcursors.zero_()
 
+    def live_games(self, envs: Optional[Sequence[int]] = None) -> List[RecordedGame]:
+        """The games in progress (every env, or ``envs``) between two rounds: ``RecordedGame`` with ``finished=False``,
+        named by the models the env's slot holds now."""
+        if self.game_log is None:
+            raise ValueError("live_games() needs an arena built with game_log > 0")
+        sp = self._state.data_ptr()
+        with torch.cuda.device(self.device):
+            return self.game_log.live(envs, pairs=sp + 4 * _HDR, pair_stride=_SLOT, envs_per_pair=self.envs_per_match,
+                                      ply_counter=sp + 8)
+
     def run_round(self, pairings: Sequence[Tuple[int, int]], games_per_match: int = 64, *, max_ply: Optional[int] = None,
                   trainable: Union[None, Callable[[int, int], int], Mapping[int, int]] = None,
                   entry_ids: Union[None, Sequence[int], Mapping[int, int]] = None, epoch: int = 0):

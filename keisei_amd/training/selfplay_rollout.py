@@ -344,6 +344,14 @@ class SelfPlayRollout:
         stats.black_wins, stats.white_wins = int(st[_BLACK]), int(st[_WHITE])
         stats.terminated, stats.truncated = int(st[_TERMINATED]), int(st[_TRUNCATED])
 
+    def live_games(self, envs: Optional[Sequence[int]] = None) -> List[RecordedGame]:
+        """The games in progress (every env, or ``envs``) between two ``collect`` calls: ``RecordedGame`` with
+        ``finished=False``."""
+        if self.game_log is None:
+            raise ValueError("live_games() needs a rollout built with game_log > 0")
+        with torch.cuda.device(self.device):
+            return self.game_log.live(envs, ply_counter=self._state.data_ptr() + 4 * _PLIES)
+
     def bootstrap_values(self) -> torch.Tensor:
         """-V(observation now) by the learner (katago_loop.py:1565-1572, :1589): ``update``'s next_values, in the frame of
         the last ply's mover."""
