@@ -698,6 +698,39 @@ int ka_gamelog_peek(const int* envs_list, int n, int envs, int max_ply, const in
                     const void* rows, int row_stride, const int* meta, const int* starts, int* out, void* stream);
 int ka_gamelog_seat(const int* jobs, int njobs, int slots, int envs_per_slot, int* meta, void* stream);
 
+/* ---- spectator feed (csrc/spectator.hip; the move_histories of the reference's VecEnv, vec_env.rs:259, 618-622, 693-714,
+ * with what its Hodges notation needs, spectator_data.rs:105-186).  Per env and move one uint32 note, computed on the
+ * device from the position and the packed legal mask of the moment of the move; the host turns notes into text.
+ * Note, from bit 0 (ka_spectator_words(which) gives the positions: 0 = bits of the action index, 14; then the shift of
+ * 1 = colour, 2 = piece type, 3 = promoted, 4 = drop, 5 = capture, 6 = suffix, 7 = disambiguation, 8 = no piece; 9 = int32
+ * words of one note; -1 for any other which):
+ *   action index; the mover's colour (state byte 95); piece type (4 bits, 1 P 2 L 3 N 4 S 5 G 6 B 7 R 8 K: of the piece
+ *   on `from`, or the dropped type); that piece is already promoted; drop; capture (a board move whose `to` is occupied);
+ *   promotion suffix class (2 bits): 1 = '+' when the move promotes or must_promote(type, to row, colour) (movegen.rs:35-47,
+ *   whatever the piece's promotion state), else 2 = '=' when the piece can promote, is unpromoted and `from` or `to` lies
+ *   in the mover's zone, else 0; disambiguation class (2 bits): 0 none, 1 file, 2 rank, 3 full square; no piece on `from`
+ *   (then type, promoted, suffix and disambiguation are 0).
+ *   The "others" of the disambiguation are the squares other than `from` and `to` that hold the same piece byte as `from`
+ *   and whose move to `to`, plain or promoting, is set in the mask row; a king is never disambiguated.
+ *   An action outside [0, A) gives note 0 and reads neither the board nor the mask row; an action inside it that points
+ *   off the board (spatial mode) gives the bare action index.  The env refuses both.
+ * Buffers, device memory owned by the caller: pending envs x uint32; hist envs x row_len uint32 (row_len >= max_ply, so a
+ *   row never fills before the env truncates the game); count envs x int32.
+ * ka_spectator_begin: every count becomes 0 (after a reset, or after positions were placed).
+ * ka_spectator_note (BEFORE ka_shogi_env_step / ka_shogi_env_step_pool, on its stream): one wave per env; env_state the
+ *   state rows (state_bytes = ka_shogi_env_state_bytes()), mask_bits the packed rows the step validates against
+ *   (prev_mask_bits), actions the step's actions, action_mode 0 default / 1 spatial.  Writes pending[e] only.
+ * ka_spectator_commit (AFTER the env step): err the step's refusal words (err[0] != 0: the step was refused and nothing is
+ *   written); otherwise pending[e] is appended at hist[e][count[e]] -- a row that already holds row_len notes stays as it
+ *   is -- and count[e] becomes 0 where terminated[e] | truncated[e] (u8 each, the step's outputs), else min(count + 1,
+ *   row_len).  Kernel launches only (a captured step holds no memset node); nothing is written outside hist and count. */
+int ka_spectator_words(int which);
+int ka_spectator_begin(int* count, int envs, void* stream);
+int ka_spectator_note(const void* env_state, int state_bytes, int envs, const void* mask_bits, const long long* actions,
+                      int action_mode, void* pending, void* stream);
+int ka_spectator_commit(const void* err, const void* terminated, const void* truncated, int envs, const void* pending,
+                        void* hist, int row_len, int* count, void* stream);
+
 /* ---- SL shard preparation (csrc/sl_prepare.hip; the replay keisei/sl/prepare.py:151-161 leaves out).  A batch of E game
  * records, game g in env g, stepped in lockstep from ka_shogi_env_reset.  One ply = ka_sl_replay_plan, ka_shogi_env_step
  * (unchanged), ka_sl_replay_record on one stream.

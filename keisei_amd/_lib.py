@@ -127,6 +127,10 @@ _SIGS = {
     "ka_gamelog_step_env": "p iii pppppp pp ppp i p p i ppp i p p",
     "ka_gamelog_peek": "p iii p ii ppp i p p i pp p p",
     "ka_gamelog_seat": "p iii p p",
+    "ka_spectator_words": "i",
+    "ka_spectator_begin": "p i p",
+    "ka_spectator_note": "p ii pp i p p",
+    "ka_spectator_commit": "ppp i pp i p p",
     "ka_sl_replay_state_words": "i",
     "ka_sl_replay_plan": "p i p i p p i pp p",
     "ka_sl_replay_record": "p i ppp i ppppppp p i p",

@@ -20,6 +20,10 @@ after `set_start_positions` / `set_start_sfens` the games of `reset()` and every
 row drawn per (seed, env, game number) -- `start_pool_index` is the same draw on the host -- instead of the standard
 position; `clear_start_positions()` returns to it.  Uploads are validated here, because the kernel assumes playable
 positions.  `parse_sfen` / `format_sfen` are the text form of a position.
+`get_spectator_data()` returns the reference's spectator dicts from one read of the state rows; `VecEnv(...,
+move_history=True)` (keyword-only) makes `step()` keep one note per move of each game in progress (csrc/spectator.hip, two
+more launches; cleared when the game ends, unchanged by a refused step), from which `hodges_notation` / `move_usi` give
+the reference's `move_history` entries.
 There is no CPU fallback: without the HIP library or a GPU the constructor raises.
 """
 from __future__ import annotations
@@ -294,6 +298,191 @@ def _static_position_errors(boards: np.ndarray, hands: np.ndarray, sides: np.nda
     return bad, why
 
 
+# ---------------------------------------------------------------------- spectator feed (spectator_data.rs)
+# the move note of csrc/spectator.hip, from bit 0 (ka_spectator_words reports the same numbers)
+NOTE_ACTION_BITS, NOTE_COLOUR, NOTE_TYPE, NOTE_PROMOTED, NOTE_DROP, NOTE_CAPTURE, NOTE_SUFFIX, NOTE_DISAMB, NOTE_NO_PIECE = \
+    14, 14, 15, 19, 20, 21, 22, 24, 26
+NOTE_WORDS = 1
+_PIECE_NAMES = ("pawn", "lance", "knight", "silver", "gold", "bishop", "rook", "king")      # spectator_data.rs:45-56
+_COLOR_NAMES = ("black", "white")
+_SPECTATOR_KEYS = ("board", "hands", "current_player", "ply", "is_over", "result", "sfen", "in_check", "move_history")
+_DIR_INDEX = {d: i for i, d in enumerate(_DIRS)}
+_MAPPERS = (DefaultActionMapper(), SpatialActionMapper())
+
+
+def _amode(action_mode) -> int:
+    if action_mode in ("default", "spatial"):
+        return int(action_mode == "spatial")
+    if action_mode in (0, 1):
+        return int(action_mode)
+    raise ValueError(f"Unknown action_mode '{action_mode}'. Valid: 'default', 'spatial' (or 0, 1)")
+
+
+def _square_hodges(sq: int) -> str:
+    """spectator_data.rs:21-25: file (9 - column) and rank letter (row)."""
+    return f"{9 - sq % 9}{'abcdefghi'[sq // 9]}"
+
+
+def _decode_action(action: int, side: int, amode: int):
+    """(from, to, promote, hand type or -1) of an action index on the real board, or None where it points off the board or
+    lies outside the action space."""
+    try:
+        m = _MAPPERS[amode].decode(int(action), bool(side))
+    except ValueError:
+        return None
+    if m["type"] == "drop":
+        return m["to_sq"], m["to_sq"], False, m["piece_type_idx"]
+    return m["from_sq"], m["to_sq"], m["promote"], -1
+
+
+def host_move_note(board, side: int, mask_bits_row, action: int, action_mode) -> int:
+    """The note kernel (`ka_spectator_note`, include/keisei_amd.h) restated on the host for one env: `board` the 81 piece
+    bytes before the move, `side` the mover, `mask_bits_row` the packed legal mask the action is validated against."""
+    amode, side = _amode(action_mode), int(side) & 1
+    A = ACTION_SPACE if amode else DEFAULT_ACTION_SPACE
+    action = int(action)
+    if not 0 <= action < A:
+        return 0
+    mv = _decode_action(action, side, amode)
+    if mv is None:
+        return action
+    board = np.asarray(board, np.uint8).reshape(81)
+    row = np.ascontiguousarray(mask_bits_row).view(np.uint32).reshape(-1)
+    frm, to, promote, drop = mv
+    note = action | (side << NOTE_COLOUR)
+    if drop >= 0:
+        return note | ((drop + 1) << NOTE_TYPE) | (1 << NOTE_DROP)
+    pc = int(board[frm])
+    if board[to]:
+        note |= 1 << NOTE_CAPTURE
+    if not pc:
+        return note | (1 << NOTE_NO_PIECE)
+    t, prom = pc & 15, (pc >> 5) & 1
+    from_row, to_row = frm // 9, to // 9
+    if t in (1, 2):
+        must = to_row == (8 if side else 0)
+    elif t == 3:
+        must = to_row >= 7 if side else to_row <= 1
+    else:
+        must = False
+    zone = (from_row >= 6 or to_row >= 6) if side else (from_row <= 2 or to_row <= 2)
+    suffix = 1 if (promote or must) else 2 if (not prom and t in _PROMOTABLE and zone) else 0
+    flip = (lambda q: 80 - q) if side else (lambda q: q)
+    to_p = flip(to)
+    others = []
+    if t != 8:
+        for sq in range(81):
+            if sq in (frm, to) or int(board[sq]) != pc:
+                continue
+            f_p = flip(sq)
+            if amode:
+                dr, dc = to_p // 9 - f_p // 9, to_p % 9 - f_p % 9
+                if dr == 0 or dc == 0 or abs(dr) == abs(dc):
+                    a0 = f_p * 139 + _DIR_INDEX[((dr > 0) - (dr < 0), (dc > 0) - (dc < 0))] * 8 + max(abs(dr), abs(dc)) - 1
+                    a1 = a0 + 64
+                elif dr == -2 and abs(dc) == 1:
+                    a0 = f_p * 139 + 128 + (2 if dc > 0 else 0)
+                    a1 = a0 + 1
+                else:
+                    continue
+            else:
+                a0 = f_p * 160 + (to_p - 1 if to_p > f_p else to_p) * 2
+                a1 = a0 + 1
+            if ((int(row[a0 >> 5]) >> (a0 & 31)) | (int(row[a1 >> 5]) >> (a1 & 31))) & 1:
+                others.append(sq)
+    if not others:
+        disamb = 0
+    elif not any(o % 9 == frm % 9 for o in others):
+        disamb = 1
+    elif not any(o // 9 == from_row for o in others):
+        disamb = 2
+    else:
+        disamb = 3
+    return note | (t << NOTE_TYPE) | (prom << NOTE_PROMOTED) | (suffix << NOTE_SUFFIX) | (disamb << NOTE_DISAMB)
+
+
+def decode_move_note(note: int, action_mode) -> dict:
+    """The fields of a move note.  `from_sq` / `to_sq` / `promote` come from the action index and the colour (`from_sq` is
+    None for a drop); `valid` is False for a note that names no move (an action the env refuses)."""
+    amode, note = _amode(action_mode), int(note) & 0xFFFFFFFF
+    action, side = note & ((1 << NOTE_ACTION_BITS) - 1), (note >> NOTE_COLOUR) & 1
+    d = {"action": action, "color": _COLOR_NAMES[side], "piece_type": (note >> NOTE_TYPE) & 15,
+         "promoted": bool((note >> NOTE_PROMOTED) & 1), "drop": bool((note >> NOTE_DROP) & 1),
+         "capture": bool((note >> NOTE_CAPTURE) & 1), "suffix": (note >> NOTE_SUFFIX) & 3,
+         "disambiguation": (note >> NOTE_DISAMB) & 3, "no_piece": bool((note >> NOTE_NO_PIECE) & 1),
+         "from_sq": None, "to_sq": None, "promote": False}
+    mv = _decode_action(action, side, amode)
+    d["valid"] = mv is not None and d["drop"] == (mv[3] >= 0) and (d["no_piece"] or 1 <= d["piece_type"] <= 8)
+    if mv is not None:
+        d["from_sq"], d["to_sq"], d["promote"] = (None if mv[3] >= 0 else mv[0]), mv[1], bool(mv[2])
+    return d
+
+
+def _hodges_of(d: dict) -> str:
+    if not d["valid"]:
+        return "?"
+    to = _square_hodges(d["to_sq"])
+    if d["drop"]:
+        return f"{_SFEN[d['piece_type']]}*{to}"
+    frm = d["from_sq"]
+    if d["no_piece"]:
+        return f"?{_square_hodges(frm)}-{to}"
+    prefix = ("+" if d["promoted"] else "") + _SFEN[d["piece_type"]]
+    dis = ("", str(9 - frm % 9), "abcdefghi"[frm // 9], _square_hodges(frm))[d["disambiguation"]]
+    return f"{prefix}{dis}{'x' if d['capture'] else '-'}{to}{('', '+', '=', '')[d['suffix']]}"
+
+
+def _usi_of(d: dict) -> str:
+    if not d["valid"]:
+        return "?"
+    if d["drop"]:
+        return f"{_SFEN[d['piece_type']]}*{_square_hodges(d['to_sq'])}"
+    return _square_hodges(d["from_sq"]) + _square_hodges(d["to_sq"]) + ("+" if d["promote"] else "")
+
+
+def hodges_notation(note: int, action_mode) -> str:
+    """spectator_data.rs:109-186 from a move note: "P-7f", "Bx3c=", "Nx7c+", "+R-5a", "G6-5h", "Gf-5g", "S4g-5f", "P*5e";
+    "?5e-5d" where no piece stood on the source square; "?" for a note that names no move."""
+    return _hodges_of(decode_move_note(note, action_mode))
+
+
+def move_usi(note: int, action_mode) -> str:
+    """spectator_data.rs:93-103 from a move note: "7g7f", "8h2b+", "P*5e"; "?" for a note that names no move."""
+    return _usi_of(decode_move_note(note, action_mode))
+
+
+def move_history_entries(notes, action_mode) -> list:
+    """The reference's `move_history` list (vec_env.rs:868-877) of one game from its notes."""
+    out = []
+    for n in notes:
+        d = decode_move_note(int(n), action_mode)
+        out.append({"action": d["action"], "notation": _hodges_of(d), "usi": _usi_of(d)})
+    return out
+
+
+def spectator_dicts(state_rows, histories=None, action_mode="spatial") -> list:
+    """`build_spectator_dict` (spectator_data.rs:190-233) over env state rows on the host: `state_rows` (n, >= 104) uint8
+    (board[81] hands[2][7] side in_check ... ply u32 at byte 100), `histories` one sequence of notes per row or None (empty
+    histories).  The games of a VecEnv restart when they end, so `is_over` is False and `result` "in_progress"."""
+    rows = np.ascontiguousarray(state_rows, dtype=np.uint8)
+    if rows.ndim != 2 or rows.shape[1] < 104:
+        raise ValueError(f"state_rows must have shape (n, >= 104), got {tuple(rows.shape)}")
+    out = []
+    for i, raw in enumerate(rows):
+        board = []
+        for sq in range(81):
+            p = int(raw[sq])
+            board.append(None if not p else {"type": _PIECE_NAMES[(p & 15) - 1], "color": _COLOR_NAMES[(p >> 4) & 1],
+                                             "promoted": bool(p & 0x20), "row": sq // 9, "col": sq % 9})
+        hands = {_COLOR_NAMES[c]: {_PIECE_NAMES[h]: int(raw[81 + c * 7 + h]) for h in range(7)} for c in (0, 1)}
+        side = int(raw[95]) & 1
+        out.append({"board": board, "hands": hands, "current_player": _COLOR_NAMES[side],
+                    "ply": int(raw[100:104].view(np.uint32)[0]), "is_over": False, "result": "in_progress",
+                    "sfen": format_sfen(raw[:81], raw[81:95], side), "in_check": bool(raw[96]),
+                    "move_history": [] if histories is None else move_history_entries(histories[i], action_mode)})
+    return out
+
+
 @dataclass
 class StepMetadata:          # step_result.rs:31-47
     captured_piece: Any
@@ -325,7 +514,7 @@ class ResetResult:           # step_result.rs:86-97
 class VecEnv:
     def __init__(self, num_envs: int = 512, max_ply: int = 500, observation_mode: str = "default",
                  action_mode: str = "default", *, device: Optional[torch.device] = None, output: str = "numpy",
-                 check_actions: bool = True, start_pool_capacity: int = 0):
+                 check_actions: bool = True, start_pool_capacity: int = 0, move_history: bool = False):
         if observation_mode not in ("default", "katago"):
             raise ValueError(f"Unknown observation_mode '{observation_mode}'. Valid: 'default', 'katago'")
         if action_mode not in ("default", "spatial"):
@@ -375,6 +564,12 @@ class VecEnv:
         if self._pool_capacity:
             self._pool = z(self._pool_capacity, POOL_ROW_BYTES, dtype=torch.uint8)
             self._pool_hdr = z(4, dtype=torch.int32)
+        # move histories (move_history=True): a note per move of the game in progress (csrc/spectator.hip), allocated once
+        self._hist = self._hist_count = self._hist_pending = None
+        if move_history:
+            self._hist = z(n, hist, dtype=torch.int32)
+            self._hist_count = z(n, dtype=torch.int32)
+            self._hist_pending = z(n, dtype=torch.int32)
         # as in the reference's constructor (vec_env.rs:574-612): the games stand at the start position, the mask buffer
         # is still all-false -- a step() before reset() is refused ("action index ... is not legal")
         self.reset()
@@ -390,6 +585,7 @@ class VecEnv:
             self._cur = 0
             self._err.zero_()                                 # (a refusal nobody asked about ends with the games it belonged to)
             self._call_reset(self._obs[0], self._mask[0], self._bits[0], self._players[0], 0)
+            self._clear_histories()
         return ResetResult(self._out(self._obs[0]), self._out(self._mask[0]),
                            self._bits[0] if self._output == "torch" else None)
 
@@ -420,10 +616,16 @@ class VecEnv:
                     self._mask[prev], self._bits[prev], self._err, self._obs[nxt], self._mask[nxt], self._bits[nxt],
                     self._rewards[nxt], self._terminated[nxt], self._truncated[nxt], self._terminal_obs, self._players[nxt],
                     self._captured[nxt], self._reason[nxt], self._ply[nxt], self._material[nxt], self._stats)
+            if self._hist is not None:                        # the move's note, from the position and the mask before it
+                _lib.call("ka_spectator_note", self._state, self._state.shape[1], n, self._bits[prev], act, self._amode,
+                          self._hist_pending, _lib.stream_ptr())
             if self._pool is None:
                 _lib.call("ka_shogi_env_step", *args, _lib.stream_ptr())
             else:
                 _lib.call("ka_shogi_env_step_pool", *args, self._pool, self._pool_hdr, _lib.stream_ptr())
+            if self._hist is not None:                        # appended unless the step was refused; finished games cleared
+                _lib.call("ka_spectator_commit", self._err, self._terminated[nxt], self._truncated[nxt], n,
+                          self._hist_pending, self._hist, self._hist.shape[1], self._hist_count, _lib.stream_ptr())
         self._cur = nxt                                       # (a refused step has re-written the unchanged positions there)
         if self._check:
             self.raise_if_refused(act)
@@ -454,6 +656,10 @@ class VecEnv:
 
     def _out(self, t: torch.Tensor):
         return t if self._output == "torch" else t.cpu().numpy()
+
+    def _clear_histories(self) -> None:
+        if self._hist is not None:
+            _lib.call("ka_spectator_begin", self._hist_count, self._n, _lib.stream_ptr())
 
     def _call_reset(self, obs, mask, bits, players, refresh: int) -> None:
         args = (self._state, self._keys, self._checks, self._n, self._max_ply, self._omode, self._amode, obs, mask, bits,
@@ -544,6 +750,7 @@ class VecEnv:
         self._state.copy_(torch.from_numpy(raw))
         with torch.cuda.device(self.device):
             self._call_reset(self._obs[self._cur], self._mask[self._cur], self._bits[self._cur], self._players[self._cur], 1)
+            self._clear_histories()
 
     # ------------------------------------------------------------------ start positions
     @property
@@ -650,5 +857,37 @@ class VecEnv:
     def get_sfens(self) -> List[str]:
         return [self.get_sfen(i) for i in range(self._n)]
 
-    def get_spectator_data(self):
-        raise NotImplementedError("spectator dictionaries belong to the reference's web UI (out of scope, DESIGN.md §7)")
+    @property
+    def move_history(self) -> bool:
+        """Whether the env keeps the move notes of the games in progress (`VecEnv(..., move_history=True)`)."""
+        return self._hist is not None
+
+    def move_notes(self, game_ids=None) -> List[np.ndarray]:
+        """The notes (uint32, `decode_move_note`) of the moves of the games in progress, one array per env (or per
+        requested id), read in one copy; empty arrays without `move_history=True`."""
+        ids = self._game_ids(game_ids)
+        if self._hist is None:
+            return [np.zeros(0, np.uint32) for _ in ids]
+        both = torch.cat([self._hist_count[:, None], self._hist], dim=1)
+        if game_ids is not None:
+            both = both[torch.as_tensor(ids, dtype=torch.int64, device=self.device)]
+        both = both.cpu().numpy()
+        return [both[j, 1:1 + max(0, min(int(both[j, 0]), both.shape[1] - 1))].copy().view(np.uint32) for j in range(len(ids))]
+
+    def _game_ids(self, game_ids) -> List[int]:
+        if game_ids is None:
+            return list(range(self._n))
+        ids = [int(i) for i in game_ids]
+        for i in ids:
+            if not 0 <= i < self._n:
+                raise IndexError(f"game_id {i} out of range for {self._n} environments")
+        return ids
+
+    def get_spectator_data(self, game_ids=None) -> List[dict]:
+        """vec_env.rs:862-882 / spectator_data.rs:190-233: one dict per env (or per requested id) with the keys `board`,
+        `hands`, `current_player`, `ply`, `is_over`, `result`, `sfen`, `in_check`, `move_history`.  The state rows are read
+        in one copy and, with `move_history=True`, the notes in one more; without it `move_history` is []."""
+        ids = self._game_ids(game_ids)
+        rows = self._state if game_ids is None else self._state[torch.as_tensor(ids, dtype=torch.int64, device=self.device)]
+        notes = self.move_notes(game_ids) if self._hist is not None else None
+        return spectator_dicts(rows.cpu().numpy(), notes, self._amode)

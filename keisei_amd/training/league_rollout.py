@@ -179,13 +179,14 @@ class LeagueRollout:
     ``carried`` where its side or its opponent changed in the middle of it (the epoch's side re-draw) and where it spans a
     ``set_opponents``.
     ``live_games()`` between two ``collect`` calls gives the games still in progress.  Without ``game_log`` the ply is
-    launch for launch what it was."""
+    launch for launch what it was.  ``move_history=True`` has the env keep the move notes of the games in progress (two
+    more launches inside ``env.step``); ``spectator_data()`` between two ``collect`` calls is the dashboard feed."""
 
     def __init__(self, learner, opponents: Sequence, opponent_ids: Sequence[int], *, num_envs: int = 512, max_ply: int = 500,
                  value_adapter=None, score_norm: float = SCORE_NORMALIZATION, color_randomization: bool = False,
                  opponent_weights: Optional[Sequence[float]] = None, sync_every: int = 32, graph: bool = True,
                  seed: Optional[int] = None, record: bool = False, start_pool_capacity: int = 0, game_log: int = 0,
-                 learner_id: int = -1) -> None:
+                 learner_id: int = -1, move_history: bool = False) -> None:
         opponents, opponent_ids = list(opponents), [int(i) for i in opponent_ids]
         _check_args(len(opponents), opponent_ids, int(num_envs), int(max_ply), int(sync_every), bool(graph), bool(record),
                     float(score_norm), value_adapter)
@@ -209,7 +210,7 @@ class LeagueRollout:
         with torch.cuda.device(dev):
             z = lambda *s, dtype=torch.int32: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731
             self.env = VecEnv(N, self.max_ply, "katago", "spatial", device=dev, output="torch", check_actions=False,
-                              start_pool_capacity=int(start_pool_capacity))
+                              start_pool_capacity=int(start_pool_capacity), move_history=bool(move_history))
             self._actions, self._logp, self._nlegal = z(N, dtype=torch.int64), z(N, dtype=torch.float32), z(N)
             self._values = z(N, dtype=torch.float32)
             self._model_of, self._learner_of = z(N), z(N)
@@ -509,6 +510,12 @@ class LeagueRollout:
         with torch.cuda.device(self.device):
             return self.game_log.live(envs, side=self._side, opp=self._opp, ids=self._ids, opponents=len(self.opponent_ids),
                                       ply_counter=self._state.data_ptr() + 4 * _PLY)
+
+    def spectator_data(self, envs: Optional[Sequence[int]] = None) -> List[dict]:
+        """``VecEnv.get_spectator_data`` of every env (or ``envs``) between two ``collect`` calls; ``move_history`` is []
+        unless the rollout was built with ``move_history=True``."""
+        with torch.cuda.device(self.device):
+            return self.env.get_spectator_data(envs)
 
     def bootstrap_values(self) -> torch.Tensor:
         """V(observation now) by the learner, in the learner's frame (katago_loop.py:1565-1580): ``update``'s next_values."""

@@ -256,12 +256,14 @@ class MatchArena:
     the referee): every result then carries its pairing's finished games, move by move, in ``recorded_games`` -- one per
     game the referee tallied, as long as ``RoundStats.games_dropped`` is 0.  A game is ``carried`` when the pairing
     inherited it from the slot's previous pairing or the slot sat idle during it (there is no per-slot reset).
-    ``collect``, ``features`` and ``game_log`` are independent."""
+    ``collect``, ``features`` and ``game_log`` are independent.  ``move_history=True`` has the env keep the move notes of
+    the games in progress (two more launches inside ``env.step``); ``spectator_data()`` between two rounds is the
+    dashboard feed."""
 
     def __init__(self, group: SEResNetGroup, num_envs: int = 512, envs_per_match: int = 64, max_ply: int = 512, *,
                  sync_every: int = 32, graph: bool = True, seed: Optional[int] = None, record: bool = False,
                  collect: bool = False, features: bool = False, start_pool_capacity: int = 0,
-                 game_log: int = 0) -> None:
+                 game_log: int = 0, move_history: bool = False) -> None:
         if game_log < 0:
             raise ValueError(f"game_log must not be negative, got {game_log}")
         if len(group) == 0:
@@ -293,7 +295,7 @@ class MatchArena:
         N, dev = self.num_envs, self.device
         with torch.cuda.device(dev):
             self.env = VecEnv(N, self.max_ply, "katago", "spatial", device=dev, output="torch", check_actions=False,
-                              start_pool_capacity=int(start_pool_capacity))
+                              start_pool_capacity=int(start_pool_capacity), move_history=bool(move_history))
             self._ws = group._tables.workspace(N)
             self._state = torch.zeros(_lib.query("ka_arena_state_words", self.num_slots), dtype=torch.int32, device=dev)
             self._state_host = torch.zeros(self._state.shape, dtype=torch.int32).pin_memory()
@@ -489,6 +491,12 @@ class MatchArena:
         with torch.cuda.device(self.device):
             return self.game_log.live(envs, pairs=sp + 4 * _HDR, pair_stride=_SLOT, envs_per_pair=self.envs_per_match,
                                       ply_counter=sp + 8)
+
+    def spectator_data(self, envs: Optional[Sequence[int]] = None) -> List[dict]:
+        """``VecEnv.get_spectator_data`` of every env (or ``envs``) between two rounds; ``move_history`` is [] unless the
+        arena was built with ``move_history=True``."""
+        with torch.cuda.device(self.device):
+            return self.env.get_spectator_data(envs)
 
     def run_round(self, pairings: Sequence[Tuple[int, int]], games_per_match: int = 64, *, max_ply: Optional[int] = None,
                   trainable: Union[None, Callable[[int, int], int], Mapping[int, int]] = None,

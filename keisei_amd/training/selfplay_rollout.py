@@ -112,12 +112,14 @@ class SelfPlayRollout:
     start positions of that size: ``roll.env.set_start_positions(...)`` / ``set_start_sfens(...)`` between ``collect`` calls make later
     games start from them (no re-capture; see ``VecEnv``).  ``game_log=K > 0`` adds a device-resident ``GameLog`` of K
     records to the ply (one launch, ``ka_gamelog_step``, between the env step and ``ka_selfplay_step``): ``collect``
-    drains it at every sync point onto ``SelfPlayStats.games``.  Without it the ply is launch for launch what it was."""
+    drains it at every sync point onto ``SelfPlayStats.games``.  Without it the ply is launch for launch what it was.
+    ``move_history=True`` has the env keep the move notes of the games in progress (two more launches inside ``env.step``,
+    see ``VecEnv``); ``spectator_data()`` between two ``collect`` calls is the dashboard feed either way."""
 
     def __init__(self, learner, *, num_envs: int = 512, max_ply: int = 500, value_adapter=None,
                  score_norm: float = SCORE_NORMALIZATION, sync_every: int = 32, graph: bool = True,
                  seed: Optional[int] = None, record: bool = False, start_pool_capacity: int = 0,
-                 game_log: int = 0) -> None:
+                 game_log: int = 0, move_history: bool = False) -> None:
         _check_args(int(num_envs), int(max_ply), int(sync_every), bool(graph), bool(record), float(score_norm), value_adapter)
         if start_pool_capacity < 0:
             raise ValueError(f"start_pool_capacity must not be negative, got {start_pool_capacity}")
@@ -136,7 +138,7 @@ class SelfPlayRollout:
         with torch.cuda.device(dev):
             z = lambda *s, dtype=torch.int32: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731
             self.env = VecEnv(N, self.max_ply, "katago", "spatial", device=dev, output="torch", check_actions=False,
-                              start_pool_capacity=int(start_pool_capacity))
+                              start_pool_capacity=int(start_pool_capacity), move_history=bool(move_history))
             self._actions, self._logp, self._nlegal = z(N, dtype=torch.int64), z(N, dtype=torch.float32), z(N)
             self._values = z(N, dtype=torch.float32)
             self._model_of = z(N)                                    # every row on model 0
@@ -351,6 +353,18 @@ class SelfPlayRollout:
             raise ValueError("live_games() needs a rollout built with game_log > 0")
         with torch.cuda.device(self.device):
             return self.game_log.live(envs, ply_counter=self._state.data_ptr() + 4 * _PLIES)
+
+    def spectator_data(self, envs: Optional[Sequence[int]] = None) -> List[dict]:
+        """``VecEnv.get_spectator_data`` of every env (or ``envs``) between two ``collect`` calls, each dict with
+        ``value_estimate``: the learner's value at the env's last ply (the reference's snapshot row takes it from
+        ``latest_values``, katago_loop.py:1938-1942).  ``move_history`` is [] unless built with ``move_history=True``."""
+        with torch.cuda.device(self.device):
+            data = self.env.get_spectator_data(envs)
+            values = self._values.cpu().numpy()
+        ids = range(self.num_envs) if envs is None else [int(e) for e in envs]
+        for d, e in zip(data, ids):
+            d["value_estimate"] = float(values[e])
+        return data
 
     def bootstrap_values(self) -> torch.Tensor:
         """-V(observation now) by the learner (katago_loop.py:1565-1572, :1589): ``update``'s next_values, in the frame of

@@ -1,21 +1,22 @@
 """Which of the reference's own tests for SURVEY 8 f3 are restated in tests/?  (build container only: reads /root/reference.)
 For every #[test] / def test_ of the reference's rule, env, observation and mapper modules: is there a citation of a line inside
-that test's span in tests/test_shogi*.py, tests/test_hip_shogi_env.py or the oracle?  `explicit` = written as file.rs:LINE;
+that test's span in tests/test_shogi*.py, tests/test_hip_shogi_env.py, the spectator tests or the oracle?  `explicit` = written as file.rs:LINE;
 `any` = additionally the abbreviated form (":LINE-LINE" behind a file named earlier in the same docstring).  Tests that exercise
 data structures this build does not have are listed in NOT_APPLICABLE with the reason.   python tools/ref_test_coverage.py"""
 import glob, os, re, sys
 REF = "/root/reference/shogi-engine/crates/"
 FILES = ["shogi-core/src/rules.rs", "shogi-core/src/game.rs", "shogi-core/src/movegen.rs", "shogi-core/src/attack.rs", "shogi-gym/src/vec_env.rs",
          "shogi-gym/src/katago_observation.rs", "shogi-gym/src/observation.rs", "shogi-gym/src/spatial_action_mapper.rs",
-         "shogi-gym/src/action_mapper.rs", "shogi-gym/src/step_result.rs", "shogi-gym/tests/test_vec_env.py",
+         "shogi-gym/src/action_mapper.rs", "shogi-gym/src/step_result.rs", "shogi-gym/src/spectator_data.rs",
+         "shogi-gym/tests/test_vec_env.py",
          "shogi-gym/tests/test_observation.py", "shogi-gym/tests/test_action_mapper.py"]
 NOT_APPLICABLE = {
     "incremental attack map / ray updates / would_wrap_file helper (the oracle and the device kernel recompute attacks per query)":
         r"attack\.rs::test_(incremental|update_rays|would_wrap)",
     "make / unmake and incremental hash / pawn-column state (nothing is unmade here: legality is decided on an overlay)":
         r"game\.rs::test_(make_unmake|hash_matches|attack_map_matches|unmake|deep_make_unmake|hot_path|multi_ply_hash|pawn_columns_after|compute_pawn_columns|full_game_make_unmake|from_position)",
-    "SFEN parsing, spectator dictionaries (web UI feeds: DESIGN section 7)":
-        r"(game\.rs::test_from_sfen|test_vec_env\.py::test_get_spectator|test_vec_env\.py::test_get_sfen_matches_spectator)",
+    "SFEN parsing of a GameState (the env parses SFEN on the host: DESIGN section 7)":
+        r"(game\.rs::test_from_sfen)",
     "Rust panic isolation / caller-provided buffer length checks (no such API surface: the env owns its buffers)":
         r"(vec_env\.rs::test_(apply_moves|katago_spatial_apply_moves)|katago_observation\.rs::test_(wrong_buffer_length|katago_observation_wrong_buffer_length|from_position_inserts))",
 }
@@ -23,7 +24,7 @@ def main():
     if not os.path.isdir(REF):
         sys.exit("needs /root/reference (build container only)")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    ours = "".join(open(f).read() for f in sorted(glob.glob(root + "/tests/test_shogi*.py")) + [root + "/tests/test_hip_shogi_env.py", root + "/oracle/shogi.py", root + "/oracle/shogi_oracle.c"])
+    ours = "".join(open(f).read() for f in sorted(glob.glob(root + "/tests/test_shogi*.py")) + [root + "/tests/test_hip_shogi_env.py", root + "/tests/test_spectator_cpu.py", root + "/tests/test_hip_spectator.py", root + "/oracle/shogi.py", root + "/oracle/shogi_oracle.c"])
     explicit, loose = {}, set()
     for m in re.finditer(r"([a-z_]+\.(?:rs|py)):(\d+)(?:-(\d+))?", ours):
         explicit.setdefault(m.group(1), []).append((int(m.group(2)), int(m.group(3) or m.group(2))))

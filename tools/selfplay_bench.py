@@ -10,7 +10,12 @@ plies/s (epoch plies over wall time), rows/s, ms per ply and host syncs (SelfPla
 loop's figure is a tally kept by hand where it is known to read from the device).  Clocks are not pinned.  One JSON line
 per workload.
 
+--move-history runs every device config a second time with SelfPlayRollout(move_history=True) (the env then keeps the move
+notes of the games in progress: two more launches per ply) under the key suffix "_hist", and times one spectator_data()
+call over all envs behind each device config's last epoch ("spectator_data_ms").
+
     python tools/selfplay_bench.py [--workload a|b|all] [--configs g32,e2,host] [--steps N] [--max-ply 512] [--repeat 2]
+                                   [--move-history]
 """
 from __future__ import annotations
 
@@ -104,9 +109,9 @@ def host_loop_epoch(ppo, env, buffer, steps, adapter, score_norm=76.0):
             "next_values_finite": bool(torch.isfinite(next_values).all())}
 
 
-def device_epochs(model, N, max_ply, graph, sync_every, steps, adapter, repeat):
+def device_epochs(model, N, max_ply, graph, sync_every, steps, adapter, repeat, move_history=False, feed=False):
     roll = SelfPlayRollout(model, num_envs=N, max_ply=max_ply, value_adapter=adapter, sync_every=sync_every, graph=graph,
-                           seed=1234)
+                           seed=1234, move_history=move_history)
     buf = KataGoRolloutBuffer(N, OBS, ACTION_SPACE, device="cuda")
     roll.collect(buf, steps)                                     # warm-up: graph capture, buffer growth
     roll.bootstrap_values()
@@ -120,9 +125,15 @@ def device_epochs(model, N, max_ply, graph, sync_every, steps, adapter, repeat):
         torch.cuda.synchronize()
         dt = time.monotonic() - t0
         runs.append(round(steps / dt, 1))
-    return {"plies_per_s_runs": runs, "epoch_s": round(dt, 3), "plies_per_s": round(steps / dt, 1),
-            "ms_per_ply": round(1e3 * dt / steps, 3), "rows": st.rows, "rows_per_s": round(st.rows / dt, 1),
-            "host_syncs": st.host_syncs, "games": st.terminated + st.truncated, "truncation_overrides": st.truncation_overrides}
+    out = {"plies_per_s_runs": runs, "epoch_s": round(dt, 3), "plies_per_s": round(steps / dt, 1),
+           "ms_per_ply": round(1e3 * dt / steps, 3), "rows": st.rows, "rows_per_s": round(st.rows / dt, 1),
+           "host_syncs": st.host_syncs, "games": st.terminated + st.truncated, "truncation_overrides": st.truncation_overrides}
+    if feed:
+        t0 = time.monotonic()
+        data = roll.spectator_data()
+        out["spectator_data_ms"] = round(1e3 * (time.monotonic() - t0), 2)
+        out["history_moves"] = sum(len(d["move_history"]) for d in data)
+    return out
 
 
 def main() -> None:
@@ -132,6 +143,7 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=None, help="plies per epoch (default: the workload's)")
     ap.add_argument("--max-ply", type=int, default=512)
     ap.add_argument("--repeat", type=int, default=2)
+    ap.add_argument("--move-history", action="store_true", help="also run the device configs with move_history=True")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "selfplay_bench needs a GPU"
@@ -158,8 +170,12 @@ def main() -> None:
                 row["host_loop"] = dict(res, plies_per_s_runs=runs)
             else:
                 graph, se = CONFIGS[c]
-                row[f"selfplay_{'graph' if graph else 'eager'}_sync{se}"] = device_epochs(model.eval(), N, args.max_ply, graph, se,
-                                                                                        steps, adapter, args.repeat)
+                key = f"selfplay_{'graph' if graph else 'eager'}_sync{se}"
+                row[key] = device_epochs(model.eval(), N, args.max_ply, graph, se, steps, adapter, args.repeat,
+                                         feed=args.move_history)
+                if args.move_history:
+                    row[key + "_hist"] = device_epochs(_model(shape).eval(), N, args.max_ply, graph, se, steps, adapter,
+                                                       args.repeat, move_history=True, feed=True)
             torch.cuda.synchronize()
         print(json.dumps(row), flush=True)
         lines.append(row)
