@@ -731,6 +731,38 @@ int ka_spectator_note(const void* env_state, int state_bytes, int envs, const vo
 int ka_spectator_commit(const void* err, const void* terminated, const void* truncated, int envs, const void* pending,
                         void* hist, int row_len, int* count, void* stream);
 
+/* ---- policy insight (csrc/insight.hip; what the reference's showcase shows next to a board, showcase/runner.py:151-173,
+ * showcase/heatmap.py:40-49, showcase/inference.py:95, plus entropy, rank and the number of legal moves).  One launch
+ * after the sampler and before the env step, one workgroup per row, the spatial action space only (A = 81 * 139, action =
+ * from-square * 139 + slot in the mover's perspective).
+ * Inputs per row b: logits (B, A) fp32 or bf16 (logits_bf16 != 0); legal: packed rows, legal_words == ka_mask_words(A);
+ *   actions (B) int64: the chosen action; vlogits (B, 3) fp32 or NULL; players (B) uint8: the mover's colour, or NULL;
+ *   model_of (B) int32 with K as in ka_policy_sample_play, or NULL (every row seated); temperature > 0; top_k in 1..8.
+ * p = softmax(logits / temperature) over the legal actions (the row maximum is subtracted first).  One record of
+ * ka_policy_insight_words(0, top_k) = 8 + 2 top_k 32-bit words per row; ka_policy_insight_words(which, top_k) gives the
+ * word offsets: 1 flags (bit 0 valid, bit 1 the mover's colour, bit 2 the chosen action is legal), 2 chosen action (int32;
+ *   -1 / A for an action below / above the action space), 3 n_legal (int32), 4 chosen_rank (int32: the legal actions whose
+ *   raw logit is strictly greater than the chosen action's; -1 where the chosen action is not legal), 5 chosen_probability
+ *   (fp32: p[action], 0 where it is not legal), 6 entropy (fp32: -sum p ln p in nats, 0 ln 0 = 0), 7 win_probability (fp32:
+ *   softmax(vlogits)[0], 0 without vlogits), 8 the top_k candidate actions (int32), 9 their probabilities (fp32); which 10 =
+ *   floats of a heat row (132); -1 for any other which or a top_k outside 1..8.  Word 7 of the record is reserved (0).
+ *   Candidates: the legal actions ordered by raw logit, descending, equal logits by lower action; unused entries are
+ *   action -1, probability 0.  A legal logit that is -inf or NaN is never a candidate.
+ * heat (B, 132) fp32, the chosen move's family (the legal moves with its USI prefix): for a board move (slot < 132)
+ *   heat[s] = p[from * 139 + s]; for a drop (slot 132 + d) heat[sq] = p[sq * 139 + 132 + d], sq in 0..80, the rest 0;
+ *   illegal members 0; all 0 where the chosen action is not legal.
+ * A row whose model_of lies outside [0, K), or without a legal action, is invalid: record and heat row all zeros.
+ * flags[0] |= NaN in a legal logit of a valid row.
+ * Written: last (B, words): the row's record, every launch; heat; and, with hist != NULL, hist (B, row_len, words) at slot
+ *   count[b] (int32, the env's spectator move count read BEFORE the env step) when 0 <= count[b] < row_len -- nothing
+ *   otherwise, never past the row.  No commit launch: a refused step leaves the count alone (the slot is overwritten by
+ *   the next ply), a finished game sets it to 0 in ka_spectator_commit; entries [0, count) are the moves of the game in
+ *   progress.  Kernel launch only, caller-owned buffers, no workgroup waits for another. */
+int ka_policy_insight_words(int which, int top_k);
+int ka_policy_insight(const void* logits, int logits_bf16, const void* legal, int legal_words, const long long* actions,
+                      const float* vlogits, const void* players, const int* model_of, int K, float temperature, int top_k,
+                      void* last, float* heat, void* hist, int row_len, const int* count, int* flags, int B, int A, void* stream);
+
 /* ---- SL shard preparation (csrc/sl_prepare.hip; the replay keisei/sl/prepare.py:151-161 leaves out).  A batch of E game
  * records, game g in env g, stepped in lockstep from ka_shogi_env_reset.  One ply = ka_sl_replay_plan, ka_shogi_env_step
  * (unchanged), ka_sl_replay_record on one stream.

@@ -5,4 +5,5 @@ from .game_log import GameLog, RecordedGame, game_log_host, write_sfen_games  # 
 from .game_feature_tracker import GameFeatureAccumulator, GameFeatureRow, GameFeatureTracker, classify_action  # noqa: F401
 from .league_rollout import LeagueRollout, LeagueRolloutStats  # noqa: F401
 from .match_arena import MatchArena, MatchResult, RoundStats  # noqa: F401
+from .policy_insight import InsightRecorder, PolicyInsight, action_usi, insight_dict, policy_insight  # noqa: F401
 from .selfplay_rollout import SelfPlayRollout, SelfPlayStats  # noqa: F401

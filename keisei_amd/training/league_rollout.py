@@ -47,6 +47,7 @@ from .katago_loop import (_ZERO_LEGAL, PendingTransitions, _compute_value_cats, 
                           to_learner_perspective)
 from .katago_ppo import SCORE_NORMALIZATION, KataGoRolloutBuffer, _check_step_inputs
 from .model_group import SEResNetGroup
+from .policy_insight import InsightRecorder
 from .value_adapter import MultiHeadValueAdapter
 
 __all__ = ["LeagueRollout", "LeagueRolloutStats", "league_draw", "draw_opponents", "draw_sides", "cum_thresholds"]
@@ -180,13 +181,18 @@ class LeagueRollout:
     ``set_opponents``.
     ``live_games()`` between two ``collect`` calls gives the games still in progress.  Without ``game_log`` the ply is
     launch for launch what it was.  ``move_history=True`` has the env keep the move notes of the games in progress (two
-    more launches inside ``env.step``); ``spectator_data()`` between two ``collect`` calls is the dashboard feed."""
+    more launches inside ``env.step``); ``spectator_data()`` between two ``collect`` calls is the dashboard feed.
+    ``insight=top_k > 0`` adds the policy insight to the ply (one launch, ``ka_policy_insight``, between the sampler and the
+    env step; ``policy_insight.py``), for the learner's and the opponents' moves alike: every ``spectator_data()`` dict gains
+    ``insight``, the figures of the env's last move at ``insight_temperature``, and with ``move_history=True`` every history
+    entry gains its move's probability, rank, entropy, win probability and top candidates.  With 0 nothing changes."""
 
     def __init__(self, learner, opponents: Sequence, opponent_ids: Sequence[int], *, num_envs: int = 512, max_ply: int = 500,
                  value_adapter=None, score_norm: float = SCORE_NORMALIZATION, color_randomization: bool = False,
                  opponent_weights: Optional[Sequence[float]] = None, sync_every: int = 32, graph: bool = True,
                  seed: Optional[int] = None, record: bool = False, start_pool_capacity: int = 0, game_log: int = 0,
-                 learner_id: int = -1, move_history: bool = False) -> None:
+                 learner_id: int = -1, move_history: bool = False, insight: int = 0,
+                 insight_temperature: float = 1.0) -> None:
         opponents, opponent_ids = list(opponents), [int(i) for i in opponent_ids]
         _check_args(len(opponents), opponent_ids, int(num_envs), int(max_ply), int(sync_every), bool(graph), bool(record),
                     float(score_norm), value_adapter)
@@ -223,6 +229,7 @@ class LeagueRollout:
             self._desc_host = torch.zeros(q(1), dtype=torch.int64).pin_memory()
             self._side_host = torch.zeros(N, dtype=torch.uint8).pin_memory()
             self.game_log: Optional[GameLog] = GameLog(self.env, capacity=int(game_log), envs_per_slot=N) if game_log else None
+            self.insight: Optional[InsightRecorder] = InsightRecorder(self.env, insight, insight_temperature) if insight else None
             self._every_env = z(1, 4)                             # a seat job naming the one slot of all envs
             self._ids: Optional[torch.Tensor] = None
         self._graphs: Dict[int, torch.cuda.CUDAGraph] = {}
@@ -313,6 +320,8 @@ class LeagueRollout:
             self.env.reset()
             if self.game_log is not None:
                 self.game_log.begin()
+            if self.insight is not None:
+                self.insight.clear()
             self._seat()
         self._collects = 0
         self.record = []
@@ -337,6 +346,9 @@ class LeagueRollout:
         sp = self._state.data_ptr()
         _lib.call("ka_policy_sample_play", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of, K + 1,
                   self._actions, self._logp, self._nlegal, sp + 4 * _SAMP, N, ACTION_SPACE, st)
+        if self.insight is not None:                      # while the logits exist, before the step moves the history count
+            self.insight.step(logits, cur.legal_mask_bits, self._actions, value, env._players[prev], self._model_of, K + 1,
+                              sp + 4 * _SAMP, st)
         r = env.step(self._actions)
         if self.game_log is not None:                     # before ka_league_step re-draws side and opp of finished envs
             self.game_log.step_env(self._actions, r.rewards, r.terminated, r.truncated, env._players[prev],
@@ -513,9 +525,11 @@ class LeagueRollout:
 
     def spectator_data(self, envs: Optional[Sequence[int]] = None) -> List[dict]:
         """``VecEnv.get_spectator_data`` of every env (or ``envs``) between two ``collect`` calls; ``move_history`` is []
-        unless the rollout was built with ``move_history=True``."""
+        unless the rollout was built with ``move_history=True``; ``insight`` (built with ``insight > 0``) is the
+        ``insight_dict`` of the env's last move, None before its first move after ``reset()``."""
         with torch.cuda.device(self.device):
-            return self.env.get_spectator_data(envs)
+            data = self.env.get_spectator_data(envs)
+            return data if self.insight is None else self.insight.annotate(data, envs)
 
     def bootstrap_values(self) -> torch.Tensor:
         """V(observation now) by the learner, in the learner's frame (katago_loop.py:1565-1580): ``update``'s next_values."""

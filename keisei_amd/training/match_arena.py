@@ -43,6 +43,7 @@ from .dynamic_trainer import MatchRollout
 from .game_feature_tracker import GameFeatureTracker
 from .game_log import GameLog, RecordedGame
 from .model_group import SEResNetGroup
+from .policy_insight import InsightRecorder
 
 _HDR, _SLOT = 8, 8                      # int32 words of the state header and of one slot (csrc/arena.hip)
 _CUR = 4                                # int32 words of one slot's collection cursors: rows, rows of this ply, dropped, -
@@ -258,12 +259,16 @@ class MatchArena:
     inherited it from the slot's previous pairing or the slot sat idle during it (there is no per-slot reset).
     ``collect``, ``features`` and ``game_log`` are independent.  ``move_history=True`` has the env keep the move notes of
     the games in progress (two more launches inside ``env.step``); ``spectator_data()`` between two rounds is the
-    dashboard feed."""
+    dashboard feed.  ``insight=top_k > 0`` adds the policy insight to the ply (one launch, ``ka_policy_insight``, between
+    the sampler and the env step; ``policy_insight.py``): every ``spectator_data()`` dict gains ``insight``, the figures of
+    the env's last move at ``insight_temperature`` (None for the envs of an idle slot), and with ``move_history=True`` every
+    history entry gains its move's probability, rank, entropy, win probability and top candidates.  With 0 nothing changes."""
 
     def __init__(self, group: SEResNetGroup, num_envs: int = 512, envs_per_match: int = 64, max_ply: int = 512, *,
                  sync_every: int = 32, graph: bool = True, seed: Optional[int] = None, record: bool = False,
                  collect: bool = False, features: bool = False, start_pool_capacity: int = 0,
-                 game_log: int = 0, move_history: bool = False) -> None:
+                 game_log: int = 0, move_history: bool = False, insight: int = 0,
+                 insight_temperature: float = 1.0) -> None:
         if game_log < 0:
             raise ValueError(f"game_log must not be negative, got {game_log}")
         if len(group) == 0:
@@ -340,6 +345,7 @@ class MatchArena:
             self.game_log: Optional[GameLog] = None
             if game_log:
                 self.game_log = GameLog(self.env, capacity=int(game_log), envs_per_slot=self.envs_per_match)
+            self.insight: Optional[InsightRecorder] = InsightRecorder(self.env, insight, insight_temperature) if insight else None
         self._graph: Optional[torch.cuda.CUDAGraph] = None
 
     # ------------------------------------------------------------------ one ply
@@ -348,10 +354,13 @@ class MatchArena:
         env, N = self.env, self.num_envs
         st = _lib.stream_ptr(self.device)
         cur, prev = env.current(), env._cur
-        logits, _, _ = self.group._tables.forward(cur.observations, self._model_of, ws=self._ws)
+        logits, value, _ = self.group._tables.forward(cur.observations, self._model_of, ws=self._ws)
         sp = self._state.data_ptr()
         _lib.call("ka_policy_sample_play", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of,
                   len(self.group), self._actions, self._logp, self._nlegal, sp + 16, N, ACTION_SPACE, st)
+        if self.insight is not None:                      # while the logits exist, before the step moves the history count
+            self.insight.step(logits, cur.legal_mask_bits, self._actions, value, env._players[prev], self._model_of,
+                              len(self.group), sp + 16, st)
         if self.collect:
             sto = self._store
             _lib.call("ka_arena_record_pre", self._state, self._bits, self.num_slots, self.envs_per_match, cur.observations,
@@ -494,9 +503,11 @@ class MatchArena:
 
     def spectator_data(self, envs: Optional[Sequence[int]] = None) -> List[dict]:
         """``VecEnv.get_spectator_data`` of every env (or ``envs``) between two rounds; ``move_history`` is [] unless the
-        arena was built with ``move_history=True``."""
+        arena was built with ``move_history=True``; ``insight`` (built with ``insight > 0``) is the ``insight_dict`` of
+        the env's last move: None before its first move of the round and for the envs of an idle slot."""
         with torch.cuda.device(self.device):
-            return self.env.get_spectator_data(envs)
+            data = self.env.get_spectator_data(envs)
+            return data if self.insight is None else self.insight.annotate(data, envs)
 
     def run_round(self, pairings: Sequence[Tuple[int, int]], games_per_match: int = 64, *, max_ply: Optional[int] = None,
                   trainable: Union[None, Callable[[int, int], int], Mapping[int, int]] = None,
@@ -547,6 +558,8 @@ class MatchArena:
         self.env.reset()
         if self.game_log is not None:
             self.game_log.begin()
+        if self.insight is not None:
+            self.insight.clear()
         logged: Dict[int, List[RecordedGame]] = {}
         self.record = []
         chunks: Dict[int, list] = {}

@@ -42,6 +42,7 @@ from .game_log import GameLog, RecordedGame
 from .katago_loop import _compute_value_cats
 from .katago_ppo import SCORE_NORMALIZATION, KataGoRolloutBuffer, _check_step_inputs
 from .model_group import SEResNetGroup
+from .policy_insight import InsightRecorder
 from .value_adapter import MultiHeadValueAdapter
 
 __all__ = ["SelfPlayRollout", "SelfPlayStats"]
@@ -114,12 +115,17 @@ class SelfPlayRollout:
     records to the ply (one launch, ``ka_gamelog_step``, between the env step and ``ka_selfplay_step``): ``collect``
     drains it at every sync point onto ``SelfPlayStats.games``.  Without it the ply is launch for launch what it was.
     ``move_history=True`` has the env keep the move notes of the games in progress (two more launches inside ``env.step``,
-    see ``VecEnv``); ``spectator_data()`` between two ``collect`` calls is the dashboard feed either way."""
+    see ``VecEnv``); ``spectator_data()`` between two ``collect`` calls is the dashboard feed either way.
+    ``insight=top_k > 0`` adds the policy insight to the ply (one launch, ``ka_policy_insight``, between the sampler and the
+    env step; ``policy_insight.py``): every ``spectator_data()`` dict gains ``insight``, the figures of the env's last move at
+    ``insight_temperature``, and with ``move_history=True`` every history entry gains its move's probability, rank, entropy,
+    win probability and top candidates.  With 0 the ply and every dict are what they were."""
 
     def __init__(self, learner, *, num_envs: int = 512, max_ply: int = 500, value_adapter=None,
                  score_norm: float = SCORE_NORMALIZATION, sync_every: int = 32, graph: bool = True,
                  seed: Optional[int] = None, record: bool = False, start_pool_capacity: int = 0,
-                 game_log: int = 0, move_history: bool = False) -> None:
+                 game_log: int = 0, move_history: bool = False, insight: int = 0,
+                 insight_temperature: float = 1.0) -> None:
         _check_args(int(num_envs), int(max_ply), int(sync_every), bool(graph), bool(record), float(score_norm), value_adapter)
         if start_pool_capacity < 0:
             raise ValueError(f"start_pool_capacity must not be negative, got {start_pool_capacity}")
@@ -151,6 +157,7 @@ class SelfPlayRollout:
             self._state_host = torch.zeros(self._state.shape, dtype=torch.int32).pin_memory()
             self._ws = self.group._tables.workspace(N)
             self.game_log: Optional[GameLog] = GameLog(self.env, capacity=int(game_log)) if game_log else None
+            self.insight: Optional[InsightRecorder] = InsightRecorder(self.env, insight, insight_temperature) if insight else None
         self._graphs: Dict[int, torch.cuda.CUDAGraph] = {}
         with torch.cuda.device(dev), torch.no_grad():            # load every kernel of the ply before any capture
             self.reset()                                         # (a zeroed descriptor reserves no row: nothing is written)
@@ -188,6 +195,8 @@ class SelfPlayRollout:
             self.env.reset()
             if self.game_log is not None:
                 self.game_log.begin()
+            if self.insight is not None:
+                self.insight.clear()
         self.record = []
 
     @property
@@ -205,6 +214,9 @@ class SelfPlayRollout:
         sp = self._state.data_ptr()
         _lib.call("ka_policy_sample_play", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of, 1,
                   self._actions, self._logp, self._nlegal, sp + 4 * _SAMP, N, ACTION_SPACE, st)
+        if self.insight is not None:                      # while the logits exist, before the step moves the history count
+            self.insight.step(logits, cur.legal_mask_bits, self._actions, value, env._players[prev], self._model_of, 1,
+                              sp + 4 * _SAMP, st)
         r = env.step(self._actions)
         if self.game_log is not None:                     # before ka_selfplay_step advances the ply counter it stamps
             self.game_log.step(self._actions, r.rewards, r.terminated, r.truncated, env._players[prev],
@@ -357,13 +369,18 @@ class SelfPlayRollout:
     def spectator_data(self, envs: Optional[Sequence[int]] = None) -> List[dict]:
         """``VecEnv.get_spectator_data`` of every env (or ``envs``) between two ``collect`` calls, each dict with
         ``value_estimate``: the learner's value at the env's last ply (the reference's snapshot row takes it from
-        ``latest_values``, katago_loop.py:1938-1942).  ``move_history`` is [] unless built with ``move_history=True``."""
+        ``latest_values``, katago_loop.py:1938-1942).  ``move_history`` is [] unless built with ``move_history=True``;
+        ``insight`` (built with ``insight > 0``) is the ``insight_dict`` of the env's last move, None before its first move
+        after ``reset()``."""
         with torch.cuda.device(self.device):
             data = self.env.get_spectator_data(envs)
             values = self._values.cpu().numpy()
         ids = range(self.num_envs) if envs is None else [int(e) for e in envs]
         for d, e in zip(data, ids):
             d["value_estimate"] = float(values[e])
+        if self.insight is not None:
+            with torch.cuda.device(self.device):
+                self.insight.annotate(data, envs)
         return data
 
     def bootstrap_values(self) -> torch.Tensor:

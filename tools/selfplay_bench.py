@@ -14,8 +14,12 @@ per workload.
 notes of the games in progress: two more launches per ply) under the key suffix "_hist", and times one spectator_data()
 call over all envs behind each device config's last epoch ("spectator_data_ms").
 
+--insight K runs every device config once more with SelfPlayRollout(insight=K) (the policy insight of every move: one
+more launch per ply, ka_policy_insight) under the key suffix "_insight"; with --move-history the "_hist" run carries the
+switch as well (the per-move records are then kept), under "_hist_insight".
+
     python tools/selfplay_bench.py [--workload a|b|all] [--configs g32,e2,host] [--steps N] [--max-ply 512] [--repeat 2]
-                                   [--move-history]
+                                   [--move-history] [--insight K]
 """
 from __future__ import annotations
 
@@ -109,9 +113,10 @@ def host_loop_epoch(ppo, env, buffer, steps, adapter, score_norm=76.0):
             "next_values_finite": bool(torch.isfinite(next_values).all())}
 
 
-def device_epochs(model, N, max_ply, graph, sync_every, steps, adapter, repeat, move_history=False, feed=False):
+def device_epochs(model, N, max_ply, graph, sync_every, steps, adapter, repeat, move_history=False, feed=False, insight=0):
+    extra = {"insight": insight} if insight else {}              # (nothing new is passed where the switch is off)
     roll = SelfPlayRollout(model, num_envs=N, max_ply=max_ply, value_adapter=adapter, sync_every=sync_every, graph=graph,
-                           seed=1234, move_history=move_history)
+                           seed=1234, move_history=move_history, **extra)
     buf = KataGoRolloutBuffer(N, OBS, ACTION_SPACE, device="cuda")
     roll.collect(buf, steps)                                     # warm-up: graph capture, buffer growth
     roll.bootstrap_values()
@@ -144,6 +149,7 @@ def main() -> None:
     ap.add_argument("--max-ply", type=int, default=512)
     ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--move-history", action="store_true", help="also run the device configs with move_history=True")
+    ap.add_argument("--insight", type=int, default=0, help="also run the device configs with insight=K (top_k of the policy insight)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "selfplay_bench needs a GPU"
@@ -176,6 +182,12 @@ def main() -> None:
                 if args.move_history:
                     row[key + "_hist"] = device_epochs(_model(shape).eval(), N, args.max_ply, graph, se, steps, adapter,
                                                        args.repeat, move_history=True, feed=True)
+                if args.insight:
+                    row[key + "_insight"] = device_epochs(_model(shape).eval(), N, args.max_ply, graph, se, steps, adapter,
+                                                          args.repeat, feed=True, insight=args.insight)
+                    if args.move_history:
+                        row[key + "_hist_insight"] = device_epochs(_model(shape).eval(), N, args.max_ply, graph, se, steps, adapter,
+                                                                   args.repeat, move_history=True, feed=True, insight=args.insight)
             torch.cuda.synchronize()
         print(json.dumps(row), flush=True)
         lines.append(row)
