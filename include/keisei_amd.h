@@ -455,7 +455,7 @@ int ka_heads_eval_grouped(const void* x, const float* pool, const int* model_of,
  *   seed from the header, so new contents apply from the next ply of a captured graph.  A game starting in env e draws
  *     h = mix(seed ^ mix(((u64)e << 32 | g) + 0x706F6F6C)),  idx = ((h >> 32) * count) >> 32,  mix = the splitmix64 finaliser,
  *   with g = games started in e since the last reset (u32 at byte 116 of the state row: reset writes 0, a restart adds 1,
- *   refresh leaves it), and starts from row idx with ply 0, an empty history, repetition count 1, in_check and key derived.
+ *   refresh leaves it; the game ply, the ply of the position to move in, is the u32 at byte 100), and starts from row idx with ply 0, an empty history, repetition count 1, in_check and key derived.
  *   The rows must be playable positions (keisei_amd.shogi_gym validates them).  count <= 0 or pool = pool_hdr = NULL is
  *   the standard start: exactly ka_shogi_env_reset / ka_shogi_env_step, which never touch byte 116. */
 int ka_shogi_env_state_bytes(void);
@@ -762,6 +762,37 @@ int ka_policy_insight_words(int which, int top_k);
 int ka_policy_insight(const void* logits, int logits_bf16, const void* legal, int legal_words, const long long* actions,
                       const float* vlogits, const void* players, const int* model_of, int K, float temperature, int top_k,
                       void* last, float* heat, void* hist, int row_len, const int* count, int* flags, int B, int A, void* stream);
+
+/* ---- sampling controls (csrc/sampling.hip; the reference's showcase plays at SAMPLING_TEMPERATURE = 0.5,
+ * showcase/runner.py:52, :155-163; its rollouts and tournaments draw at temperature 1).  ka_policy_sample_ctl is
+ * ka_policy_sample_play with a temperature, a top-k cut and an opening schedule per model.  logits, legal, legal_words,
+ * seed_dev, model_of, K, actions, logp, nlegal, flags, B, A as in ka_policy_sample_play; one workgroup per row.
+ * ctl: K rows of 4 32-bit words in device memory, row m for model m, read on every launch (a new table applies from the
+ *   next ply of a captured graph; the same contract as the start pool's header):
+ *     word 0 fp32 temperature   1 fp32 opening_temperature   2 int32 opening_plies   3 int32 top_k
+ * plies / ply_stride: the u32 game ply of row b at plies + b * ply_stride (both multiples of 4); NULL = ply "infinite".
+ *   The game ply is the u32 at byte 100 of the env's state row: the ply of the position to move in, 0 at the start of every
+ *   game, restarted games included (owners pass state + 100 with stride ka_shogi_env_state_bytes()).  The ply_count output
+ *   of the step is NOT it: for a finished game that holds the finished game's length.
+ * A seated row (m = model_of[b] in [0, K)) with game ply p:
+ *   T = p < opening_plies ? opening_temperature : temperature
+ *   S = every legal action when top_k == 0 or n_legal <= top_k, else the top_k legal actions that come first by raw logit
+ *       descending, equal logits by lower action (the candidate order of ka_policy_insight); 1 <= top_k <= 64
+ *   T == 0: greedy, the first action of that order, probability 1
+ *   T > 0:  q_j ~ exp((z_j - max_S z) * (1 / T)) over S; the draw is the inverse CDF over S in ascending action order at the
+ *           play sampler's uniform (the same 64-bit mix of (*seed_dev, b), the same 24 bits); where rounding leaves
+ *           target >= total, the last action of S
+ *   logp[b] = log(clamp(q_action, FLT_EPSILON, 1 - FLT_EPSILON)); nlegal[b] counts every legal action, not |S|.
+ * flags[0] |= a NaN logit, flags[1] |= a row without a legal action (action 0, log-prob 0); a row outside [0, K) gets its
+ * first legal action and log-prob 0 -- all as in ka_policy_sample_play.
+ * The neutral row (T == 1, top_k == 0) gives ka_policy_sample_play's actions and logp for the same inputs and seed, bit for
+ * bit.  The table's contents cannot be checked on the host side of a launch: a row with top_k outside [0, 64] or a negative
+ * or non-finite temperature is read as the neutral row (keisei_amd.training.sampling validates before upload).
+ * Refused: null tensors, a packed mask width other than ka_mask_words(A), a row that does not fit 64 KB of LDS, K < 1,
+ * ply_stride < 4 with plies, misaligned ctl / plies.  Kernel launch only, no workgroup waits for another. */
+int ka_policy_sample_ctl(const void* logits, int logits_bf16, const void* legal, int legal_words, const long long* seed_dev,
+                         const int* model_of, int K, const void* ctl, const void* plies, int ply_stride, long long* actions,
+                         float* logp, int* nlegal, int* flags, int B, int A, void* stream);
 
 /* ---- SL shard preparation (csrc/sl_prepare.hip; the replay keisei/sl/prepare.py:151-161 leaves out).  A batch of E game
  * records, game g in env g, stepped in lockstep from ka_shogi_env_reset.  One ply = ka_sl_replay_plan, ka_shogi_env_step

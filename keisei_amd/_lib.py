@@ -133,6 +133,7 @@ _SIGS = {
     "ka_spectator_commit": "ppp i pp i p p",
     "ka_policy_insight_words": "ii",
     "ka_policy_insight": "pi pi pppp i f i ppp i pp ii p",
+    "ka_policy_sample_ctl": "pi pi pp i p pi pppp ii p",
     "ka_sl_replay_state_words": "i",
     "ka_sl_replay_plan": "p i p i p p i pp p",
     "ka_sl_replay_record": "p i ppp i ppppppp p i p",

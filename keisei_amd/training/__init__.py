@@ -6,4 +6,5 @@ from .game_feature_tracker import GameFeatureAccumulator, GameFeatureRow, GameFe
 from .league_rollout import LeagueRollout, LeagueRolloutStats  # noqa: F401
 from .match_arena import MatchArena, MatchResult, RoundStats  # noqa: F401
 from .policy_insight import InsightRecorder, PolicyInsight, action_usi, insight_dict, policy_insight  # noqa: F401
+from .sampling import ControlledSample, SamplingControls, controls_table, sample_controlled  # noqa: F401
 from .selfplay_rollout import SelfPlayRollout, SelfPlayStats  # noqa: F401

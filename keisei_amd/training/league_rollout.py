@@ -48,6 +48,7 @@ from .katago_loop import (_ZERO_LEGAL, PendingTransitions, _compute_value_cats, 
 from .katago_ppo import SCORE_NORMALIZATION, KataGoRolloutBuffer, _check_step_inputs
 from .model_group import SEResNetGroup
 from .policy_insight import InsightRecorder
+from .sampling import GAME_PLY_BYTE, SamplingControls, league_controls
 from .value_adapter import MultiHeadValueAdapter
 
 __all__ = ["LeagueRollout", "LeagueRolloutStats", "league_draw", "draw_opponents", "draw_sides", "cum_thresholds"]
@@ -185,17 +186,24 @@ class LeagueRollout:
     ``insight=top_k > 0`` adds the policy insight to the ply (one launch, ``ka_policy_insight``, between the sampler and the
     env step; ``policy_insight.py``), for the learner's and the opponents' moves alike: every ``spectator_data()`` dict gains
     ``insight``, the figures of the env's last move at ``insight_temperature``, and with ``move_history=True`` every history
-    entry gains its move's probability, rank, entropy, win probability and top candidates.  With 0 nothing changes."""
+    entry gains its move's probability, rank, entropy, win probability and top candidates.  With 0 nothing changes.
+    ``opponent_sampling=`` (one ``SamplingControls`` for every opponent, or one per opponent; ``sampling.py``) has the
+    opponents play through ``ka_policy_sample_ctl`` -- sharper, greedy or more diverse.  The learner's row of the controls
+    table is always neutral, which is the play sampler bit for bit: its actions and the log-probs that reach the buffer stay
+    draws from its own distribution, the PPO behaviour policy.  With None the ply is launch for launch what it was."""
 
     def __init__(self, learner, opponents: Sequence, opponent_ids: Sequence[int], *, num_envs: int = 512, max_ply: int = 500,
                  value_adapter=None, score_norm: float = SCORE_NORMALIZATION, color_randomization: bool = False,
                  opponent_weights: Optional[Sequence[float]] = None, sync_every: int = 32, graph: bool = True,
                  seed: Optional[int] = None, record: bool = False, start_pool_capacity: int = 0, game_log: int = 0,
                  learner_id: int = -1, move_history: bool = False, insight: int = 0,
-                 insight_temperature: float = 1.0) -> None:
+                 insight_temperature: float = 1.0, opponent_sampling=None) -> None:
         opponents, opponent_ids = list(opponents), [int(i) for i in opponent_ids]
         _check_args(len(opponents), opponent_ids, int(num_envs), int(max_ply), int(sync_every), bool(graph), bool(record),
                     float(score_norm), value_adapter)
+        self._ctl_host = league_controls(opponent_sampling, len(opponents))
+        self._opponent_sampling = opponent_sampling
+        self._ctl: Optional[torch.Tensor] = None
         if start_pool_capacity < 0:
             raise ValueError(f"start_pool_capacity must not be negative, got {start_pool_capacity}")
         if game_log < 0:
@@ -265,6 +273,8 @@ class LeagueRollout:
             self._state_host = torch.zeros(self._state.shape, dtype=torch.int32).pin_memory()
             self._cum = torch.from_numpy(self._cum_host.view(np.int32).copy()).to(dev)
             self._ws = self.group._tables.workspace(self.num_envs)
+            # the controls table of ka_policy_sample_ctl (row 0, the learner, neutral): the graphs are captured anew below
+            self._ctl = None if self._ctl_host is None else torch.from_numpy(self._ctl_host).to(dev)
             if self.game_log is not None:                         # the ids the log names the players by: the same words
                 ids = torch.tensor([self.learner_id, *self.opponent_ids], dtype=torch.int32)       # where K is unchanged
                 if self._ids is None or self._ids.numel() != K + 1:
@@ -273,13 +283,23 @@ class LeagueRollout:
                     self._ids.copy_(ids)
         self._graphs = {}
 
+    _KEEP = object()                                              # set_opponents(sampling=) not given
+
     def set_opponents(self, opponents: Sequence, opponent_ids: Sequence[int],
-                      opponent_weights: Optional[Sequence[float]] = None) -> None:
-        """A new cohort (epoch start): every env draws its opponent afresh; games in progress go on."""
+                      opponent_weights: Optional[Sequence[float]] = None, *, sampling=_KEEP) -> None:
+        """A new cohort (epoch start): every env draws its opponent afresh; games in progress go on.  ``sampling=`` as
+        the constructor's ``opponent_sampling``; without it a single ``SamplingControls`` stays in force, and a
+        per-opponent list stays while the cohort keeps its size and is reset to neutral when the size changes."""
         opponents, opponent_ids = list(opponents), [int(i) for i in opponent_ids]
         _check_args(len(opponents), opponent_ids, self.num_envs, self.max_ply, self.sync_every, self.graph,
                     self.record_enabled, self.score_norm, self.value_adapter)
         cum = cum_thresholds(opponent_weights, len(opponents))
+        if sampling is LeagueRollout._KEEP:
+            sampling = self._opponent_sampling
+            if not (sampling is None or isinstance(sampling, SamplingControls)) and len(sampling) != len(opponents):
+                sampling = None
+        self._ctl_host = league_controls(sampling, len(opponents))
+        self._opponent_sampling = sampling
         same = len(opponents) + 1 == len(self.group) and all(a is b for a, b in zip(opponents, self.group.models[1:]))
         if not same:
             self.group = self._make_group(self.learner, opponents)
@@ -344,8 +364,13 @@ class LeagueRollout:
         cur, prev = env.current(), env._cur
         logits, value, score = self.group._tables.forward(cur.observations, self._model_of, ws=self._ws)
         sp = self._state.data_ptr()
-        _lib.call("ka_policy_sample_play", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of, K + 1,
-                  self._actions, self._logp, self._nlegal, sp + 4 * _SAMP, N, ACTION_SPACE, st)
+        if self._ctl is None:
+            _lib.call("ka_policy_sample_play", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of, K + 1,
+                      self._actions, self._logp, self._nlegal, sp + 4 * _SAMP, N, ACTION_SPACE, st)
+        else:                                             # the game ply of the position to move in: byte 100 of the state row
+            _lib.call("ka_policy_sample_ctl", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of, K + 1,
+                      self._ctl, env._state.data_ptr() + GAME_PLY_BYTE, env._state.shape[1], self._actions, self._logp,
+                      self._nlegal, sp + 4 * _SAMP, N, ACTION_SPACE, st)
         if self.insight is not None:                      # while the logits exist, before the step moves the history count
             self.insight.step(logits, cur.legal_mask_bits, self._actions, value, env._players[prev], self._model_of, K + 1,
                               sp + 4 * _SAMP, st)
@@ -367,7 +392,8 @@ class LeagueRollout:
         rec = {"seed": int(self._state[:2].view(torch.int64).item()), "obs": cur.observations.cpu(),
                "mask_bits": cur.legal_mask_bits.cpu(), "model_of": self._model_of.cpu().numpy(),
                "pre_players": env._players[prev].cpu().numpy(), "side": self._side.cpu().numpy(),
-               "opp": self._opp.cpu().numpy()}
+               "opp": self._opp.cpu().numpy(),
+               "game_plies": env._state[:, GAME_PLY_BYTE:GAME_PLY_BYTE + 4].cpu().contiguous().view(torch.int32).reshape(-1).numpy()}
         self._ply()
         c = env._cur
         trunc = (env._truncated[c] & ~env._terminated[c]).nonzero(as_tuple=True)[0]

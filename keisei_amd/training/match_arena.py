@@ -8,7 +8,9 @@ synchronisation:
 
     grouped stem / tower / heads on model_of   (csrc/tower.hip, SEResNetGroup's tables)
     ka_policy_sample_play                       (csrc/loss.hip: seed read from the device; unseated rows take their
-                                                 first legal action, as the reference does for idle partitions)
+                                                 first legal action, as the reference does for idle partitions;
+                                                 with sampling= its place is taken by ka_policy_sample_ctl,
+                                                 csrc/sampling.hip: temperature, top-k cut and opening plies per model)
     ka_shogi_env_step                           (csrc/shogi_env.hip)
     ka_arena_features_step                      (csrc/arena.hip, only with features=True: the reference's per-slot
                                                  GameFeatureTracker, one record per finished game)
@@ -44,6 +46,7 @@ from .game_feature_tracker import GameFeatureTracker
 from .game_log import GameLog, RecordedGame
 from .model_group import SEResNetGroup
 from .policy_insight import InsightRecorder
+from .sampling import GAME_PLY_BYTE, arena_controls, controls_table
 
 _HDR, _SLOT = 8, 8                      # int32 words of the state header and of one slot (csrc/arena.hip)
 _CUR = 4                                # int32 words of one slot's collection cursors: rows, rows of this ply, dropped, -
@@ -262,13 +265,18 @@ class MatchArena:
     dashboard feed.  ``insight=top_k > 0`` adds the policy insight to the ply (one launch, ``ka_policy_insight``, between
     the sampler and the env step; ``policy_insight.py``): every ``spectator_data()`` dict gains ``insight``, the figures of
     the env's last move at ``insight_temperature`` (None for the envs of an idle slot), and with ``move_history=True`` every
-    history entry gains its move's probability, rank, entropy, win probability and top candidates.  With 0 nothing changes."""
+    history entry gains its move's probability, rank, entropy, win probability and top candidates.  With 0 nothing changes.
+    ``sampling=`` (a ``SamplingControls`` for every model, or one per model; ``sampling.py``) replaces the play sampler of the
+    ply by ``ka_policy_sample_ctl`` -- temperature, top-k cut and opening schedule per model, read from a table on the device
+    that ``set_sampling`` rewrites between rounds without a new capture.  With None the ply is launch for launch what it
+    was.  Not with ``collect=True``.  The insight keeps its own ``insight_temperature``: under a cut or an opening
+    schedule its probabilities are those of the uncut, single-temperature softmax."""
 
     def __init__(self, group: SEResNetGroup, num_envs: int = 512, envs_per_match: int = 64, max_ply: int = 512, *,
                  sync_every: int = 32, graph: bool = True, seed: Optional[int] = None, record: bool = False,
                  collect: bool = False, features: bool = False, start_pool_capacity: int = 0,
                  game_log: int = 0, move_history: bool = False, insight: int = 0,
-                 insight_temperature: float = 1.0) -> None:
+                 insight_temperature: float = 1.0, sampling=None) -> None:
         if game_log < 0:
             raise ValueError(f"game_log must not be negative, got {game_log}")
         if len(group) == 0:
@@ -290,6 +298,7 @@ class MatchArena:
                              "style features are defined from the standard start position")
         if group.device.type != "cuda" or group._tables is None:
             raise ValueError(f"MatchArena runs on a GPU group; this group is on {group.device} (VecEnv has no CPU path)")
+        table = arena_controls(sampling, len(group), bool(collect))
         self.group = group
         self.device = group.device
         self.num_envs, self.envs_per_match, self.max_ply = int(num_envs), int(envs_per_match), int(max_ply)
@@ -346,7 +355,21 @@ class MatchArena:
             if game_log:
                 self.game_log = GameLog(self.env, capacity=int(game_log), envs_per_slot=self.envs_per_match)
             self.insight: Optional[InsightRecorder] = InsightRecorder(self.env, insight, insight_temperature) if insight else None
+            # the controls table of ka_policy_sample_ctl, allocated once: set_sampling writes into it, the ply reads it
+            self._ctl: Optional[torch.Tensor] = None if table is None else torch.from_numpy(table).to(dev)
         self._graph: Optional[torch.cuda.CUDAGraph] = None
+
+    def set_sampling(self, sampling) -> None:
+        """New sampling controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
+        writes neutral rows.  An arena built without ``sampling=`` holds the play sampler in its ply and refuses."""
+        if self._ctl is None:
+            raise ValueError("this arena was built without sampling=: its ply (and its captured graph) holds "
+                             "ka_policy_sample_play; build the arena with sampling controls to change them later")
+        table = arena_controls(sampling, len(self.group), self.collect)
+        if table is None:
+            table = controls_table(None, len(self.group))
+        with torch.cuda.device(self.device):
+            self._ctl.copy_(torch.from_numpy(table))
 
     # ------------------------------------------------------------------ one ply
     def _ply(self) -> None:
@@ -356,8 +379,13 @@ class MatchArena:
         cur, prev = env.current(), env._cur
         logits, value, _ = self.group._tables.forward(cur.observations, self._model_of, ws=self._ws)
         sp = self._state.data_ptr()
-        _lib.call("ka_policy_sample_play", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of,
-                  len(self.group), self._actions, self._logp, self._nlegal, sp + 16, N, ACTION_SPACE, st)
+        if self._ctl is None:
+            _lib.call("ka_policy_sample_play", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of,
+                      len(self.group), self._actions, self._logp, self._nlegal, sp + 16, N, ACTION_SPACE, st)
+        else:                                             # the game ply of the position to move in: byte 100 of the state row
+            _lib.call("ka_policy_sample_ctl", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of,
+                      len(self.group), self._ctl, env._state.data_ptr() + GAME_PLY_BYTE, env._state.shape[1], self._actions,
+                      self._logp, self._nlegal, sp + 16, N, ACTION_SPACE, st)
         if self.insight is not None:                      # while the logits exist, before the step moves the history count
             self.insight.step(logits, cur.legal_mask_bits, self._actions, value, env._players[prev], self._model_of,
                               len(self.group), sp + 16, st)
@@ -391,7 +419,8 @@ class MatchArena:
         cur = self.env.current()
         rec = {"seed": int(self._state[:2].view(torch.int64).item()), "obs": cur.observations.cpu(),
                "mask_bits": cur.legal_mask_bits.cpu(), "model_of": self._model_of.cpu(),
-               "pre_players": self.env._players[self.env._cur].cpu()}
+               "pre_players": self.env._players[self.env._cur].cpu(),
+               "game_plies": self.env._state[:, GAME_PLY_BYTE:GAME_PLY_BYTE + 4].cpu().contiguous().view(torch.int32).reshape(-1)}
         self._ply()
         rec.update(actions=self._actions.cpu(), log_probs=self._logp.cpu(), n_legal=self._nlegal.cpu(),
                    rewards=self.env._rewards[self.env._cur].cpu(), terminated=self.env._terminated[self.env._cur].cpu(),

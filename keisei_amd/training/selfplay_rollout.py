@@ -119,7 +119,9 @@ class SelfPlayRollout:
     ``insight=top_k > 0`` adds the policy insight to the ply (one launch, ``ka_policy_insight``, between the sampler and the
     env step; ``policy_insight.py``): every ``spectator_data()`` dict gains ``insight``, the figures of the env's last move at
     ``insight_temperature``, and with ``move_history=True`` every history entry gains its move's probability, rank, entropy,
-    win probability and top candidates.  With 0 the ply and every dict are what they were."""
+    win probability and top candidates.  With 0 the ply and every dict are what they were.
+    There are no sampling controls here (``sampling.py``), on purpose: the single model is the learner, and its draws are
+    the PPO behaviour policy."""
 
     def __init__(self, learner, *, num_envs: int = 512, max_ply: int = 500, value_adapter=None,
                  score_norm: float = SCORE_NORMALIZATION, sync_every: int = 32, graph: bool = True,
