@@ -794,6 +794,57 @@ int ka_policy_sample_ctl(const void* logits, int logits_bf16, const void* legal,
                          const int* model_of, int K, const void* ctl, const void* plies, int ply_stride, long long* actions,
                          float* logp, int* nlegal, int* flags, int B, int A, void* stream);
 
+/* ---- lookahead (csrc/lookahead.hip; the reference never searches).  A one-ply value lookahead inside the ply, between the
+ * sampler and the env step, per model: fork the env rows into one child row per candidate move, step the children with
+ * ka_shogi_env_step as it is, evaluate them with the grouped forward as it is, and play the candidate whose child is worst
+ * for the side to move there.  Four stages on one stream, kernel launches only, caller-owned buffers, no workgroup waits for
+ * another, nothing on the host in between:
+ *   ka_lookahead_fork(...)                                   records, child rows
+ *   ka_shogi_env_step(child_state, child_keys, child_checks, child_actions, N * width, max_ply, 1, 1, NULL, child_mask_bits,
+ *                     child_err, ...)                        its own err, stats and output buffers, no pool
+ *   ka_stem / tower / heads_eval_grouped                     over the child observations with child_model_of, in a workspace
+ *                                                            of their own (the parent's logits stay where they are)
+ *   ka_lookahead_choose(...)                                 q, the choice, actions[e] of the active envs
+ * table: K rows of 4 32-bit words in device memory, row m for model m, read by every launch (a new table applies from the
+ *   next ply of a captured graph):   word 0 int32 width   1 fp32 prior_weight   2 int32 skip_plies   3 reserved (0)
+ *   A row with width outside [0, 8], a negative or non-finite prior_weight or a negative skip_plies reads as off (width 0);
+ *   a width above the launch's `width` is cut to it.
+ * Env e with m = model_of[e] is active when m lies in [0, K), the row's width is positive, its game ply (the u32 at byte
+ *   100 of its state row; without state rows: "infinite") is >= skip_plies, and it has a candidate.
+ * Candidates: the first `width` legal actions by raw logit descending, equal logits by lower action (the order of
+ *   ka_policy_insight and ka_policy_sample_ctl); a legal logit that is -inf or NaN is never one.  prior_j = the candidate's
+ *   softmax probability over ALL legal actions at temperature 1 (row maximum subtracted; a NaN logit weighs nothing).
+ * q_j = the child's reward (for the mover) where the child step terminated or truncated the game, else P(L) - P(W) of
+ *   softmax(child_vlogits_j): the child is seen by its side to move.  A non-finite value logit of a live child: q_j = -inf
+ *   and err bit 0.  u_j = q_j + prior_weight * prior_j (q_j alone at weight 0); the choice is the first j of the greatest u.
+ * Record of an env, ka_lookahead_words(0, width) = 4 + 3 width 32-bit words:
+ *   0 flags (bit 0 active, bit 1 the choice differs from the sampler's action, bit 2 the chosen move ended the game as a win
+ *   for the mover)   1 chosen slot   2 n_cand   3 chosen action (the sampler's for an inactive env)   4.. width candidate
+ *   actions (int32, -1 = unused)   4 + width.. width priors (fp32)   4 + 2 width.. width q (fp32)
+ * ka_lookahead_words(which, width): 0 record words, 1 table words per model (4), 2 stats words (4: positions searched,
+ *   choices that differ from the sampler's, chosen moves that won the game, reserved), 3 the maximum width (8); -1 otherwise.
+ * ka_lookahead_fork: logits (N, A) fp32 or bf16, legal packed rows (legal_words == ka_mask_words(A), A = 81 * 139), actions
+ *   (N) int64 the sampler's, state (N, 128) / keys (N, max(max_ply, 1)) u64 / checks (N, max(max_ply, 1)) u8: the env's rows,
+ *   only read.  Written: records (N, words); child rows c = e * width + j: child_state (the 128-byte row), child_keys /
+ *   child_checks (entries [0, ply) of the env's rows, slots in use only; same row stride), child_mask_bits (the env's current
+ *   packed mask row: the child step validates against it), child_actions (candidate j; the env's own sampled action for an
+ *   unused or inactive slot, legal whenever the main step's is), child_model_of (m; -1 for an unused or inactive slot).
+ *   The env rows and child rows may all be NULL: records only (candidates and priors).
+ * ka_lookahead_choose: child_vlogits (N * width, 3), child_rewards, child_terminated / child_truncated (u8) as the child step
+ *   and the forward wrote them; child_err: the child step's two 64-bit error words (or NULL) -- non-zero means the child
+ *   step refused an action, which is a bug: err bit 1, and no action is replaced.  actions (N) int64 is overwritten for the
+ *   active envs; stats (4 int32) is added to with atomics, err (1 int32) is ORed; the caller clears both.
+ * Refused: null tensors, another action space or mask width, width outside [1, 8], K < 1, misaligned rows (state, history
+ *   and mask rows are copied in 16-byte pieces). */
+int ka_lookahead_words(int which, int width);
+int ka_lookahead_fork(const void* logits, int logits_bf16, const void* legal, int legal_words, const long long* actions,
+                      const int* model_of, int K, const void* table, const void* state, const void* keys, const void* checks,
+                      int max_ply, int width, void* records, void* child_state, void* child_keys, void* child_checks,
+                      void* child_mask_bits, long long* child_actions, int* child_model_of, int N, int A, void* stream);
+int ka_lookahead_choose(void* records, int width, const void* table, const int* model_of, int K, const float* child_vlogits,
+                        const float* child_rewards, const void* child_terminated, const void* child_truncated,
+                        const void* child_err, long long* actions, int* stats, int* err, int N, void* stream);
+
 /* ---- SL shard preparation (csrc/sl_prepare.hip; the replay keisei/sl/prepare.py:151-161 leaves out).  A batch of E game
  * records, game g in env g, stepped in lockstep from ka_shogi_env_reset.  One ply = ka_sl_replay_plan, ka_shogi_env_step
  * (unchanged), ka_sl_replay_record on one stream.

@@ -134,6 +134,9 @@ _SIGS = {
     "ka_policy_insight_words": "ii",
     "ka_policy_insight": "pi pi pppp i f i ppp i pp ii p",
     "ka_policy_sample_ctl": "pi pi pp i p pi pppp ii p",
+    "ka_lookahead_words": "ii",
+    "ka_lookahead_fork": "pi pi pp i p ppp ii p pppp pp ii p",
+    "ka_lookahead_choose": "p i pp i pppp p ppp i p",
     "ka_sl_replay_state_words": "i",
     "ka_sl_replay_plan": "p i p i p p i pp p",
     "ka_sl_replay_record": "p i ppp i ppppppp p i p",

@@ -1,0 +1,343 @@
+// One-ply value lookahead in the device ply.  The reference never searches: every move of its matches is one draw from the raw
+// policy.  Here a game's complete state is a few rows of device memory (a 128-byte state row plus `ply` words of key / check
+// history) and the grouped forward evaluates thousands of boards of mixed models in three launches, so a one-ply search is
+// "copy rows, step them with the env kernel as it is, evaluate them with the forward as it is, arg-max":
+//
+//   ka_lookahead_fork       the first `width` legal actions of every active env in the candidate order of the insight and the
+//                           sampling controls, their priors, and one child row per candidate: state, history, mask, action
+//   ka_shogi_env_step       (csrc/shogi_env.hip, unchanged) over the N * width child rows
+//   grouped forward         (csrc/tower.hip, unchanged) over the child observations
+//   ka_lookahead_choose     q of every child (its reward when the game ended there, else P(L) - P(W) of the child's value
+//                           head: the child is seen by its side to move), u = q + prior_weight * prior, the arg-max replaces
+//                           the sampler's action
+//
+// Row m of the controls table (device memory, read by every launch: a new table applies from the next ply of a captured
+// graph) belongs to model m:   word 0 int32 width   1 fp32 prior_weight   2 int32 skip_plies   3 reserved (0)
+// A row with width outside [0, 8], a negative or non-finite weight or a negative skip_plies reads as "off"; a width above
+// the launch's width is cut to it.  An env is active when its model lies in [0, K), the row's width is positive, its game
+// ply (the u32 at byte 100 of its state row) is at least skip_plies and it has a candidate.
+//
+// Record of an env, 4 + 3 width 32-bit words:
+//   0 flags (bit 0 active, bit 1 the choice differs from the sampler's action, bit 2 the chosen move won the game)
+//   1 chosen slot   2 n_cand   3 chosen action (the sampler's for an inactive env)
+//   4.. candidate actions (int32, -1 = unused)   4 + width.. priors (fp32)   4 + 2 width.. q (fp32)
+//
+// The fork is one workgroup per env and walks the set bits of the packed mask row, never the action space; the copies are
+// what it is for, and every thread takes part in them, 16 bytes per lane where the rows allow it.  Unused and inactive child
+// slots get the state, the mask and the env's own sampled action (legal whenever the main step's is: one refused action
+// makes the env step hold every row of its launch) and model -1; their history is not copied -- the env kernel only counts
+// repetitions in it, and nothing reads such a child's outcome.  The parent's rows are only read.  Kernel nodes only,
+// caller-owned buffers, no workgroup waits for another.
+#include "common.h"
+
+#include <climits>
+
+namespace {
+
+constexpr int kLaThreads = 256, kLaWaves = kLaThreads / 64;
+constexpr int kLaSlots = 139, kLaA = 81 * kLaSlots, kLaMaxWidth = 8;
+constexpr int kLaWords = (kLaA + 31) / 32;
+constexpr uint32_t kLaTailBits = (1u << (kLaA - 32 * (kLaWords - 1))) - 1u;       // the bits of the last word that are actions
+constexpr int kLaStateBytes = 128, kLaPlyByte = 100;                              // csrc/shogi_env.hip, kStateBytes
+constexpr int kLaFlags = 0, kLaSlot = 1, kLaNCand = 2, kLaAction = 3, kLaCand = 4;
+constexpr int kLaTableWords = 4, kLaStatsWords = 4;
+constexpr int kLaStateUnits = kLaStateBytes / 16, kLaMaskUnits = kLaWords * 4 / 16;     // 16-byte pieces of a state / mask row
+static_assert(kLaWords * 4 % 16 == 0 && kLaStateBytes % 16 == 0, "state and mask rows are copied in 16-byte pieces");
+
+__host__ __device__ constexpr int la_words(int width) { return kLaCand + 3 * width; }
+
+struct ForkArgs {
+    const void* logits; int logits_bf16; const uint32_t* legal; const long long* actions; const int* model_of; int K;
+    const uint32_t* table; const uint8_t* state; const unsigned long long* keys; const uint8_t* checks; int hist; int width;
+    uint32_t* rec; uint8_t* c_state; unsigned long long* c_keys; uint8_t* c_checks; uint32_t* c_bits; long long* c_actions;
+    int* c_model_of;
+};
+
+struct ChooseArgs {
+    uint32_t* rec; int width; const uint32_t* table; const int* model_of; int K; const float* vl; const float* rewards;
+    const uint8_t* term; const uint8_t* trunc; const unsigned long long* c_err; long long* actions; int* stats; int* err; int n;
+};
+
+__device__ __forceinline__ float la_reduce(float v, float* red, bool is_max) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const float t = __shfl_xor(v, o); v = is_max ? fmaxf(v, t) : v + t; }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float r = red[0];
+    for (int w = 1; w < kLaWaves; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
+    return r;
+}
+
+// f(j) for every legal action j of this thread's mask words, in ascending j
+template <class F>
+__device__ __forceinline__ void la_for_legal(const uint32_t* msk, F f) {
+    for (int w = threadIdx.x; w < kLaWords; w += kLaThreads) {
+        uint32_t m = msk[w];
+        while (m) {
+            f((w << 5) + __builtin_ctz(m));
+            m &= m - 1u;
+        }
+    }
+}
+
+// (v, i) comes before (bv, bi) in the candidate order: greater logit, equal logits by lower action
+__device__ __forceinline__ bool la_before(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+// the controls of model m as the kernels read them: the width (0 = off) and the prior weight
+__device__ __forceinline__ int la_controls(const uint32_t* table, int m, int K, float* pw, int* skip) {
+    *pw = 0.f; *skip = 0;
+    if (m < 0 || m >= K) return 0;
+    const uint32_t* c = table + (size_t)m * kLaTableWords;
+    const int w = (int)c[0], s = (int)c[2];
+    const float p = __uint_as_float(c[1]);
+    if (!(w >= 0 && w <= kLaMaxWidth && p >= 0.f && p <= 3.0e38f && s >= 0)) return 0;
+    *pw = p; *skip = s;
+    return w;
+}
+
+__global__ __launch_bounds__(kLaThreads) void lookahead_fork_kernel(ForkArgs a) {
+    __shared__ float row[kLaA];
+    __shared__ uint32_t msk[kLaWords];
+    __shared__ float red[kLaWaves];
+    __shared__ int red_i[kLaWaves];
+    __shared__ int s_cand[kLaMaxWidth];
+    __shared__ float s_prior[kLaMaxWidth];
+    const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int width = a.width, W = la_words(width);
+    const uint32_t* lw = a.legal + (size_t)e * kLaWords;
+    const int m = a.model_of[e];
+    const uint32_t ply = a.state ? *reinterpret_cast<const uint32_t*>(a.state + (size_t)e * kLaStateBytes + kLaPlyByte) : UINT_MAX;
+    float pw;
+    int skip;
+    int want = min(la_controls(a.table, m, a.K, &pw, &skip), width);       // (uniform over the workgroup, as every branch below)
+    if (ply < (uint32_t)skip) want = 0;
+
+    int n_cand = 0;
+    if (want > 0) {
+        for (int w = tid; w < kLaWords; w += kLaThreads)       // (bits past the action space are dropped: no index reaches A)
+            msk[w] = w == kLaWords - 1 ? lw[w] & kLaTailBits : lw[w];
+        float mx = -INFINITY;
+        la_for_legal(msk, [&](int j) {                         // (a thread reads back the words it wrote itself)
+            const float v = a.logits_bf16 ? bf2f(static_cast<const uint16_t*>(a.logits)[(size_t)e * kLaA + j])
+                                          : static_cast<const float*>(a.logits)[(size_t)e * kLaA + j];
+            row[j] = v;
+            mx = fmaxf(mx, v);                                 // (a NaN is passed over)
+        });
+        mx = la_reduce(mx, red, true);
+        float s = 0.f;
+        la_for_legal(msk, [&](int j) {
+            const float v = row[j];
+            if (v == v) s += expf(v - mx);                     // (a NaN logit weighs nothing; -inf gives 0)
+        });
+        s = la_reduce(s, red, false);
+        // round r takes the first action behind round r - 1's winner in the candidate order
+        float prev_v = INFINITY;
+        int prev_i = -1;
+        for (int r = 0; r < want; ++r) {
+            float bv = -INFINITY;
+            int bi = INT_MAX;
+            la_for_legal(msk, [&](int j) {
+                const float v = row[j];
+                if (v > -INFINITY && la_before(prev_v, prev_i, v, j) && v > bv) { bv = v; bi = j; }     // (j ascends: ties keep the lower)
+            });
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ov = __shfl_xor(bv, o);
+                const int oi = __shfl_xor(bi, o);
+                if (la_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+            }
+            __syncthreads();
+            if (lane == 0) { red[wave] = bv; red_i[wave] = bi; }
+            __syncthreads();
+            bv = red[0]; bi = red_i[0];
+            for (int w = 1; w < kLaWaves; ++w)
+                if (la_before(red[w], red_i[w], bv, bi)) { bv = red[w]; bi = red_i[w]; }
+            if (bi == INT_MAX) break;                          // nothing behind the last winner
+            if (tid == 0) { s_cand[r] = bi; s_prior[r] = expf(bv - mx) / s; }
+            prev_v = bv; prev_i = bi;
+            n_cand = r + 1;
+        }
+    }
+    __syncthreads();                                           // s_cand, s_prior
+
+    const long long sampled = a.actions[e];
+    if (tid < W) {
+        const int r = tid >= kLaCand ? (tid - kLaCand) % width : 0, part = tid >= kLaCand ? (tid - kLaCand) / width : -1;
+        uint32_t word = 0u;
+        if (tid == kLaFlags) word = n_cand > 0 ? 1u : 0u;
+        else if (tid == kLaNCand) word = (uint32_t)n_cand;
+        else if (tid == kLaAction) word = (uint32_t)(int)(sampled < -1 ? -1 : sampled > kLaA ? kLaA : sampled);
+        else if (part == 0) word = (uint32_t)(r < n_cand ? s_cand[r] : -1);
+        else if (part == 1) word = __float_as_uint(r < n_cand ? s_prior[r] : 0.f);
+        a.rec[(size_t)e * W + tid] = word;
+    }
+    if (!a.c_state) return;                                    // candidates and priors only
+
+    // ---- the child rows e * width + j: state and mask for every slot, the history for the slots in use
+    {
+        const uint4* s_src = reinterpret_cast<const uint4*>(a.state + (size_t)e * kLaStateBytes);
+        const uint4* m_src = reinterpret_cast<const uint4*>(lw);
+        constexpr int kUnits = kLaStateUnits + kLaMaskUnits;
+        for (int u = tid; u < kUnits * width; u += kLaThreads) {
+            const int j = u / kUnits, r = u % kUnits;
+            const size_t c = (size_t)e * width + j;
+            if (r < kLaStateUnits) reinterpret_cast<uint4*>(a.c_state + c * kLaStateBytes)[r] = s_src[r];
+            else reinterpret_cast<uint4*>(a.c_bits + c * kLaWords)[r - kLaStateUnits] = m_src[r - kLaStateUnits];
+        }
+    }
+    const int hist = a.hist, n = (int)min(ply, (uint32_t)hist);            // entries [0, ply) of the env's history rows
+    if (n_cand > 0 && n > 0) {
+        const unsigned long long* k_src = a.keys + (size_t)e * hist;
+        if ((hist & 1) == 0) {                                 // rows of an even number of keys start at 16-byte boundaries
+            const int units = (n + 1) >> 1;                    // (an odd count takes one stale key along: it stays inside the row)
+            for (int u = tid; u < units * n_cand; u += kLaThreads) {
+                const int j = u / units, r = u % units;
+                reinterpret_cast<uint4*>(a.c_keys + ((size_t)e * width + j) * hist)[r] = reinterpret_cast<const uint4*>(k_src)[r];
+            }
+        } else {
+            for (int u = tid; u < n * n_cand; u += kLaThreads) {
+                const int j = u / n, r = u % n;
+                a.c_keys[((size_t)e * width + j) * hist + r] = k_src[r];
+            }
+        }
+        const uint8_t* c_src = a.checks + (size_t)e * hist;
+        if ((hist & 15) == 0) {
+            const int units = (n + 15) >> 4;
+            for (int u = tid; u < units * n_cand; u += kLaThreads) {
+                const int j = u / units, r = u % units;
+                reinterpret_cast<uint4*>(a.c_checks + ((size_t)e * width + j) * hist)[r] = reinterpret_cast<const uint4*>(c_src)[r];
+            }
+        } else if ((hist & 3) == 0) {
+            const int units = (n + 3) >> 2;
+            for (int u = tid; u < units * n_cand; u += kLaThreads) {
+                const int j = u / units, r = u % units;
+                reinterpret_cast<uint32_t*>(a.c_checks + ((size_t)e * width + j) * hist)[r] = reinterpret_cast<const uint32_t*>(c_src)[r];
+            }
+        } else {
+            for (int u = tid; u < n * n_cand; u += kLaThreads) {
+                const int j = u / n, r = u % n;
+                a.c_checks[((size_t)e * width + j) * hist + r] = c_src[r];
+            }
+        }
+    }
+    if (tid < width) {
+        const size_t c = (size_t)e * width + tid;
+        const bool used = tid < n_cand;
+        a.c_actions[c] = used ? (long long)s_cand[tid] : sampled;
+        a.c_model_of[c] = used ? m : -1;
+    }
+}
+
+// one thread per env: at most eight children each
+__global__ __launch_bounds__(kLaThreads) void lookahead_choose_kernel(ChooseArgs a) {
+    const int e = blockIdx.x * kLaThreads + threadIdx.x, lane = threadIdx.x & 63;
+    const int width = a.width, W = la_words(width);
+    // a refused child step moved no child: its outputs are the unchanged positions, so nothing is chosen from them
+    const bool held = a.c_err && (a.c_err[0] | a.c_err[1]) != 0ull;
+    bool searched = false, changed = false, won = false, bad = false;
+    if (e < a.n && !held) {
+        uint32_t* rec = a.rec + (size_t)e * W;
+        if (rec[kLaFlags] & 1u) {
+            const int n_cand = min(max((int)rec[kLaNCand], 1), width);
+            float pw;
+            int skip;
+            la_controls(a.table, a.model_of[e], a.K, &pw, &skip);
+            int best = 0;
+            float bu = 0.f;
+            for (int j = 0; j < n_cand; ++j) {
+                const size_t c = (size_t)e * width + j;
+                float q;
+                if (a.term[c] | a.trunc[c]) {
+                    q = a.rewards[c];
+                } else {
+                    const float l0 = a.vl[c * 3], l1 = a.vl[c * 3 + 1], l2 = a.vl[c * 3 + 2];
+                    const float mx = fmaxf(l0, fmaxf(l1, l2));
+                    const float e0 = expf(l0 - mx), e1 = expf(l1 - mx), e2 = expf(l2 - mx);
+                    q = (e2 - e0) / (e0 + e1 + e2);            // the child's side to move loses = the mover wins
+                    if (!(fabsf(l0) <= 3.4e38f && fabsf(l1) <= 3.4e38f && fabsf(l2) <= 3.4e38f)) { bad = true; q = -INFINITY; }
+                }
+                rec[kLaCand + 2 * width + j] = __float_as_uint(q);
+                const float u = pw > 0.f ? q + pw * __uint_as_float(rec[kLaCand + width + j]) : q;
+                if (j == 0 || u > bu) { bu = u; best = j; }    // (ties keep the lower slot)
+            }
+            const size_t cb = (size_t)e * width + best;
+            const int act = (int)rec[kLaCand + best];
+            changed = (long long)act != a.actions[e];
+            won = a.term[cb] && a.rewards[cb] > 0.f;
+            searched = true;
+            rec[kLaSlot] = (uint32_t)best;
+            rec[kLaAction] = (uint32_t)act;
+            rec[kLaFlags] = 1u | ((uint32_t)changed << 1) | ((uint32_t)won << 2);
+            a.actions[e] = act;
+        }
+    }
+    const int ns = __popcll(__ballot(searched)), nc = __popcll(__ballot(changed)), nw = __popcll(__ballot(won));
+    const bool any_bad = __ballot(bad) != 0ull;
+    if (lane == 0) {
+        if (ns) atomicAdd(&a.stats[0], ns);
+        if (nc) atomicAdd(&a.stats[1], nc);
+        if (nw) atomicAdd(&a.stats[2], nw);
+        if (any_bad) atomicOr(&a.err[0], 1);
+        if (held && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&a.err[0], 2);
+    }
+}
+
+}  // namespace
+
+extern "C" int ka_lookahead_words(int which, int width) {
+    if (width < 0 || width > kLaMaxWidth) return -1;
+    return which == 0 ? la_words(width) : which == 1 ? kLaTableWords : which == 2 ? kLaStatsWords : which == 3 ? kLaMaxWidth : -1;
+}
+
+extern "C" int ka_lookahead_fork(const void* logits, int logits_bf16, const void* legal, int legal_words, const long long* actions,
+                                 const int* model_of, int K, const void* table, const void* state, const void* keys,
+                                 const void* checks, int max_ply, int width, void* records, void* child_state, void* child_keys,
+                                 void* child_checks, void* child_mask_bits, long long* child_actions, int* child_model_of, int N,
+                                 int A, void* stream) {
+    KA_REQUIRE(logits && legal && actions && model_of && table && records && N > 0, "lookahead_fork: null tensor");
+    KA_REQUIRE(A == kLaA, "lookahead_fork: the spatial action space only (A = %d), got %d", kLaA, A);
+    KA_REQUIRE(legal_words == kLaWords, "lookahead_fork: packed mask rows of %d words", kLaWords);
+    KA_REQUIRE(width >= 1 && width <= kLaMaxWidth, "lookahead_fork: width must lie in [1, %d], got %d", kLaMaxWidth, width);
+    KA_REQUIRE(K >= 1, "lookahead_fork: the controls table needs at least one row, got K = %d", K);
+    const bool rows = state || keys || checks || child_state || child_keys || child_checks || child_mask_bits || child_actions ||
+                      child_model_of;
+    KA_REQUIRE(!rows || (state && keys && checks && child_state && child_keys && child_checks && child_mask_bits &&
+                         child_actions && child_model_of),
+               "lookahead_fork: the env rows and the child rows are all given or all NULL");
+    KA_REQUIRE(max_ply >= 0 && max_ply <= 65535, "lookahead_fork: max_ply must lie in [0, 65535], got %d", max_ply);
+    KA_REQUIRE((long long)N * width <= INT_MAX, "lookahead_fork: %d envs of width %d are too many child rows", N, width);
+    KA_REQUIRE((uintptr_t)logits % (logits_bf16 ? 2 : 4) == 0 && (uintptr_t)legal % 16 == 0 && (uintptr_t)actions % 8 == 0 &&
+               (uintptr_t)model_of % 4 == 0 && (uintptr_t)table % 4 == 0 && (uintptr_t)records % 4 == 0 &&
+               (uintptr_t)state % 16 == 0 && (uintptr_t)keys % 16 == 0 && (uintptr_t)checks % 16 == 0 &&
+               (uintptr_t)child_state % 16 == 0 && (uintptr_t)child_keys % 16 == 0 && (uintptr_t)child_checks % 16 == 0 &&
+               (uintptr_t)child_mask_bits % 16 == 0 && (uintptr_t)child_actions % 8 == 0 && (uintptr_t)child_model_of % 4 == 0,
+               "lookahead_fork: state, history and mask rows are 16-byte aligned, every other tensor to its element size");
+    ForkArgs a{logits, logits_bf16, static_cast<const uint32_t*>(legal), actions, model_of, K, static_cast<const uint32_t*>(table),
+               static_cast<const uint8_t*>(state), static_cast<const unsigned long long*>(keys),
+               static_cast<const uint8_t*>(checks), max_ply > 0 ? max_ply : 1, width, static_cast<uint32_t*>(records),
+               static_cast<uint8_t*>(child_state), static_cast<unsigned long long*>(child_keys),
+               static_cast<uint8_t*>(child_checks), static_cast<uint32_t*>(child_mask_bits), child_actions, child_model_of};
+    hipLaunchKernelGGL(lookahead_fork_kernel, dim3(N), dim3(kLaThreads), 0, static_cast<hipStream_t>(stream), a);
+    return ka_check_launch("lookahead_fork");
+}
+
+extern "C" int ka_lookahead_choose(void* records, int width, const void* table, const int* model_of, int K,
+                                   const float* child_vlogits, const float* child_rewards, const void* child_terminated,
+                                   const void* child_truncated, const void* child_err, long long* actions, int* stats, int* err,
+                                   int N, void* stream) {
+    KA_REQUIRE(records && table && model_of && child_vlogits && child_rewards && child_terminated && child_truncated && actions &&
+               stats && err && N > 0, "lookahead_choose: null tensor");
+    KA_REQUIRE(width >= 1 && width <= kLaMaxWidth, "lookahead_choose: width must lie in [1, %d], got %d", kLaMaxWidth, width);
+    KA_REQUIRE(K >= 1, "lookahead_choose: the controls table needs at least one row, got K = %d", K);
+    KA_REQUIRE((uintptr_t)records % 4 == 0 && (uintptr_t)table % 4 == 0 && (uintptr_t)model_of % 4 == 0 &&
+               (uintptr_t)child_vlogits % 4 == 0 && (uintptr_t)child_rewards % 4 == 0 && (uintptr_t)child_err % 8 == 0 &&
+               (uintptr_t)actions % 8 == 0 && (uintptr_t)stats % 4 == 0 && (uintptr_t)err % 4 == 0,
+               "lookahead_choose: actions and the child error words are 8-byte aligned, every other tensor to its element size");
+    ChooseArgs a{static_cast<uint32_t*>(records), width, static_cast<const uint32_t*>(table), model_of, K, child_vlogits,
+                 child_rewards, static_cast<const uint8_t*>(child_terminated), static_cast<const uint8_t*>(child_truncated),
+                 static_cast<const unsigned long long*>(child_err), actions, stats, err, N};
+    hipLaunchKernelGGL(lookahead_choose_kernel, dim3((N + kLaThreads - 1) / kLaThreads), dim3(kLaThreads), 0,
+                       static_cast<hipStream_t>(stream), a);
+    return ka_check_launch("lookahead_choose");
+}

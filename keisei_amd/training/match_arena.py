@@ -11,6 +11,10 @@ synchronisation:
                                                  first legal action, as the reference does for idle partitions;
                                                  with sampling= its place is taken by ka_policy_sample_ctl,
                                                  csrc/sampling.hip: temperature, top-k cut and opening plies per model)
+    lookahead                                   (only with lookahead=: ka_lookahead_fork, ka_shogi_env_step over the child
+                                                 rows, the grouped forward over the child observations,
+                                                 ka_lookahead_choose -- csrc/lookahead.hip, lookahead.py: the models with a
+                                                 width play the best of their top moves by their own value head)
     ka_shogi_env_step                           (csrc/shogi_env.hip)
     ka_arena_features_step                      (csrc/arena.hip, only with features=True: the reference's per-slot
                                                  GameFeatureTracker, one record per finished game)
@@ -44,6 +48,7 @@ from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS, VecEnv
 from .dynamic_trainer import MatchRollout
 from .game_feature_tracker import GameFeatureTracker
 from .game_log import GameLog, RecordedGame
+from .lookahead import Lookahead, LookaheadStats, arena_lookahead, lookahead_table
 from .model_group import SEResNetGroup
 from .policy_insight import InsightRecorder
 from .sampling import GAME_PLY_BYTE, arena_controls, controls_table
@@ -90,6 +95,7 @@ class RoundStats:
     feature_rows: int = 0               # rows handed out in feature trackers (two per finished game)
     features_dropped: int = 0           # finished games whose record did not fit the feature store
     games_dropped: int = 0              # finished games that did not fit the game log between two sync points
+    lookahead: Optional[LookaheadStats] = None      # the round's lookahead counters (arenas built with lookahead=)
 
 
 def _side_bits(trainable, pairings: Sequence[Tuple[int, int]]) -> List[int]:
@@ -270,13 +276,21 @@ class MatchArena:
     ply by ``ka_policy_sample_ctl`` -- temperature, top-k cut and opening schedule per model, read from a table on the device
     that ``set_sampling`` rewrites between rounds without a new capture.  With None the ply is launch for launch what it
     was.  Not with ``collect=True``.  The insight keeps its own ``insight_temperature``: under a cut or an opening
-    schedule its probabilities are those of the uncut, single-temperature softmax."""
+    schedule its probabilities are those of the uncut, single-temperature softmax.
+    ``lookahead=`` (a ``LookaheadControls`` for every model, or one per model; ``lookahead.py``) adds a one-ply value
+    lookahead between the sampler and the insight: a model with ``width > 0`` plays, of its ``width`` most probable legal
+    moves, the one whose child position its own value head likes best (a move that ends the game counts by its reward), so
+    the insight, the game log and the spectator notes describe the move actually played.  The child rows and a second
+    forward workspace are sized by the largest ``width`` given; ``set_lookahead`` rewrites the table on the device between
+    rounds without a new capture, up to that width.  ``RoundStats.lookahead`` carries the counters.  With None the ply is
+    launch for launch what it was; with every width 0 nothing is allocated and nothing is launched.  Not with
+    ``collect=True``."""
 
     def __init__(self, group: SEResNetGroup, num_envs: int = 512, envs_per_match: int = 64, max_ply: int = 512, *,
                  sync_every: int = 32, graph: bool = True, seed: Optional[int] = None, record: bool = False,
                  collect: bool = False, features: bool = False, start_pool_capacity: int = 0,
                  game_log: int = 0, move_history: bool = False, insight: int = 0,
-                 insight_temperature: float = 1.0, sampling=None) -> None:
+                 insight_temperature: float = 1.0, sampling=None, lookahead=None) -> None:
         if game_log < 0:
             raise ValueError(f"game_log must not be negative, got {game_log}")
         if len(group) == 0:
@@ -299,6 +313,7 @@ class MatchArena:
         if group.device.type != "cuda" or group._tables is None:
             raise ValueError(f"MatchArena runs on a GPU group; this group is on {group.device} (VecEnv has no CPU path)")
         table = arena_controls(sampling, len(group), bool(collect))
+        la_table, la_width = arena_lookahead(lookahead, len(group), bool(collect))
         self.group = group
         self.device = group.device
         self.num_envs, self.envs_per_match, self.max_ply = int(num_envs), int(envs_per_match), int(max_ply)
@@ -357,7 +372,27 @@ class MatchArena:
             self.insight: Optional[InsightRecorder] = InsightRecorder(self.env, insight, insight_temperature) if insight else None
             # the controls table of ka_policy_sample_ctl, allocated once: set_sampling writes into it, the ply reads it
             self._ctl: Optional[torch.Tensor] = None if table is None else torch.from_numpy(table).to(dev)
+            # the lookahead's table (read by every launch: set_lookahead writes into it) and its child rows, allocated once
+            self._la_table: Optional[torch.Tensor] = None if la_table is None else torch.from_numpy(la_table).to(dev)
+            self._la: Optional[Lookahead] = Lookahead(self.env, group, la_width) if la_width > 0 else None
         self._graph: Optional[torch.cuda.CUDAGraph] = None
+
+    def set_lookahead(self, lookahead) -> None:
+        """New lookahead controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
+        writes rows that are off.  A width above the one the arena was built with is refused (the child rows are sized by
+        it), and so is an arena built without ``lookahead=``: its ply holds no lookahead."""
+        if self._la_table is None:
+            raise ValueError("this arena was built without lookahead=: its ply (and its captured graph) holds no "
+                             "lookahead; build the arena with lookahead controls to change them later")
+        table, width = arena_lookahead(lookahead, len(self.group), self.collect)
+        if table is None:
+            table = lookahead_table(None, len(self.group))
+        built = 0 if self._la is None else self._la.width
+        if width > built:
+            raise ValueError(f"lookahead width {width} is above the width this arena was built with ({built}): the child "
+                             "rows are allocated once, by the largest width given to the constructor")
+        with torch.cuda.device(self.device):
+            self._la_table.copy_(torch.from_numpy(table))
 
     def set_sampling(self, sampling) -> None:
         """New sampling controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
@@ -386,6 +421,8 @@ class MatchArena:
             _lib.call("ka_policy_sample_ctl", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of,
                       len(self.group), self._ctl, env._state.data_ptr() + GAME_PLY_BYTE, env._state.shape[1], self._actions,
                       self._logp, self._nlegal, sp + 16, N, ACTION_SPACE, st)
+        if self._la is not None:                          # the active envs' actions become the lookahead's choices
+            self._la.step(logits, cur.legal_mask_bits, self._actions, self._model_of, self._la_table, st)
         if self.insight is not None:                      # while the logits exist, before the step moves the history count
             self.insight.step(logits, cur.legal_mask_bits, self._actions, value, env._players[prev], self._model_of,
                               len(self.group), sp + 16, st)
@@ -422,6 +459,12 @@ class MatchArena:
                "pre_players": self.env._players[self.env._cur].cpu(),
                "game_plies": self.env._state[:, GAME_PLY_BYTE:GAME_PLY_BYTE + 4].cpu().contiguous().view(torch.int32).reshape(-1)}
         self._ply()
+        if self._la is not None:
+            la, w = self._la, self._la.width
+            rec.update(lookahead_records=la.records().cpu(), child_value_logits=la.child_value_logits.cpu().reshape(-1, w, 3),
+                       child_rewards=la.child_rewards.cpu().reshape(-1, w),
+                       child_done=(la.child_terminated | la.child_truncated).cpu().reshape(-1, w),
+                       child_obs=la.child_obs.cpu(), child_mask_bits=la.child_mask_bits.cpu())
         rec.update(actions=self._actions.cpu(), log_probs=self._logp.cpu(), n_legal=self._nlegal.cpu(),
                    rewards=self.env._rewards[self.env._cur].cpu(), terminated=self.env._terminated[self.env._cur].cpu(),
                    truncated=self.env._truncated[self.env._cur].cpu())
@@ -562,6 +605,8 @@ class MatchArena:
         if max_ply < 1:
             raise ValueError(f"max_ply must be positive, got {max_ply}")
         stats = RoundStats(pairings_requested=len(pairings))
+        if self._la_table is not None:                    # (every width 0: nothing is searched)
+            stats.lookahead = LookaheadStats()
         if not pairings:
             return [], stats
         with torch.cuda.device(self.device), torch.no_grad():
@@ -589,6 +634,8 @@ class MatchArena:
             self.game_log.begin()
         if self.insight is not None:
             self.insight.clear()
+        if self._la is not None:
+            self._la.clear()
         logged: Dict[int, List[RecordedGame]] = {}
         self.record = []
         chunks: Dict[int, list] = {}
@@ -611,6 +658,8 @@ class MatchArena:
         while active:
             self._chunk()
             st = self._read_state()
+            if self._la is not None:                      # raises on its error word
+                stats.lookahead = self._la.read()
             stats.host_syncs += 1
             slot = st[_HDR:].reshape(self.num_slots, _SLOT)
             if self.collect:
