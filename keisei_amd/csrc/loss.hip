@@ -85,13 +85,27 @@ __global__ __launch_bounds__(kPolThreads) void policy_loss_kernel(PolicyArgs a) 
         if (nanf_ > 0.f) atomicOr(&a.flags[0], 1);
         if (nlegal == 0.f) atomicOr(&a.flags[1], 1);
     }
-    float s = 0.f, t = 0.f;
+    // The REPORTED entropy is taken from the logits relative to the maximum, log s - sum e (z - mx) / s.  As lse - sum e z / s
+    // it is the difference of two numbers of the logits' magnitude and carries their ulp (1e-5 at |z| ~ 60) whatever its own
+    // size.  The gradient below keeps that second form, H: there the error is multiplied by w_entropy * p, far below the
+    // gradient's own rounding, and a minibatch step stays what it was to the bit.
+    float s = 0.f, t = 0.f, td = 0.f;
     for (int j = tid; j < a.A; j += kPolThreads)
-        if (msk[j]) { const float e = expf(row[j] - mx); s += e; t += e * row[j]; }
+        if (msk[j]) {
+            const float d = row[j] - mx, e = expf(d);
+            s += e; td += e * d;
+            {   // the product is rounded before it is added (no fused multiply-add): the sum the gradient has always used
+#pragma clang fp contract(off)
+                t += e * row[j];
+            }
+        }
     s = block_reduce(s, red, false);
     t = block_reduce(t, red, false);
-    const float lse = mx + logf(s);
+    td = block_reduce(td, red, false);
+    const float logs = logf(s);
+    const float lse = mx + logs;
     const float H = lse - t / s;
+    const float H_out = logs - td / s;
     // an action id outside [0, A) (the reference's gather would trap on the device) is flagged and read as action 0
     const long long act_raw = a.actions[src];
     const bool act_ok = act_raw >= 0 && act_raw < a.A;
@@ -107,11 +121,13 @@ __global__ __launch_bounds__(kPolThreads) void policy_loss_kernel(PolicyArgs a) 
     if (s1 < s2) gr = adv;
     else if (s1 > s2) gr = inrange ? adv : 0.f;
     else gr = 0.5f * adv + (inrange ? 0.5f * adv : 0.f);
-    if (tid == 0) { a.new_lp[b] = nlp; a.rowloss[b] = -fminf(s1, s2); a.rowent[b] = H; }
+    if (tid == 0) { a.new_lp[b] = nlp; a.rowloss[b] = -fminf(s1, s2); a.rowent[b] = H_out; }
     if (a.dlogits) {
+        // the loss scale multiplies the FINISHED gradient: a power-of-two scale then gives scale x the unscaled gradient to the
+        // bit, also where w * p underflows to a subnormal (scaled weights would round those products on a finer grid)
         const float gs = a.gscale ? *a.gscale : 1.f;
-        const float dnlp = -gr * ratio * a.w_policy * gs;     // dL/d new_log_prob
-        const float we = a.w_entropy * gs;
+        const float dnlp = -gr * ratio * a.w_policy;          // dL/d new_log_prob
+        const float we = a.w_entropy;
         float* dl = a.dlogits + (size_t)b * a.A;
         for (int j = tid; j < a.A; j += kPolThreads) {
             float g = 0.f;
@@ -120,7 +136,7 @@ __global__ __launch_bounds__(kPolThreads) void policy_loss_kernel(PolicyArgs a) 
                 g = -dnlp * p + we * p * (lp + H);
                 if (j == act) g += dnlp;
             }
-            dl[j] = g;
+            dl[j] = g * gs;
         }
     }
 }
