@@ -22,17 +22,6 @@ constexpr int kArenaThreads = 256;
 constexpr int kHdrWords = 8, kSlotWords = 8;
 constexpr int kSeated = 1, kDone = 2, kPartial = 4, kStalled = 8;
 
-__device__ __forceinline__ int block_sum_int(int v, int* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int r = 0;
-    for (int w = 0; w < kArenaThreads / 64; ++w) r += red[w];
-    return r;
-}
-
 struct RefereeArgs {
     int* state; int E;
     const float* rewards; const uint8_t* terminated; const uint8_t* truncated; const uint8_t* players;
@@ -47,7 +36,7 @@ __global__ __launch_bounds__(kArenaThreads) void arena_referee_kernel(RefereeArg
     int* st = a.state + kHdrWords + s * kSlotWords;
     if (s == 0 && tid == 0) {
         auto* seed = reinterpret_cast<unsigned long long*>(a.state);
-        *seed += 0x9E3779B97F4A7C15ull;                        // next ply's seed (a Weyl step; the sampler mixes it)
+        *seed += kKaWeyl;                                      // next ply's seed (a Weyl step; the sampler mixes it)
         a.state[2] += 1;
         if (a.refusal) *reinterpret_cast<long long*>(a.state + 6) = *a.refusal;
     }
@@ -65,10 +54,10 @@ __global__ __launch_bounds__(kArenaThreads) void arena_referee_kernel(RefereeArg
                 else dr += 1;
             }
         }
-        aw = block_sum_int(aw, red);
-        bw = block_sum_int(bw, red);
-        dr = block_sum_int(dr, red);
-        stalled = block_sum_int(stalled, red);
+        aw = ka_block_sum<kArenaThreads>(aw, red);
+        bw = ka_block_sum<kArenaThreads>(bw, red);
+        dr = ka_block_sum<kArenaThreads>(dr, red);
+        stalled = ka_block_sum<kArenaThreads>(stalled, red);
         if (tid == 0) {
             int ns = status;
             const int plies = st[6] + 1;
@@ -156,7 +145,7 @@ __global__ __launch_bounds__(kArenaThreads) void arena_record_pre_kernel(RecordP
     if (live) {
         int stalled = 0;
         for (int k = tid; k < a.E; k += kArenaThreads) stalled |= a.nlegal[e0 + k] == 0;
-        live = block_sum_int(stalled, red) == 0;               // :303-314: a slot with a zero-legal env appends nothing
+        live = ka_block_sum<kArenaThreads>(stalled, red) == 0; // :303-314: a slot with a zero-legal env appends nothing
     }
     if (!live) {
         if (blockIdx.y == 0) {
@@ -263,7 +252,7 @@ __global__ __launch_bounds__(kArenaThreads) void arena_features_kernel(FeaturesA
     if (!(status & kSeated) || (status & kDone)) return;        // uniform over the workgroup
     int stalled = 0;
     for (int k = tid; k < a.E; k += kArenaThreads) stalled |= a.nlegal[e0 + k] == 0;
-    if (block_sum_int(stalled, red) != 0) return;               // concurrent_matches.py:303-314, :410: a skipped slot records nothing
+    if (ka_block_sum<kArenaThreads>(stalled, red) != 0) return; // concurrent_matches.py:303-314, :410: a skipped slot records nothing
     const int round_ply = a.state[2];
     const int first = a.fcursors[s * kFeatCursorWords + 0];
     const int room = first < 0 ? 0 : max(0, a.cap - first);     // records of this ply that still fit

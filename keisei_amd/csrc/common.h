@@ -167,6 +167,52 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
+// Integer sum / max over a workgroup of THREADS threads (whole waves); red: THREADS / 64 ints of LDS.  Every thread calls
+// it and every thread gets the result.  The leading barrier lets the same `red` serve one reduction after another.
+template <int THREADS> __device__ __forceinline__ int ka_block_sum(int v, int* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int r = 0;
+    for (int w = 0; w < THREADS / 64; ++w) r += red[w];
+    return r;
+}
+template <int THREADS> __device__ __forceinline__ int ka_block_max(int v, int* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int r = red[0];
+    for (int w = 1; w < THREADS / 64; ++w) r = max(r, red[w]);
+    return r;
+}
+
+// One fp32 row copied by a workgroup of THREADS threads: 8-byte vectors where the row length and both addresses allow it
+// (a 50 x 9 x 9 observation row is 16 200 B: 8-byte aligned, not 16).
+template <int THREADS> __device__ __forceinline__ void ka_copy_row(float* dst, const float* src, int n, int tid) {
+    if ((n & 1) == 0 && (((uintptr_t)dst | (uintptr_t)src) & 7) == 0) {
+        const f32x2* s2 = reinterpret_cast<const f32x2*>(src);
+        f32x2* d2 = reinterpret_cast<f32x2*>(dst);
+        for (int i = tid; i < n / 2; i += THREADS) d2[i] = s2[i];
+    } else {
+        for (int i = tid; i < n; i += THREADS) dst[i] = src[i];
+    }
+}
+
+// The splitmix64 finaliser behind every draw on the device (the samplers' uniforms, the league's opponents and sides, the
+// SL mirror, the env's position hash): ONE body, so the same (seed, key) gives the same bits in every kernel and in the
+// numpy restatement (league_rollout._mix).  kKaWeyl is also the step by which a ply advances the sampler seed.
+constexpr unsigned long long kKaWeyl = 0x9E3779B97F4A7C15ull;
+__device__ __forceinline__ unsigned long long ka_mix64(unsigned long long x) {
+    x += kKaWeyl;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
 // workgroup barrier that orders LDS traffic only: __syncthreads() also drains the vector-memory counter, i.e. it waits
 // for every global load in flight (a weight prefetch issued before the barrier) and for global stores to complete
 #define KA_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")

@@ -52,36 +52,10 @@ enum { kSeed = 0, kPly = 2, kRows = 3, kBlocks = 4, kDropped = 5, kSamp = 6, kRe
 enum { kPAction = 0, kPLogp = 1, kPValue = 2, kPReward = 3, kPScore = 4, kPValid = 5, kPendCols = 6 };
 constexpr unsigned long long kSaltOpp = 0x6F70706Full, kSaltSide = 0x73696465ull;
 
-__device__ __forceinline__ unsigned long long league_mix(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 __device__ __forceinline__ unsigned long long league_draw(unsigned long long seed, unsigned long long salt, int env, int n) {
-    return league_mix(seed ^ league_mix((((unsigned long long)(unsigned)env << 32) | (unsigned)n) + salt));
+    return ka_mix64(seed ^ ka_mix64((((unsigned long long)(unsigned)env << 32) | (unsigned)n) + salt));
 }
 
-__device__ __forceinline__ int lg_block_sum(int v, int* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int r = 0;
-    for (int w = 0; w < kLgThreads / 64; ++w) r += red[w];
-    return r;
-}
-__device__ __forceinline__ int lg_block_max(int v, int* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int r = red[0];
-    for (int w = 1; w < kLgThreads / 64; ++w) r = max(r, red[w]);
-    return r;
-}
 struct LeagueArgs {
     int* state; int E, K, flush;
     // the ply before the env step
@@ -173,8 +147,8 @@ __global__ __launch_bounds__(kLgThreads) void league_plan_kernel(LeagueArgs a) {
         n1 += settle;
         nt1 += settle && done && !tm;
     }
-    n1 = lg_block_sum(n1, red);
-    nt1 = lg_block_sum(nt1, red);
+    n1 = ka_block_sum<kLgThreads>(n1, red);
+    nt1 = ka_block_sum<kLgThreads>(nt1, red);
 
     int run1 = 0, run2 = 0, runt1 = 0, runt2 = 0;
     int wins = 0, losses = 0, draws = 0, black = 0, white = 0, nterm = 0, ntrunc = 0, conflicts = 0, stall = 0;
@@ -287,13 +261,14 @@ __global__ __launch_bounds__(kLgThreads) void league_plan_kernel(LeagueArgs a) {
         // 8. seat the next ply: slot 0 is the learner, slot o + 1 opponent o
         a.model_of[k] = (a.players[k] & 1) == sd ? 0 : o + 1;
     }
-    wins = lg_block_sum(wins, red); losses = lg_block_sum(losses, red); draws = lg_block_sum(draws, red);
-    black = lg_block_sum(black, red); white = lg_block_sum(white, red);
-    nterm = lg_block_sum(nterm, red); ntrunc = lg_block_sum(ntrunc, red);
-    conflicts = lg_block_sum(conflicts, red); stall = lg_block_max(stall & 1, red) | (lg_block_max(stall & 2, red));
-    dropped = lg_block_sum(dropped, red); tdropped = lg_block_sum(tdropped, red);
-    const int g0 = lg_block_max(g.term_not_done, red), g1 = lg_block_max(g.bad_cat, red), g2 = lg_block_max(g.nan_score, red);
-    const int g3 = lg_block_max(g.peak, red);
+    constexpr int T = kLgThreads;
+    wins = ka_block_sum<T>(wins, red); losses = ka_block_sum<T>(losses, red); draws = ka_block_sum<T>(draws, red);
+    black = ka_block_sum<T>(black, red); white = ka_block_sum<T>(white, red);
+    nterm = ka_block_sum<T>(nterm, red); ntrunc = ka_block_sum<T>(ntrunc, red);
+    conflicts = ka_block_sum<T>(conflicts, red); stall = ka_block_max<T>(stall & 1, red) | (ka_block_max<T>(stall & 2, red));
+    dropped = ka_block_sum<T>(dropped, red); tdropped = ka_block_sum<T>(tdropped, red);
+    const int g0 = ka_block_max<T>(g.term_not_done, red), g1 = ka_block_max<T>(g.bad_cat, red), g2 = ka_block_max<T>(g.nan_score, red);
+    const int g3 = ka_block_max<T>(g.peak, red);
     if (tid == 0) {
         const int offered = run1 + run2;
         st[kRows] = first + (int)min((long long)offered, room);
@@ -305,7 +280,7 @@ __global__ __launch_bounds__(kLgThreads) void league_plan_kernel(LeagueArgs a) {
         st[kGuards + 3] = max(st[kGuards + 3], g3);
         if (step) {
             auto* seed = reinterpret_cast<unsigned long long*>(st);
-            *seed += 0x9E3779B97F4A7C15ull;                    // next ply's sampler seed, as the arena's referee steps it
+            *seed += kKaWeyl;                                  // next ply's sampler seed, as the arena's referee steps it
             st[kPly] += 1;
             if (a.refusal) *reinterpret_cast<long long*>(st + kRefusal) = *a.refusal;
             st[kWins] += wins; st[kLosses] += losses; st[kDraws] += draws; st[kBlack] += black; st[kWhite] += white;
@@ -327,16 +302,6 @@ __global__ __launch_bounds__(kLgThreads) void league_plan_kernel(LeagueArgs a) {
     }
 }
 
-__device__ __forceinline__ void copy_row(float* dst, const float* src, int n, int tid) {
-    if ((n & 1) == 0 && (((uintptr_t)dst | (uintptr_t)src) & 7) == 0) {
-        const f32x2* s2 = reinterpret_cast<const f32x2*>(src);
-        f32x2* d2 = reinterpret_cast<f32x2*>(dst);
-        for (int i = tid; i < n / 2; i += kLgThreads) d2[i] = s2[i];
-    } else {
-        for (int i = tid; i < n; i += kLgThreads) dst[i] = src[i];
-    }
-}
-
 __global__ __launch_bounds__(kLgThreads) void league_copy_kernel(LeagueArgs a) {
     const int e = blockIdx.x, tid = threadIdx.x;
     const int* plan = a.plan + (size_t)e * kLgPlan;
@@ -345,18 +310,18 @@ __global__ __launch_bounds__(kLgThreads) void league_copy_kernel(LeagueArgs a) {
     const Columns c = load_columns(a.desc);
     const size_t n = a.obs_elems, w = a.words;
     if (row1 >= 0) {                                            // the pending slot leaves before this ply's move takes it
-        copy_row(c.obs + row1 * n, a.p_obs + e * n, a.obs_elems, tid);
+        ka_copy_row<kLgThreads>(c.obs + row1 * n, a.p_obs + e * n, a.obs_elems, tid);
         for (int i = tid; i < a.words; i += kLgThreads) c.bits[row1 * w + i] = a.p_bits[e * w + i];
     }
-    if (ts1 >= 0) copy_row(a.t_obs + ts1 * n, a.term_obs + e * n, a.obs_elems, tid);
-    if (ts2 >= 0) copy_row(a.t_obs + ts2 * n, a.term_obs + e * n, a.obs_elems, tid);
+    if (ts1 >= 0) ka_copy_row<kLgThreads>(a.t_obs + ts1 * n, a.term_obs + e * n, a.obs_elems, tid);
+    if (ts2 >= 0) ka_copy_row<kLgThreads>(a.t_obs + ts2 * n, a.term_obs + e * n, a.obs_elems, tid);
     if (row2 >= 0) {
-        copy_row(c.obs + row2 * n, a.obs + e * n, a.obs_elems, tid);
+        ka_copy_row<kLgThreads>(c.obs + row2 * n, a.obs + e * n, a.obs_elems, tid);
         for (int i = tid; i < a.words; i += kLgThreads) c.bits[row2 * w + i] = a.bits[e * w + i];
     }
     if (keep) {
         __syncthreads();                                        // row1's reads of the slot are done
-        copy_row(a.p_obs + e * n, a.obs + e * n, a.obs_elems, tid);
+        ka_copy_row<kLgThreads>(a.p_obs + e * n, a.obs + e * n, a.obs_elems, tid);
         for (int i = tid; i < a.words; i += kLgThreads) a.p_bits[e * w + i] = a.bits[e * w + i];
     }
 }

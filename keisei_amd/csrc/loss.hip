@@ -450,13 +450,6 @@ struct SampleArgs {
     const long long* seed_dev; const int* model_of; int K;      // play form only
 };
 
-__device__ __forceinline__ unsigned long long sample_mix(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
 template <bool Play>
 __global__ __launch_bounds__(kPolThreads) void policy_sample_kernel(SampleArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -516,7 +509,7 @@ __global__ __launch_bounds__(kPolThreads) void policy_sample_kernel(SampleArgs a
     for (int w = 0; w < kPolThreads / 64; ++w) { if (w < wave) base += wave_tot[w]; total += wave_tot[w]; }
     incl += base;
     const unsigned long long seed = Play ? (unsigned long long)*a.seed_dev : a.seed;
-    const unsigned long long h = sample_mix(seed ^ sample_mix((unsigned long long)b + 0x5851F42D4C957F2Dull));
+    const unsigned long long h = ka_mix64(seed ^ ka_mix64((unsigned long long)b + 0x5851F42D4C957F2Dull));
     const float u = (float)(h >> 40) * (1.0f / 16777216.0f);   // 24 bits: [0, 1)
     const float target = u * total;
     if (local > 0.f) {

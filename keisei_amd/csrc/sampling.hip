@@ -51,14 +51,6 @@ __device__ __forceinline__ float sc_reduce(float v, float* red, bool is_max) {
     return r;
 }
 
-// the play sampler's mix (loss.hip, sample_mix): the same (seed, row) gives the same uniform
-__device__ __forceinline__ unsigned long long sc_mix(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
 // (v, i) comes before (bv, bi) in the candidate order: greater logit, equal logits by lower action (a NaN never does)
 __device__ __forceinline__ bool sc_before(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
@@ -187,7 +179,8 @@ __global__ __launch_bounds__(kScThreads) void policy_sample_ctl_kernel(CtlArgs a
     for (int w = 0; w < kScWaves; ++w) { if (w < wave) base += wave_tot[w]; total += wave_tot[w]; }
     incl += base;
     const unsigned long long seed = (unsigned long long)*a.seed_dev;
-    const unsigned long long h = sc_mix(seed ^ sc_mix((unsigned long long)b + 0x5851F42D4C957F2Dull));
+    // the play sampler's draw (loss.hip): the same (seed, row) gives the same uniform
+    const unsigned long long h = ka_mix64(seed ^ ka_mix64((unsigned long long)b + 0x5851F42D4C957F2Dull));
     const float u = (float)(h >> 40) * (1.0f / 16777216.0f);   // 24 bits: [0, 1)
     const float target = u * total;
     if (local > 0.f) {                                         // (as the play sampler: a chunk whose weights all underflow is no chunk of S)

@@ -39,27 +39,6 @@ enum { kSeed = 0, kPly = 2, kRows = 3, kPlies = 4, kDropped = 5, kSamp = 6, kRef
        kWins = 14, kLosses = 15, kDraws = 16, kBlack = 17, kWhite = 18, kTerminated = 19, kTruncated = 20, kGuards = 21,
        kStall = 25 };
 
-__device__ __forceinline__ int sp_block_sum(int v, int* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int r = 0;
-    for (int w = 0; w < kSpThreads / 64; ++w) r += red[w];
-    return r;
-}
-__device__ __forceinline__ int sp_block_max(int v, int* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int r = red[0];
-    for (int w = 1; w < kSpThreads / 64; ++w) r = max(r, red[w]);
-    return r;
-}
-
 struct SelfPlayArgs {
     int* state; int E;
     // the ply before the env step
@@ -147,16 +126,17 @@ __global__ __launch_bounds__(kSpThreads) void selfplay_plan_kernel(SelfPlayArgs 
         }
         plan[0] = (int)row; plan[1] = ts;
     }
-    wins = sp_block_sum(wins, red); losses = sp_block_sum(losses, red); draws = sp_block_sum(draws, red);
-    black = sp_block_sum(black, red); white = sp_block_sum(white, red);
-    nterm = sp_block_sum(nterm, red); ntrunc = sp_block_sum(ntrunc, red);
-    written = sp_block_sum(written, red); dropped = sp_block_sum(dropped, red); tdropped = sp_block_sum(tdropped, red);
-    stall = sp_block_max(stall, red);
-    g_term = sp_block_max(g_term, red); g_cat = sp_block_max(g_cat, red); g_nan = sp_block_max(g_nan, red);
-    g_peak = sp_block_max(g_peak, red);
+    constexpr int T = kSpThreads;
+    wins = ka_block_sum<T>(wins, red); losses = ka_block_sum<T>(losses, red); draws = ka_block_sum<T>(draws, red);
+    black = ka_block_sum<T>(black, red); white = ka_block_sum<T>(white, red);
+    nterm = ka_block_sum<T>(nterm, red); ntrunc = ka_block_sum<T>(ntrunc, red);
+    written = ka_block_sum<T>(written, red); dropped = ka_block_sum<T>(dropped, red); tdropped = ka_block_sum<T>(tdropped, red);
+    stall = ka_block_max<T>(stall, red);
+    g_term = ka_block_max<T>(g_term, red); g_cat = ka_block_max<T>(g_cat, red); g_nan = ka_block_max<T>(g_nan, red);
+    g_peak = ka_block_max<T>(g_peak, red);
     if (tid == 0) {
         auto* seed = reinterpret_cast<unsigned long long*>(st);
-        *seed += 0x9E3779B97F4A7C15ull;                         // next ply's sampler seed, as the arena's referee steps it
+        *seed += kKaWeyl;                                       // next ply's sampler seed, as the arena's referee steps it
         st[kPly] = ply + 1;
         st[kPlies] += 1;
         st[kRows] += written;
@@ -172,17 +152,6 @@ __global__ __launch_bounds__(kSpThreads) void selfplay_plan_kernel(SelfPlayArgs 
     }
 }
 
-// 8-byte vectors where the row length and both addresses allow it (a 50 x 9 x 9 row is 16 200 B: 8-byte aligned, not 16)
-__device__ __forceinline__ void sp_copy_row(float* dst, const float* src, int n, int tid) {
-    if ((n & 1) == 0 && (((uintptr_t)dst | (uintptr_t)src) & 7) == 0) {
-        const f32x2* s2 = reinterpret_cast<const f32x2*>(src);
-        f32x2* d2 = reinterpret_cast<f32x2*>(dst);
-        for (int i = tid; i < n / 2; i += kSpThreads) d2[i] = s2[i];
-    } else {
-        for (int i = tid; i < n; i += kSpThreads) dst[i] = src[i];
-    }
-}
-
 __global__ __launch_bounds__(kSpThreads) void selfplay_copy_kernel(SelfPlayArgs a) {
     const int e = blockIdx.x, tid = threadIdx.x;
     const long long row = a.plan[(size_t)e * kSpPlan];
@@ -191,9 +160,9 @@ __global__ __launch_bounds__(kSpThreads) void selfplay_copy_kernel(SelfPlayArgs 
     const size_t n = a.obs_elems, w = a.words;
     float* c_obs = reinterpret_cast<float*>(a.desc[0]);
     uint32_t* c_bits = reinterpret_cast<uint32_t*>(a.desc[1]);
-    sp_copy_row(c_obs + row * n, a.obs + e * n, a.obs_elems, tid);
+    ka_copy_row<kSpThreads>(c_obs + row * n, a.obs + e * n, a.obs_elems, tid);
     for (int i = tid; i < a.words; i += kSpThreads) c_bits[row * w + i] = a.bits[e * w + i];
-    if (ts >= 0) sp_copy_row(a.t_obs + ts * n, a.term_obs + e * n, a.obs_elems, tid);
+    if (ts >= 0) ka_copy_row<kSpThreads>(a.t_obs + ts * n, a.term_obs + e * n, a.obs_elems, tid);
 }
 
 }  // namespace

@@ -151,12 +151,6 @@ __device__ bool pawn_drop_mates(lds_board board, lds_dirs dirs, int to, int me, 
     return true;
 }
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 __device__ __forceinline__ unsigned long long wave_xor64(unsigned long long v) {
     unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
 #pragma unroll
@@ -242,10 +236,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     };
     auto position_key = [&]() {
         unsigned long long h = 0;
-        for (int i = lane; i < 81; i += 64) { const int p = s_board[i]; if (p) h ^= mix64((unsigned long long)(i * 64 + p)); }
-        if (lane < 14 && s_hands[lane]) h ^= mix64(0x4000ull + lane * 32 + s_hands[lane]);
+        for (int i = lane; i < 81; i += 64) { const int p = s_board[i]; if (p) h ^= ka_mix64((unsigned long long)(i * 64 + p)); }
+        if (lane < 14 && s_hands[lane]) h ^= ka_mix64(0x4000ull + lane * 32 + s_hands[lane]);
         h = wave_xor64(h);
-        return side ? h ^ mix64(0x8000ull) : h;
+        return side ? h ^ ka_mix64(0x8000ull) : h;
     };
     auto side_in_check = [&](int color) {                      // game.rs:98-105 (wave-uniform result); ten lanes, one probe each
         const int k = king_of(color);
@@ -267,7 +261,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
         const int count = a.pool_hdr[0];
         if (count > 0) {
             const unsigned long long seed = (unsigned long long)(unsigned)a.pool_hdr[2] | ((unsigned long long)(unsigned)a.pool_hdr[3] << 32);
-            const unsigned long long h = mix64(seed ^ mix64((((unsigned long long)(unsigned)env << 32) | games) + kSaltPool));
+            const unsigned long long h = ka_mix64(seed ^ ka_mix64((((unsigned long long)(unsigned)env << 32) | games) + kSaltPool));
             const uint8_t* row = a.pool + (size_t)(((h >> 32) * (unsigned long long)count) >> 32) * kPoolRowBytes;
             for (int i = lane; i < 81; i += 64) s_board[i] = row[i];
             if (lane < 14) s_hands[lane] = row[81 + lane];

@@ -92,12 +92,6 @@ __global__ __launch_bounds__(kPkThreads) void sl_pack_kernel(const uint32_t* __r
     }
 }
 
-__device__ __forceinline__ unsigned long long sl_mix(unsigned long long x) {      // the splitmix64 finaliser
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 constexpr unsigned long long kSaltMirror = 0x6D6972726F72ull;     // "mirror"
 
 // The reflected action of a spatial action index square * 139 + slot (keisei_amd/shogi_gym.py, _DIRS clockwise from north):
@@ -127,7 +121,7 @@ __global__ __launch_bounds__(kPkThreads) void sl_gather_kernel(const uint32_t* _
     if constexpr (kAug) {
         if (inside && mode == 1) reflect = true;
         if (inside && mode == 2)
-            reflect = (sl_mix(seed ^ sl_mix((((unsigned long long)epoch << 32) | (uint32_t)r) + kSaltMirror)) >> 63) != 0ull;
+            reflect = (ka_mix64(seed ^ ka_mix64((((unsigned long long)epoch << 32) | (uint32_t)r) + kSaltMirror)) >> 63) != 0ull;
     }
     if (tid < kPkWords) s_row[tid] = inside ? packed[(size_t)r * kPkWords + tid] : 0u;
     __syncthreads();

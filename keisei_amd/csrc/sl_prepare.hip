@@ -51,17 +51,6 @@ struct SlArgs {
     uint32_t* shard; int rows;
 };
 
-__device__ __forceinline__ int sl_block_sum(int v, int* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int r = 0;
-    for (int w = 0; w < kSlThreads / 64; ++w) r += red[w];
-    return r;
-}
-
 __global__ __launch_bounds__(kSlThreads) void sl_plan_kernel(SlArgs a) {
     __shared__ int red[kSlThreads / 64];
     const int tid = threadIdx.x, E = a.E;
@@ -93,8 +82,9 @@ __global__ __launch_bounds__(kSlThreads) void sl_plan_kernel(SlArgs a) {
         a.write[k] = legal;
         written += legal; filler += !legal;
     }
-    written = sl_block_sum(written, red); filler = sl_block_sum(filler, red); illegal = sl_block_sum(illegal, red);
-    rules = sl_block_sum(rules, red); stall = sl_block_sum(stall, red);
+    constexpr int T = kSlThreads;
+    written = ka_block_sum<T>(written, red); filler = ka_block_sum<T>(filler, red); illegal = ka_block_sum<T>(illegal, red);
+    rules = ka_block_sum<T>(rules, red); stall = ka_block_sum<T>(stall, red);
     if (tid == 0) {
         st[kSlPlies] += 1; st[kSlWritten] += written; st[kSlFiller] += filler; st[kSlIllegal] += illegal;
         st[kSlRules] += rules; st[kSlStall] += stall;

@@ -133,7 +133,7 @@ def mirror_records(records) -> np.ndarray:
 
 
 def _mix64(x: np.ndarray) -> np.ndarray:
-    """The splitmix64 finaliser over uint64 arrays (wrapping arithmetic), ``sl_mix`` of csrc/sl_data.hip."""
+    """The splitmix64 finaliser over uint64 arrays (wrapping arithmetic), ``ka_mix64`` of csrc/common.h."""
     x = x + np.uint64(0x9E3779B97F4A7C15)
     x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
     x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)

@@ -25,14 +25,13 @@ that grows.  The bootstrap override of truncated games (:1250-1283) is deferred:
 observation, the host runs one learner forward over exactly those rows at the sync point.  The learner's weights do
 not change inside ``collect`` and eval mode couples no two boards, so the values are what an in-ply forward gives.
 
-``_league_host`` restates the protocol on the CPU from this package's host pieces (``PendingTransitions``,
-``to_learner_perspective``, ``_compute_value_cats``, a host ``KataGoRolloutBuffer``); the tests hold the kernel to it and
-hold it to the reference (tests/golden/g13_league_rollout.npz).
+The front of the ply and the skeleton around it are ``_device_ply.py``'s (``DevicePly``, ``DeviceRollout``), shared with
+``SelfPlayRollout``.  ``_league_host`` restates the protocol on the CPU from this package's host pieces
+(``PendingTransitions``, ``to_learner_perspective``, ``_compute_value_cats``, a host ``KataGoRolloutBuffer``); the tests
+hold the kernel to it and hold it to the reference (tests/golden/g13_league_rollout.npz).
 """
 from __future__ import annotations
 
-import gc
-import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
@@ -40,30 +39,27 @@ import numpy as np
 import torch
 
 from keisei_amd import _lib
-from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS, OBS_CHANNELS, POOL_ROW_BYTES, VecEnv
+from keisei_amd.shogi_gym import MASK_WORDS, POOL_ROW_BYTES
 
-from .game_log import GameLog, RecordedGame
+from ._device_ply import (_OBS_ELEMS, _OBS_SHAPE, _DROPPED, _PLY, _ROWS, _SAMP, _SEED, _TRUNC, _TRUNC_DROPPED,  # noqa: F401
+                          DeviceRollout, check_loop_args, check_value_args)
+from .game_log import RecordedGame
 from .katago_loop import (_ZERO_LEGAL, PendingTransitions, _compute_value_cats, sign_correct_bootstrap,
                           to_learner_perspective)
-from .katago_ppo import SCORE_NORMALIZATION, KataGoRolloutBuffer, _check_step_inputs
+from .katago_ppo import SCORE_NORMALIZATION, KataGoRolloutBuffer
 from .model_group import SEResNetGroup
-from .policy_insight import InsightRecorder
 from .sampling import GAME_PLY_BYTE, SamplingControls, league_controls
-from .value_adapter import MultiHeadValueAdapter
 
 __all__ = ["LeagueRollout", "LeagueRolloutStats", "league_draw", "draw_opponents", "draw_sides", "cum_thresholds"]
 
-_OBS_SHAPE = (OBS_CHANNELS, 9, 9)
-_OBS_ELEMS = OBS_CHANNELS * 81
-# state words (csrc/league.hip)
-_SEED, _PLY, _ROWS, _BLOCKS, _DROPPED, _SAMP, _REFUSAL, _DRAW_SEED, _TRUNC, _TRUNC_DROPPED = 0, 2, 3, 4, 5, 6, 8, 10, 12, 13
-_WINS, _LOSSES, _DRAWS, _BLACK, _WHITE, _TERMINATED, _TRUNCATED, _GUARDS, _CONFLICT, _STALL, _HDR = 14, 15, 16, 17, 18, 19, 20, 21, 25, 26, 32
+# state words of csrc/league.hip beside the ones it shares with the self-play kernel; _HDR: the per-opponent results begin
+_BLOCKS, _DRAW_SEED, _CONFLICT, _STALL, _HDR = 4, 10, 25, 26, 32
 SALT_OPPONENT, SALT_SIDE, SALT_EPOCH_SIDE = 0x6F70706F, 0x73696465, 0x65706F63
 
 
 # ---------------------------------------------------------------------------------------------- draws (numpy form)
 def _mix(x: np.ndarray) -> np.ndarray:
-    """splitmix64 finaliser on uint64 arrays (wrapping arithmetic), as ``sample_mix`` of csrc/loss.hip."""
+    """splitmix64 finaliser on uint64 arrays (wrapping arithmetic), as ``ka_mix64`` of csrc/common.h."""
     with np.errstate(over="ignore"):
         x = x + np.uint64(0x9E3779B97F4A7C15)
         x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
@@ -125,16 +121,8 @@ class LeagueRolloutStats:
     games_dropped: int = 0              # finished games that did not fit the log between two sync points
 
 
-def _stats_from_state(st: np.ndarray, opponent_ids: Sequence[int], stats: LeagueRolloutStats) -> None:
-    stats.rows, stats.adds = int(st[_ROWS]), int(st[_BLOCKS])
-    stats.wins, stats.losses, stats.draws = int(st[_WINS]), int(st[_LOSSES]), int(st[_DRAWS])
-    stats.black_wins, stats.white_wins = int(st[_BLACK]), int(st[_WHITE])
-    stats.terminated, stats.truncated = int(st[_TERMINATED]), int(st[_TRUNCATED])
-    stats.opponent_results = {oid: [int(v) for v in st[_HDR + 3 * k:_HDR + 3 * k + 3]] for k, oid in enumerate(opponent_ids)}
-
-
 def _check_args(num_opponents: int, opponent_ids, num_envs: int, max_ply: int, sync_every: int, graph: bool, record: bool,
-                score_norm: float, value_adapter) -> None:
+                score_norm: float, value_adapter, start_pool_capacity: int = 0, game_log: int = 0) -> None:
     if num_opponents == 0:
         raise ValueError("LeagueRollout needs at least one opponent (the no-opponent branch is select_actions' loop)")
     if len(opponent_ids) != num_opponents or len(set(opponent_ids)) != num_opponents:
@@ -145,25 +133,11 @@ def _check_args(num_opponents: int, opponent_ids, num_envs: int, max_ply: int, s
             raise ValueError(f"num_envs must lie in [1, {top}], got {num_envs}")
     elif num_envs < 1:
         raise ValueError(f"num_envs must be positive, got {num_envs}")
-    if not 1 <= max_ply <= 65535:
-        raise ValueError(f"max_ply must lie in [1, 65535], got {max_ply}")
-    if sync_every < 1:
-        raise ValueError(f"sync_every must be at least 1, got {sync_every}")
-    if sync_every > max_ply:
-        raise ValueError(f"sync_every ({sync_every}) must not exceed max_ply ({max_ply}): an env may truncate only once "
-                         "between two sync points (one truncation slot per env)")
-    if graph and record:
-        raise ValueError("record=True runs without a graph (graph=False)")
-    if graph and sync_every % 2:
-        raise ValueError(f"graph=True needs an even sync_every (VecEnv alternates two result buffers), got {sync_every}")
-    if not math.isfinite(score_norm) or score_norm == 0:
-        raise ValueError(f"score_norm must be finite and non-zero, got {score_norm}")
-    if value_adapter is not None and type(value_adapter) is not MultiHeadValueAdapter:
-        raise ValueError(f"value_adapter must be None or a MultiHeadValueAdapter (the kernel blends by its "
-                         f"score_blend_alpha), got {type(value_adapter).__name__}")
+    check_loop_args(max_ply, sync_every, graph, record, start_pool_capacity, game_log, one_truncation_slot=True)
+    check_value_args(score_norm, value_adapter)
 
 
-class LeagueRollout:
+class LeagueRollout(DeviceRollout):
     """The learner's rollout against its league cohort, resident on the device (see module docstring).
 
     ``roll = LeagueRollout(learner, opponents, opponent_ids, num_envs=512, max_ply=500, ...)``;
@@ -172,25 +146,20 @@ class LeagueRollout:
     ``KataGoPPOAlgorithm.update``; ``roll.refresh()`` after the update brings the learner's new weights into the group;
     ``roll.set_opponents`` seats a new cohort.  The env is not reset between ``collect`` calls (the reference carries
     games over epochs); ``reset()`` is explicit.  ``seed`` fixes sampling and re-draws from the last ``reset()`` on.
-    ``record=True`` (no graph) keeps every ply's inputs and outputs in ``self.record`` for tests.  ``start_pool_capacity > 0`` gives the env a pool of
-    start positions of that size: ``roll.env.set_start_positions(...)`` / ``set_start_sfens(...)`` between ``collect`` calls make later
-    games start from them (no re-capture; see ``VecEnv``).  ``game_log=K > 0`` adds a device-resident ``GameLog`` of K
-    records to the ply (one launch, ``ka_gamelog_step_env``, between the env step and ``ka_league_step``): ``collect``
-    drains it at every sync point onto ``LeagueRolloutStats.games``.  A game names its players by id (``learner_id`` and
-    ``opponent_ids``: the players who ended it, the ones its result is tallied for) and the learner's colour; it is
-    ``carried`` where its side or its opponent changed in the middle of it (the epoch's side re-draw) and where it spans a
-    ``set_opponents``.
-    ``live_games()`` between two ``collect`` calls gives the games still in progress.  Without ``game_log`` the ply is
-    launch for launch what it was.  ``move_history=True`` has the env keep the move notes of the games in progress (two
-    more launches inside ``env.step``); ``spectator_data()`` between two ``collect`` calls is the dashboard feed.
-    ``insight=top_k > 0`` adds the policy insight to the ply (one launch, ``ka_policy_insight``, between the sampler and the
-    env step; ``policy_insight.py``), for the learner's and the opponents' moves alike: every ``spectator_data()`` dict gains
-    ``insight``, the figures of the env's last move at ``insight_temperature``, and with ``move_history=True`` every history
-    entry gains its move's probability, rank, entropy, win probability and top candidates.  With 0 nothing changes.
+    ``record=True`` (no graph) keeps every ply's inputs and outputs in ``self.record`` for tests.
+    ``start_pool_capacity``, ``game_log``, ``move_history``, ``insight`` and ``insight_temperature`` are ``DevicePly``'s
+    (``_device_ply.py``).  Here the log's launch is ``ka_gamelog_step_env`` and ``collect`` drains it onto
+    ``LeagueRolloutStats.games``: a game names its players by id (``learner_id`` and ``opponent_ids``: the players who
+    ended it, the ones its result is tallied for) and the learner's colour; it is ``carried`` where its side or its
+    opponent changed in the middle of it (the epoch's side re-draw) and where it spans a ``set_opponents``.  The insight
+    covers the learner's and the opponents' moves alike.
     ``opponent_sampling=`` (one ``SamplingControls`` for every opponent, or one per opponent; ``sampling.py``) has the
     opponents play through ``ka_policy_sample_ctl`` -- sharper, greedy or more diverse.  The learner's row of the controls
     table is always neutral, which is the play sampler bit for bit: its actions and the log-probs that reach the buffer stay
-    draws from its own distribution, the PPO behaviour policy.  With None the ply is launch for launch what it was."""
+    draws from its own distribution, the PPO behaviour policy.  Without an option the ply is launch for launch what it is
+    without it."""
+
+    _LAYOUT = "ka_league_layout"
 
     def __init__(self, learner, opponents: Sequence, opponent_ids: Sequence[int], *, num_envs: int = 512, max_ply: int = 500,
                  value_adapter=None, score_norm: float = SCORE_NORMALIZATION, color_randomization: bool = False,
@@ -200,54 +169,32 @@ class LeagueRollout:
                  insight_temperature: float = 1.0, opponent_sampling=None) -> None:
         opponents, opponent_ids = list(opponents), [int(i) for i in opponent_ids]
         _check_args(len(opponents), opponent_ids, int(num_envs), int(max_ply), int(sync_every), bool(graph), bool(record),
-                    float(score_norm), value_adapter)
+                    float(score_norm), value_adapter, start_pool_capacity, game_log)
         self._ctl_host = league_controls(opponent_sampling, len(opponents))
         self._opponent_sampling = opponent_sampling
-        self._ctl: Optional[torch.Tensor] = None
-        if start_pool_capacity < 0:
-            raise ValueError(f"start_pool_capacity must not be negative, got {start_pool_capacity}")
-        if game_log < 0:
-            raise ValueError(f"game_log must not be negative, got {game_log}")
         self.learner_id = int(learner_id)
         self._cum_host = cum_thresholds(opponent_weights, len(opponents))
-        self.group = self._make_group(learner, opponents)
         self.learner, self.opponent_ids = learner, opponent_ids
-        self.device = self.group.device
-        self.num_envs, self.max_ply, self.sync_every = int(num_envs), int(max_ply), int(sync_every)
-        self.graph, self.seed, self.record_enabled = bool(graph), seed, bool(record)
-        self.value_adapter, self.score_norm = value_adapter, float(score_norm)
-        self.alpha = 0.0 if value_adapter is None else float(value_adapter.score_blend_alpha)
         self.color_randomization = bool(color_randomization)
-        self.record: List[dict] = []
-        N, dev = self.num_envs, self.device
         q = lambda which: _lib.query("ka_league_layout", which)  # noqa: E731
+        # the controls table of ka_policy_sample_ctl holds row 0, the learner, neutral
+        self._build(self._make_group(learner, opponents), num_envs=num_envs, max_ply=max_ply, sync_every=sync_every,
+                    graph=graph, seed=seed, record=record, value_adapter=value_adapter, score_norm=score_norm,
+                    trunc_words=q(3), start_pool_capacity=int(start_pool_capacity), game_log=game_log, envs_per_slot=int(num_envs),
+                    move_history=move_history, insight=insight, insight_temperature=insight_temperature,
+                    controls=self._ctl_host)
+        N, dev = self.num_envs, self.device
         with torch.cuda.device(dev):
             z = lambda *s, dtype=torch.int32: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731
-            self.env = VecEnv(N, self.max_ply, "katago", "spatial", device=dev, output="torch", check_actions=False,
-                              start_pool_capacity=int(start_pool_capacity), move_history=bool(move_history))
-            self._actions, self._logp, self._nlegal = z(N, dtype=torch.int64), z(N, dtype=torch.float32), z(N)
-            self._values = z(N, dtype=torch.float32)
-            self._model_of, self._learner_of = z(N), z(N)
-            self._side, self._opp, self._games, self._stall = z(N, dtype=torch.uint8), z(N), z(N), z(N, dtype=torch.uint8)
+            self._side, self._opp, self._games = z(N, dtype=torch.uint8), z(N), z(N)
             self._p_obs, self._p_bits = z(N, *_OBS_SHAPE, dtype=torch.float32), z(N, MASK_WORDS)
             self._p_scal = z(q(2), N)
-            self._t_obs, self._t_list = z(N, *_OBS_SHAPE, dtype=torch.float32), z(N, q(3))
-            self._plan = z(N, q(0))
-            self._desc = z(q(1), dtype=torch.int64)
-            self._desc_host = torch.zeros(q(1), dtype=torch.int64).pin_memory()
             self._side_host = torch.zeros(N, dtype=torch.uint8).pin_memory()
-            self.game_log: Optional[GameLog] = GameLog(self.env, capacity=int(game_log), envs_per_slot=N) if game_log else None
-            self.insight: Optional[InsightRecorder] = InsightRecorder(self.env, insight, insight_temperature) if insight else None
             self._every_env = z(1, 4)                             # a seat job naming the one slot of all envs
             self._ids: Optional[torch.Tensor] = None
-        self._graphs: Dict[int, torch.cuda.CUDAGraph] = {}
         self._collects = 0
         self._seat_cohort()
-        with torch.cuda.device(dev), torch.no_grad():            # load every kernel of the ply before any capture
-            self.reset()
-            self._ply()
-            self._ply()
-        self.reset()
+        self._warm_up()
 
     # ------------------------------------------------------------------ cohort
     @staticmethod
@@ -265,16 +212,12 @@ class LeagueRollout:
     def _seat_cohort(self) -> None:
         """Buffers whose size follows the number of opponents; the header of an existing state is kept."""
         K, dev = len(self.opponent_ids), self.device
+        old = getattr(self, "_state", None)
+        self._new_state(_lib.query("ka_league_state_words", K))
         with torch.cuda.device(dev):
-            old = getattr(self, "_state", None)
-            self._state = torch.zeros(_lib.query("ka_league_state_words", K), dtype=torch.int32, device=dev)
             if old is not None:
                 self._state[:_HDR].copy_(old[:_HDR])
-            self._state_host = torch.zeros(self._state.shape, dtype=torch.int32).pin_memory()
             self._cum = torch.from_numpy(self._cum_host.view(np.int32).copy()).to(dev)
-            self._ws = self.group._tables.workspace(self.num_envs)
-            # the controls table of ka_policy_sample_ctl (row 0, the learner, neutral): the graphs are captured anew below
-            self._ctl = None if self._ctl_host is None else torch.from_numpy(self._ctl_host).to(dev)
             if self.game_log is not None:                         # the ids the log names the players by: the same words
                 ids = torch.tensor([self.learner_id, *self.opponent_ids], dtype=torch.int32)       # where K is unchanged
                 if self._ids is None or self._ids.numel() != K + 1:
@@ -306,6 +249,7 @@ class LeagueRollout:
         else:
             self.group.refresh()
         self.opponent_ids, self._cum_host = opponent_ids, cum
+        self.ply.seat(self.group, self._ctl_host)                 # a new workspace and table: the graphs are captured anew
         self._seat_cohort()
         with torch.cuda.device(self.device):
             if self.game_log is not None:                         # an unchanged index may name another model now: every game
@@ -314,15 +258,11 @@ class LeagueRollout:
             self._opp.copy_(torch.from_numpy(draw_opponents(self._draw_seed, np.arange(self.num_envs), games, cum)))
             self._seat()
 
-    def refresh(self) -> None:
-        """After ``ppo.update()`` (or any in-place edit of weights): the group's snapshot follows the models."""
-        self.group.refresh()
-
     # ------------------------------------------------------------------ state
     def reset(self) -> None:
         """Every env back to the start position, no pending transition, fresh seed, opponents and sides drawn anew."""
         N, dev = self.num_envs, self.device
-        seed = self.seed if self.seed is not None else int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        seed = self._fresh_seed()
         self._draw_seed = int(seed)
         with torch.cuda.device(dev):
             hdr = torch.zeros(self._state.shape, dtype=torch.int32)
@@ -337,11 +277,7 @@ class LeagueRollout:
             self._opp.copy_(torch.from_numpy(draw_opponents(seed, envs, np.zeros(N, np.int64), self._cum_host)))
             side = draw_sides(seed, envs, np.zeros(N, np.int64)) if self.color_randomization else np.zeros(N, np.uint8)
             self._side.copy_(torch.from_numpy(side))
-            self.env.reset()
-            if self.game_log is not None:
-                self.game_log.begin()
-            if self.insight is not None:
-                self.insight.clear()
+            self.ply.reset()
             self._seat()
         self._collects = 0
         self.record = []
@@ -359,30 +295,16 @@ class LeagueRollout:
     # ------------------------------------------------------------------ one ply
     def _ply(self) -> None:
         """forward -> sample -> step -> league bookkeeping on the current stream; no host synchronisation."""
-        env, N, K = self.env, self.num_envs, len(self.opponent_ids)
-        st = _lib.stream_ptr(self.device)
-        cur, prev = env.current(), env._cur
-        logits, value, score = self.group._tables.forward(cur.observations, self._model_of, ws=self._ws)
+        ply, N, K = self.ply, self.num_envs, len(self.opponent_ids)
         sp = self._state.data_ptr()
-        if self._ctl is None:
-            _lib.call("ka_policy_sample_play", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of, K + 1,
-                      self._actions, self._logp, self._nlegal, sp + 4 * _SAMP, N, ACTION_SPACE, st)
-        else:                                             # the game ply of the position to move in: byte 100 of the state row
-            _lib.call("ka_policy_sample_ctl", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of, K + 1,
-                      self._ctl, env._state.data_ptr() + GAME_PLY_BYTE, env._state.shape[1], self._actions, self._logp,
-                      self._nlegal, sp + 4 * _SAMP, N, ACTION_SPACE, st)
-        if self.insight is not None:                      # while the logits exist, before the step moves the history count
-            self.insight.step(logits, cur.legal_mask_bits, self._actions, value, env._players[prev], self._model_of, K + 1,
-                              sp + 4 * _SAMP, st)
-        r = env.step(self._actions)
-        if self.game_log is not None:                     # before ka_league_step re-draws side and opp of finished envs
-            self.game_log.step_env(self._actions, r.rewards, r.terminated, r.truncated, env._players[prev],
-                                   r.step_metadata.termination_reason, side=self._side, opp=self._opp, ids=self._ids,
-                                   opponents=K, nlegal=self._nlegal, ply_counter=sp + 4 * _PLY)
+        cur, pre, value, score, st = ply.move(self._model_of, K + 1, sp, sp + 4 * self._SAMP)
+        r = ply.step()
+        # before ka_league_step re-draws side and opp of finished envs
+        ply.log(r, pre, side=self._side, opp=self._opp, ids=self._ids, opponents=K, ply_counter=sp + 4 * _PLY)
         _lib.call("ka_league_step", self._state, N, K, 0, cur.observations, cur.legal_mask_bits, self._actions, self._logp,
-                  value, score if self.alpha != 0.0 else None, self.alpha, self._nlegal, env._players[prev], r.rewards,
+                  value, score if self.alpha != 0.0 else None, self.alpha, self._nlegal, pre, r.rewards,
                   r.terminated, r.truncated, r.current_players, r.step_metadata.material_balance, self.score_norm,
-                  r.terminal_observations, env._err.data_ptr() + 8, self._side, self._opp, self._games, self._cum,
+                  r.terminal_observations, self.env._err.data_ptr() + 8, self._side, self._opp, self._games, self._cum,
                   int(self.color_randomization), self._model_of, self._stall, self._values, self._p_obs, self._p_bits,
                   self._p_scal, self._t_obs, self._t_list, self._desc, self._plan, _OBS_ELEMS, MASK_WORDS, st)
 
@@ -405,63 +327,17 @@ class LeagueRollout:
                    reason=env._reason[c].cpu().numpy(), state=env._state[:, :POOL_ROW_BYTES].cpu().numpy())
         self.record.append(rec)
 
-    def _capture(self, parity: int) -> torch.cuda.CUDAGraph:
-        """Capture sync_every plies for the env's current buffer parity (an even count: the parity is the same afterwards)."""
-        g = torch.cuda.CUDAGraph()
-        # torch.cuda.graph does not collect garbage on entry.  Observed: a dead rollout object (captured graphs, pinned
-        # buffers) still waiting in a reference cycle was collected inside a later capture, and the process aborted in its
-        # destructor.  After a collection here, what the capture itself allocates holds no such object.
-        gc.collect()
-        with torch.cuda.graph(g):
-            for _ in range(self.sync_every):
-                self._ply()
-        self._graphs[parity] = g
-        return g
-
-    def _chunk(self, plies: int) -> None:
-        if self.graph and plies == self.sync_every:
-            (self._graphs.get(self.env._cur) or self._capture(self.env._cur)).replay()
-            return
-        for _ in range(plies):
-            self._ply_recorded() if self.record_enabled else self._ply()
-
     # ------------------------------------------------------------------ host side
-    def _describe(self, buffer: KataGoRolloutBuffer, base: int, rows: int) -> dict:
-        """Reserve ``rows`` rows behind the ones committed and point the kernel at the columns."""
-        cols = buffer.reserve(rows, self.device)
-        d = self._desc_host
-        for i, key in enumerate(("observations", "legal_masks", "actions", "log_probs", "values", "rewards", "dones",
-                                 "terminated", "value_categories", "score_targets", "env_ids", "next_value_override")):
-            d[i] = cols[key].data_ptr()
-        d[12], d[13] = base, buffer._write_offset - base + rows
-        self._desc.copy_(d, non_blocking=True)
-        return cols
-
-    def _read_state(self, stats: LeagueRolloutStats) -> np.ndarray:
-        self._state_host.copy_(self._state)           # the one device -> host read of a sync point
-        stats.host_syncs += 1
-        st = self._state_host.numpy()
+    def _zero_legal(self, st: np.ndarray) -> None:
         if st[_STALL]:
             stall = self._stall.cpu().numpy()
             for bit, who in ((1, "Learner"), (2, "Opponent")):
                 if st[_STALL] & bit:
                     raise RuntimeError(_ZERO_LEGAL.format(who=who, envs=np.flatnonzero(stall & bit).tolist()))
-        if st[_SAMP]:
-            raise RuntimeError("NaN in raw policy logits in LeagueRollout — probability tensor contains nan "
-                               "(a model has diverged)")
-        if st[_REFUSAL] or st[_REFUSAL + 1]:
-            self.env.raise_if_refused()
+
+    def _protocol_guards(self, st: np.ndarray) -> None:
         if st[_CONFLICT]:
             PendingTransitions._conflict()
-        g = st[_GUARDS:_GUARDS + 4]
-        peak = float(g[3:4].view(np.float32)[0])
-        if g[:3].any() or peak > 3.5:                  # the rollout store's input guards, with the reference's messages
-            _check_step_inputs(torch.tensor([not g[0]]), torch.tensor([True]), torch.tensor([5 if g[1] else 0]),
-                               torch.tensor([float("nan") if g[2] else peak]))
-        if st[_DROPPED] or st[_TRUNC_DROPPED]:
-            raise RuntimeError(f"LeagueRollout: {int(st[_DROPPED])} rows did not fit the rows reserved in the rollout "
-                               f"buffer, {int(st[_TRUNC_DROPPED])} truncations found no slot")
-        return st
 
     def _overrides(self, cols: dict, n: int) -> None:
         """The deferred truncation bootstrap (:1250-1283): one learner forward over the n parked terminal observations,
@@ -473,28 +349,10 @@ class LeagueRollout:
         cols["next_value_override"].index_copy_(0, tl[:, 1].long(), v)
         self._state[_TRUNC:_TRUNC + 1].zero_()
 
-    def _learner_values(self, obs: torch.Tensor, n: int, ws: Optional[dict]) -> torch.Tensor:
-        _, vl, sc = self.group._tables.forward(obs, self._learner_of[:n], ws=ws)
-        v = torch.empty(n, device=self.device)
-        _lib.call("ka_scalar_value", vl, sc if self.alpha != 0.0 else None, self.alpha, v, n, _lib.stream_ptr(self.device))
-        return v
-
     def collect(self, buffer: KataGoRolloutBuffer, steps: int) -> LeagueRolloutStats:
         """Step every env ``steps`` plies; the learner's transitions land in ``buffer`` in the reference's order."""
-        if steps < 1:
-            raise ValueError(f"steps must be positive, got {steps}")
-        if not isinstance(buffer, KataGoRolloutBuffer):
-            raise ValueError(f"collect() writes a KataGoRolloutBuffer, got {type(buffer).__name__}")
-        if tuple(buffer.obs_shape) != _OBS_SHAPE or buffer.action_space != ACTION_SPACE:
-            raise ValueError(f"buffer holds obs {tuple(buffer.obs_shape)} / {buffer.action_space} actions, the env gives "
-                             f"{_OBS_SHAPE} / {ACTION_SPACE}")
-        bd = buffer._device
-        if bd is not None and (bd.type != "cuda" or (bd.index is not None and bd.index != self.device.index)):
-            raise ValueError(f"buffer lives on {buffer._device}, the rollout on {self.device} (a device-resident buffer)")
-        stats = LeagueRolloutStats()
-        with torch.cuda.device(self.device), torch.no_grad():
-            self._collect(buffer, int(steps), stats)
-        return stats
+        self._check_buffer(buffer, steps)
+        return self._run_collect(buffer, steps, LeagueRolloutStats())
 
     def _collect(self, buffer, steps, stats) -> None:
         N = self.num_envs
@@ -516,13 +374,7 @@ class LeagueRollout:
             st = self._read_state(stats)
             buffer.commit(int(st[_ROWS]) - rows, int(st[_BLOCKS]) - adds)
             rows, adds = int(st[_ROWS]), int(st[_BLOCKS])
-            if self.game_log is not None:
-                stats.games += self.game_log.drain()
-                stats.games_dropped = self.game_log.dropped - dropped_before
-            n = int(st[_TRUNC])
-            if n:
-                self._overrides(cols, n)
-                stats.truncation_overrides += n
+            self._after_commit(st, cols, stats, dropped_before)
             return st
 
         while done < steps:
@@ -537,25 +389,20 @@ class LeagueRollout:
                   self._plan, _OBS_ELEMS, MASK_WORDS, _lib.stream_ptr(self.device))
         before = rows
         st = sync(cols)
-        stats.plies, stats.flushed = steps, rows - before
-        _stats_from_state(st, self.opponent_ids, stats)
+        stats.plies, stats.flushed, stats.adds = steps, rows - before, int(st[_BLOCKS])
+        self._tallies(st, stats)
+        stats.opponent_results = {oid: [int(v) for v in st[_HDR + 3 * k:_HDR + 3 * k + 3]]
+                                  for k, oid in enumerate(self.opponent_ids)}
 
     def live_games(self, envs: Optional[Sequence[int]] = None) -> List[RecordedGame]:
         """The games in progress (every env, or ``envs``) between two ``collect`` calls: ``RecordedGame`` with
         ``finished=False``, named by the players seated now."""
-        if self.game_log is None:
-            raise ValueError("live_games() needs a rollout built with game_log > 0")
-        with torch.cuda.device(self.device):
-            return self.game_log.live(envs, side=self._side, opp=self._opp, ids=self._ids, opponents=len(self.opponent_ids),
-                                      ply_counter=self._state.data_ptr() + 4 * _PLY)
+        return self.ply.live_games("a rollout", envs, side=self._side, opp=self._opp, ids=self._ids,
+                                   opponents=len(self.opponent_ids), ply_counter=self._state.data_ptr() + 4 * _PLY)
 
     def spectator_data(self, envs: Optional[Sequence[int]] = None) -> List[dict]:
-        """``VecEnv.get_spectator_data`` of every env (or ``envs``) between two ``collect`` calls; ``move_history`` is []
-        unless the rollout was built with ``move_history=True``; ``insight`` (built with ``insight > 0``) is the
-        ``insight_dict`` of the env's last move, None before its first move after ``reset()``."""
-        with torch.cuda.device(self.device):
-            data = self.env.get_spectator_data(envs)
-            return data if self.insight is None else self.insight.annotate(data, envs)
+        """``DevicePly.spectator_data`` between two ``collect`` calls."""
+        return self.ply.spectator_data(envs)
 
     def bootstrap_values(self) -> torch.Tensor:
         """V(observation now) by the learner, in the learner's frame (katago_loop.py:1565-1580): ``update``'s next_values."""

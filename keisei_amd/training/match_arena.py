@@ -32,6 +32,10 @@ action) until the next sync, where the reference swaps the next pairing in at on
 schedule a captured graph allows (``VecEnv`` alternates two result buffers, so a graph must hold an even number of
 plies); ``graph=False, sync_every=1`` is the reference's schedule exactly.  As in the reference there is one
 ``reset()`` per round and no per-slot reset: a pairing seated in a freed slot continues the games in progress there.
+
+The front of the ply (forward, sampler, lookahead, insight, env step, game log) is ``_device_ply.DevicePly``, shared with
+``LeagueRollout`` and ``SelfPlayRollout``; the arena adds its collection and feature launches, the referee, its own
+single-graph capture and the round.
 """
 from __future__ import annotations
 
@@ -43,19 +47,20 @@ import numpy as np
 import torch
 
 from keisei_amd import _lib
-from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS, VecEnv
+from keisei_amd.shogi_gym import MASK_WORDS
 
+from ._device_ply import _OBS_ELEMS, DevicePly, check_loop_args
 from .dynamic_trainer import MatchRollout
 from .game_feature_tracker import GameFeatureTracker
-from .game_log import GameLog, RecordedGame
-from .lookahead import Lookahead, LookaheadStats, arena_lookahead, lookahead_table
+from .game_log import RecordedGame
+from .lookahead import LookaheadStats, arena_lookahead, lookahead_table
 from .model_group import SEResNetGroup
-from .policy_insight import InsightRecorder
 from .sampling import GAME_PLY_BYTE, arena_controls, controls_table
 
 _HDR, _SLOT = 8, 8                      # int32 words of the state header and of one slot (csrc/arena.hip)
+_PLY, _MAX_PLY, _SAMP, _REFUSAL = 2, 3, 4, 6    # header words: plies of the round, the ply ceiling's max_ply, the
+                                        # sampler's two flags, the env's refusal latch (int64)
 _CUR = 4                                # int32 words of one slot's collection cursors: rows, rows of this ply, dropped, -
-_OBS_ELEMS = 50 * 9 * 9                 # one observation row as the env hands it over (fp32)
 DONE, PARTIAL = 2, 4                   # slot status bits (csrc/arena.hip; 1 = seated, 8 = stalled)
 
 
@@ -259,19 +264,13 @@ class MatchArena:
     ``ka_arena_record_pre`` / ``ka_arena_record_post``, into a store allocated here) for ``run_round(trainable=)``.
     ``features=True`` adds the reference's per-slot ``GameFeatureTracker`` to the ply (one launch,
     ``ka_arena_features_step``): every result then carries a ``feature_tracker``.  Without it the ply is launch for
-    launch what it was.  ``start_pool_capacity > 0`` gives the env a pool of
-    start positions of that size: ``arena.env.set_start_positions(...)`` / ``set_start_sfens(...)`` between rounds make later
-    games start from them (no re-capture; see ``VecEnv``).  Not with ``features=True``.
-    ``game_log=K > 0`` adds a device-resident ``GameLog`` of K records to the ply (one launch, ``ka_gamelog_step``, before
-    the referee): every result then carries its pairing's finished games, move by move, in ``recorded_games`` -- one per
-    game the referee tallied, as long as ``RoundStats.games_dropped`` is 0.  A game is ``carried`` when the pairing
+    launch what it was.  ``start_pool_capacity``, ``game_log``, ``move_history``, ``insight`` and ``insight_temperature``
+    are ``DevicePly``'s (``_device_ply.py``).  Here ``start_pool_capacity`` is not for ``features=True``; the log's launch
+    is ``ka_gamelog_step`` and every result carries its pairing's finished games, move by move, in ``recorded_games`` --
+    one per game the referee tallied, as long as ``RoundStats.games_dropped`` is 0.  A game is ``carried`` when the pairing
     inherited it from the slot's previous pairing or the slot sat idle during it (there is no per-slot reset).
-    ``collect``, ``features`` and ``game_log`` are independent.  ``move_history=True`` has the env keep the move notes of
-    the games in progress (two more launches inside ``env.step``); ``spectator_data()`` between two rounds is the
-    dashboard feed.  ``insight=top_k > 0`` adds the policy insight to the ply (one launch, ``ka_policy_insight``, between
-    the sampler and the env step; ``policy_insight.py``): every ``spectator_data()`` dict gains ``insight``, the figures of
-    the env's last move at ``insight_temperature`` (None for the envs of an idle slot), and with ``move_history=True`` every
-    history entry gains its move's probability, rank, entropy, win probability and top candidates.  With 0 nothing changes.
+    ``collect``, ``features`` and ``game_log`` are independent.  The ``insight`` of ``spectator_data()`` is None for the
+    envs of an idle slot.
     ``sampling=`` (a ``SamplingControls`` for every model, or one per model; ``sampling.py``) replaces the play sampler of the
     ply by ``ka_policy_sample_ctl`` -- temperature, top-k cut and opening schedule per model, read from a table on the device
     that ``set_sampling`` rewrites between rounds without a new capture.  With None the ply is launch for launch what it
@@ -291,22 +290,11 @@ class MatchArena:
                  collect: bool = False, features: bool = False, start_pool_capacity: int = 0,
                  game_log: int = 0, move_history: bool = False, insight: int = 0,
                  insight_temperature: float = 1.0, sampling=None, lookahead=None) -> None:
-        if game_log < 0:
-            raise ValueError(f"game_log must not be negative, got {game_log}")
         if len(group) == 0:
             raise ValueError("MatchArena needs a group with at least one model")
         if num_envs <= 0 or envs_per_match <= 0 or num_envs % envs_per_match != 0:
             raise ValueError(f"num_envs ({num_envs}) must be a positive multiple of envs_per_match ({envs_per_match})")
-        if not 1 <= max_ply <= 65535:
-            raise ValueError(f"max_ply must lie in [1, 65535], got {max_ply}")
-        if sync_every < 1:
-            raise ValueError(f"sync_every must be at least 1, got {sync_every}")
-        if graph and sync_every % 2:
-            raise ValueError(f"graph=True needs an even sync_every (VecEnv alternates two result buffers), got {sync_every}")
-        if graph and record:
-            raise ValueError("record=True runs without a graph (graph=False)")
-        if start_pool_capacity < 0:
-            raise ValueError(f"start_pool_capacity must not be negative, got {start_pool_capacity}")
+        check_loop_args(max_ply, sync_every, graph, record, start_pool_capacity, game_log)
         if features and start_pool_capacity > 0:
             raise ValueError("features=True cannot be combined with start_pool_capacity > 0: the opening and rook-square "
                              "style features are defined from the standard start position")
@@ -322,17 +310,20 @@ class MatchArena:
         self.record_enabled = bool(record)
         self.record: List[dict] = []
         N, dev = self.num_envs, self.device
+        # the controls table of ka_policy_sample_ctl and the lookahead's table are allocated once: set_sampling and
+        # set_lookahead write into them, the ply reads them
+        self.ply = ply = DevicePly(group, N, self.max_ply, start_pool_capacity=int(start_pool_capacity), game_log=game_log,
+                                   envs_per_slot=self.envs_per_match, move_history=move_history, insight=insight,
+                                   insight_temperature=insight_temperature, controls=table, lookahead_table=la_table,
+                                   lookahead_width=la_width)
+        self.env, self.game_log, self.insight = ply.env, ply.game_log, ply.insight
+        self._actions, self._logp, self._nlegal = ply.actions, ply.log_probs, ply.n_legal
+        self._ctl, self._la_table, self._la = ply.ctl, ply.lookahead_table, ply.lookahead
         with torch.cuda.device(dev):
-            self.env = VecEnv(N, self.max_ply, "katago", "spatial", device=dev, output="torch", check_actions=False,
-                              start_pool_capacity=int(start_pool_capacity), move_history=bool(move_history))
-            self._ws = group._tables.workspace(N)
             self._state = torch.zeros(_lib.query("ka_arena_state_words", self.num_slots), dtype=torch.int32, device=dev)
             self._state_host = torch.zeros(self._state.shape, dtype=torch.int32).pin_memory()
             self._model_of = torch.full((N,), -1, dtype=torch.int32, device=dev)
             self._pre = torch.zeros(N, dtype=torch.uint8, device=dev)
-            self._actions = torch.zeros(N, dtype=torch.int64, device=dev)
-            self._logp = torch.zeros(N, device=dev)
-            self._nlegal = torch.zeros(N, dtype=torch.int32, device=dev)
             self._jobs = torch.zeros(self.num_slots, 4, dtype=torch.int32, device=dev)
             self._jobs_host = torch.zeros(self.num_slots, 4, dtype=torch.int32).pin_memory()
             self.collect = bool(collect)
@@ -366,15 +357,6 @@ class MatchArena:
                 every = torch.zeros(S, 4, dtype=torch.int32)
                 every[:, 0] = torch.arange(S, dtype=torch.int32)
                 self._every_slot = every.to(dev)                  # seat jobs naming every slot: the round-start clear
-            self.game_log: Optional[GameLog] = None
-            if game_log:
-                self.game_log = GameLog(self.env, capacity=int(game_log), envs_per_slot=self.envs_per_match)
-            self.insight: Optional[InsightRecorder] = InsightRecorder(self.env, insight, insight_temperature) if insight else None
-            # the controls table of ka_policy_sample_ctl, allocated once: set_sampling writes into it, the ply reads it
-            self._ctl: Optional[torch.Tensor] = None if table is None else torch.from_numpy(table).to(dev)
-            # the lookahead's table (read by every launch: set_lookahead writes into it) and its child rows, allocated once
-            self._la_table: Optional[torch.Tensor] = None if la_table is None else torch.from_numpy(la_table).to(dev)
-            self._la: Optional[Lookahead] = Lookahead(self.env, group, la_width) if la_width > 0 else None
         self._graph: Optional[torch.cuda.CUDAGraph] = None
 
     def set_lookahead(self, lookahead) -> None:
@@ -409,30 +391,16 @@ class MatchArena:
     # ------------------------------------------------------------------ one ply
     def _ply(self) -> None:
         """forward -> sample -> step -> referee on the current stream; no host synchronisation."""
-        env, N = self.env, self.num_envs
-        st = _lib.stream_ptr(self.device)
-        cur, prev = env.current(), env._cur
-        logits, value, _ = self.group._tables.forward(cur.observations, self._model_of, ws=self._ws)
+        ply = self.ply
         sp = self._state.data_ptr()
-        if self._ctl is None:
-            _lib.call("ka_policy_sample_play", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of,
-                      len(self.group), self._actions, self._logp, self._nlegal, sp + 16, N, ACTION_SPACE, st)
-        else:                                             # the game ply of the position to move in: byte 100 of the state row
-            _lib.call("ka_policy_sample_ctl", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of,
-                      len(self.group), self._ctl, env._state.data_ptr() + GAME_PLY_BYTE, env._state.shape[1], self._actions,
-                      self._logp, self._nlegal, sp + 16, N, ACTION_SPACE, st)
-        if self._la is not None:                          # the active envs' actions become the lookahead's choices
-            self._la.step(logits, cur.legal_mask_bits, self._actions, self._model_of, self._la_table, st)
-        if self.insight is not None:                      # while the logits exist, before the step moves the history count
-            self.insight.step(logits, cur.legal_mask_bits, self._actions, value, env._players[prev], self._model_of,
-                              len(self.group), sp + 16, st)
+        cur, pre, _, _, st = ply.move(self._model_of, len(self.group), sp, sp + 4 * _SAMP)
         if self.collect:
             sto = self._store
             _lib.call("ka_arena_record_pre", self._state, self._bits, self.num_slots, self.envs_per_match, cur.observations,
                       cur.legal_mask_bits, self._actions, self._pre, self._nlegal, self._cursors, self._row_of,
                       sto["observations"], sto["legal_mask_bits"], sto["actions"], sto["perspective"], self._cap,
                       _OBS_ELEMS, MASK_WORDS, st)
-        r = env.step(self._actions)
+        r = ply.step()
         if self.collect:
             _lib.call("ka_arena_record_post", self._cursors, self._row_of, self.num_slots, self.envs_per_match, r.rewards,
                       r.terminated, r.truncated, sto["rewards"], sto["dones"], self._cap, st)
@@ -441,15 +409,13 @@ class MatchArena:
             _lib.call("ka_arena_features_step", self._state, self.num_slots, self.envs_per_match, self._actions, self._pre,
                       self._nlegal, meta.captured_piece, meta.termination_reason, meta.ply_count, r.rewards, r.terminated,
                       r.truncated, self._facc, self._frecords, self._fcursors, self._fcap, st)
-        if self.game_log is not None:                     # before the referee: it rewrites model_of and the round ply
-            self.game_log.step(self._actions, r.rewards, r.terminated, r.truncated, env._players[prev],
-                               r.step_metadata.termination_reason, nlegal=self._nlegal, live=self._model_of,
-                               pairs=sp + 4 * _HDR, pair_stride=_SLOT, envs_per_pair=self.envs_per_match,
-                               ply_counter=sp + 8)
+        # before the referee: it rewrites model_of and the round ply
+        ply.log(r, pre, live=self._model_of, pairs=sp + 4 * _HDR, pair_stride=_SLOT, envs_per_pair=self.envs_per_match,
+                ply_counter=sp + 4 * _PLY)
         # env._err[1] is the VecEnv's refusal latch: the referee copies it into the state so the host sees a refused
         # step in the same read
         _lib.call("ka_arena_referee", self._state, self.num_slots, self.envs_per_match, r.rewards,
-                  r.terminated, r.truncated, r.current_players, self._nlegal, env._err.data_ptr() + 8, self._model_of,
+                  r.terminated, r.truncated, r.current_players, self._nlegal, self.env._err.data_ptr() + 8, self._model_of,
                   self._pre, st)
 
     def _ply_recorded(self) -> None:
@@ -505,10 +471,10 @@ class MatchArena:
             self._fcursors_host.copy_(self._fcursors, non_blocking=True)
         self._state_host.copy_(self._state)           # the one device -> host read of a sync point
         st = self._state_host.numpy()
-        if st[4]:
+        if st[_SAMP]:
             raise RuntimeError("NaN in raw policy logits in MatchArena — probability tensor contains nan "
                                "(a model has diverged)")
-        if st[6] or st[7]:
+        if st[_REFUSAL] or st[_REFUSAL + 1]:
             self.env.raise_if_refused()               # a refused step here is a bug: it raises
         return st
 
@@ -566,20 +532,14 @@ class MatchArena:
     def live_games(self, envs: Optional[Sequence[int]] = None) -> List[RecordedGame]:
         """The games in progress (every env, or ``envs``) between two rounds: ``RecordedGame`` with ``finished=False``,
         named by the models the env's slot holds now."""
-        if self.game_log is None:
-            raise ValueError("live_games() needs an arena built with game_log > 0")
         sp = self._state.data_ptr()
-        with torch.cuda.device(self.device):
-            return self.game_log.live(envs, pairs=sp + 4 * _HDR, pair_stride=_SLOT, envs_per_pair=self.envs_per_match,
-                                      ply_counter=sp + 8)
+        return self.ply.live_games("an arena", envs, pairs=sp + 4 * _HDR, pair_stride=_SLOT,
+                                   envs_per_pair=self.envs_per_match, ply_counter=sp + 4 * _PLY)
 
     def spectator_data(self, envs: Optional[Sequence[int]] = None) -> List[dict]:
-        """``VecEnv.get_spectator_data`` of every env (or ``envs``) between two rounds; ``move_history`` is [] unless the
-        arena was built with ``move_history=True``; ``insight`` (built with ``insight > 0``) is the ``insight_dict`` of
-        the env's last move: None before its first move of the round and for the envs of an idle slot."""
-        with torch.cuda.device(self.device):
-            data = self.env.get_spectator_data(envs)
-            return data if self.insight is None else self.insight.annotate(data, envs)
+        """``DevicePly.spectator_data`` between two rounds; ``insight`` is None before an env's first move of the round
+        and for the envs of an idle slot."""
+        return self.ply.spectator_data(envs)
 
     def run_round(self, pairings: Sequence[Tuple[int, int]], games_per_match: int = 64, *, max_ply: Optional[int] = None,
                   trainable: Union[None, Callable[[int, int], int], Mapping[int, int]] = None,
@@ -619,7 +579,7 @@ class MatchArena:
         seed = self.seed if self.seed is not None else int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
         hdr = torch.zeros(self._state.shape, dtype=torch.int32)
         hdr[:2].view(torch.int64)[0] = seed
-        hdr[3] = max_ply
+        hdr[_MAX_PLY] = max_ply
         self._state.copy_(hdr)
         self._model_of.fill_(-1)
         if self.collect:
@@ -629,13 +589,7 @@ class MatchArena:
             self._fcursors.zero_()
             _lib.call("ka_arena_features_seat", self._every_slot, self.num_slots, self.num_slots, self.envs_per_match,
                       self._facc, _lib.stream_ptr(self.device))
-        self.env.reset()
-        if self.game_log is not None:
-            self.game_log.begin()
-        if self.insight is not None:
-            self.insight.clear()
-        if self._la is not None:
-            self._la.clear()
+        self.ply.reset()
         logged: Dict[int, List[RecordedGame]] = {}
         self.record = []
         chunks: Dict[int, list] = {}
@@ -700,7 +654,7 @@ class MatchArena:
                     active.append(s)
                     nxt += 1
             self._assign(jobs, [bits[slot_pairing[j[0]]] for j in jobs])
-        stats.round_plies = int(self._state_host[2])
+        stats.round_plies = int(self._state_host[_PLY])
         stats.round_duration_s = time.monotonic() - t0
         ordered = [results[i] for i in range(P)]
         stats.pairings_completed = len(ordered)

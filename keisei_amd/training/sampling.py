@@ -139,7 +139,7 @@ def _mix(x: int) -> int:
 
 def sample_uniform(seed: int, row: int) -> float:
     """The sampler's uniform of ``(seed, row)``: the top 24 bits of ``mix(seed ^ mix(row + 0x5851F42D4C957F2D))`` over 2^24,
-    with the splitmix64 finaliser as ``mix`` (csrc/loss.hip, ``sample_mix``)."""
+    with the splitmix64 finaliser as ``mix`` (csrc/common.h, ``ka_mix64``)."""
     h = _mix((int(seed) & _M64) ^ _mix((int(row) + 0x5851F42D4C957F2D) & _M64))
     return (h >> 40) / 16777216.0
 

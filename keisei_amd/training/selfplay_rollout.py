@@ -21,40 +21,33 @@ observation, the host runs one learner forward over exactly those rows at the sy
 learner's weights do not change inside ``collect`` and eval mode couples no two boards, so the values are what an in-ply
 forward gives.
 
-``_selfplay_host`` restates the branch on the CPU from this package's host pieces (a host ``KataGoRolloutBuffer``,
-``_compute_value_cats``, the tallies); the tests hold the kernel to it and hold it to the reference
-(tests/golden/g14_selfplay_rollout.npz).
+The front of the ply and the skeleton around it are ``_device_ply.py``'s (``DevicePly``, ``DeviceRollout``), shared with
+``LeagueRollout``.  ``_selfplay_host`` restates the branch on the CPU from this package's host pieces (a host
+``KataGoRolloutBuffer``, ``_compute_value_cats``, the tallies); the tests hold the kernel to it and hold it to the
+reference (tests/golden/g14_selfplay_rollout.npz).
 """
 from __future__ import annotations
 
-import gc
-import math
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence
+from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
 
 from keisei_amd import _lib
-from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS, OBS_CHANNELS, VecEnv
+from keisei_amd.shogi_gym import MASK_WORDS
 
-from .game_log import GameLog, RecordedGame
+from ._device_ply import (_OBS_ELEMS, _DROPPED, _PLY, _ROWS, _SAMP, _SEED, _TRUNC, _TRUNC_DROPPED,  # noqa: F401
+                          DeviceRollout, check_loop_args, check_value_args)
+from .game_log import RecordedGame
 from .katago_loop import _compute_value_cats
-from .katago_ppo import SCORE_NORMALIZATION, KataGoRolloutBuffer, _check_step_inputs
+from .katago_ppo import SCORE_NORMALIZATION, KataGoRolloutBuffer
 from .model_group import SEResNetGroup
-from .policy_insight import InsightRecorder
-from .value_adapter import MultiHeadValueAdapter
 
 __all__ = ["SelfPlayRollout", "SelfPlayStats"]
 
-_OBS_SHAPE = (OBS_CHANNELS, 9, 9)
-_OBS_ELEMS = OBS_CHANNELS * 81
-# state words (csrc/selfplay.hip)
-_SEED, _PLY, _ROWS, _PLIES, _DROPPED, _SAMP, _REFUSAL, _TRUNC, _TRUNC_DROPPED = 0, 2, 3, 4, 5, 6, 8, 12, 13
-_WINS, _LOSSES, _DRAWS, _BLACK, _WHITE, _TERMINATED, _TRUNCATED, _GUARDS, _STALL = 14, 15, 16, 17, 18, 19, 20, 21, 25
+_PLIES, _STALL = 4, 25                  # state words of csrc/selfplay.hip beside the ones it shares with the league's
 _ZERO_LEGAL = "Environments {envs} have zero legal actions — all-False legal mask would produce NaN"      # select_actions' text
-_DESC_KEYS = ("observations", "legal_masks", "actions", "log_probs", "values", "rewards", "dones", "terminated",
-              "value_categories", "score_targets", "env_ids", "next_value_override")
 
 
 @dataclass
@@ -75,32 +68,18 @@ class SelfPlayStats:
 
 
 def _check_args(num_envs: int, max_ply: int, sync_every: int, graph: bool, record: bool, score_norm: float,
-                value_adapter) -> None:
+                value_adapter, start_pool_capacity: int = 0, game_log: int = 0) -> None:
     if _lib.available():
         top = _lib.query("ka_selfplay_layout", 3)
         if not 1 <= num_envs <= top:
             raise ValueError(f"num_envs must lie in [1, {top}], got {num_envs}")
     elif num_envs < 1:
         raise ValueError(f"num_envs must be positive, got {num_envs}")
-    if not 1 <= max_ply <= 65535:
-        raise ValueError(f"max_ply must lie in [1, 65535], got {max_ply}")
-    if sync_every < 1:
-        raise ValueError(f"sync_every must be at least 1, got {sync_every}")
-    if sync_every > max_ply:
-        raise ValueError(f"sync_every ({sync_every}) must not exceed max_ply ({max_ply}): an env may truncate only once "
-                         "between two sync points (one truncation slot per env)")
-    if graph and record:
-        raise ValueError("record=True runs without a graph (graph=False)")
-    if graph and sync_every % 2:
-        raise ValueError(f"graph=True needs an even sync_every (VecEnv alternates two result buffers), got {sync_every}")
-    if not math.isfinite(score_norm) or score_norm == 0:
-        raise ValueError(f"score_norm must be finite and non-zero, got {score_norm}")
-    if value_adapter is not None and type(value_adapter) is not MultiHeadValueAdapter:
-        raise ValueError(f"value_adapter must be None or a MultiHeadValueAdapter (the kernel blends by its "
-                         f"score_blend_alpha), got {type(value_adapter).__name__}")
+    check_loop_args(max_ply, sync_every, graph, record, start_pool_capacity, game_log, one_truncation_slot=True)
+    check_value_args(score_norm, value_adapter)
 
 
-class SelfPlayRollout:
+class SelfPlayRollout(DeviceRollout):
     """The learner's self-play rollout, resident on the device (see module docstring).
 
     ``roll = SelfPlayRollout(learner, num_envs=512, max_ply=500, ...)``; ``stats = roll.collect(buffer, steps)`` steps
@@ -109,63 +88,29 @@ class SelfPlayRollout:
     ``next_values`` of ``KataGoPPOAlgorithm.update``; ``roll.refresh()`` after the update brings the learner's new weights
     into the group.  The env is not reset between ``collect`` calls (the reference carries games over epochs);
     ``reset()`` is explicit.  ``seed`` fixes sampling from the last ``reset()`` on.  ``record=True`` (no graph) keeps every
-    ply's inputs and outputs in ``self.record`` for tests.  ``start_pool_capacity > 0`` gives the env a pool of
-    start positions of that size: ``roll.env.set_start_positions(...)`` / ``set_start_sfens(...)`` between ``collect`` calls make later
-    games start from them (no re-capture; see ``VecEnv``).  ``game_log=K > 0`` adds a device-resident ``GameLog`` of K
-    records to the ply (one launch, ``ka_gamelog_step``, between the env step and ``ka_selfplay_step``): ``collect``
-    drains it at every sync point onto ``SelfPlayStats.games``.  Without it the ply is launch for launch what it was.
-    ``move_history=True`` has the env keep the move notes of the games in progress (two more launches inside ``env.step``,
-    see ``VecEnv``); ``spectator_data()`` between two ``collect`` calls is the dashboard feed either way.
-    ``insight=top_k > 0`` adds the policy insight to the ply (one launch, ``ka_policy_insight``, between the sampler and the
-    env step; ``policy_insight.py``): every ``spectator_data()`` dict gains ``insight``, the figures of the env's last move at
-    ``insight_temperature``, and with ``move_history=True`` every history entry gains its move's probability, rank, entropy,
-    win probability and top candidates.  With 0 the ply and every dict are what they were.
+    ply's inputs and outputs in ``self.record`` for tests.  ``start_pool_capacity``, ``game_log``, ``move_history``,
+    ``insight`` and ``insight_temperature`` are ``DevicePly``'s (``_device_ply.py``); here the log's launch is
+    ``ka_gamelog_step``, ``collect`` drains it onto ``SelfPlayStats.games``, and every ``spectator_data()`` dict carries
+    ``value_estimate``.  Without an option the ply is launch for launch what it is without it.
     There are no sampling controls here (``sampling.py``), on purpose: the single model is the learner, and its draws are
     the PPO behaviour policy."""
+
+    _LAYOUT, _ENV_IDS, _DIVERGED = "ka_selfplay_layout", False, "the model"
 
     def __init__(self, learner, *, num_envs: int = 512, max_ply: int = 500, value_adapter=None,
                  score_norm: float = SCORE_NORMALIZATION, sync_every: int = 32, graph: bool = True,
                  seed: Optional[int] = None, record: bool = False, start_pool_capacity: int = 0,
                  game_log: int = 0, move_history: bool = False, insight: int = 0,
                  insight_temperature: float = 1.0) -> None:
-        _check_args(int(num_envs), int(max_ply), int(sync_every), bool(graph), bool(record), float(score_norm), value_adapter)
-        if start_pool_capacity < 0:
-            raise ValueError(f"start_pool_capacity must not be negative, got {start_pool_capacity}")
-        if game_log < 0:
-            raise ValueError(f"game_log must not be negative, got {game_log}")
-        self.group = self._make_group(learner)
+        _check_args(int(num_envs), int(max_ply), int(sync_every), bool(graph), bool(record), float(score_norm), value_adapter,
+                    start_pool_capacity, game_log)
         self.learner = learner
-        self.device = self.group.device
-        self.num_envs, self.max_ply, self.sync_every = int(num_envs), int(max_ply), int(sync_every)
-        self.graph, self.seed, self.record_enabled = bool(graph), seed, bool(record)
-        self.value_adapter, self.score_norm = value_adapter, float(score_norm)
-        self.alpha = 0.0 if value_adapter is None else float(value_adapter.score_blend_alpha)
-        self.record: List[dict] = []
-        N, dev = self.num_envs, self.device
-        q = lambda which: _lib.query("ka_selfplay_layout", which)  # noqa: E731
-        with torch.cuda.device(dev):
-            z = lambda *s, dtype=torch.int32: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731
-            self.env = VecEnv(N, self.max_ply, "katago", "spatial", device=dev, output="torch", check_actions=False,
-                              start_pool_capacity=int(start_pool_capacity), move_history=bool(move_history))
-            self._actions, self._logp, self._nlegal = z(N, dtype=torch.int64), z(N, dtype=torch.float32), z(N)
-            self._values = z(N, dtype=torch.float32)
-            self._model_of = z(N)                                    # every row on model 0
-            self._stall = z(N, dtype=torch.uint8)
-            self._t_obs, self._t_list = z(N, *_OBS_SHAPE, dtype=torch.float32), z(N, q(2))
-            self._plan = z(N, q(0))
-            self._desc = z(q(1), dtype=torch.int64)
-            self._desc_host = torch.zeros(q(1), dtype=torch.int64).pin_memory()
-            self._state = z(_lib.query("ka_selfplay_state_words"))
-            self._state_host = torch.zeros(self._state.shape, dtype=torch.int32).pin_memory()
-            self._ws = self.group._tables.workspace(N)
-            self.game_log: Optional[GameLog] = GameLog(self.env, capacity=int(game_log)) if game_log else None
-            self.insight: Optional[InsightRecorder] = InsightRecorder(self.env, insight, insight_temperature) if insight else None
-        self._graphs: Dict[int, torch.cuda.CUDAGraph] = {}
-        with torch.cuda.device(dev), torch.no_grad():            # load every kernel of the ply before any capture
-            self.reset()                                         # (a zeroed descriptor reserves no row: nothing is written)
-            self._ply()
-            self._ply()
-        self.reset()
+        self._build(self._make_group(learner), num_envs=num_envs, max_ply=max_ply, sync_every=sync_every, graph=graph,
+                    seed=seed, record=record, value_adapter=value_adapter, score_norm=score_norm,
+                    trunc_words=_lib.query("ka_selfplay_layout", 2), start_pool_capacity=int(start_pool_capacity),
+                    game_log=game_log, move_history=move_history, insight=insight, insight_temperature=insight_temperature)
+        self._new_state(_lib.query("ka_selfplay_state_words"))
+        self._warm_up()
 
     @staticmethod
     def _make_group(learner) -> SEResNetGroup:
@@ -179,14 +124,10 @@ class SelfPlayRollout:
                              "loop for this model")
         return group
 
-    def refresh(self) -> None:
-        """After ``ppo.update()`` (or any in-place edit of weights): the group's snapshot follows the model."""
-        self.group.refresh()
-
     # ------------------------------------------------------------------ state
     def reset(self) -> None:
         """Every env back to the start position, counters cleared, fresh seed."""
-        seed = self.seed if self.seed is not None else int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        seed = self._fresh_seed()
         with torch.cuda.device(self.device):
             hdr = torch.zeros(self._state.shape, dtype=torch.int32)
             hdr[_SEED:_SEED + 2].view(torch.int64)[0] = seed
@@ -194,11 +135,7 @@ class SelfPlayRollout:
             self._desc.zero_()
             self._stall.zero_()
             self._values.zero_()
-            self.env.reset()
-            if self.game_log is not None:
-                self.game_log.begin()
-            if self.insight is not None:
-                self.insight.clear()
+            self.ply.reset()
         self.record = []
 
     @property
@@ -209,24 +146,15 @@ class SelfPlayRollout:
     # ------------------------------------------------------------------ one ply
     def _ply(self) -> None:
         """forward -> sample -> step -> bookkeeping on the current stream; no host synchronisation."""
-        env, N = self.env, self.num_envs
-        st = _lib.stream_ptr(self.device)
-        cur, prev = env.current(), env._cur
-        logits, value, score = self.group._tables.forward(cur.observations, self._model_of, ws=self._ws)
+        ply, N = self.ply, self.num_envs
         sp = self._state.data_ptr()
-        _lib.call("ka_policy_sample_play", logits, 0, cur.legal_mask_bits, MASK_WORDS, sp, self._model_of, 1,
-                  self._actions, self._logp, self._nlegal, sp + 4 * _SAMP, N, ACTION_SPACE, st)
-        if self.insight is not None:                      # while the logits exist, before the step moves the history count
-            self.insight.step(logits, cur.legal_mask_bits, self._actions, value, env._players[prev], self._model_of, 1,
-                              sp + 4 * _SAMP, st)
-        r = env.step(self._actions)
-        if self.game_log is not None:                     # before ka_selfplay_step advances the ply counter it stamps
-            self.game_log.step(self._actions, r.rewards, r.terminated, r.truncated, env._players[prev],
-                               r.step_metadata.termination_reason, nlegal=self._nlegal, ply_counter=sp + 4 * _PLIES)
+        cur, pre, value, score, st = ply.move(self._model_of, 1, sp, sp + 4 * self._SAMP)
+        r = ply.step()
+        ply.log(r, pre, ply_counter=sp + 4 * _PLIES)      # before ka_selfplay_step advances the ply counter it stamps
         _lib.call("ka_selfplay_step", self._state, N, cur.observations, cur.legal_mask_bits, self._actions, self._logp,
-                  value, score if self.alpha != 0.0 else None, self.alpha, self._nlegal, env._players[prev], r.rewards,
+                  value, score if self.alpha != 0.0 else None, self.alpha, self._nlegal, pre, r.rewards,
                   r.terminated, r.truncated, r.step_metadata.material_balance, self.score_norm, r.terminal_observations,
-                  env._err.data_ptr() + 8, self._stall, self._values, self._t_obs, self._t_list, self._desc, self._plan,
+                  self.env._err.data_ptr() + 8, self._stall, self._values, self._t_obs, self._t_list, self._desc, self._plan,
                   _OBS_ELEMS, MASK_WORDS, st)
 
     def _ply_recorded(self) -> None:
@@ -244,56 +172,10 @@ class SelfPlayRollout:
                    terminal_envs=trunc.cpu().numpy(), terminal_obs=env._terminal_obs[trunc].cpu())
         self.record.append(rec)
 
-    def _capture(self, parity: int) -> torch.cuda.CUDAGraph:
-        """Capture sync_every plies for the env's current buffer parity (an even count: the parity is the same afterwards)."""
-        g = torch.cuda.CUDAGraph()
-        # torch.cuda.graph does not collect garbage on entry: a dead rollout object (captured graphs, pinned buffers) still
-        # waiting in a reference cycle must not be collected inside the capture (see LeagueRollout._capture)
-        gc.collect()
-        with torch.cuda.graph(g):
-            for _ in range(self.sync_every):
-                self._ply()
-        self._graphs[parity] = g
-        return g
-
-    def _chunk(self, plies: int) -> None:
-        if self.graph and plies == self.sync_every:
-            (self._graphs.get(self.env._cur) or self._capture(self.env._cur)).replay()
-            return
-        for _ in range(plies):
-            self._ply_recorded() if self.record_enabled else self._ply()
-
     # ------------------------------------------------------------------ host side
-    def _describe(self, buffer: KataGoRolloutBuffer, base: int, rows: int) -> dict:
-        """Reserve ``rows`` dense rows behind the ones committed and point the kernel at the columns."""
-        cols = buffer.reserve(rows, self.device, env_ids=False)
-        d = self._desc_host
-        for i, key in enumerate(_DESC_KEYS):
-            d[i] = cols[key].data_ptr() if key in cols else 0
-        d[12], d[13] = base, buffer._write_offset - base + rows
-        self._desc.copy_(d, non_blocking=True)
-        return cols
-
-    def _read_state(self, stats: SelfPlayStats) -> np.ndarray:
-        self._state_host.copy_(self._state)           # the one device -> host read of a sync point
-        stats.host_syncs += 1
-        st = self._state_host.numpy()
-        if st[_STALL] or st[_SAMP + 1]:
+    def _zero_legal(self, st: np.ndarray) -> None:
+        if st[_STALL] or st[self._SAMP + 1]:
             raise RuntimeError(_ZERO_LEGAL.format(envs=np.flatnonzero(self._stall.cpu().numpy()).tolist()))
-        if st[_SAMP]:
-            raise RuntimeError("NaN in raw policy logits in SelfPlayRollout — probability tensor contains nan "
-                               "(the model has diverged)")
-        if st[_REFUSAL] or st[_REFUSAL + 1]:
-            self.env.raise_if_refused()
-        g = st[_GUARDS:_GUARDS + 4]
-        peak = float(g[3:4].view(np.float32)[0])
-        if g[:3].any() or peak > 3.5:                  # the rollout store's input guards, with the reference's messages
-            _check_step_inputs(torch.tensor([not g[0]]), torch.tensor([True]), torch.tensor([5 if g[1] else 0]),
-                               torch.tensor([float("nan") if g[2] else peak]))
-        if st[_DROPPED] or st[_TRUNC_DROPPED]:
-            raise RuntimeError(f"SelfPlayRollout: {int(st[_DROPPED])} rows did not fit the rows reserved in the rollout "
-                               f"buffer, {int(st[_TRUNC_DROPPED])} truncations found no slot")
-        return st
 
     def _overrides(self, cols: dict, n: int) -> None:
         """The deferred truncation bootstrap (:1496-1521): one learner forward over the n parked terminal observations,
@@ -303,33 +185,13 @@ class SelfPlayRollout:
         cols["next_value_override"].index_copy_(0, tl[:, 1].long(), -v)
         self._state[_TRUNC:_TRUNC + 1].zero_()
 
-    def _learner_values(self, obs: torch.Tensor, n: int, ws: Optional[dict]) -> torch.Tensor:
-        _, vl, sc = self.group._tables.forward(obs, self._model_of[:n], ws=ws)
-        v = torch.empty(n, device=self.device)
-        _lib.call("ka_scalar_value", vl, sc if self.alpha != 0.0 else None, self.alpha, v, n, _lib.stream_ptr(self.device))
-        return v
-
     def collect(self, buffer: KataGoRolloutBuffer, steps: int) -> SelfPlayStats:
         """Step every env ``steps`` plies; ply p's transitions are rows [p * N, (p + 1) * N) behind the buffer's rows."""
-        if steps < 1:
-            raise ValueError(f"steps must be positive, got {steps}")
-        if not isinstance(buffer, KataGoRolloutBuffer):
-            raise ValueError(f"collect() writes a KataGoRolloutBuffer, got {type(buffer).__name__}")
-        if tuple(buffer.obs_shape) != _OBS_SHAPE or buffer.action_space != ACTION_SPACE:
-            raise ValueError(f"buffer holds obs {tuple(buffer.obs_shape)} / {buffer.action_space} actions, the env gives "
-                             f"{_OBS_SHAPE} / {ACTION_SPACE}")
-        if buffer.num_envs != self.num_envs:
-            raise ValueError(f"buffer is laid out for {buffer.num_envs} envs, the rollout steps {self.num_envs}")
-        bd = buffer._device
-        if bd is not None and (bd.type != "cuda" or (bd.index is not None and bd.index != self.device.index)):
-            raise ValueError(f"buffer lives on {buffer._device}, the rollout on {self.device} (a device-resident buffer)")
+        self._check_buffer(buffer, steps, self.num_envs)
         if buffer._write_offset and buffer._has_env_ids:
             raise ValueError("buffer already holds rows in the env_ids layout (split-merge / LeagueRollout); SelfPlayRollout "
                              "writes the dense (T, N) layout without env_ids: clear() the buffer or use another one")
-        stats = SelfPlayStats()
-        with torch.cuda.device(self.device), torch.no_grad():
-            self._collect(buffer, int(steps), stats)
-        return stats
+        return self._run_collect(buffer, steps, SelfPlayStats())
 
     def _collect(self, buffer, steps, stats) -> None:
         N = self.num_envs
@@ -346,44 +208,22 @@ class SelfPlayRollout:
             self._chunk(plies)
             st = self._read_state(stats)               # raises before the commit: a chunk with a guard fired is not kept
             buffer.commit(plies * N, plies)
-            if self.game_log is not None:
-                stats.games += self.game_log.drain()
-                stats.games_dropped = self.game_log.dropped - dropped_before
-            n = int(st[_TRUNC])
-            if n:
-                self._overrides(cols, n)
-                stats.truncation_overrides += n
+            self._after_commit(st, cols, stats, dropped_before)
             done += plies
         buffer.fill_alternating_perspective_overrides()            # :1590; fills NaN cells of non-terminal rows only
-        stats.plies, stats.rows = steps, int(st[_ROWS])
-        stats.wins, stats.losses, stats.draws = int(st[_WINS]), int(st[_LOSSES]), int(st[_DRAWS])
-        stats.black_wins, stats.white_wins = int(st[_BLACK]), int(st[_WHITE])
-        stats.terminated, stats.truncated = int(st[_TERMINATED]), int(st[_TRUNCATED])
+        stats.plies = steps
+        self._tallies(st, stats)
 
     def live_games(self, envs: Optional[Sequence[int]] = None) -> List[RecordedGame]:
         """The games in progress (every env, or ``envs``) between two ``collect`` calls: ``RecordedGame`` with
         ``finished=False``."""
-        if self.game_log is None:
-            raise ValueError("live_games() needs a rollout built with game_log > 0")
-        with torch.cuda.device(self.device):
-            return self.game_log.live(envs, ply_counter=self._state.data_ptr() + 4 * _PLIES)
+        return self.ply.live_games("a rollout", envs, ply_counter=self._state.data_ptr() + 4 * _PLIES)
 
     def spectator_data(self, envs: Optional[Sequence[int]] = None) -> List[dict]:
-        """``VecEnv.get_spectator_data`` of every env (or ``envs``) between two ``collect`` calls, each dict with
-        ``value_estimate``: the learner's value at the env's last ply (the reference's snapshot row takes it from
-        ``latest_values``, katago_loop.py:1938-1942).  ``move_history`` is [] unless built with ``move_history=True``;
-        ``insight`` (built with ``insight > 0``) is the ``insight_dict`` of the env's last move, None before its first move
-        after ``reset()``."""
-        with torch.cuda.device(self.device):
-            data = self.env.get_spectator_data(envs)
-            values = self._values.cpu().numpy()
-        ids = range(self.num_envs) if envs is None else [int(e) for e in envs]
-        for d, e in zip(data, ids):
-            d["value_estimate"] = float(values[e])
-        if self.insight is not None:
-            with torch.cuda.device(self.device):
-                self.insight.annotate(data, envs)
-        return data
+        """``DevicePly.spectator_data`` between two ``collect`` calls, each dict with ``value_estimate``: the learner's
+        value at the env's last ply (the reference's snapshot row takes it from ``latest_values``,
+        katago_loop.py:1938-1942)."""
+        return self.ply.spectator_data(envs, self._values)
 
     def bootstrap_values(self) -> torch.Tensor:
         """-V(observation now) by the learner (katago_loop.py:1565-1572, :1589): ``update``'s next_values, in the frame of
