@@ -806,8 +806,8 @@ int ka_policy_sample_ctl(const void* logits, int logits_bf16, const void* legal,
  *                                                            of their own (the parent's logits stay where they are)
  *   ka_lookahead_choose(...)                                 q, the choice, actions[e] of the active envs
  * table: K rows of 4 32-bit words in device memory, row m for model m, read by every launch (a new table applies from the
- *   next ply of a captured graph):   word 0 int32 width   1 fp32 prior_weight   2 int32 skip_plies   3 reserved (0)
- *   A row with width outside [0, 8], a negative or non-finite prior_weight or a negative skip_plies reads as off (width 0);
+ *   next ply of a captured graph):   word 0 int32 width   1 fp32 prior_weight   2 int32 skip_plies   3 int32 reply_width
+ *   (0 = one ply; outside [0, 8] reads as 0; ka_lookahead_fork and ka_lookahead_choose ignore it).  A row with width outside [0, 8], a negative or non-finite prior_weight or a negative skip_plies reads as off (width 0);
  *   a width above the launch's `width` is cut to it.
  * Env e with m = model_of[e] is active when m lies in [0, K), the row's width is positive, its game ply (the u32 at byte
  *   100 of its state row; without state rows: "infinite") is >= skip_plies, and it has a candidate.
@@ -822,7 +822,9 @@ int ka_policy_sample_ctl(const void* logits, int logits_bf16, const void* legal,
  *   for the mover)   1 chosen slot   2 n_cand   3 chosen action (the sampler's for an inactive env)   4.. width candidate
  *   actions (int32, -1 = unused)   4 + width.. width priors (fp32)   4 + 2 width.. width q (fp32)
  * ka_lookahead_words(which, width): 0 record words, 1 table words per model (4), 2 stats words (4: positions searched,
- *   choices that differ from the sampler's, chosen moves that won the game, reserved), 3 the maximum width (8); -1 otherwise.
+ *   choices that differ from the sampler's, chosen moves that won the game, choices of the reply search that differ from
+ *   the one-ply choice), 3 the maximum width (8), 4 the maximum reply width (8), 5 the most grandchildren of an env (64); -1
+ *   otherwise.  A reply record has ka_lookahead_words(0, reply_width) words.
  * ka_lookahead_fork: logits (N, A) fp32 or bf16, legal packed rows (legal_words == ka_mask_words(A), A = 81 * 139), actions
  *   (N) int64 the sampler's, state (N, 128) / keys (N, max(max_ply, 1)) u64 / checks (N, max(max_ply, 1)) u8: the env's rows,
  *   only read.  Written: records (N, words); child rows c = e * width + j: child_state (the 128-byte row), child_keys /
@@ -835,7 +837,34 @@ int ka_policy_sample_ctl(const void* logits, int logits_bf16, const void* legal,
  *   step refused an action, which is a bug: err bit 1, and no action is replaced.  actions (N) int64 is overwritten for the
  *   active envs; stats (4 int32) is added to with atomics, err (1 int32) is ORed; the caller clears both.
  * Refused: null tensors, another action space or mask width, width outside [1, 8], K < 1, misaligned rows (state, history
- *   and mask rows are copied in 16-byte pieces). */
+ *   and mask rows are copied in 16-byte pieces).
+ *
+ * Reply search, for the models whose table row has reply_width = r > 0: three more stages between the children's forward and
+ * the choice, and ka_lookahead_choose_replies in the place of ka_lookahead_choose:
+ *   ka_lookahead_fork_replies(...)                           reply records, grandchild rows g = (e * width + j) * r + k
+ *   ka_shogi_env_step / ka_stem / tower / heads_eval_grouped over the N * width * reply_width grandchild rows, with an err, stats,
+ *                                                            output buffers and a workspace of their own
+ *   ka_lookahead_choose_replies(...)                         v, the min per child, the choice, actions[e]
+ * Replies of child j of an active env, where the child is live (neither terminated nor truncated): its first r legal actions
+ *   of the child's post-step mask by the raw policy logit of the env's model on the child's observation (child_logits, as the
+ *   children's forward wrote them), in the candidate order; their priors are recorded and not used; skip_plies plays no part.
+ * v_jk, the grandchild's value for the root mover: 0 - reward of the grandchild step where the game ended there (the env's
+ *   reward is for the reply's mover), else P(W) - P(L) of softmax(grand_vlogits); a non-finite value logit of a live
+ *   grandchild: v_jk = -inf and err bit 0.  q_j = min_k v_jk, the first minimum; a done child keeps its reward, a live child
+ *   without a reply candidate its one-ply q.  u_j and the choice as above.  The one-ply q of every candidate is computed as
+ *   well (a non-finite value logit of a live child stays err bit 0): the one-ply choice is its arg-max of u, and env flag bit 3
+ *   and stats word 3 say that the choice differs from it.  An env whose model has reply_width 0 gets the record, action and
+ *   counters of ka_lookahead_choose, to the bit.
+ * Reply record of a child, 4 + 3 reply_width words, the env record's layout: 0 flags (bit 0 the child has replies)   1 the slot
+ *   of the first minimum   2 the number of replies   3 that reply's action (without replies: the lowest legal action of the
+ *   child's mask)   4.. reply actions   4 + r.. priors   4 + 2 r.. v (fp32).
+ * ka_lookahead_fork_replies: the child rows as the child step and forward left them, only read: child_logits (M, A) fp32 or
+ *   bf16, child_mask_bits (the post-step masks), child_model_of, child_state / child_keys / child_checks, child_terminated /
+ *   child_truncated (u8), M = N * width.  Written: reply_records (M, words) and the grandchild rows as ka_lookahead_fork writes
+ *   child rows; an unused or inactive grandchild slot (a done child's row is a restarted game) gets the lowest legal action of
+ *   the child's own post-step mask and model -1.
+ * ka_lookahead_choose_replies: the arguments of ka_lookahead_choose, the reply records and the grandchild step's and
+ *   forward's outputs (N * width * reply_width rows); grand_err as child_err: err bit 2, and on bit 1 or 2 no action is replaced. */
 int ka_lookahead_words(int which, int width);
 int ka_lookahead_fork(const void* logits, int logits_bf16, const void* legal, int legal_words, const long long* actions,
                       const int* model_of, int K, const void* table, const void* state, const void* keys, const void* checks,
@@ -844,6 +873,18 @@ int ka_lookahead_fork(const void* logits, int logits_bf16, const void* legal, in
 int ka_lookahead_choose(void* records, int width, const void* table, const int* model_of, int K, const float* child_vlogits,
                         const float* child_rewards, const void* child_terminated, const void* child_truncated,
                         const void* child_err, long long* actions, int* stats, int* err, int N, void* stream);
+int ka_lookahead_fork_replies(const void* child_logits, int logits_bf16, const void* child_mask_bits, int legal_words,
+                              const int* child_model_of, int K, const void* table, const void* child_state,
+                              const void* child_keys, const void* child_checks, const void* child_terminated,
+                              const void* child_truncated, int max_ply, int reply_width, void* reply_records, void* grand_state,
+                              void* grand_keys, void* grand_checks, void* grand_mask_bits, long long* grand_actions,
+                              int* grand_model_of, int M, int A, void* stream);
+int ka_lookahead_choose_replies(void* records, int width, void* reply_records, int reply_width, const void* table,
+                                const int* model_of, int K, const float* child_vlogits, const float* child_rewards,
+                                const void* child_terminated, const void* child_truncated, const void* child_err,
+                                const float* grand_vlogits, const float* grand_rewards, const void* grand_terminated,
+                                const void* grand_truncated, const void* grand_err, long long* actions, int* stats, int* err,
+                                int N, void* stream);
 
 /* ---- SL shard preparation (csrc/sl_prepare.hip; the replay keisei/sl/prepare.py:151-161 leaves out).  A batch of E game
  * records, game g in env g, stepped in lockstep from ka_shogi_env_reset.  One ply = ka_sl_replay_plan, ka_shogi_env_step

@@ -137,6 +137,8 @@ _SIGS = {
     "ka_lookahead_words": "ii",
     "ka_lookahead_fork": "pi pi pp i p ppp ii p pppp pp ii p",
     "ka_lookahead_choose": "p i pp i pppp p ppp i p",
+    "ka_lookahead_fork_replies": "pi pi pi p ppp pp ii p pppp pp ii p",
+    "ka_lookahead_choose_replies": "pi pi pp i ppppp ppppp ppp i p",
     "ka_sl_replay_state_words": "i",
     "ka_sl_replay_plan": "p i p i p p i pp p",
     "ka_sl_replay_record": "p i ppp i ppppppp p i p",

@@ -12,7 +12,7 @@
 //                           the sampler's action
 //
 // Row m of the controls table (device memory, read by every launch: a new table applies from the next ply of a captured
-// graph) belongs to model m:   word 0 int32 width   1 fp32 prior_weight   2 int32 skip_plies   3 reserved (0)
+// graph) belongs to model m:   word 0 int32 width   1 fp32 prior_weight   2 int32 skip_plies   3 int32 reply_width
 // A row with width outside [0, 8], a negative or non-finite weight or a negative skip_plies reads as "off"; a width above
 // the launch's width is cut to it.  An env is active when its model lies in [0, K), the row's width is positive, its game
 // ply (the u32 at byte 100 of its state row) is at least skip_plies and it has a candidate.
@@ -28,6 +28,21 @@
 // makes the env step hold every row of its launch) and model -1; their history is not copied -- the env kernel only counts
 // repetitions in it, and nothing reads such a child's outcome.  The parent's rows are only read.  Kernel nodes only,
 // caller-owned buffers, no workgroup waits for another.
+//
+// Reply search (word 3 of the row, reply_width 0..8; 0 = one ply, outside the range reads as 0; ka_lookahead_fork and
+// ka_lookahead_choose ignore it).  A child after the env step is again a complete env row, and the children's forward wrote
+// their policy logits anyway, so a second ply is three more stages and another choice:
+//
+//   ka_lookahead_fork_replies     the fork kernel with the child as "env": the first reply_width legal actions of every live
+//                                 child by the child's own logits, a reply record per child, the grandchild rows
+//   ka_shogi_env_step, forward    unchanged, over the N * width * reply_width grandchild rows
+//   ka_lookahead_choose_replies   v of every grandchild for the root mover (0 - reward where the game ended there, else
+//                                 P(W) - P(L): it is seen by the root mover again), q = the first minimum over the replies
+//                                 (a done child keeps its reward, a live child without replies its one-ply q), the choice as
+//                                 above; flag bit 3 and stats word 3: the choice differs from the one-ply choice
+//
+// A reply record has the env record's layout with reply_width in the place of width: slot and action are the first worst
+// reply for the mover, the q words the grandchildren's values.  A done child's row is a restarted game and gets no replies.
 #include "common.h"
 
 #include <climits>
@@ -51,11 +66,15 @@ struct ForkArgs {
     const uint32_t* table; const uint8_t* state; const unsigned long long* keys; const uint8_t* checks; int hist; int width;
     uint32_t* rec; uint8_t* c_state; unsigned long long* c_keys; uint8_t* c_checks; uint32_t* c_bits; long long* c_actions;
     int* c_model_of;
+    const uint8_t* term; const uint8_t* trunc;                 // the reply fork only: the "envs" are child rows, these their done bytes
 };
 
 struct ChooseArgs {
     uint32_t* rec; int width; const uint32_t* table; const int* model_of; int K; const float* vl; const float* rewards;
     const uint8_t* term; const uint8_t* trunc; const unsigned long long* c_err; long long* actions; int* stats; int* err; int n;
+    // the reply search only: the children's reply records and what the grandchild step and forward wrote
+    uint32_t* r_rec; int rwidth; const float* g_vl; const float* g_rewards; const uint8_t* g_term; const uint8_t* g_trunc;
+    const unsigned long long* g_err;
 };
 
 __device__ __forceinline__ float la_reduce(float v, float* red, bool is_max) {
@@ -96,6 +115,28 @@ __device__ __forceinline__ int la_controls(const uint32_t* table, int m, int K, 
     return w;
 }
 
+// the reply width of model m: word 3 of a row that is on; a word outside [0, 8] reads as 0
+__device__ __forceinline__ int la_reply_width(const uint32_t* table, int m, int K) {
+    float pw;
+    int skip;
+    if (la_controls(table, m, K, &pw, &skip) <= 0) return 0;
+    const int r = (int)table[(size_t)m * kLaTableWords + 3];
+    return r >= 0 && r <= kLaMaxWidth ? r : 0;
+}
+
+// P(L) - P(W) of the value logits of row c; a non-finite logit sets *bad
+__device__ __forceinline__ float la_loss_minus_win(const float* vl, size_t c, bool* bad) {
+    const float l0 = vl[c * 3], l1 = vl[c * 3 + 1], l2 = vl[c * 3 + 2];
+    const float mx = fmaxf(l0, fmaxf(l1, l2));
+    const float e0 = expf(l0 - mx), e1 = expf(l1 - mx), e2 = expf(l2 - mx);
+    *bad = !(fabsf(l0) <= 3.4e38f && fabsf(l1) <= 3.4e38f && fabsf(l2) <= 3.4e38f);
+    return (e2 - e0) / (e0 + e1 + e2);
+}
+
+// kReply = false: the envs fork into their children.  kReply = true: the "envs" are the child rows after their step -- a done
+// child is inactive, the width is the reply width of the child's model, skip_plies plays no part, and the action of an unused
+// or inactive slot is the lowest legal action of the row's own mask (there is no sampled action to fall back on).
+template <bool kReply>
 __global__ __launch_bounds__(kLaThreads) void lookahead_fork_kernel(ForkArgs a) {
     __shared__ float row[kLaA];
     __shared__ uint32_t msk[kLaWords];
@@ -108,10 +149,15 @@ __global__ __launch_bounds__(kLaThreads) void lookahead_fork_kernel(ForkArgs a) 
     const uint32_t* lw = a.legal + (size_t)e * kLaWords;
     const int m = a.model_of[e];
     const uint32_t ply = a.state ? *reinterpret_cast<const uint32_t*>(a.state + (size_t)e * kLaStateBytes + kLaPlyByte) : UINT_MAX;
-    float pw;
-    int skip;
-    int want = min(la_controls(a.table, m, a.K, &pw, &skip), width);       // (uniform over the workgroup, as every branch below)
-    if (ply < (uint32_t)skip) want = 0;
+    int want;                                                  // (uniform over the workgroup, as every branch below)
+    if constexpr (kReply) {
+        want = (a.term[e] | a.trunc[e]) ? 0 : min(la_reply_width(a.table, m, a.K), width);
+    } else {
+        float pw;
+        int skip;
+        want = min(la_controls(a.table, m, a.K, &pw, &skip), width);
+        if (ply < (uint32_t)skip) want = 0;
+    }
 
     int n_cand = 0;
     if (want > 0) {
@@ -161,7 +207,22 @@ __global__ __launch_bounds__(kLaThreads) void lookahead_fork_kernel(ForkArgs a) 
     }
     __syncthreads();                                           // s_cand, s_prior
 
-    const long long sampled = a.actions[e];
+    long long sampled;
+    if constexpr (kReply) {                                    // a block min over the first set bits
+        int lo = INT_MAX;
+        for (int w = tid; w < kLaWords; w += kLaThreads) {
+            const uint32_t mw = w == kLaWords - 1 ? lw[w] & kLaTailBits : lw[w];
+            if (mw) lo = min(lo, (w << 5) + __builtin_ctz(mw));
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) lo = min(lo, __shfl_xor(lo, o));
+        if (lane == 0) red_i[wave] = lo;
+        __syncthreads();
+        for (int w = 0; w < kLaWaves; ++w) lo = min(lo, red_i[w]);
+        sampled = lo == INT_MAX ? 0 : lo;
+    } else {
+        sampled = a.actions[e];
+    }
     if (tid < W) {
         const int r = tid >= kLaCand ? (tid - kLaCand) % width : 0, part = tid >= kLaCand ? (tid - kLaCand) / width : -1;
         uint32_t word = 0u;
@@ -229,13 +290,16 @@ __global__ __launch_bounds__(kLaThreads) void lookahead_fork_kernel(ForkArgs a) 
     }
 }
 
-// one thread per env: at most eight children each
+// one thread per env: at most eight children each, and with kReplies at most eight grandchildren behind each of them
+template <bool kReplies>
 __global__ __launch_bounds__(kLaThreads) void lookahead_choose_kernel(ChooseArgs a) {
     const int e = blockIdx.x * kLaThreads + threadIdx.x, lane = threadIdx.x & 63;
     const int width = a.width, W = la_words(width);
     // a refused child step moved no child: its outputs are the unchanged positions, so nothing is chosen from them
-    const bool held = a.c_err && (a.c_err[0] | a.c_err[1]) != 0ull;
-    bool searched = false, changed = false, won = false, bad = false;
+    const bool held_c = a.c_err && (a.c_err[0] | a.c_err[1]) != 0ull;
+    const bool held_g = kReplies && a.g_err && (a.g_err[0] | a.g_err[1]) != 0ull;
+    const bool held = held_c || held_g;
+    bool searched = false, changed = false, won = false, bad = false, replied = false;
     if (e < a.n && !held) {
         uint32_t* rec = a.rec + (size_t)e * W;
         if (rec[kLaFlags] & 1u) {
@@ -243,22 +307,49 @@ __global__ __launch_bounds__(kLaThreads) void lookahead_choose_kernel(ChooseArgs
             float pw;
             int skip;
             la_controls(a.table, a.model_of[e], a.K, &pw, &skip);
-            int best = 0;
-            float bu = 0.f;
+            int best = 0, best1 = 0;
+            float bu = 0.f, bu1 = 0.f;
             for (int j = 0; j < n_cand; ++j) {
                 const size_t c = (size_t)e * width + j;
+                const bool done = (a.term[c] | a.trunc[c]) != 0;
                 float q;
-                if (a.term[c] | a.trunc[c]) {
+                if (done) {
                     q = a.rewards[c];
                 } else {
-                    const float l0 = a.vl[c * 3], l1 = a.vl[c * 3 + 1], l2 = a.vl[c * 3 + 2];
-                    const float mx = fmaxf(l0, fmaxf(l1, l2));
-                    const float e0 = expf(l0 - mx), e1 = expf(l1 - mx), e2 = expf(l2 - mx);
-                    q = (e2 - e0) / (e0 + e1 + e2);            // the child's side to move loses = the mover wins
-                    if (!(fabsf(l0) <= 3.4e38f && fabsf(l1) <= 3.4e38f && fabsf(l2) <= 3.4e38f)) { bad = true; q = -INFINITY; }
+                    bool b;
+                    q = la_loss_minus_win(a.vl, c, &b);        // the child's side to move loses = the mover wins
+                    if (b) { bad = true; q = -INFINITY; }
+                }
+                const float prior = __uint_as_float(rec[kLaCand + width + j]);
+                if constexpr (kReplies) {
+                    const float u1 = pw > 0.f ? q + pw * prior : q;
+                    if (j == 0 || u1 > bu1) { bu1 = u1; best1 = j; }
+                    const int R = a.rwidth;
+                    uint32_t* rr = a.r_rec + c * la_words(R);
+                    if (!done && (rr[kLaFlags] & 1u)) {        // a live child with replies: the worst of them for the mover
+                        const int n_rep = min(max((int)rr[kLaNCand], 1), R);
+                        int bk = 0;
+                        float mn = 0.f;
+                        for (int k = 0; k < n_rep; ++k) {
+                            const size_t g = c * R + k;
+                            float v;
+                            if (a.g_term[g] | a.g_trunc[g]) {
+                                v = 0.f - a.g_rewards[g];      // the env's reward is for the reply's mover (0 - 0 = +0)
+                            } else {
+                                bool b;
+                                v = 0.f - la_loss_minus_win(a.g_vl, g, &b);       // seen by the root mover again
+                                if (b) { bad = true; v = -INFINITY; }
+                            }
+                            rr[kLaCand + 2 * R + k] = __float_as_uint(v);
+                            if (k == 0 || v < mn) { mn = v; bk = k; }             // (ties keep the lower slot)
+                        }
+                        rr[kLaSlot] = (uint32_t)bk;
+                        rr[kLaAction] = rr[kLaCand + bk];
+                        q = mn;
+                    }
                 }
                 rec[kLaCand + 2 * width + j] = __float_as_uint(q);
-                const float u = pw > 0.f ? q + pw * __uint_as_float(rec[kLaCand + width + j]) : q;
+                const float u = pw > 0.f ? q + pw * prior : q;
                 if (j == 0 || u > bu) { bu = u; best = j; }    // (ties keep the lower slot)
             }
             const size_t cb = (size_t)e * width + best;
@@ -266,20 +357,23 @@ __global__ __launch_bounds__(kLaThreads) void lookahead_choose_kernel(ChooseArgs
             changed = (long long)act != a.actions[e];
             won = a.term[cb] && a.rewards[cb] > 0.f;
             searched = true;
+            replied = kReplies && best != best1;
             rec[kLaSlot] = (uint32_t)best;
             rec[kLaAction] = (uint32_t)act;
-            rec[kLaFlags] = 1u | ((uint32_t)changed << 1) | ((uint32_t)won << 2);
+            rec[kLaFlags] = 1u | ((uint32_t)changed << 1) | ((uint32_t)won << 2) | ((uint32_t)replied << 3);
             a.actions[e] = act;
         }
     }
     const int ns = __popcll(__ballot(searched)), nc = __popcll(__ballot(changed)), nw = __popcll(__ballot(won));
+    const int nr = __popcll(__ballot(replied));
     const bool any_bad = __ballot(bad) != 0ull;
     if (lane == 0) {
         if (ns) atomicAdd(&a.stats[0], ns);
         if (nc) atomicAdd(&a.stats[1], nc);
         if (nw) atomicAdd(&a.stats[2], nw);
+        if (nr) atomicAdd(&a.stats[3], nr);
         if (any_bad) atomicOr(&a.err[0], 1);
-        if (held && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&a.err[0], 2);
+        if (held && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&a.err[0], (held_c ? 2 : 0) | (held_g ? 4 : 0));
     }
 }
 
@@ -287,7 +381,8 @@ __global__ __launch_bounds__(kLaThreads) void lookahead_choose_kernel(ChooseArgs
 
 extern "C" int ka_lookahead_words(int which, int width) {
     if (width < 0 || width > kLaMaxWidth) return -1;
-    return which == 0 ? la_words(width) : which == 1 ? kLaTableWords : which == 2 ? kLaStatsWords : which == 3 ? kLaMaxWidth : -1;
+    return which == 0 ? la_words(width) : which == 1 ? kLaTableWords : which == 2 ? kLaStatsWords : which == 3 ? kLaMaxWidth :
+           which == 4 ? kLaMaxWidth /* reply width */ : which == 5 ? kLaMaxWidth * kLaMaxWidth /* grandchildren per env */ : -1;
 }
 
 extern "C" int ka_lookahead_fork(const void* logits, int logits_bf16, const void* legal, int legal_words, const long long* actions,
@@ -317,8 +412,9 @@ extern "C" int ka_lookahead_fork(const void* logits, int logits_bf16, const void
                static_cast<const uint8_t*>(state), static_cast<const unsigned long long*>(keys),
                static_cast<const uint8_t*>(checks), max_ply > 0 ? max_ply : 1, width, static_cast<uint32_t*>(records),
                static_cast<uint8_t*>(child_state), static_cast<unsigned long long*>(child_keys),
-               static_cast<uint8_t*>(child_checks), static_cast<uint32_t*>(child_mask_bits), child_actions, child_model_of};
-    hipLaunchKernelGGL(lookahead_fork_kernel, dim3(N), dim3(kLaThreads), 0, static_cast<hipStream_t>(stream), a);
+               static_cast<uint8_t*>(child_checks), static_cast<uint32_t*>(child_mask_bits), child_actions, child_model_of,
+               nullptr, nullptr};
+    hipLaunchKernelGGL(lookahead_fork_kernel<false>, dim3(N), dim3(kLaThreads), 0, static_cast<hipStream_t>(stream), a);
     return ka_check_launch("lookahead_fork");
 }
 
@@ -336,8 +432,73 @@ extern "C" int ka_lookahead_choose(void* records, int width, const void* table, 
                "lookahead_choose: actions and the child error words are 8-byte aligned, every other tensor to its element size");
     ChooseArgs a{static_cast<uint32_t*>(records), width, static_cast<const uint32_t*>(table), model_of, K, child_vlogits,
                  child_rewards, static_cast<const uint8_t*>(child_terminated), static_cast<const uint8_t*>(child_truncated),
-                 static_cast<const unsigned long long*>(child_err), actions, stats, err, N};
-    hipLaunchKernelGGL(lookahead_choose_kernel, dim3((N + kLaThreads - 1) / kLaThreads), dim3(kLaThreads), 0,
+                 static_cast<const unsigned long long*>(child_err), actions, stats, err, N,
+                 nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipLaunchKernelGGL(lookahead_choose_kernel<false>, dim3((N + kLaThreads - 1) / kLaThreads), dim3(kLaThreads), 0,
                        static_cast<hipStream_t>(stream), a);
     return ka_check_launch("lookahead_choose");
+}
+
+extern "C" int ka_lookahead_fork_replies(const void* child_logits, int logits_bf16, const void* child_mask_bits, int legal_words,
+                                         const int* child_model_of, int K, const void* table, const void* child_state,
+                                         const void* child_keys, const void* child_checks, const void* child_terminated,
+                                         const void* child_truncated, int max_ply, int reply_width, void* reply_records,
+                                         void* grand_state, void* grand_keys, void* grand_checks, void* grand_mask_bits,
+                                         long long* grand_actions, int* grand_model_of, int M, int A, void* stream) {
+    KA_REQUIRE(child_logits && child_mask_bits && child_model_of && table && child_state && child_keys && child_checks &&
+               child_terminated && child_truncated && reply_records && grand_state && grand_keys && grand_checks &&
+               grand_mask_bits && grand_actions && grand_model_of && M > 0, "lookahead_fork_replies: null tensor");
+    KA_REQUIRE(A == kLaA, "lookahead_fork_replies: the spatial action space only (A = %d), got %d", kLaA, A);
+    KA_REQUIRE(legal_words == kLaWords, "lookahead_fork_replies: packed mask rows of %d words", kLaWords);
+    KA_REQUIRE(reply_width >= 1 && reply_width <= kLaMaxWidth, "lookahead_fork_replies: reply_width must lie in [1, %d], got %d",
+               kLaMaxWidth, reply_width);
+    KA_REQUIRE(K >= 1, "lookahead_fork_replies: the controls table needs at least one row, got K = %d", K);
+    KA_REQUIRE(max_ply >= 0 && max_ply <= 65535, "lookahead_fork_replies: max_ply must lie in [0, 65535], got %d", max_ply);
+    KA_REQUIRE((long long)M * reply_width <= INT_MAX, "lookahead_fork_replies: %d children of reply width %d are too many rows", M,
+               reply_width);
+    KA_REQUIRE((uintptr_t)child_logits % (logits_bf16 ? 2 : 4) == 0 && (uintptr_t)child_mask_bits % 16 == 0 &&
+               (uintptr_t)child_model_of % 4 == 0 && (uintptr_t)table % 4 == 0 && (uintptr_t)reply_records % 4 == 0 &&
+               (uintptr_t)child_state % 16 == 0 && (uintptr_t)child_keys % 16 == 0 && (uintptr_t)child_checks % 16 == 0 &&
+               (uintptr_t)grand_state % 16 == 0 && (uintptr_t)grand_keys % 16 == 0 && (uintptr_t)grand_checks % 16 == 0 &&
+               (uintptr_t)grand_mask_bits % 16 == 0 && (uintptr_t)grand_actions % 8 == 0 && (uintptr_t)grand_model_of % 4 == 0,
+               "lookahead_fork_replies: state, history and mask rows are 16-byte aligned, every other tensor to its element size");
+    ForkArgs a{child_logits, logits_bf16, static_cast<const uint32_t*>(child_mask_bits), nullptr, child_model_of, K,
+               static_cast<const uint32_t*>(table), static_cast<const uint8_t*>(child_state),
+               static_cast<const unsigned long long*>(child_keys), static_cast<const uint8_t*>(child_checks),
+               max_ply > 0 ? max_ply : 1, reply_width, static_cast<uint32_t*>(reply_records), static_cast<uint8_t*>(grand_state),
+               static_cast<unsigned long long*>(grand_keys), static_cast<uint8_t*>(grand_checks),
+               static_cast<uint32_t*>(grand_mask_bits), grand_actions, grand_model_of,
+               static_cast<const uint8_t*>(child_terminated), static_cast<const uint8_t*>(child_truncated)};
+    hipLaunchKernelGGL(lookahead_fork_kernel<true>, dim3(M), dim3(kLaThreads), 0, static_cast<hipStream_t>(stream), a);
+    return ka_check_launch("lookahead_fork_replies");
+}
+
+extern "C" int ka_lookahead_choose_replies(void* records, int width, void* reply_records, int reply_width, const void* table,
+                                           const int* model_of, int K, const float* child_vlogits, const float* child_rewards,
+                                           const void* child_terminated, const void* child_truncated, const void* child_err,
+                                           const float* grand_vlogits, const float* grand_rewards, const void* grand_terminated,
+                                           const void* grand_truncated, const void* grand_err, long long* actions, int* stats,
+                                           int* err, int N, void* stream) {
+    KA_REQUIRE(records && reply_records && table && model_of && child_vlogits && child_rewards && child_terminated &&
+               child_truncated && grand_vlogits && grand_rewards && grand_terminated && grand_truncated && actions && stats &&
+               err && N > 0, "lookahead_choose_replies: null tensor");
+    KA_REQUIRE(width >= 1 && width <= kLaMaxWidth, "lookahead_choose_replies: width must lie in [1, %d], got %d", kLaMaxWidth, width);
+    KA_REQUIRE(reply_width >= 1 && reply_width <= kLaMaxWidth, "lookahead_choose_replies: reply_width must lie in [1, %d], got %d",
+               kLaMaxWidth, reply_width);
+    KA_REQUIRE(K >= 1, "lookahead_choose_replies: the controls table needs at least one row, got K = %d", K);
+    KA_REQUIRE((long long)N * width * reply_width <= INT_MAX, "lookahead_choose_replies: too many grandchild rows");
+    KA_REQUIRE((uintptr_t)records % 4 == 0 && (uintptr_t)reply_records % 4 == 0 && (uintptr_t)table % 4 == 0 &&
+               (uintptr_t)model_of % 4 == 0 && (uintptr_t)child_vlogits % 4 == 0 && (uintptr_t)child_rewards % 4 == 0 &&
+               (uintptr_t)child_err % 8 == 0 && (uintptr_t)grand_vlogits % 4 == 0 && (uintptr_t)grand_rewards % 4 == 0 &&
+               (uintptr_t)grand_err % 8 == 0 && (uintptr_t)actions % 8 == 0 && (uintptr_t)stats % 4 == 0 && (uintptr_t)err % 4 == 0,
+               "lookahead_choose_replies: actions and the error words are 8-byte aligned, every other tensor to its element size");
+    ChooseArgs a{static_cast<uint32_t*>(records), width, static_cast<const uint32_t*>(table), model_of, K, child_vlogits,
+                 child_rewards, static_cast<const uint8_t*>(child_terminated), static_cast<const uint8_t*>(child_truncated),
+                 static_cast<const unsigned long long*>(child_err), actions, stats, err, N,
+                 static_cast<uint32_t*>(reply_records), reply_width, grand_vlogits, grand_rewards,
+                 static_cast<const uint8_t*>(grand_terminated), static_cast<const uint8_t*>(grand_truncated),
+                 static_cast<const unsigned long long*>(grand_err)};
+    hipLaunchKernelGGL(lookahead_choose_kernel<true>, dim3((N + kLaThreads - 1) / kLaThreads), dim3(kLaThreads), 0,
+                       static_cast<hipStream_t>(stream), a);
+    return ka_check_launch("lookahead_choose_replies");
 }

@@ -4,8 +4,9 @@ from .dynamic_trainer import DynamicTrainer, MatchRollout  # noqa: F401
 from .game_log import GameLog, RecordedGame, game_log_host, write_sfen_games  # noqa: F401
 from .game_feature_tracker import GameFeatureAccumulator, GameFeatureRow, GameFeatureTracker, classify_action  # noqa: F401
 from .league_rollout import LeagueRollout, LeagueRolloutStats  # noqa: F401
-from .lookahead import (Lookahead, LookaheadChoice, LookaheadControls, LookaheadStats, lookahead_active,  # noqa: F401
-                        lookahead_candidates, lookahead_choose, lookahead_table)
+from .lookahead import (Lookahead, LookaheadChoice, LookaheadControls, LookaheadReplyChoice, LookaheadStats,  # noqa: F401
+                        lookahead_active, lookahead_candidates, lookahead_choose, lookahead_choose_replies,
+                        lookahead_reply_widths, lookahead_table)
 from .match_arena import MatchArena, MatchResult, RoundStats  # noqa: F401
 from .policy_insight import InsightRecorder, PolicyInsight, action_usi, insight_dict, policy_insight  # noqa: F401
 from .sampling import ControlledSample, SamplingControls, controls_table, sample_controlled  # noqa: F401

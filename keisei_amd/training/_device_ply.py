@@ -83,12 +83,13 @@ class DevicePly:
     with ``move_history=True`` every history entry gains its move's probability, rank, entropy, win probability and top
     candidates.  ``controls`` (a table of ``sampling.py``) puts ``ka_policy_sample_ctl`` in the place of
     ``ka_policy_sample_play``; ``lookahead_table`` / ``lookahead_width`` (``lookahead.py``) add the one-ply value lookahead
-    between the sampler and the insight.  An option left at 0 / None adds no launch and allocates nothing."""
+    between the sampler and the insight, ``lookahead_reply_width > 0`` its reply search (three more stages).  An option left at 0 / None adds no launch and allocates nothing."""
 
     def __init__(self, group, num_envs: int, max_ply: int, *, start_pool_capacity: int = 0, game_log: int = 0,
                  envs_per_slot: Optional[int] = None, move_history: bool = False, insight: int = 0,
                  insight_temperature: float = 1.0, controls: Optional[np.ndarray] = None,
-                 lookahead_table: Optional[np.ndarray] = None, lookahead_width: int = 0) -> None:
+                 lookahead_table: Optional[np.ndarray] = None, lookahead_width: int = 0,
+                 lookahead_reply_width: int = 0) -> None:
         N, dev = int(num_envs), group.device
         self.device, self.num_envs = dev, N
         with torch.cuda.device(dev):
@@ -103,7 +104,9 @@ class DevicePly:
             self.insight: Optional[InsightRecorder] = InsightRecorder(self.env, insight, insight_temperature) if insight else None
             # the lookahead's table (read by every launch) and its child rows, allocated once
             self.lookahead_table: Optional[torch.Tensor] = None if lookahead_table is None else torch.from_numpy(lookahead_table).to(dev)
-            self.lookahead: Optional[Lookahead] = Lookahead(self.env, group, lookahead_width) if lookahead_width > 0 else None
+            self.lookahead: Optional[Lookahead] = None
+            if lookahead_width > 0:
+                self.lookahead = Lookahead(self.env, group, lookahead_width, lookahead_reply_width)
             self.seat(group, controls)
 
     def seat(self, group, controls: Optional[np.ndarray]) -> None:

@@ -13,7 +13,9 @@ synchronisation:
                                                  csrc/sampling.hip: temperature, top-k cut and opening plies per model)
     lookahead                                   (only with lookahead=: ka_lookahead_fork, ka_shogi_env_step over the child
                                                  rows, the grouped forward over the child observations,
-                                                 ka_lookahead_choose -- csrc/lookahead.hip, lookahead.py: the models with a
+                                                 ka_lookahead_choose -- or, with a reply_width, three more stages over the
+                                                 grandchild rows and ka_lookahead_choose_replies -- csrc/lookahead.hip,
+                                                 lookahead.py: the models with a
                                                  width play the best of their top moves by their own value head)
     ka_shogi_env_step                           (csrc/shogi_env.hip)
     ka_arena_features_step                      (csrc/arena.hip, only with features=True: the reference's per-slot
@@ -47,13 +49,13 @@ import numpy as np
 import torch
 
 from keisei_amd import _lib
-from keisei_amd.shogi_gym import MASK_WORDS
+from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS
 
 from ._device_ply import _OBS_ELEMS, DevicePly, check_loop_args
 from .dynamic_trainer import MatchRollout
 from .game_feature_tracker import GameFeatureTracker
 from .game_log import RecordedGame
-from .lookahead import LookaheadStats, arena_lookahead, lookahead_table
+from .lookahead import LookaheadStats, arena_lookahead, arena_reply_width, lookahead_table
 from .model_group import SEResNetGroup
 from .sampling import GAME_PLY_BYTE, arena_controls, controls_table
 
@@ -283,7 +285,12 @@ class MatchArena:
     forward workspace are sized by the largest ``width`` given; ``set_lookahead`` rewrites the table on the device between
     rounds without a new capture, up to that width.  ``RoundStats.lookahead`` carries the counters.  With None the ply is
     launch for launch what it was; with every width 0 nothing is allocated and nothing is launched.  Not with
-    ``collect=True``."""
+    ``collect=True``.  A model with ``reply_width = r > 0`` searches a second ply: every live child gets the model's ``r``
+    most probable replies (by the child logits the children's forward wrote anyway), the grandchildren are stepped and
+    evaluated like the children, and a candidate is worth the worst of its replies for the mover -- so a move that walks into a
+    mate in one or hangs a piece to a one-move capture is seen.  The grandchild rows and a third workspace are sized by the
+    largest ``reply_width`` given (``set_lookahead`` goes up to it); ``RoundStats.lookahead.reply_changed`` counts the choices
+    that differ from the one-ply choice.  With every ``reply_width`` 0 the launches are those of the one-ply lookahead."""
 
     def __init__(self, group: SEResNetGroup, num_envs: int = 512, envs_per_match: int = 64, max_ply: int = 512, *,
                  sync_every: int = 32, graph: bool = True, seed: Optional[int] = None, record: bool = False,
@@ -302,6 +309,7 @@ class MatchArena:
             raise ValueError(f"MatchArena runs on a GPU group; this group is on {group.device} (VecEnv has no CPU path)")
         table = arena_controls(sampling, len(group), bool(collect))
         la_table, la_width = arena_lookahead(lookahead, len(group), bool(collect))
+        la_reply = arena_reply_width(lookahead, len(group))
         self.group = group
         self.device = group.device
         self.num_envs, self.envs_per_match, self.max_ply = int(num_envs), int(envs_per_match), int(max_ply)
@@ -315,7 +323,7 @@ class MatchArena:
         self.ply = ply = DevicePly(group, N, self.max_ply, start_pool_capacity=int(start_pool_capacity), game_log=game_log,
                                    envs_per_slot=self.envs_per_match, move_history=move_history, insight=insight,
                                    insight_temperature=insight_temperature, controls=table, lookahead_table=la_table,
-                                   lookahead_width=la_width)
+                                   lookahead_width=la_width, lookahead_reply_width=la_reply)
         self.env, self.game_log, self.insight = ply.env, ply.game_log, ply.insight
         self._actions, self._logp, self._nlegal = ply.actions, ply.log_probs, ply.n_legal
         self._ctl, self._la_table, self._la = ply.ctl, ply.lookahead_table, ply.lookahead
@@ -373,6 +381,10 @@ class MatchArena:
         if width > built:
             raise ValueError(f"lookahead width {width} is above the width this arena was built with ({built}): the child "
                              "rows are allocated once, by the largest width given to the constructor")
+        reply, built = arena_reply_width(lookahead, len(self.group)), 0 if self._la is None else self._la.reply_width
+        if reply > built:
+            raise ValueError(f"lookahead reply_width {reply} is above the reply_width this arena was built with ({built}): "
+                             "the grandchild rows are allocated once, by the largest reply_width given to the constructor")
         with torch.cuda.device(self.device):
             self._la_table.copy_(torch.from_numpy(table))
 
@@ -431,6 +443,13 @@ class MatchArena:
                        child_rewards=la.child_rewards.cpu().reshape(-1, w),
                        child_done=(la.child_terminated | la.child_truncated).cpu().reshape(-1, w),
                        child_obs=la.child_obs.cpu(), child_mask_bits=la.child_mask_bits.cpu())
+            if la.reply_width:
+                r = la.reply_width
+                rec.update(lookahead_reply_records=la.reply_records().cpu(),
+                           grand_value_logits=la.grand_value_logits.cpu().reshape(-1, w, r, 3),
+                           grand_rewards=la.grand_rewards.cpu().reshape(-1, w, r),
+                           grand_done=(la.grand_terminated | la.grand_truncated).cpu().reshape(-1, w, r),
+                           child_logits=la.child_logits.cpu().reshape(-1, ACTION_SPACE))
         rec.update(actions=self._actions.cpu(), log_probs=self._logp.cpu(), n_legal=self._nlegal.cpu(),
                    rewards=self.env._rewards[self.env._cur].cpu(), terminated=self.env._terminated[self.env._cur].cpu(),
                    truncated=self.env._truncated[self.env._cur].cpu())
