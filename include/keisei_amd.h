@@ -227,6 +227,8 @@ int ka_block_dx_tail_bwd_du_gate(const void* dxc, const void* du_up, const void*
  * *_bf16 flags mark bf16 operands/outputs; nsplit > 1 writes raw fp32 partial slabs (reduce with ka_reduce_slabs). */
 int ka_gemm(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, int lda, int ldb, int ldc,
             int transA, int transB, int a_bf16, int b_bf16, int c_bf16, int relu, int accumulate, int nsplit, void* stream);
+/* waves per workgroup (4 or 16) of the kernel ka_gemm launches for this output shape and split count: a pure query */
+int ka_gemm_waves(int M, int N, int nsplit);
 /* Every FC weight / bias gradient of a backward pass in one launch (autograd's nn.Linear weight / bias backward for
  * se_resnet.py:57-66 global_fc / se_fc1 / se_fc2 and :125-130 value / score heads): job j computes dW_j (N,K) = dY_j^T X_j and, when db_j
  * is non-zero, db_j (N) = column sums of dY_j (dY_j (M,N) fp32; X_j M rows of ldx floats or bf16).  table: device int64

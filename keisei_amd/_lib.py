@@ -60,6 +60,7 @@ _SIGS = {
     "ka_block_dx_tail_bwd_du": "ppppp p ppppppppp p pppp iii i p",
     "ka_block_dx_tail_bwd_du_gate": "ppppp p ppppppppp pp pppp iii i p",
     "ka_gemm": "pppp iii iii ii iii i i i p",
+    "ka_gemm_waves": "iii",
     "ka_reduce_slabs": "pp i q i p",
     "ka_reduce_slabs2": "pp q pp q i p",
     "ka_colsum": "pppp ii i p",

@@ -501,6 +501,12 @@ inline int grid1d(size_t n, int cap) { size_t b = (n + 255) / 256; return (int)(
 
 }  // namespace
 
+// Waves per workgroup of the kernel ka_gemm launches for an (M, N) output in nsplit K ranges: 16 below 128 workgroups (few
+// workgroups: 16 waves shorten the per-wave MFMA chain of the latency-bound small-batch GEMMs), else 4.
+extern "C" int ka_gemm_waves(int M, int N, int nsplit) {
+    return (long long)((N + 63) / 64) * ((M + 63) / 64) * nsplit < 128 ? 16 : 4;
+}
+
 // nsplit > 1: C must hold nsplit slabs of M*ldc floats (no bias/relu/bf16 then); reduce with ka_reduce_slabs.
 extern "C" int ka_gemm(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, int lda, int ldb,
                        int ldc, int transA, int transB, int a_bf16, int b_bf16, int c_bf16, int relu, int accumulate,
@@ -519,8 +525,7 @@ extern "C" int ka_gemm(const void* A, const void* B, void* C, const float* bias,
     };
     g.a_vec = rows_aligned(A, lda, a_bf16);
     g.b_vec = rows_aligned(B, ldb, b_bf16);
-    // few workgroups: 16 waves per workgroup shorten the per-wave MFMA chain (latency-bound small-batch GEMMs)
-    const bool wide = (long long)grid.x * grid.y * grid.z < 128;
+    const bool wide = ka_gemm_waves(M, N, nsplit) == 16;
 #define KA_GEMM_LAUNCH(TA_, TB_) \
     do { if (wide) hipLaunchKernelGGL((gemm_f32_fast_kernel<TA_, TB_, 16>), grid, dim3(1024), 0, st, g); \
          else hipLaunchKernelGGL((gemm_f32_fast_kernel<TA_, TB_, 4>), grid, dim3(256), 0, st, g); } while (0)
@@ -555,8 +560,10 @@ extern "C" int ka_fc_chain(const float* x, const float* in_scale, const float* i
     KA_REQUIRE(ka_fc_chain_supported(K1, ldx, H, N2), "fc_chain: unsupported shape (K1=%d ldx=%d H=%d N2=%d)", K1, ldx, H, N2);
     KA_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "fc_chain: in_scale / in_shift come together");
     KA_REQUIRE(!x_out || in_scale, "fc_chain: x_out is the transformed input; without a transform pass x itself");
-    KA_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(W1) & 15) == 0 &&
-               (reinterpret_cast<uintptr_t>(W2) & 15) == 0, "fc_chain: operands must be 16-byte aligned");
+    // (null pointers pass: in_scale, in_shift and x_out are read / written as 16-byte vectors like x and the weights)
+    KA_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(W1) | reinterpret_cast<uintptr_t>(W2) |
+                 reinterpret_cast<uintptr_t>(in_scale) | reinterpret_cast<uintptr_t>(in_shift) |
+                 reinterpret_cast<uintptr_t>(x_out)) & 15) == 0, "fc_chain: operands must be 16-byte aligned");
     const int T1 = H / 16, ksplit = T1 >= 8 ? 1 : 8 / T1;
     const size_t lds = (size_t)(16 * (K1 + 4) + 16 * (H + 4) + (ksplit > 1 ? ksplit * 16 * H : 0)) * sizeof(float);
     KA_REQUIRE(lds <= 160 * 1024, "fc_chain: LDS %zu B", lds);
