@@ -865,6 +865,12 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T* __restrict_
     for (int c = lane; c < d; c += 64) stT<T>(y + (size_t)row * d, c, (ldT<T>(xr, c) - mu) * rs * gamma[c] + beta[c]);
     if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
 }
+// One term dy * xhat of dgamma, rounded ONCE: from the fp32 xhat = (x - mean) * rstd it would carry three fp32 roundings of
+// its own, up to 1.5 x 2^-23 of the term, on top of the sum's -- for a single row more than the whole error a sum of M terms is
+// allowed (M * 2^-23 * sum |terms|).  Formed in double, the term is exact before its one rounding.  dx keeps the fp32 xhat.
+__device__ __forceinline__ float ln_dgamma_term(float dy, float x, float mean, float rstd) {
+    return (float)((double)dy * (((double)x - (double)mean) * (double)rstd));
+}
 // dx = rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dy * gamma; dx is ADDED to dres (the residual-stream gradient)
 // when dres != NULL.  Per-workgroup partial sums of dgamma / dbeta: part[blockIdx.x][2][d].
 template <typename T>
@@ -893,7 +899,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
             float v = rs * (dyv * gamma[c] - s1 - xh * s2);
             if (dres) v += ldT<T>(dres, o);
             stT<T>(dx, o, v);
-            mine[c] += dyv * xh;
+            mine[c] += ln_dgamma_term(dyv, ldT<T>(x, o), mu, rs);
             mine[d + c] += dyv;
         }
     }
@@ -972,7 +978,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const T* __restr
     // of the next group was in flight: 3.1 TB/s on 3 passes.
     const T* drp = dres ? dres : dy;
     auto work = [&](long long row, bool ok, const vec16& q_dy, const vec16& q_x, const vec16& q_dr, float mu, float rs) __attribute__((always_inline)) {
-        float g[P], xh[P], dyv[P];
+        float g[P], xh[P], dyv[P], tg[P];
         E::unpack(q_dy, dyv); E::unpack(q_x, xh);
         if (!ok) {
 #pragma unroll
@@ -982,6 +988,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const T* __restr
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int e = 0; e < P; ++e) {
+            tg[e] = ln_dgamma_term(dyv[e], xh[e], mu, rs);
             xh[e] = (xh[e] - mu) * rs;
             g[e] = dyv[e] * gm[e];
             s1 += g[e]; s2 += g[e] * xh[e];
@@ -1008,7 +1015,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const T* __restr
                 *reinterpret_cast<vec16*>(dx_drop + (size_t)row * d + pl * P) = E::pack(w);
             }
 #pragma unroll
-            for (int e = 0; e < P; ++e) { dg[e] += dyv[e] * xh[e]; db[e] += dyv[e]; }
+            for (int e = 0; e < P; ++e) { dg[e] += tg[e]; db[e] += dyv[e]; }
         }
     };
     for (long long base = r0 + wave * rpw; base < rend; base += 8 * rpw) {
@@ -1178,6 +1185,13 @@ template <> struct Mm<float> {
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A[r * lda + k0 + q], B[r * ldb + k0 + q], acc, 0, 0, 0);
         return acc;
     }
+    // the same product with A handed over in its natural layout and read through its transpose: A[k][r], lda between the k
+    // (scalar operand reads: a transposed copy of A in LDS buys this MFMA nothing but unit-stride addresses)
+    static __device__ __forceinline__ f32x4 run_t(const elem* A, int lda, const elem* B, int ldb, int kdim, int r, int q, f32x4 acc) {
+        for (int k0 = 0; k0 < kdim; k0 += 4)
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A[(k0 + q) * lda + r], B[r * ldb + k0 + q], acc, 0, 0, 0);
+        return acc;
+    }
     static __device__ __forceinline__ elem cvt(float v) { return v; }
     static __device__ __forceinline__ float up(elem v) { return v; }
 };
@@ -1311,7 +1325,10 @@ __global__ __launch_bounds__(64) void attention_fwd_kernel(AttnArgs a) {
 // backward of one (board, head): dQ, dK, dV from dO, with P recomputed from the saved log-sum-exp.
 //   Pd = dropout(P);  dV = Pd^T dO;  dPd = dO V^T;  dP = dropout'(dPd);  dS = P * (dP - rowsum(dP * P)) * scale
 //   dQ = dS K;  dK = dS^T Q
-template <typename T, int NT>
+// LEAN (fp32, dh > 40, where the seven operand matrices pass the 160 KB of LDS: 171 KB at dh = 48, 216 KB at dh = 64): no
+// transposed copies of Q, K, dO -- the three products that read them take the natural matrices through Mm<float>::run_t.
+// Same products in the same order.
+template <typename T, int NT, bool LEAN = false>
 __global__ __launch_bounds__(64) void attention_bwd_kernel(AttnArgs a) {
     typedef typename Mm<T>::elem E;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1327,10 +1344,10 @@ __global__ __launch_bounds__(64) void attention_bwd_kernel(AttnArgs a) {
     E* Qt = dO + kSP * ldq;                    // transposed [NP][ldt]: Qt[c][s], Kt, dOt
     E* Kt = Qt + NP * ldt;
     E* dOt = Kt + NP * ldt;
-    E* dS = dOt + NP * ldt;                    // [RK][ldt]  rows of the chunk
+    E* dS = LEAN ? Qt : dOt + NP * ldt;        // [RK][ldt]  rows of the chunk (LEAN: Qt, Kt, dOt do not exist)
     E* dSt = dS + RK * ldt;                    // [96][ldc]  the same tile transposed
     E* Pdt = dSt + kSP * ldc;                  // [96][ldc]  dropped probabilities, transposed
-    const int total = 4 * kSP * ldq + 3 * NP * ldt + RK * ldt + 2 * kSP * ldc;
+    const int total = 4 * kSP * ldq + (LEAN ? 0 : 3 * NP * ldt) + RK * ldt + 2 * kSP * ldc;
     constexpr int VE = 16 / sizeof(E);
     {
         uint4* z = reinterpret_cast<uint4*>(smem);
@@ -1353,11 +1370,13 @@ __global__ __launch_bounds__(64) void attention_bwd_kernel(AttnArgs a) {
             *reinterpret_cast<uint4*>(K + s * ldq + c0) = kv;
             *reinterpret_cast<uint4*>(V + s * ldq + c0) = vv;
             *reinterpret_cast<uint4*>(dO + s * ldq + c0) = gv;
-            const E* qe = reinterpret_cast<const E*>(&qv); const E* ke = reinterpret_cast<const E*>(&kv);
-            const E* ge = reinterpret_cast<const E*>(&gv);
+            if constexpr (!LEAN) {
+                const E* qe = reinterpret_cast<const E*>(&qv); const E* ke = reinterpret_cast<const E*>(&kv);
+                const E* ge = reinterpret_cast<const E*>(&gv);
 #pragma unroll
-            for (int k = 0; k < VE; ++k) {
-                Qt[(c0 + k) * ldt + s] = qe[k]; Kt[(c0 + k) * ldt + s] = ke[k]; dOt[(c0 + k) * ldt + s] = ge[k];
+                for (int k = 0; k < VE; ++k) {
+                    Qt[(c0 + k) * ldt + s] = qe[k]; Kt[(c0 + k) * ldt + s] = ke[k]; dOt[(c0 + k) * ldt + s] = ge[k];
+                }
             }
         }
     } else {
@@ -1366,7 +1385,7 @@ __global__ __launch_bounds__(64) void attention_bwd_kernel(AttnArgs a) {
             const T* row = base + (size_t)s * 3 * a.d;
             const float qv = ldT<T>(row, c), kv = ldT<T>(row, a.d + c), vv = ldT<T>(row, 2 * a.d + c), gv = ldT<T>(dob, (size_t)s * a.d + c);
             Q[s * ldq + c] = Mm<T>::cvt(qv); K[s * ldq + c] = Mm<T>::cvt(kv); V[s * ldq + c] = Mm<T>::cvt(vv); dO[s * ldq + c] = Mm<T>::cvt(gv);
-            Qt[c * ldt + s] = Mm<T>::cvt(qv); Kt[c * ldt + s] = Mm<T>::cvt(kv); dOt[c * ldt + s] = Mm<T>::cvt(gv);
+            if constexpr (!LEAN) { Qt[c * ldt + s] = Mm<T>::cvt(qv); Kt[c * ldt + s] = Mm<T>::cvt(kv); dOt[c * ldt + s] = Mm<T>::cvt(gv); }
         }
     }
     __syncthreads();
@@ -1418,7 +1437,9 @@ __global__ __launch_bounds__(64) void attention_bwd_kernel(AttnArgs a) {
         for (int rt = 0; rt < RK / 16; ++rt) {
             const int row = r0 + rt * 16 + r;
             for (int nt = 0; nt < NT; ++nt) {
-                const f32x4 o = Mm<T>::run(Kt + nt * 16 * ldt, ldt, dS + rt * 16 * ldt, ldt, kSP, r, q, f32x4{0.f, 0.f, 0.f, 0.f});
+                f32x4 o;
+                if constexpr (LEAN) o = Mm<T>::run_t(K + nt * 16, ldq, dS + rt * 16 * ldt, ldt, kSP, r, q, f32x4{0.f, 0.f, 0.f, 0.f});
+                else o = Mm<T>::run(Kt + nt * 16 * ldt, ldt, dS + rt * 16 * ldt, ldt, kSP, r, q, f32x4{0.f, 0.f, 0.f, 0.f});
                 if (row < kS) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
@@ -1433,8 +1454,13 @@ __global__ __launch_bounds__(64) void attention_bwd_kernel(AttnArgs a) {
         for (int ct = 0; ct < 6; ++ct)
 #pragma unroll
             for (int nt = 0; nt < NTMAX; ++nt) {
-                dK[ct][nt] = Mm<T>::run(Qt + nt * 16 * ldt + r0, ldt, dSt + ct * 16 * ldc, ldc, RK, r, q, dK[ct][nt]);
-                dV[ct][nt] = Mm<T>::run(dOt + nt * 16 * ldt + r0, ldt, Pdt + ct * 16 * ldc, ldc, RK, r, q, dV[ct][nt]);
+                if constexpr (LEAN) {
+                    dK[ct][nt] = Mm<T>::run_t(Q + r0 * ldq + nt * 16, ldq, dSt + ct * 16 * ldc, ldc, RK, r, q, dK[ct][nt]);
+                    dV[ct][nt] = Mm<T>::run_t(dO + r0 * ldq + nt * 16, ldq, Pdt + ct * 16 * ldc, ldc, RK, r, q, dV[ct][nt]);
+                } else {
+                    dK[ct][nt] = Mm<T>::run(Qt + nt * 16 * ldt + r0, ldt, dSt + ct * 16 * ldc, ldc, RK, r, q, dK[ct][nt]);
+                    dV[ct][nt] = Mm<T>::run(dOt + nt * 16 * ldt + r0, ldt, Pdt + ct * 16 * ldc, ldc, RK, r, q, dV[ct][nt]);
+                }
             }
         __syncthreads();
     }
@@ -1905,11 +1931,12 @@ template <typename T> size_t attn_fwd_lds(int dh) {
     const int KP = attn_kp<T>(dh), NP = attn_np(dh);
     return sizeof(typename Mm<T>::elem) * (size_t)(2 * kSP * (KP + 8) + NP * (kSP + 8) + 16 * (kSP + 8));
 }
-template <typename T> size_t attn_bwd_lds(int dh) {
+template <typename T> size_t attn_bwd_lds(int dh, bool lean = false) {
     const int KP = attn_kp<T>(dh), NP = attn_np(dh);
     const int RK = Mm<T>::kStep < 16 ? 16 : Mm<T>::kStep;
-    return sizeof(typename Mm<T>::elem) * (size_t)(4 * kSP * (KP + 8) + 3 * NP * (kSP + 8) + RK * (kSP + 8) + 2 * kSP * (RK + 8));
+    return sizeof(typename Mm<T>::elem) * (size_t)(4 * kSP * (KP + 8) + (lean ? 0 : 3 * NP * (kSP + 8)) + RK * (kSP + 8) + 2 * kSP * (RK + 8));
 }
+constexpr size_t kAttnLdsMax = 160 * 1024;   // what ka_big_lds_once asks for
 
 // lanes per row of the 16-byte LayerNorm kernels (0: use the one-wave-per-row forms)
 inline int ln_vec_lanes(int d, int dtype, uintptr_t ptr_bits) {
@@ -2316,11 +2343,20 @@ extern "C" int ka_tf_attention_bwd(const void* qkv, const void* dout, const floa
         if (int rc = ka_big_lds_once(reinterpret_cast<const void*>(&attention_bwd_kernel<T_, NT_>), done, "tf_attention_bwd")) return rc; \
         hipLaunchKernelGGL((attention_bwd_kernel<T_, NT_>), dim3(B * H), dim3(64), attn_bwd_lds<T_>(dh), st, a);           \
     } while (0)
+#define KA_ATTN_BWD_LEAN(NT_)                                                                                             \
+    do {                                                                                                                  \
+        static std::atomic<unsigned long long> done{0};                                                                   \
+        if (int rc = ka_big_lds_once(reinterpret_cast<const void*>(&attention_bwd_kernel<float, NT_, true>), done, "tf_attention_bwd")) return rc; \
+        hipLaunchKernelGGL((attention_bwd_kernel<float, NT_, true>), dim3(B * H), dim3(64), attn_bwd_lds<float>(dh, true), st, a); \
+    } while (0)
     if (dtype == KA_DTYPE_BF16) {
         if (nt == 1) KA_ATTN_BWD(bf16_t, 1); else if (nt == 2) KA_ATTN_BWD(bf16_t, 2); else if (nt == 3) KA_ATTN_BWD(bf16_t, 3); else KA_ATTN_BWD(bf16_t, 4);
     } else if (dtype == KA_DTYPE_F32) {
-        if (nt == 1) KA_ATTN_BWD(float, 1); else if (nt == 2) KA_ATTN_BWD(float, 2); else if (nt == 3) KA_ATTN_BWD(float, 3); else KA_ATTN_BWD(float, 4);
+        if (attn_bwd_lds<float>(dh) > kAttnLdsMax) {           // dh > 40: the form without transposed copies (135 KB at dh = 64)
+            if (nt == 3) KA_ATTN_BWD_LEAN(3); else KA_ATTN_BWD_LEAN(4);
+        } else if (nt == 1) KA_ATTN_BWD(float, 1); else if (nt == 2) KA_ATTN_BWD(float, 2); else KA_ATTN_BWD(float, 3);
     } else { ka_set_error("tf_attention_bwd: unknown dtype %d", dtype); return KA_ERR_ARG; }
+#undef KA_ATTN_BWD_LEAN
 #undef KA_ATTN_BWD
     return ka_check_launch("tf_attention_bwd");
 }
