@@ -888,6 +888,53 @@ int ka_lookahead_choose_replies(void* records, int width, void* reply_records, i
                                 const void* grand_truncated, const void* grand_err, long long* actions, int* stats, int* err,
                                 int N, void* stream);
 
+/* ---- tree search (csrc/lookahead.hip): best-first minimax over `expansions` forks of `width` rows per env, in the place of
+ * the lookahead in the ply.  Expansion 0 is the lookahead's fork of the env; every later expansion forks the leaf of the
+ * current principal variation.  All node rows lie in one pool of expansions * N * width rows: node (t, j) of env e is row
+ * (t * N + e) * width + j, local node t * width + j, and slice t is the N * width rows of expansion t.  Per ply, on one stream:
+ *   ka_lookahead_fork(...)                                   expansion 0: record (0, e), the rows of slice 0
+ *   ka_shogi_env_step, ka_stem / tower / heads_eval_grouped  over slice 0 (logits and value logits stay in the pool)
+ *   ka_search_advance(t = 0)                                 leaf q, backup, the leaf to fork next
+ *   for t = 1 .. expansions - 1:  ka_search_expand(t), step and forward over slice t, ka_search_advance(t)
+ * table: the lookahead's K x 4 words with word 3 = expansions (1..16; outside reads as 1); words 0-2 as ka_lookahead_fork
+ *   reads them.  An env is active as for ka_lookahead_fork.
+ * q(t, j), for the player who moved into the node: the reward of its step where the game ended there, else P(L) - P(W) of
+ *   softmax(value logits) (non-finite: -inf and err bit 0).  val(n) = q(n) for a node never forked or forked without a
+ *   candidate, else 0 - max_k val(child k), the first maximum.  The principal leaf: from the first maximum of
+ *   u_j = val(0, j) + prior_weight * prior_j at the root (val alone at weight 0) down the first-maximum children until a node
+ *   is done or was forked without a candidate (the search of the env is finished: it is inactive from then on) or was never
+ *   forked (the leaf).  Expansion t < expansions_m forks the leaf's first width_m legal actions by the node's own logits.
+ *   Behind the last expansion: the first maximum of u at the root replaces actions[e]; flag bit 3 = it differs from the
+ *   same arg-max over q(0, j); pv (N, expansions) int32 = the chosen action, then the first-maximum children's actions down
+ *   to the first node never forked or done, padded with -1.
+ * Records: (expansions, N, 4 + 3 width) words, the lookahead's layout; slot and action of record (t, e) are the first-maximum
+ *   child of the node expansion t forked, the q words the leaf q.  Tree of an env, ka_search_words(1, ..) = E + 2 E width
+ *   words: parent[E] (the local node expansion t forked, -1 = none), val[E * width] fp32, by[E * width] (the expansion that
+ *   forked the node, -1 = never).
+ * ka_search_words(which, width, expansions): 0 record words, 1 tree words per env, 2 stats words (5: positions searched,
+ *   choices that differ from the sampler's, chosen moves that won, choices that differ from the one-ply choice, expansions
+ *   run summed over the envs), 3 the maximum width (8), 4 the maximum expansions (16), 5 table words per model; else -1.
+ * ka_search_expand: ka_lookahead_fork_replies over the pool, workgroup e reading row parent_row[e] (logits, post-step mask,
+ *   state, history, model) and writing rows e * width + j of slice t, which the node_* pointers name (checked against the
+ *   pool's).  active[e] = 0, a done parent or a parent_row outside [0, t * N * width) forks nothing: the rows get state and
+ *   mask of row e * width of slice 0 (a stepped or restarted position), the lowest legal action of that mask, model -1 and no
+ *   history, so the step over the slice is never refused by them.  Parents lie below slice t: nothing aliases.
+ * ka_search_advance: one thread per env after the forward of expansion t.  step_err: (expansions, 2) 64-bit words, the error
+ *   words of every slice's step; a non-zero word of slices 0..t is err bit 1, and then nothing is chosen and no action is
+ *   replaced.  Writes parent_row / active for expansion t + 1 and, at t = expansions - 1, actions, flags and pv; stats is
+ *   added to with atomics, err is ORed; the caller clears both. */
+int ka_search_words(int which, int width, int expansions);
+int ka_search_expand(const void* pool_logits, int logits_bf16, const void* pool_mask_bits, int legal_words,
+                     const int* pool_model_of, int K, const void* table, const void* pool_state, const void* pool_keys,
+                     const void* pool_checks, const void* pool_terminated, const void* pool_truncated, int max_ply, int width,
+                     int t, const int* parent_row, const int* active, void* records, void* node_state, void* node_keys,
+                     void* node_checks, void* node_mask_bits, long long* node_actions, int* node_model_of, int N, int A,
+                     void* stream);
+int ka_search_advance(void* records, void* tree, int width, int expansions, int t, const void* table, const int* model_of,
+                      int K, const float* pool_vlogits, const float* pool_rewards, const void* pool_terminated,
+                      const void* pool_truncated, const void* step_err, long long* actions, int* parent_row, int* active,
+                      int* pv, int* stats, int* err, int N, void* stream);
+
 /* ---- SL shard preparation (csrc/sl_prepare.hip; the replay keisei/sl/prepare.py:151-161 leaves out).  A batch of E game
  * records, game g in env g, stepped in lockstep from ka_shogi_env_reset.  One ply = ka_sl_replay_plan, ka_shogi_env_step
  * (unchanged), ka_sl_replay_record on one stream.

@@ -140,6 +140,9 @@ _SIGS = {
     "ka_lookahead_choose": "p i pp i pppp p ppp i p",
     "ka_lookahead_fork_replies": "pi pi pi p ppp pp ii p pppp pp ii p",
     "ka_lookahead_choose_replies": "pi pi pp i ppppp ppppp ppp i p",
+    "ka_search_words": "iii",
+    "ka_search_expand": "pi pi pi p ppp pp iii pp p pppp pp ii p",
+    "ka_search_advance": "pp iii pp i pppp p pppp pp i p",
     "ka_sl_replay_state_words": "i",
     "ka_sl_replay_plan": "p i p i p p i pp p",
     "ka_sl_replay_record": "p i ppp i ppppppp p i p",

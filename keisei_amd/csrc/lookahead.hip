@@ -43,6 +43,13 @@
 //
 // A reply record has the env record's layout with reply_width in the place of width: slot and action are the first worst
 // reply for the mover, the q words the grandchildren's values.  A done child's row is a restarted game and gets no replies.
+//
+// Tree search (a table whose word 3 is `expansions`, 1..16; the block above search_advance_kernel and include/keisei_amd.h
+// state it).  All forked rows of a ply lie in one pool, `width` rows per env and expansion, and every expansion after the
+// env's own fork spends its rows on the leaf of the current principal variation:
+//
+//   ka_search_expand      the fork kernel with a row of the pool as "env", named per env by parent_row / active
+//   ka_search_advance     one thread per env: leaf q, the backup by max and negation, the next leaf, at the end the choice
 #include "common.h"
 
 #include <climits>
@@ -67,6 +74,15 @@ struct ForkArgs {
     uint32_t* rec; uint8_t* c_state; unsigned long long* c_keys; uint8_t* c_checks; uint32_t* c_bits; long long* c_actions;
     int* c_model_of;
     const uint8_t* term; const uint8_t* trunc;                 // the reply fork only: the "envs" are child rows, these their done bytes
+    // the tree search only (NULL / 0 everywhere else): workgroup e reads row parent_row[e] of the node pool, whose first
+    // n_parent rows exist; active[e] = 0 or a row outside them reads as "no candidates" from row e * width, the fallback
+    const int* parent_row; const int* active; int n_parent;
+};
+
+struct AdvanceArgs {
+    uint32_t* rec; uint32_t* tree; int width; int expansions; int t; const uint32_t* table; const int* model_of; int K;
+    const float* vl; const float* rewards; const uint8_t* term; const uint8_t* trunc; const unsigned long long* step_err;
+    long long* actions; int* parent_row; int* active; int* pv; int* stats; int* err; int n;
 };
 
 struct ChooseArgs {
@@ -146,12 +162,28 @@ __global__ __launch_bounds__(kLaThreads) void lookahead_fork_kernel(ForkArgs a) 
     __shared__ float s_prior[kLaMaxWidth];
     const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int width = a.width, W = la_words(width);
-    const uint32_t* lw = a.legal + (size_t)e * kLaWords;
-    const int m = a.model_of[e];
-    const uint32_t ply = a.state ? *reinterpret_cast<const uint32_t*>(a.state + (size_t)e * kLaStateBytes + kLaPlyByte) : UINT_MAX;
+    int src = e;                                               // the row this workgroup reads; it writes rows e * width + j
+    bool tree = false, off = false;
+    if constexpr (kReply) {
+        if (a.parent_row) {                                    // the tree search: the parent is a row of the node pool
+            const int p = a.parent_row[e];
+            tree = true;
+            off = a.active[e] == 0 || p < 0 || p >= a.n_parent;
+            src = off ? e * width : p;                         // (row e * width of expansion 0 lies below n_parent >= N * width)
+        }
+    }
+    const uint32_t* lw = a.legal + (size_t)src * kLaWords;
+    const int m = a.model_of[src];
+    const uint32_t ply = a.state ? *reinterpret_cast<const uint32_t*>(a.state + (size_t)src * kLaStateBytes + kLaPlyByte) : UINT_MAX;
     int want;                                                  // (uniform over the workgroup, as every branch below)
     if constexpr (kReply) {
-        want = (a.term[e] | a.trunc[e]) ? 0 : min(la_reply_width(a.table, m, a.K), width);
+        if (tree) {                                            // the width of the model, not its reply width
+            float pw;
+            int skip;
+            want = (off || (a.term[src] | a.trunc[src])) ? 0 : min(la_controls(a.table, m, a.K, &pw, &skip), width);
+        } else {
+            want = (a.term[e] | a.trunc[e]) ? 0 : min(la_reply_width(a.table, m, a.K), width);
+        }
     } else {
         float pw;
         int skip;
@@ -165,8 +197,8 @@ __global__ __launch_bounds__(kLaThreads) void lookahead_fork_kernel(ForkArgs a) 
             msk[w] = w == kLaWords - 1 ? lw[w] & kLaTailBits : lw[w];
         float mx = -INFINITY;
         la_for_legal(msk, [&](int j) {                         // (a thread reads back the words it wrote itself)
-            const float v = a.logits_bf16 ? bf2f(static_cast<const uint16_t*>(a.logits)[(size_t)e * kLaA + j])
-                                          : static_cast<const float*>(a.logits)[(size_t)e * kLaA + j];
+            const float v = a.logits_bf16 ? bf2f(static_cast<const uint16_t*>(a.logits)[(size_t)src * kLaA + j])
+                                          : static_cast<const float*>(a.logits)[(size_t)src * kLaA + j];
             row[j] = v;
             mx = fmaxf(mx, v);                                 // (a NaN is passed over)
         });
@@ -237,7 +269,7 @@ __global__ __launch_bounds__(kLaThreads) void lookahead_fork_kernel(ForkArgs a) 
 
     // ---- the child rows e * width + j: state and mask for every slot, the history for the slots in use
     {
-        const uint4* s_src = reinterpret_cast<const uint4*>(a.state + (size_t)e * kLaStateBytes);
+        const uint4* s_src = reinterpret_cast<const uint4*>(a.state + (size_t)src * kLaStateBytes);
         const uint4* m_src = reinterpret_cast<const uint4*>(lw);
         constexpr int kUnits = kLaStateUnits + kLaMaskUnits;
         for (int u = tid; u < kUnits * width; u += kLaThreads) {
@@ -249,7 +281,7 @@ __global__ __launch_bounds__(kLaThreads) void lookahead_fork_kernel(ForkArgs a) 
     }
     const int hist = a.hist, n = (int)min(ply, (uint32_t)hist);            // entries [0, ply) of the env's history rows
     if (n_cand > 0 && n > 0) {
-        const unsigned long long* k_src = a.keys + (size_t)e * hist;
+        const unsigned long long* k_src = a.keys + (size_t)src * hist;
         if ((hist & 1) == 0) {                                 // rows of an even number of keys start at 16-byte boundaries
             const int units = (n + 1) >> 1;                    // (an odd count takes one stale key along: it stays inside the row)
             for (int u = tid; u < units * n_cand; u += kLaThreads) {
@@ -262,7 +294,7 @@ __global__ __launch_bounds__(kLaThreads) void lookahead_fork_kernel(ForkArgs a) 
                 a.c_keys[((size_t)e * width + j) * hist + r] = k_src[r];
             }
         }
-        const uint8_t* c_src = a.checks + (size_t)e * hist;
+        const uint8_t* c_src = a.checks + (size_t)src * hist;
         if ((hist & 15) == 0) {
             const int units = (n + 15) >> 4;
             for (int u = tid; u < units * n_cand; u += kLaThreads) {
@@ -374,6 +406,171 @@ __global__ __launch_bounds__(kLaThreads) void lookahead_choose_kernel(ChooseArgs
         if (nr) atomicAdd(&a.stats[3], nr);
         if (any_bad) atomicOr(&a.err[0], 1);
         if (held && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&a.err[0], (held_c ? 2 : 0) | (held_g ? 4 : 0));
+    }
+}
+
+// ---- tree search: best-first minimax over `expansions` forks of `width` rows per env (the header above ka_search_words in
+// include/keisei_amd.h states the semantics).  Node (t, j) of env e is local node t * width + j and row (t * N + e) * width + j
+// of the node pool; record (t, e) is row t * N + e of the records.  The tree of an env, E + 2 E width words:
+//   parent[E]  the local node expansion t forked (-1: expansion 0, or an expansion that did not run)
+//   val[E * width]  fp32, the backed-up value of every node for the player who moved into it
+//   by[E * width]   the expansion that forked the node, -1 = never
+constexpr int kLaMaxExpansions = 16, kSearchStatsWords = 5;
+
+__host__ __device__ constexpr int search_tree_words(int width, int expansions) { return expansions + 2 * expansions * width; }
+
+// the expansions of model m: word 3 of its row, outside [1, 16] reads as 1
+__device__ __forceinline__ int la_expansions(const uint32_t* table, int m, int K) {
+    if (m < 0 || m >= K) return 1;
+    const int x = (int)table[(size_t)m * kLaTableWords + 3];
+    return x >= 1 && x <= kLaMaxExpansions ? x : 1;
+}
+
+// u of a root candidate, the expression of lookahead_choose_kernel
+__device__ __forceinline__ float la_u(float q, float pw, float prior) { return pw > 0.f ? q + pw * prior : q; }
+
+// one thread per env, after the forward of expansion t: the leaf q of the new nodes, the backup from the forked node to the
+// root, the principal leaf for expansion t + 1, and behind the last expansion the choice
+__global__ __launch_bounds__(kLaThreads) void search_advance_kernel(AdvanceArgs a) {
+    const int e = blockIdx.x * kLaThreads + threadIdx.x, lane = threadIdx.x & 63;
+    const int width = a.width, W = la_words(width), E = a.expansions, t = a.t, N = a.n;
+    bool held = false;                                         // a refused step of any expansion so far moved no row
+    for (int x = 0; x <= t; ++x) held |= (a.step_err[2 * x] | a.step_err[2 * x + 1]) != 0ull;
+    const bool last = t == E - 1;
+    bool ran = false, bad = false, searched = false, changed = false, won = false, deepened = false;
+    if (e < N) {
+        uint32_t* tree = a.tree + (size_t)e * search_tree_words(width, E);
+        int* parent = reinterpret_cast<int*>(tree);
+        float* val = reinterpret_cast<float*>(tree + E);
+        int* by = reinterpret_cast<int*>(tree + E + E * width);
+        auto rec_of = [&](int x) { return a.rec + ((size_t)x * N + e) * W; };
+        auto row_of = [&](int node) { return ((size_t)(node / width) * N + e) * width + node % width; };
+        auto done_at = [&](size_t c) { return (a.term[c] | a.trunc[c]) != 0; };
+        auto cands_of = [&](int x) { const uint32_t* r = rec_of(x); return (r[kLaFlags] & 1u) ? min(max((int)r[kLaNCand], 1), width) : 0; };
+        uint32_t* rec0 = rec_of(0);
+        uint32_t* rect = rec_of(t);
+        const int m = a.model_of[e];
+        float pw;
+        int skip;
+        la_controls(a.table, m, a.K, &pw, &skip);
+        const int Em = min(la_expansions(a.table, m, a.K), E);
+        const bool root = !held && (rec0[kLaFlags] & 1u) != 0;
+        if (t == 0)
+            for (int x = 0; x < E; ++x) parent[x] = -1;
+        // expansion t ran for this env: the root's fork found a candidate, or the launch before this one chose a leaf
+        ran = root && (t == 0 || (a.active[e] != 0 && parent[t] >= 0));
+        const int n_new = ran ? cands_of(t) : 0;
+        for (int j = 0; j < width; ++j) {                      // ---- the leaf q of the new nodes
+            float q = 0.f;
+            if (j < n_new) {
+                const size_t c = row_of(t * width + j);
+                if (done_at(c)) {
+                    q = a.rewards[c];
+                } else {
+                    bool b;
+                    q = la_loss_minus_win(a.vl, c, &b);        // the node's side to move loses = its mover wins
+                    if (b) { bad = true; q = -INFINITY; }
+                }
+                rect[kLaCand + 2 * width + j] = __float_as_uint(q);
+            }
+            val[t * width + j] = q;
+            by[t * width + j] = -1;
+        }
+        if (n_new > 0) {                                  // ---- the backup: from the forked node to the root
+            int x = t;                                         // the expansion whose children changed
+            for (int level = 0; level < kLaMaxExpansions; ++level) {
+                uint32_t* r = rec_of(x);
+                const int n = cands_of(x);
+                int bk = 0;
+                float mx = 0.f;
+                if (x == 0) {                                  // the root orders by u
+                    for (int k = 0; k < n; ++k) {
+                        const float u = la_u(val[k], pw, __uint_as_float(r[kLaCand + width + k]));
+                        if (k == 0 || u > mx) { mx = u; bk = k; }
+                    }
+                } else {
+                    for (int k = 0; k < n; ++k) {
+                        const float v = val[x * width + k];
+                        if (k == 0 || v > mx) { mx = v; bk = k; }              // (ties keep the lower slot)
+                    }
+                }
+                r[kLaSlot] = (uint32_t)bk;
+                r[kLaAction] = r[kLaCand + bk];
+                if (x == 0) break;
+                const int p = parent[x];
+                if (p < 0 || p >= x * width) break;            // (never: a forked node lies in an earlier expansion)
+                val[p] = 0.f - mx;
+                x = p / width;
+            }
+        }
+        // ---- the principal leaf: the node expansion t + 1 forks
+        int next = -1;
+        if (root && t + 1 < Em) {
+            int node = (int)rec0[kLaSlot] < cands_of(0) ? (int)rec0[kLaSlot] : 0;
+            for (int level = 0; level < kLaMaxExpansions; ++level) {
+                if (done_at(row_of(node))) break;              // the game ends on the line: the search is finished
+                const int x = by[node];
+                if (x < 0 || x > t) { next = node; break; }    // never forked: the leaf
+                const int n = cands_of(x);
+                if (n == 0) break;                             // forked without a candidate: finished
+                const int k = (int)rec_of(x)[kLaSlot];
+                node = x * width + (k >= 0 && k < n ? k : 0);
+            }
+        }
+        if (next >= 0) {
+            by[next] = t + 1;
+            parent[t + 1] = next;
+        }
+        a.parent_row[e] = next >= 0 ? (int)row_of(next) : -1;
+        a.active[e] = next >= 0;
+        if (last) {                                            // ---- the choice
+            int* pv = a.pv + (size_t)e * E;
+            for (int x = 0; x < E; ++x) pv[x] = -1;
+            if (root) {
+                const int n = cands_of(0);
+                const int best = (int)rec0[kLaSlot] < n ? (int)rec0[kLaSlot] : 0;
+                int best1 = 0;
+                float bu1 = 0.f;
+                for (int k = 0; k < n; ++k) {                  // the one-ply choice: the same arg-max over the leaf q
+                    const float u1 = la_u(__uint_as_float(rec0[kLaCand + 2 * width + k]), pw, __uint_as_float(rec0[kLaCand + width + k]));
+                    if (k == 0 || u1 > bu1) { bu1 = u1; best1 = k; }
+                }
+                const size_t cb = row_of(best);
+                const int act = (int)rec0[kLaCand + best];
+                changed = (long long)act != a.actions[e];
+                won = a.term[cb] && a.rewards[cb] > 0.f;
+                searched = true;
+                deepened = best != best1;
+                rec0[kLaAction] = (uint32_t)act;
+                rec0[kLaFlags] = 1u | ((uint32_t)changed << 1) | ((uint32_t)won << 2) | ((uint32_t)deepened << 3);
+                a.actions[e] = act;
+                int node = best, len = 0;
+                pv[len++] = act;
+                while (len < E && !done_at(row_of(node))) {    // the first-maximum children down the line
+                    const int x = by[node];
+                    if (x < 0 || x > t) break;
+                    const int n2 = cands_of(x);
+                    if (n2 == 0) break;
+                    const uint32_t* r = rec_of(x);
+                    const int k = (int)r[kLaSlot] < n2 ? (int)r[kLaSlot] : 0;
+                    pv[len++] = (int)r[kLaCand + k];
+                    node = x * width + k;
+                }
+            }
+        }
+    }
+    const int nx = __popcll(__ballot(ran));
+    const bool any_bad = __ballot(bad) != 0ull;
+    const int ns = __popcll(__ballot(searched)), nc = __popcll(__ballot(changed)), nw = __popcll(__ballot(won));
+    const int nd = __popcll(__ballot(deepened));
+    if (lane == 0) {
+        if (ns) atomicAdd(&a.stats[0], ns);
+        if (nc) atomicAdd(&a.stats[1], nc);
+        if (nw) atomicAdd(&a.stats[2], nw);
+        if (nd) atomicAdd(&a.stats[3], nd);
+        if (nx) atomicAdd(&a.stats[4], nx);
+        if (any_bad) atomicOr(&a.err[0], 1);
+        if (held && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&a.err[0], 2);
     }
 }
 
@@ -501,4 +698,82 @@ extern "C" int ka_lookahead_choose_replies(void* records, int width, void* reply
     hipLaunchKernelGGL(lookahead_choose_kernel<true>, dim3((N + kLaThreads - 1) / kLaThreads), dim3(kLaThreads), 0,
                        static_cast<hipStream_t>(stream), a);
     return ka_check_launch("lookahead_choose_replies");
+}
+
+extern "C" int ka_search_words(int which, int width, int expansions) {
+    if (width < 0 || width > kLaMaxWidth || expansions < 0 || expansions > kLaMaxExpansions) return -1;
+    return which == 0 ? la_words(width) : which == 1 ? search_tree_words(width, expansions) : which == 2 ? kSearchStatsWords :
+           which == 3 ? kLaMaxWidth : which == 4 ? kLaMaxExpansions : which == 5 ? kLaTableWords : -1;
+}
+
+extern "C" int ka_search_expand(const void* pool_logits, int logits_bf16, const void* pool_mask_bits, int legal_words,
+                                const int* pool_model_of, int K, const void* table, const void* pool_state,
+                                const void* pool_keys, const void* pool_checks, const void* pool_terminated,
+                                const void* pool_truncated, int max_ply, int width, int t, const int* parent_row,
+                                const int* active, void* records, void* node_state, void* node_keys, void* node_checks,
+                                void* node_mask_bits, long long* node_actions, int* node_model_of, int N, int A, void* stream) {
+    KA_REQUIRE(pool_logits && pool_mask_bits && pool_model_of && table && pool_state && pool_keys && pool_checks &&
+               pool_terminated && pool_truncated && parent_row && active && records && node_state && node_keys && node_checks &&
+               node_mask_bits && node_actions && node_model_of && N > 0, "search_expand: null tensor");
+    KA_REQUIRE(A == kLaA, "search_expand: the spatial action space only (A = %d), got %d", kLaA, A);
+    KA_REQUIRE(legal_words == kLaWords, "search_expand: packed mask rows of %d words", kLaWords);
+    KA_REQUIRE(width >= 1 && width <= kLaMaxWidth, "search_expand: width must lie in [1, %d], got %d", kLaMaxWidth, width);
+    KA_REQUIRE(t >= 1 && t < kLaMaxExpansions, "search_expand: the expansion must lie in [1, %d), got %d", kLaMaxExpansions, t);
+    KA_REQUIRE(K >= 1, "search_expand: the controls table needs at least one row, got K = %d", K);
+    KA_REQUIRE(max_ply >= 0 && max_ply <= 65535, "search_expand: max_ply must lie in [0, 65535], got %d", max_ply);
+    KA_REQUIRE((long long)N * width * (t + 1) <= INT_MAX, "search_expand: %d envs of width %d are too many rows at expansion %d", N,
+               width, t);
+    const size_t below = (size_t)t * N * width;                // the rows of the expansions before this one
+    KA_REQUIRE(static_cast<const uint8_t*>(node_state) == static_cast<const uint8_t*>(pool_state) + below * kLaStateBytes &&
+               static_cast<const int*>(node_model_of) == pool_model_of + below,
+               "search_expand: the rows written are slice %d of the pool: they start %zu rows behind it", t, below);
+    KA_REQUIRE((uintptr_t)pool_logits % (logits_bf16 ? 2 : 4) == 0 && (uintptr_t)pool_mask_bits % 16 == 0 &&
+               (uintptr_t)pool_model_of % 4 == 0 && (uintptr_t)table % 4 == 0 && (uintptr_t)records % 4 == 0 &&
+               (uintptr_t)parent_row % 4 == 0 && (uintptr_t)active % 4 == 0 &&
+               (uintptr_t)pool_state % 16 == 0 && (uintptr_t)pool_keys % 16 == 0 && (uintptr_t)pool_checks % 16 == 0 &&
+               (uintptr_t)node_state % 16 == 0 && (uintptr_t)node_mask_bits % 16 == 0 && (uintptr_t)node_actions % 8 == 0 &&
+               (uintptr_t)node_model_of % 4 == 0,
+               "search_expand: state, history and mask rows are 16-byte aligned, every other tensor to its element size");
+    // a slice of the pool starts a whole number of history rows behind it: aligned to the pieces its rows are copied in
+    const int hist = max_ply > 0 ? max_ply : 1;
+    KA_REQUIRE((uintptr_t)node_keys % (hist % 2 == 0 ? 16 : 8) == 0 &&
+               (uintptr_t)node_checks % (hist % 16 == 0 ? 16 : hist % 4 == 0 ? 4 : 1) == 0,
+               "search_expand: the history rows written are aligned to the pieces rows of %d entries are copied in", hist);
+    ForkArgs a{pool_logits, logits_bf16, static_cast<const uint32_t*>(pool_mask_bits), nullptr, pool_model_of, K,
+               static_cast<const uint32_t*>(table), static_cast<const uint8_t*>(pool_state),
+               static_cast<const unsigned long long*>(pool_keys), static_cast<const uint8_t*>(pool_checks),
+               max_ply > 0 ? max_ply : 1, width, static_cast<uint32_t*>(records), static_cast<uint8_t*>(node_state),
+               static_cast<unsigned long long*>(node_keys), static_cast<uint8_t*>(node_checks),
+               static_cast<uint32_t*>(node_mask_bits), node_actions, node_model_of,
+               static_cast<const uint8_t*>(pool_terminated), static_cast<const uint8_t*>(pool_truncated),
+               parent_row, active, (int)below};
+    hipLaunchKernelGGL(lookahead_fork_kernel<true>, dim3(N), dim3(kLaThreads), 0, static_cast<hipStream_t>(stream), a);
+    return ka_check_launch("search_expand");
+}
+
+extern "C" int ka_search_advance(void* records, void* tree, int width, int expansions, int t, const void* table,
+                                 const int* model_of, int K, const float* pool_vlogits, const float* pool_rewards,
+                                 const void* pool_terminated, const void* pool_truncated, const void* step_err,
+                                 long long* actions, int* parent_row, int* active, int* pv, int* stats, int* err, int N,
+                                 void* stream) {
+    KA_REQUIRE(records && tree && table && model_of && pool_vlogits && pool_rewards && pool_terminated && pool_truncated &&
+               step_err && actions && parent_row && active && pv && stats && err && N > 0, "search_advance: null tensor");
+    KA_REQUIRE(width >= 1 && width <= kLaMaxWidth, "search_advance: width must lie in [1, %d], got %d", kLaMaxWidth, width);
+    KA_REQUIRE(expansions >= 1 && expansions <= kLaMaxExpansions, "search_advance: expansions must lie in [1, %d], got %d",
+               kLaMaxExpansions, expansions);
+    KA_REQUIRE(t >= 0 && t < expansions, "search_advance: the expansion must lie in [0, %d), got %d", expansions, t);
+    KA_REQUIRE(K >= 1, "search_advance: the controls table needs at least one row, got K = %d", K);
+    KA_REQUIRE((long long)N * width * expansions <= INT_MAX, "search_advance: too many node rows");
+    KA_REQUIRE((uintptr_t)records % 4 == 0 && (uintptr_t)tree % 4 == 0 && (uintptr_t)table % 4 == 0 && (uintptr_t)model_of % 4 == 0 &&
+               (uintptr_t)pool_vlogits % 4 == 0 && (uintptr_t)pool_rewards % 4 == 0 && (uintptr_t)step_err % 8 == 0 &&
+               (uintptr_t)actions % 8 == 0 && (uintptr_t)parent_row % 4 == 0 && (uintptr_t)active % 4 == 0 &&
+               (uintptr_t)pv % 4 == 0 && (uintptr_t)stats % 4 == 0 && (uintptr_t)err % 4 == 0,
+               "search_advance: actions and the step error words are 8-byte aligned, every other tensor to its element size");
+    AdvanceArgs a{static_cast<uint32_t*>(records), static_cast<uint32_t*>(tree), width, expansions, t,
+                  static_cast<const uint32_t*>(table), model_of, K, pool_vlogits, pool_rewards,
+                  static_cast<const uint8_t*>(pool_terminated), static_cast<const uint8_t*>(pool_truncated),
+                  static_cast<const unsigned long long*>(step_err), actions, parent_row, active, pv, stats, err, N};
+    hipLaunchKernelGGL(search_advance_kernel, dim3((N + kLaThreads - 1) / kLaThreads), dim3(kLaThreads), 0,
+                       static_cast<hipStream_t>(stream), a);
+    return ka_check_launch("search_advance");
 }

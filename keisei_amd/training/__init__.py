@@ -11,3 +11,5 @@ from .match_arena import MatchArena, MatchResult, RoundStats  # noqa: F401
 from .policy_insight import InsightRecorder, PolicyInsight, action_usi, insight_dict, policy_insight  # noqa: F401
 from .sampling import ControlledSample, SamplingControls, controls_table, sample_controlled  # noqa: F401
 from .selfplay_rollout import SelfPlayRollout, SelfPlayStats  # noqa: F401
+from .tree_search import (SearchControls, SearchStats, SearchTree, TreeSearch, search_backup_select,  # noqa: F401
+                          search_expansions, search_leaf_q, search_records, search_table)

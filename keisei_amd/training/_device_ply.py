@@ -26,6 +26,7 @@ from .katago_ppo import KataGoRolloutBuffer, _check_step_inputs
 from .lookahead import Lookahead
 from .policy_insight import InsightRecorder
 from .sampling import GAME_PLY_BYTE
+from .tree_search import TreeSearch
 from .value_adapter import MultiHeadValueAdapter
 
 _OBS_SHAPE = (OBS_CHANNELS, 9, 9)
@@ -83,13 +84,18 @@ class DevicePly:
     with ``move_history=True`` every history entry gains its move's probability, rank, entropy, win probability and top
     candidates.  ``controls`` (a table of ``sampling.py``) puts ``ka_policy_sample_ctl`` in the place of
     ``ka_policy_sample_play``; ``lookahead_table`` / ``lookahead_width`` (``lookahead.py``) add the one-ply value lookahead
-    between the sampler and the insight, ``lookahead_reply_width > 0`` its reply search (three more stages).  An option left at 0 / None adds no launch and allocates nothing."""
+    between the sampler and the insight, ``lookahead_reply_width > 0`` its reply search (three more stages).  ``search_table`` / ``search_width`` /
+    ``search_expansions`` (``tree_search.py``) put the tree search where the lookahead stands (not both).  An option left at
+    0 / None adds no launch and allocates nothing."""
 
     def __init__(self, group, num_envs: int, max_ply: int, *, start_pool_capacity: int = 0, game_log: int = 0,
                  envs_per_slot: Optional[int] = None, move_history: bool = False, insight: int = 0,
                  insight_temperature: float = 1.0, controls: Optional[np.ndarray] = None,
                  lookahead_table: Optional[np.ndarray] = None, lookahead_width: int = 0,
-                 lookahead_reply_width: int = 0) -> None:
+                 lookahead_reply_width: int = 0, search_table: Optional[np.ndarray] = None, search_width: int = 0,
+                 search_expansions: int = 0) -> None:
+        if search_table is not None and lookahead_table is not None:
+            raise ValueError("search_table cannot be combined with lookahead_table: the search stands where the lookahead stands")
         N, dev = int(num_envs), group.device
         self.device, self.num_envs = dev, N
         with torch.cuda.device(dev):
@@ -107,6 +113,11 @@ class DevicePly:
             self.lookahead: Optional[Lookahead] = None
             if lookahead_width > 0:
                 self.lookahead = Lookahead(self.env, group, lookahead_width, lookahead_reply_width)
+            # the search's table and its node pool, likewise
+            self.search_table: Optional[torch.Tensor] = None if search_table is None else torch.from_numpy(search_table).to(dev)
+            self.search: Optional[TreeSearch] = None
+            if search_table is not None and search_width > 0:
+                self.search = TreeSearch(self.env, group, search_width, max(int(search_expansions), 1))
             self.seat(group, controls)
 
     def seat(self, group, controls: Optional[np.ndarray]) -> None:
@@ -126,6 +137,8 @@ class DevicePly:
             self.insight.clear()
         if self.lookahead is not None:
             self.lookahead.clear()
+        if self.search is not None:
+            self.search.clear()
 
     def move(self, model_of: torch.Tensor, num_models: int, state: int, flags: int):
         """forward -> sampler -> lookahead -> insight on the current stream.  ``state``: the device pointer of the loop's
@@ -145,6 +158,8 @@ class DevicePly:
                       self.n_legal, flags, N, ACTION_SPACE, st)
         if self.lookahead is not None:                    # the active envs' actions become the lookahead's choices
             self.lookahead.step(logits, cur.legal_mask_bits, self.actions, model_of, self.lookahead_table, st)
+        if self.search is not None:                       # likewise the search's
+            self.search.step(logits, cur.legal_mask_bits, self.actions, model_of, self.search_table, st)
         if self.insight is not None:                      # while the logits exist, before the step moves the history count
             self.insight.step(logits, cur.legal_mask_bits, self.actions, value, pre, model_of, num_models, flags, st)
         return cur, pre, value, score, st

@@ -11,6 +11,10 @@ synchronisation:
                                                  first legal action, as the reference does for idle partitions;
                                                  with sampling= its place is taken by ka_policy_sample_ctl,
                                                  csrc/sampling.hip: temperature, top-k cut and opening plies per model)
+    tree search                                 (only with search=, in the lookahead's place: per expansion a fork
+                                                 (ka_lookahead_fork, then ka_search_expand), ka_shogi_env_step and the
+                                                 grouped forward over its slice of the node pool, ka_search_advance --
+                                                 csrc/lookahead.hip, tree_search.py)
     lookahead                                   (only with lookahead=: ka_lookahead_fork, ka_shogi_env_step over the child
                                                  rows, the grouped forward over the child observations,
                                                  ka_lookahead_choose -- or, with a reply_width, three more stages over the
@@ -58,6 +62,7 @@ from .game_log import RecordedGame
 from .lookahead import LookaheadStats, arena_lookahead, arena_reply_width, lookahead_table
 from .model_group import SEResNetGroup
 from .sampling import GAME_PLY_BYTE, arena_controls, controls_table
+from .tree_search import SearchStats, arena_search, search_table
 
 _HDR, _SLOT = 8, 8                      # int32 words of the state header and of one slot (csrc/arena.hip)
 _PLY, _MAX_PLY, _SAMP, _REFUSAL = 2, 3, 4, 6    # header words: plies of the round, the ply ceiling's max_ply, the
@@ -103,6 +108,7 @@ class RoundStats:
     features_dropped: int = 0           # finished games whose record did not fit the feature store
     games_dropped: int = 0              # finished games that did not fit the game log between two sync points
     lookahead: Optional[LookaheadStats] = None      # the round's lookahead counters (arenas built with lookahead=)
+    search: Optional[SearchStats] = None            # the round's tree-search counters (arenas built with search=)
 
 
 def _side_bits(trainable, pairings: Sequence[Tuple[int, int]]) -> List[int]:
@@ -290,13 +296,19 @@ class MatchArena:
     evaluated like the children, and a candidate is worth the worst of its replies for the mover -- so a move that walks into a
     mate in one or hangs a piece to a one-move capture is seen.  The grandchild rows and a third workspace are sized by the
     largest ``reply_width`` given (``set_lookahead`` goes up to it); ``RoundStats.lookahead.reply_changed`` counts the choices
-    that differ from the one-ply choice.  With every ``reply_width`` 0 the launches are those of the one-ply lookahead."""
+    that differ from the one-ply choice.  With every ``reply_width`` 0 the launches are those of the one-ply lookahead.
+    ``search=`` (a ``SearchControls`` for every model, or one per model; ``tree_search.py``) puts a best-first minimax search
+    where the lookahead stands: ``expansions`` forks of ``width`` rows per env, each spent on the leaf of the current principal
+    variation, values backed up by max and negation.  The node pool is sized by the largest ``width`` and ``expansions``
+    given; ``set_search`` rewrites the table between rounds without a new capture, up to those.  ``RoundStats.search``
+    carries the counters.  With None nothing is allocated and the launches are what they were.  Not together with
+    ``lookahead=`` and not with ``collect=True``."""
 
     def __init__(self, group: SEResNetGroup, num_envs: int = 512, envs_per_match: int = 64, max_ply: int = 512, *,
                  sync_every: int = 32, graph: bool = True, seed: Optional[int] = None, record: bool = False,
                  collect: bool = False, features: bool = False, start_pool_capacity: int = 0,
                  game_log: int = 0, move_history: bool = False, insight: int = 0,
-                 insight_temperature: float = 1.0, sampling=None, lookahead=None) -> None:
+                 insight_temperature: float = 1.0, sampling=None, lookahead=None, search=None) -> None:
         if len(group) == 0:
             raise ValueError("MatchArena needs a group with at least one model")
         if num_envs <= 0 or envs_per_match <= 0 or num_envs % envs_per_match != 0:
@@ -310,6 +322,7 @@ class MatchArena:
         table = arena_controls(sampling, len(group), bool(collect))
         la_table, la_width = arena_lookahead(lookahead, len(group), bool(collect))
         la_reply = arena_reply_width(lookahead, len(group))
+        se_table, se_width, se_expansions = arena_search(search, len(group), bool(collect), lookahead)
         self.group = group
         self.device = group.device
         self.num_envs, self.envs_per_match, self.max_ply = int(num_envs), int(envs_per_match), int(max_ply)
@@ -323,10 +336,12 @@ class MatchArena:
         self.ply = ply = DevicePly(group, N, self.max_ply, start_pool_capacity=int(start_pool_capacity), game_log=game_log,
                                    envs_per_slot=self.envs_per_match, move_history=move_history, insight=insight,
                                    insight_temperature=insight_temperature, controls=table, lookahead_table=la_table,
-                                   lookahead_width=la_width, lookahead_reply_width=la_reply)
+                                   lookahead_width=la_width, lookahead_reply_width=la_reply, search_table=se_table,
+                                   search_width=se_width, search_expansions=se_expansions)
         self.env, self.game_log, self.insight = ply.env, ply.game_log, ply.insight
         self._actions, self._logp, self._nlegal = ply.actions, ply.log_probs, ply.n_legal
         self._ctl, self._la_table, self._la = ply.ctl, ply.lookahead_table, ply.lookahead
+        self._se_table, self._se = ply.search_table, ply.search
         with torch.cuda.device(dev):
             self._state = torch.zeros(_lib.query("ka_arena_state_words", self.num_slots), dtype=torch.int32, device=dev)
             self._state_host = torch.zeros(self._state.shape, dtype=torch.int32).pin_memory()
@@ -387,6 +402,27 @@ class MatchArena:
                              "the grandchild rows are allocated once, by the largest reply_width given to the constructor")
         with torch.cuda.device(self.device):
             self._la_table.copy_(torch.from_numpy(table))
+
+    def set_search(self, search) -> None:
+        """New search controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
+        writes rows that are off.  A width or ``expansions`` above what the arena was built with is refused (the node pool is
+        sized by them), and so is an arena built without ``search=``: its ply holds no search."""
+        if self._se_table is None:
+            raise ValueError("this arena was built without search=: its ply (and its captured graph) holds no search; "
+                             "build the arena with search controls to change them later")
+        table, width, expansions = arena_search(search, len(self.group), self.collect)
+        if table is None:
+            table = search_table(None, len(self.group))
+        built = 0 if self._se is None else self._se.width
+        if width > built:
+            raise ValueError(f"search width {width} is above the width this arena was built with ({built}): the node pool "
+                             "is allocated once, by the largest width given to the constructor")
+        built = 1 if self._se is None else self._se.expansions
+        if expansions > built:
+            raise ValueError(f"search expansions {expansions} is above the expansions this arena was built with ({built}): "
+                             "the node pool is allocated once, by the largest expansions given to the constructor")
+        with torch.cuda.device(self.device):
+            self._se_table.copy_(torch.from_numpy(table))
 
     def set_sampling(self, sampling) -> None:
         """New sampling controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
@@ -450,6 +486,14 @@ class MatchArena:
                            grand_rewards=la.grand_rewards.cpu().reshape(-1, w, r),
                            grand_done=(la.grand_terminated | la.grand_truncated).cpu().reshape(-1, w, r),
                            child_logits=la.child_logits.cpu().reshape(-1, ACTION_SPACE))
+        if self._se is not None:
+            se = self._se
+            shape = (se.expansions, self.num_envs, se.width)
+            rec.update(search_records=se.records().cpu(), search_tree={k: v.cpu() for k, v in se.tree().items()},
+                       search_pv=se.principal_variations().cpu(), node_value_logits=se.value_logits.cpu().reshape(*shape, 3),
+                       node_rewards=se.rewards.cpu().reshape(shape), node_done=(se.terminated | se.truncated).cpu().reshape(shape),
+                       node_logits=se.logits.cpu().reshape(-1, ACTION_SPACE), node_mask_bits=se.mask_bits.cpu(),
+                       node_model_of=se.model_of.cpu().reshape(shape))
         rec.update(actions=self._actions.cpu(), log_probs=self._logp.cpu(), n_legal=self._nlegal.cpu(),
                    rewards=self.env._rewards[self.env._cur].cpu(), terminated=self.env._terminated[self.env._cur].cpu(),
                    truncated=self.env._truncated[self.env._cur].cpu())
@@ -586,6 +630,8 @@ class MatchArena:
         stats = RoundStats(pairings_requested=len(pairings))
         if self._la_table is not None:                    # (every width 0: nothing is searched)
             stats.lookahead = LookaheadStats()
+        if self._se_table is not None:
+            stats.search = SearchStats()
         if not pairings:
             return [], stats
         with torch.cuda.device(self.device), torch.no_grad():
@@ -633,6 +679,8 @@ class MatchArena:
             st = self._read_state()
             if self._la is not None:                      # raises on its error word
                 stats.lookahead = self._la.read()
+            if self._se is not None:
+                stats.search = self._se.read()
             stats.host_syncs += 1
             slot = st[_HDR:].reshape(self.num_slots, _SLOT)
             if self.collect:

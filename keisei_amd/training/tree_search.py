@@ -1,0 +1,471 @@
+"""Tree search for the device ply: best-first minimax over ``expansions`` forks of ``width`` rows per env.
+
+The lookahead of ``lookahead.py`` searches one ply, its reply search two, at ``width * reply_width`` rows per env.  A forked
+row after ``ka_shogi_env_step`` is a complete env row and the forward over the forked rows writes their policy logits anyway,
+so a deeper search needs only a tree: remember every node, spend each new batch of ``width`` rows on the leaf of the current
+principal variation, back the values up.  ``expansions = E`` and ``width = W`` evaluate ``E * W`` rows per env and follow the
+best line up to ``E`` plies deep.  The reference never searches: the float64 restatement below is the meaning.
+
+Semantics.  Row ``m`` of the controls table belongs to model ``m``: int32 ``width`` (0..8), fp32 ``prior_weight``, int32
+``skip_plies`` -- read exactly as the lookahead reads them, and an env is active by the lookahead's rule -- and int32
+``expansions`` (1..16; a word outside reads as 1).  *Expansion 0* is the lookahead's fork of the env: candidates, priors and
+one child per candidate.  *Node* ``(t, j)`` is candidate ``j`` of expansion ``t`` (local node ``t * width + j``).  Its leaf
+value ``q(t, j)`` is for the player who moved into it: the env's reward of that step where the game ended there, else
+``P(L) - P(W)`` of ``softmax(value_logits)`` of the env's model on the node's observation; a non-finite value logit of a live
+node makes it -inf and is an error.  *Backed-up value*: ``val(n) = q(n)`` for a node never expanded or whose expansion found
+no candidate, else ``0 - max_k val(child k)``, the first maximum over the node's candidates.  *Principal leaf*: at the root
+the first maximum of ``u_j = val(0, j) + prior_weight * p_j`` (``val`` alone at weight 0), below it the first maximum of
+``val`` over the node's children (priors below the root are recorded and not used); descend until the node is done or was
+expanded without a candidate -- the env's search is finished and it is inactive in every later expansion -- or is unexpanded:
+the leaf.  *Expansion* ``t``, ``1 <= t < expansions_m``, forks the leaf's first ``width_m`` legal moves by the node's own
+logits in the candidate order; the children carry the node's full history and are stepped and evaluated like any row.
+*Choice*: after the last expansion the first maximum of ``u_j`` at the root replaces the sampler's action; the one-ply choice
+is the same arg-max over ``q(0, j)``, and a row where the two differ sets flag bit 3 (``SearchStats.deepened``).  The
+*principal variation* is the chosen move, then the first-maximum children down to the first unexpanded or done node, at most
+``expansions`` actions, padded with -1.  Values back up by max and negation only, which are exact in fp32: the one rounded
+operation is the root's ``q + prior_weight * prior``.  ``expansions = 1`` is the one-ply lookahead bit for bit.
+"""
+from __future__ import annotations
+
+import math
+import struct
+from dataclasses import dataclass
+from typing import ClassVar, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from keisei_amd import _lib
+from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS
+
+from .lookahead import (FLAG_ACTIVE, MAX_SKIP_PLIES, MAX_WIDTH, REC_CAND, REC_FLAGS, REC_NCAND, _check_width,
+                        _loss_minus_win, _row_controls, lookahead_words)
+
+__all__ = ["SearchControls", "SearchStats", "SearchTree", "TreeSearch", "search_table", "search_expansions", "search_records",
+           "search_leaf_q", "search_backup_select", "arena_search", "MAX_EXPANSIONS", "FLAG_DEEPENED"]
+
+MAX_EXPANSIONS = 16
+FLAG_DEEPENED = 8
+ERR_VALUE, ERR_STEP = 1, 2
+
+
+def _check_expansions(expansions, lo: int = 1) -> int:
+    if isinstance(expansions, bool) or not isinstance(expansions, (int, np.integer)) or not lo <= expansions <= MAX_EXPANSIONS:
+        raise ValueError(f"expansions must be an integer in [{lo}, {MAX_EXPANSIONS}], got {expansions!r}")
+    return int(expansions)
+
+
+@dataclass(frozen=True)
+class SearchControls:
+    """One model's search controls.  ``width`` 0 is off; ``expansions`` 1 is the one-ply lookahead."""
+    width: int = 0
+    expansions: int = 1
+    prior_weight: float = 0.0
+    skip_plies: int = 0
+
+    OFF: ClassVar["SearchControls"]
+
+    def __post_init__(self) -> None:
+        for name, hi in (("width", MAX_WIDTH), ("skip_plies", MAX_SKIP_PLIES)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= hi:
+                raise ValueError(f"{name} must be an integer in [0, {hi}], got {v!r}")
+            object.__setattr__(self, name, int(v))
+        object.__setattr__(self, "expansions", _check_expansions(self.expansions))
+        w = self.prior_weight
+        if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w) or w < 0:
+            raise ValueError(f"prior_weight must be finite and >= 0, got {w!r}")
+        object.__setattr__(self, "prior_weight", float(w))
+        if self.prior_weight > 3.0e38:
+            raise ValueError(f"prior_weight must fit a float32 (at most 3.0e38), got {w!r}")
+        if self.expansions > 1 and self.width == 0:
+            raise ValueError(f"expansions {self.expansions} needs a width above 0: there is no node to expand")
+
+    def row(self) -> np.ndarray:
+        """The table row: int32 width, fp32 prior_weight, int32 skip_plies, int32 expansions, as four int32."""
+        return np.frombuffer(struct.pack("<ifii", self.width, self.prior_weight, self.skip_plies, self.expansions),
+                             dtype=np.int32).copy()
+
+
+SearchControls.OFF = SearchControls()
+
+
+@dataclass
+class SearchStats:
+    """The counters ``ka_search_advance`` adds to."""
+    searched: int = 0      # positions searched (active envs, summed over the plies)
+    changed: int = 0       # choices that differ from the sampler's action
+    won: int = 0           # chosen moves that ended the game as a win for the mover
+    deepened: int = 0      # choices that differ from the one-ply choice
+    expansions: int = 0    # expansions run, summed over the envs and plies (expansion 0 included)
+
+
+def _rows(controls, K) -> List[SearchControls]:
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1:
+        raise ValueError(f"a search table needs at least one row, got K = {K!r}")
+    K = int(K)
+    if controls is None:
+        return [SearchControls.OFF] * K
+    if isinstance(controls, SearchControls):
+        return [controls] * K
+    if isinstance(controls, (list, tuple)):
+        rows = list(controls)
+        if len(rows) != K:
+            raise ValueError(f"expected {K} SearchControls (one per model), got {len(rows)}")
+        for r in rows:
+            if not isinstance(r, SearchControls):
+                raise ValueError(f"every entry must be a SearchControls, got {type(r).__name__}")
+        return rows
+    raise ValueError(f"search must be None, a SearchControls or a sequence of {K}, got {type(controls).__name__}")
+
+
+def search_table(controls, K: int) -> np.ndarray:
+    """The ``(K, 4)`` int32 table (the weight bit-cast).  ``controls``: None (K rows ``OFF``), one ``SearchControls`` (every
+    model) or a sequence of exactly K."""
+    return np.stack([r.row() for r in _rows(controls, K)]).astype(np.int32, copy=False)
+
+
+def arena_search(search, num_models: int, collect: bool, lookahead=None) -> Tuple[Optional[np.ndarray], int, int]:
+    """``MatchArena``'s reading of ``search=``: None stays None (the ply is what it was); everything else is a table of
+    ``num_models`` rows, the largest width and the largest ``expansions`` in it -- refused together with ``lookahead=`` (the
+    search stands where the lookahead stands) and with ``collect=True`` (a searched move is no draw from the policy)."""
+    if search is None:
+        return None, 0, 0
+    if lookahead is not None:
+        raise ValueError("search= cannot be combined with lookahead=: the search stands where the lookahead stands in the "
+                         "ply, and with expansions=1 it is the lookahead")
+    if collect:
+        raise ValueError("a search cannot be combined with collect=True: DynamicTrainer treats the recorded actions as "
+                         "draws from the entry's own policy, and a move chosen by the search is not one")
+    rows = _rows(search, num_models)
+    return search_table(rows, num_models), max(r.width for r in rows), max(r.expansions for r in rows)
+
+
+def _table_of(controls, K: Optional[int] = None) -> np.ndarray:
+    if isinstance(controls, torch.Tensor):
+        controls = controls.detach().cpu().numpy()
+    if isinstance(controls, np.ndarray):                  # a table as it lies in device memory: taken as it is
+        if controls.dtype != np.int32 or controls.ndim != 2 or controls.shape[1] != 4 or controls.shape[0] < 1:
+            raise ValueError(f"a search table is a (K, 4) int32 array, got {controls.dtype} {controls.shape}")
+        return np.ascontiguousarray(controls)
+    if K is None:
+        K = len(controls) if isinstance(controls, (list, tuple)) else 1
+    return search_table(controls, K)
+
+
+def search_expansions(controls, model_of, *, expansions: int = MAX_EXPANSIONS):
+    """Per row: ``(prior_weight, expansions)`` as ``ka_search_advance`` reads them from the table: the weight of a row that
+    is on (else 0), word 3 outside [1, 16] or a model outside ``[0, K)`` reads as 1, a value above ``expansions`` (the
+    launch's) is cut to it."""
+    table = _table_of(controls)
+    mo = np.asarray(torch.as_tensor(model_of).cpu().numpy(), np.int64).reshape(-1)
+    weights, exps = np.zeros(mo.shape[0], np.float64), np.ones(mo.shape[0], np.int64)
+    for b, m in enumerate(mo):
+        if 0 <= m < table.shape[0]:
+            weights[b] = _row_controls(table[m])[1]
+            x = int(table[m, 3])
+            exps[b] = min(x if 1 <= x <= MAX_EXPANSIONS else 1, int(expansions))
+    return weights, exps
+
+
+# ---------------------------------------------------------------------------------------------- the restatement
+def search_records(n_cand, priors=None, q=None, cands=None) -> torch.Tensor:
+    """Records ``(T, B, 4 + 3 width)`` int32 as the kernels lay them out, from ``n_cand`` (T, B), ``priors`` and ``q``
+    (T, B, width) (default 0) and ``cands`` (T, B, width) int (default: candidate j is "action" ``t * width + j``)."""
+    n_cand = np.asarray(n_cand, np.int64)
+    T, B = n_cand.shape
+    width = (np.asarray(q).shape[2] if q is not None else np.asarray(priors).shape[2])
+    rec = np.zeros((T, B, lookahead_words(width)), np.int32)
+    rec[:, :, REC_FLAGS] = n_cand > 0
+    rec[:, :, REC_NCAND] = n_cand
+    used = np.arange(width)[None, None, :] < n_cand[:, :, None]
+    if cands is None:
+        cands = np.broadcast_to((np.arange(T)[:, None, None] * width + np.arange(width)[None, None, :]), (T, B, width))
+    rec[:, :, REC_CAND:REC_CAND + width] = np.where(used, np.asarray(cands, np.int64), -1)
+    f = rec.view(np.float32)
+    if priors is not None:
+        f[:, :, REC_CAND + width:REC_CAND + 2 * width] = np.where(used, np.asarray(priors, np.float32), 0)
+    if q is not None:
+        f[:, :, REC_CAND + 2 * width:REC_CAND + 3 * width] = np.where(used, np.asarray(q, np.float32), 0)
+    return torch.from_numpy(rec)
+
+
+def search_leaf_q(value_logits, rewards, done) -> Tuple[np.ndarray, int]:
+    """The leaf values in float64 and the error word: ``value_logits`` (..., 3), ``rewards`` and ``done`` (...)."""
+    vl = np.asarray(torch.as_tensor(value_logits).double().numpy())
+    rw = np.asarray(torch.as_tensor(rewards).double().numpy())
+    dn = np.asarray(torch.as_tensor(done).numpy()).astype(bool)
+    q = np.zeros(rw.shape, np.float64)
+    error = 0
+    for i in np.ndindex(*rw.shape):
+        if dn[i]:
+            q[i] = rw[i]
+        elif not np.isfinite(vl[i]).all():
+            q[i] = -np.inf
+            error |= ERR_VALUE
+        else:
+            q[i] = _loss_minus_win(vl[i])
+    return q, error
+
+
+@dataclass
+class SearchTree:
+    """What ``search_backup_select`` returns for B rows after T expansions of width W."""
+    val: np.ndarray         # (B, T, W) float64: the backed-up values (0 in the unused slots)
+    by: np.ndarray          # (B, T, W) int: the expansion that forked the node (-1 = never), the next one included
+    slot: np.ndarray        # (T, B) int: the first-maximum child of the node expansion t forked (-1: it has no candidate)
+    u: np.ndarray           # (B, W) float64: val(0, j) + prior_weight * prior (-inf in the unused slots)
+    next_node: np.ndarray   # (B,) int: the local node expansion T forks, -1 = none (inactive, finished or past expansions_m)
+    finished: np.ndarray    # (B,) bool: the principal line ends in a done node or one expanded without a candidate
+    choice: np.ndarray      # (B,) int: the first maximum of u (-1 for an inactive row)
+    one_ply: np.ndarray     # (B,) int: the same arg-max over q(0, j)
+    deepened: np.ndarray    # (B,) bool
+    pv: np.ndarray          # (B, T) int: the principal variation's actions, padded with -1
+
+
+def search_backup_select(records, done, parent, controls, model_of=None, *, q=None) -> SearchTree:
+    """The float64 restatement of ``ka_search_advance`` after T expansions.  ``records`` (T, B, 4 + 3 W) int32 as the fork
+    kernels and the advance wrote them (flags bit 0, n_cand, candidates, priors, leaf q), ``done`` (T, B, W) the nodes'
+    terminated-or-truncated flags, ``parent`` (T, B) the local node ``t' * W + j`` that expansion t forked (-1: expansion 0,
+    or an expansion that did not run for the row), ``controls`` a ``SearchControls``, a sequence of them or a (K, 4) table and
+    ``model_of`` (B,) (default: model 0).  ``q`` (T, B, W) float64 replaces the records' fp32 leaf values."""
+    rec = np.asarray(torch.as_tensor(records).cpu().numpy()).view(np.int32)
+    T, B = rec.shape[:2]
+    W = (rec.shape[2] - REC_CAND) // 3
+    dn = np.asarray(torch.as_tensor(done).cpu().numpy()).astype(bool).reshape(T, B, W)
+    par = np.asarray(torch.as_tensor(parent).cpu().numpy(), np.int64).reshape(T, B)
+    mo = np.zeros(B, np.int64) if model_of is None else np.asarray(torch.as_tensor(model_of).cpu().numpy(), np.int64)
+    weights, exps = search_expansions(controls, mo)
+    f = rec.view(np.float32)
+    prior = f[0, :, REC_CAND + W:REC_CAND + 2 * W].astype(np.float64)
+    leaf = f[:, :, REC_CAND + 2 * W:REC_CAND + 3 * W].astype(np.float64) if q is None else np.asarray(q, np.float64).reshape(T, B, W)
+    out = SearchTree(np.zeros((B, T, W)), np.full((B, T, W), -1, np.int64), np.full((T, B), -1, np.int64),
+                     np.full((B, W), -np.inf), np.full(B, -1, np.int64), np.zeros(B, bool), np.full(B, -1, np.int64),
+                     np.full(B, -1, np.int64), np.zeros(B, bool), np.full((B, T), -1, np.int64))
+    for b in range(B):
+        root = bool(rec[0, b, REC_FLAGS] & FLAG_ACTIVE)
+        if not root:
+            continue
+        pw = float(weights[b])
+        val, by, slot = out.val[b].reshape(-1), out.by[b].reshape(-1), out.slot[:, b]
+        n_of = [0] * T
+
+        def u_of(j, v):
+            return v + pw * prior[b, j] if pw > 0 else v
+
+        def first_max(x):
+            best = 0
+            for k in range(n_of[x]):
+                vk = u_of(k, val[k]) if x == 0 else val[x * W + k]
+                vb = u_of(best, val[best]) if x == 0 else val[x * W + best]
+                if vk > vb:                                    # ties keep the lower slot
+                    best = k
+            return best
+
+        for t in range(T):
+            ran = t == 0 or par[t, b] >= 0
+            n = min(max(int(rec[t, b, REC_NCAND]), 1), W) if ran and rec[t, b, REC_FLAGS] & FLAG_ACTIVE else 0
+            n_of[t] = n
+            val[t * W:t * W + n] = leaf[t, b, :n]
+            if t > 0 and ran:
+                by[par[t, b]] = t
+            x = t
+            while n > 0:                                       # the backup: from the forked node to the root
+                slot[x] = first_max(x)
+                if x == 0:
+                    break
+                p = int(par[x, b])
+                val[p] = 0.0 - val[x * W + slot[x]]
+                x = p // W
+        for j in range(n_of[0]):
+            out.u[b, j] = u_of(j, val[j])
+        out.choice[b] = slot[0]
+        best1 = 0
+        for k in range(n_of[0]):
+            if u_of(k, leaf[0, b, k]) > u_of(best1, leaf[0, b, best1]):
+                best1 = k
+        out.one_ply[b] = best1
+        out.deepened[b] = best1 != slot[0]
+        # the principal line
+        node, line = int(slot[0]), [int(rec[0, b, REC_CAND + slot[0]])]
+        while True:
+            if dn.reshape(T * B * W)[(node // W * B + b) * W + node % W]:
+                out.finished[b] = True
+                break
+            x = int(by[node])
+            if x < 0:
+                if T < exps[b]:
+                    out.next_node[b] = node
+                break
+            if n_of[x] == 0:
+                out.finished[b] = True
+                break
+            line.append(int(rec[x, b, REC_CAND + slot[x]]))
+            node = x * W + int(slot[x])
+        if out.next_node[b] >= 0:
+            by[out.next_node[b]] = T
+        out.pv[b, :len(line)] = line[:T]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- in the ply
+class TreeSearch:
+    """The node pool of a device ``VecEnv`` and the stages of the search.  Everything is allocated here, once: ``expansions *
+    envs * width`` node rows -- state, key and check history, both packed mask rows, action, model, policy logits, value
+    logits and the step's scalars -- and one scratch of ``envs * width`` rows that every expansion's step and forward write
+    and nothing else reads: observations, terminal observations and the forward's activation maps.  Slice ``t`` of the pool is
+    rows ``[t * envs * width, (t + 1) * envs * width)``; node ``(t, j)`` of env ``e`` is row ``(t * envs + e) * width + j``."""
+
+    def __init__(self, env, group, width: int, expansions: int) -> None:
+        width = _check_width(width)
+        expansions = _check_expansions(expansions)
+        if env._amode != 1 or env._omode != 1:
+            raise ValueError("the search covers the katago observation and the spatial action mode only")
+        index = lambda d: torch.cuda.current_device() if d.index is None else d.index  # noqa: E731
+        if getattr(group, "_tables", None) is None or group.device.type != "cuda" or index(group.device) != index(env.device):
+            raise ValueError(f"the search runs on a GPU group on the env's device ({env.device}); this group is on {group.device}")
+        if env._state.shape[1] != 128:
+            raise ValueError(f"the search copies state rows of 128 bytes, the env's have {env._state.shape[1]}")
+        self.env, self.group, self.width, self.expansions = env, group, width, expansions
+        n, dev, hist = env.num_envs, env.device, env._keys.shape[1]
+        self.words = _lib.query("ka_search_words", 0, width, expansions)
+        self.tree_words = _lib.query("ka_search_words", 1, width, expansions)
+        assert self.words == lookahead_words(width) and self.tree_words == expansions + 2 * expansions * width
+        assert width <= _lib.query("ka_search_words", 3, 0, 0) == MAX_WIDTH
+        assert expansions <= _lib.query("ka_search_words", 4, 0, 0) == MAX_EXPANSIONS
+        self.M = M = n * width
+        P = expansions * M
+        with torch.cuda.device(dev):
+            z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)  # noqa: E731
+            self.state = z(P, 128, dtype=torch.uint8)
+            self.keys = z(P, hist, dtype=torch.int64)
+            self.checks = z(P, hist, dtype=torch.uint8)
+            self.bits_in = z(P, MASK_WORDS, dtype=torch.int32)         # the parents' masks: the step validates against them
+            self.mask_bits = z(P, MASK_WORDS, dtype=torch.int32)
+            self.actions = z(P, dtype=torch.int64)
+            self.model_of = torch.full((P,), -1, dtype=torch.int32, device=dev)
+            self.logits = z(P, 9, 9, ACTION_SPACE // 81, dtype=torch.float32)
+            self.value_logits = z(P, 3, dtype=torch.float32)
+            self.rewards = z(P, dtype=torch.float32)
+            self.terminated = z(P, dtype=torch.bool)
+            self.truncated = z(P, dtype=torch.bool)
+            self.players = z(P, dtype=torch.uint8)
+            self.reason = z(P, dtype=torch.uint8)
+            self.captured = z(P, dtype=torch.uint8)
+            self.ply = z(P, dtype=torch.int16)
+            self.material = z(P, dtype=torch.int32)
+            # the scratch of one expansion, shared by all
+            self.obs = z(M, env._C, 9, 9, dtype=torch.float32)
+            self.terminal_obs = z(M, env._C, 9, 9, dtype=torch.float32)
+            scratch = group._tables.workspace(M)
+            self._ws = [dict(scratch, logits=self.logits[t * M:(t + 1) * M], value=self.value_logits[t * M:(t + 1) * M])
+                        for t in range(expansions)]
+            self._env_stats = z(4, dtype=torch.int64)
+            self._step_err = z(expansions, 2, dtype=torch.int64)
+            self._records = z(expansions, n, self.words, dtype=torch.int32)
+            self._tree = z(n, self.tree_words, dtype=torch.int32)
+            self.parent_row = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            self.active = z(n, dtype=torch.int32)
+            self._pv = torch.full((n, expansions), -1, dtype=torch.int32, device=dev)
+            self._nstats = _lib.query("ka_search_words", 2, width, expansions)
+            self._counters = z(self._nstats + 1, dtype=torch.int32)    # stats, then the error word
+            self._counters_host = torch.zeros(self._counters.shape, dtype=torch.int32).pin_memory()
+
+    def rows(self, t: int) -> slice:
+        """The pool rows of expansion ``t``."""
+        if not 0 <= t < self.expansions:
+            raise ValueError(f"expansion {t} lies outside [0, {self.expansions})")
+        return slice(t * self.M, (t + 1) * self.M)
+
+    def node_row(self, e, node):
+        """The pool row of local node ``node`` (``t * width + j``) of env ``e``."""
+        return (node // self.width * self.env.num_envs + e) * self.width + node % self.width
+
+    def clear(self) -> None:
+        """Zero the counters, the error word and the refusal latches of every slice's step (a round's start)."""
+        self._counters.zero_()
+        self._step_err.zero_()
+
+    # ------------------------------------------------------------------ the stages
+    def fork(self, logits, mask_bits, actions, model_of, table, stream) -> None:
+        """Expansion 0: the lookahead's fork of the envs into slice 0."""
+        env, s = self.env, self.rows(0)
+        _lib.call("ka_lookahead_fork", logits, int(logits.dtype == torch.bfloat16), mask_bits, MASK_WORDS, actions, model_of,
+                  int(table.shape[0]), table, env._state, env._keys, env._checks, env._max_ply, self.width, self._records[0],
+                  self.state[s], self.keys[s], self.checks[s], self.bits_in[s], self.actions[s], self.model_of[s],
+                  env.num_envs, ACTION_SPACE, stream)
+
+    def expand(self, t: int, table, stream) -> None:
+        """Expansion ``t >= 1``, after ``advance(t - 1)``: the leaves named by ``parent_row`` / ``active`` fork into slice t."""
+        env, s = self.env, self.rows(t)
+        _lib.call("ka_search_expand", self.logits, 0, self.mask_bits, MASK_WORDS, self.model_of, int(table.shape[0]), table,
+                  self.state, self.keys, self.checks, self.terminated, self.truncated, env._max_ply, self.width, t,
+                  self.parent_row, self.active, self._records[t], self.state[s], self.keys[s], self.checks[s], self.bits_in[s],
+                  self.actions[s], self.model_of[s], env.num_envs, ACTION_SPACE, stream)
+
+    def step_nodes(self, t: int, stream) -> None:
+        env, s = self.env, self.rows(t)
+        _lib.call("ka_shogi_env_step", self.state[s], self.keys[s], self.checks[s], self.actions[s], self.M, env._max_ply,
+                  env._omode, env._amode, None, self.bits_in[s], self._step_err[t], self.obs, None, self.mask_bits[s],
+                  self.rewards[s], self.terminated[s], self.truncated[s], self.terminal_obs, self.players[s], self.captured[s],
+                  self.reason[s], self.ply[s], self.material[s], self._env_stats, stream)
+
+    def evaluate(self, t: int) -> None:
+        self.group._tables.forward(self.obs, self.model_of[self.rows(t)], ws=self._ws[t])
+
+    def advance(self, t: int, actions, model_of, table, stream) -> None:
+        """After ``evaluate(t)``: leaf q, backup, the leaf of expansion t + 1; at the last expansion the choice."""
+        self.rows(t)
+        _lib.call("ka_search_advance", self._records, self._tree, self.width, self.expansions, t, table, model_of,
+                  int(table.shape[0]), self.value_logits, self.rewards, self.terminated, self.truncated, self._step_err,
+                  actions, self.parent_row, self.active, self._pv, self._counters,
+                  self._counters.data_ptr() + 4 * self._nstats, self.env.num_envs, stream)
+
+    def step(self, logits, mask_bits, actions, model_of, table, stream) -> None:
+        """Every stage on the current stream (``stream``: its pointer), after the sampler and before ``env.step``:
+        ``actions`` (envs,) int64 is overwritten for the active envs.  Arguments as ``Lookahead.step``; ``table`` is the
+        (K, 4) int32 search table on the device."""
+        for t in range(self.expansions):
+            if t == 0:
+                self.fork(logits, mask_bits, actions, model_of, table, stream)
+            else:
+                self.expand(t, table, stream)
+            self.step_nodes(t, stream)
+            self.evaluate(t)
+            self.advance(t, actions, model_of, table, stream)
+
+    # ------------------------------------------------------------------ host side
+    def read(self) -> SearchStats:
+        """At a sync point: the counters since ``clear()`` (one small device -> host copy).  Raises on the error word."""
+        self._counters_host.copy_(self._counters)
+        c = self._counters_host.numpy()
+        err = int(c[self._nstats])
+        if err & ERR_STEP:
+            words = self._step_err.cpu()
+            t = int(torch.nonzero(words.ne(0).any(1))[0]) if bool(words.ne(0).any()) else 0
+            raise RuntimeError(f"the search's step of expansion {t} refused an action (word "
+                               f"{int(words[t, 1]) or int(words[t, 0]):#x}): a forked row does not match the mask it was "
+                               "forked with")
+        if err & ERR_VALUE:
+            raise RuntimeError("non-finite value logits in the search (a model has diverged)")
+        return SearchStats(*(int(v) for v in c[:5]))
+
+    def records(self, t: Optional[int] = None) -> torch.Tensor:
+        """The records of the last ``step`` (a copy on the device): (envs, 4 + 3 width) of expansion ``t``, or all
+        (expansions, envs, 4 + 3 width)."""
+        if t is None:
+            return self._records.clone()
+        self.rows(t)
+        return self._records[t].clone()
+
+    def tree(self) -> dict:
+        """The trees of the last ``step`` (copies on the device): ``parent`` (envs, expansions) int32, ``val`` (envs,
+        expansions, width) fp32 and ``by`` (envs, expansions, width) int32."""
+        E, W, n = self.expansions, self.width, self.env.num_envs
+        t = self._tree.clone()
+        return {"parent": t[:, :E], "val": t[:, E:E + E * W].view(torch.float32).reshape(n, E, W),
+                "by": t[:, E + E * W:].reshape(n, E, W)}
+
+    def principal_variations(self) -> torch.Tensor:
+        """(envs, expansions) int32: per env the chosen action and the line behind it, padded with -1."""
+        return self._pv.clone()
