@@ -935,6 +935,53 @@ int ka_search_advance(void* records, void* tree, int width, int expansions, int 
                       const void* pool_truncated, const void* step_err, long long* actions, int* parent_row, int* active,
                       int* pv, int* stats, int* err, int N, void* stream);
 
+/* ---- mate in one (csrc/mate.hip; the reference never searches).  A rules-only mate check inside the ply, behind the
+ * lookahead or the search and before the insight, per model: fork the env rows into one child row per checking move, step
+ * the children with ka_shogi_env_step as it is, and play a child that ended by checkmate.  No forward runs.  Three stages on
+ * one stream, kernel launches only, caller-owned buffers, no workgroup waits for another, nothing on the host in between:
+ *   ka_mate_fork(...)                                        records, child rows
+ *   ka_shogi_env_step(child_state, child_keys, child_checks, child_actions, N * cap, max_ply, 1, 1, NULL, child_mask_bits,
+ *                     child_err, ...)                        its own err, stats and output buffers, no pool
+ *   ka_mate_choose(...)                                      the mates, actions[e] of the envs that have one
+ * table: K rows of 4 32-bit words in device memory, row m for model m, read by every launch (a new table applies from the
+ *   next ply of a captured graph):   word 0 int32 max_checks (0 = off, 1..64)   1 int32 skip_plies (>= 0)   2, 3 reserved,
+ *   zero.  A row with max_checks outside [0, 64] or a negative skip_plies reads as off; max_checks above the launch's `cap`
+ *   is cut to it.
+ * Env e with m = model_of[e] is active when m lies in [0, K), the row's max_checks is positive, its game ply (the u32 at
+ *   byte 100 of its state row) is >= skip_plies, and it has a checking move.
+ * Checking moves: the legal actions (the set bits of the env's packed mask row) after which the other king is attacked by
+ *   the mover -- direct, discovered and double checks alike -- in ascending action order.  The first min(max_checks, cap)
+ *   are forked.  A child is a mate when its slot is used, the child step set `terminated`, its termination reason is
+ *   checkmate (1) and its reward is positive: the env step's verdict is the definition, so a checking move that ends the
+ *   game by repetition, perpetual check or the move limit is not a mate.  If the incoming action is itself one of the
+ *   mates it stays; otherwise the mate with the lowest action index replaces actions[e].
+ * Record of an env, ka_mate_words(0, cap) = 4 + cap int32 words:
+ *   0 flags (bit 0 active, bit 1 mate found, bit 2 the action was changed, bit 3 truncated: more checking moves than were
+ *   forked)   1 checking moves, uncapped (0 for an env the controls leave out: its moves are not looked at)   2 the slot of
+ *   the mate played, or -1   3 the action played (the incoming action unless bit 2)   4.. cap checking actions forked,
+ *   ascending, -1 = unused
+ * ka_mate_words(which, cap): 0 record words, 1 table words per model (4), 2 counter words (6: positions active, children
+ *   forked, mates found, actions changed, positions truncated, then the error word), 3 the maximum cap (64); -1 otherwise.
+ * ka_mate_fork: legal packed rows (legal_words == ka_mask_words(A), A = 81 * 139), actions (N) int64 the incoming actions,
+ *   state (N, 128) / keys (N, max(max_ply, 1)) u64 / checks (N, max(max_ply, 1)) u8: the env's rows, only read.  Written:
+ *   records (N, words); child rows c = e * cap + j: child_state (the 128-byte row), child_keys / child_checks (entries
+ *   [0, ply) of the env's rows, slots in use only; same row stride), child_mask_bits (the env's current packed mask row: the
+ *   child step validates against it), child_actions (checking move j; the env's own incoming action for an unused or
+ *   inactive slot, legal whenever the main step's is -- nothing reads such a child's outcome).
+ * ka_mate_choose: child_rewards, child_terminated (u8), child_reason (u8) as the child step wrote them; child_err: the child
+ *   step's two 64-bit error words (or NULL) -- non-zero means the child step refused an action, which is a bug: err bit 1,
+ *   and no action is replaced.  actions (N) int64 is overwritten where a mate replaces it; stats (5 int32) is added to with
+ *   atomics, err (1 int32) is ORed; the caller clears both.
+ * Refused: null tensors, another action space or mask width, cap outside [1, 64], K < 1, a misaligned table, misaligned rows
+ *   (state, history and mask rows are copied in 16-byte pieces). */
+int ka_mate_words(int which, int cap);
+int ka_mate_fork(const void* legal, int legal_words, const long long* actions, const int* model_of, int K, const void* table,
+                 const void* state, const void* keys, const void* checks, int max_ply, int cap, void* records,
+                 void* child_state, void* child_keys, void* child_checks, void* child_mask_bits, long long* child_actions,
+                 int N, int A, void* stream);
+int ka_mate_choose(void* records, int cap, const float* child_rewards, const void* child_terminated, const void* child_reason,
+                   const void* child_err, long long* actions, int* stats, int* err, int N, void* stream);
+
 /* ---- SL shard preparation (csrc/sl_prepare.hip; the replay keisei/sl/prepare.py:151-161 leaves out).  A batch of E game
  * records, game g in env g, stepped in lockstep from ka_shogi_env_reset.  One ply = ka_sl_replay_plan, ka_shogi_env_step
  * (unchanged), ka_sl_replay_record on one stream.

@@ -143,6 +143,9 @@ _SIGS = {
     "ka_search_words": "iii",
     "ka_search_expand": "pi pi pi p ppp pp iii pp p pppp pp ii p",
     "ka_search_advance": "pp iii pp i pppp p pppp pp i p",
+    "ka_mate_words": "ii",
+    "ka_mate_fork": "pi pp i p ppp ii p pppp p ii p",
+    "ka_mate_choose": "pi pppp ppp i p",
     "ka_sl_replay_state_words": "i",
     "ka_sl_replay_plan": "p i p i p p i pp p",
     "ka_sl_replay_record": "p i ppp i ppppppp p i p",

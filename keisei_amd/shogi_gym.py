@@ -28,6 +28,7 @@ There is no CPU fallback: without the HIP library or a GPU the constructor raise
 """
 from __future__ import annotations
 
+import weakref
 from dataclasses import dataclass
 from typing import Any, List, Optional
 
@@ -557,6 +558,7 @@ class VecEnv:
         self._stats = z(4, dtype=torch.int64)
         self._err = z(2, dtype=torch.int64)                   # [this step's refusal, the latch raise_if_refused reads and clears]
         self._actions = z(n, dtype=torch.int64)
+        self._mate: dict = {}                                 # mate_in_one's scratch rows by cap, allocated at the first call
         # start positions (set_start_positions): allocated once, so that a captured graph keeps valid pointers; the
         # header {count, 0, seed lo, seed hi} is read by every launch.  Capacity 0: no pool, the entry points without one.
         self._pool_capacity = int(start_pool_capacity)
@@ -848,6 +850,46 @@ class VecEnv:
         """Observation and masks of the positions to move (what the last reset / step / set_state wrote)."""
         c = self._cur
         return ResetResult(self._out(self._obs[c]), self._out(self._mask[c]), self._bits[c] if self._output == "torch" else None)
+
+    def mate_in_one(self, max_checks: int = 32):
+        """Does the side to move have a mate in one?  `(actions, n_checks, truncated)`, (N,) int64 tensors on the env's
+        device for the positions now to move: the mating action with the lowest index or -1, the number of legal moves
+        that give check, and 1 where more than `max_checks` (1..64) of them exist -- only the first `max_checks` in
+        ascending action order are tried, so a -1 beside a 1 is no proof.  Three stages (`training/mate_search.py`,
+        csrc/mate.hip): the checking moves are forked into scratch rows, stepped by the env's own step kernel, and a row
+        that ended by checkmate names the move.  The env is only read: calling it twice gives the same answer.  For
+        katago / spatial envs; any other mode raises `ValueError`."""
+        from keisei_amd.training.mate_search import FLAG_MATE, FLAG_TRUNCATED, REC_ACTION, REC_FLAGS, REC_NCHECKS, \
+            MateControls, MateSearch, mate_table
+        if self._omode != 1 or self._amode != 1:
+            raise ValueError("mate_in_one covers the katago observation and the spatial action mode only")
+        cap = MateControls(max_checks).max_checks
+        if cap < 1:
+            raise ValueError(f"max_checks must be an integer in [1, 64], got {max_checks!r}")
+        with torch.cuda.device(self.device):
+            ms = self._mate.get(cap)
+            if ms is None:                                    # the scratch rows of this cap, allocated at the first call
+                # (a weak reference back: no cycle, so the rows and the pinned counters die with the env, at once)
+                ms = self._mate[cap] = (MateSearch(weakref.proxy(self), cap), torch.from_numpy(mate_table(MateControls(cap), 1)).to(self.device),
+                                        torch.zeros(self._n, dtype=torch.int32, device=self.device))
+            search, table, model_of = ms
+            # the unused slots replay a legal move of the position: its first
+            actions = self._mask[self._cur].to(torch.uint8).argmax(dim=1)
+            search.clear()
+            search.step(self._bits[self._cur], actions, model_of, table, _lib.stream_ptr())
+            search.read()                                     # raises on the error word
+            rec = search.records().to(torch.int64)
+        flags = rec[:, REC_FLAGS]
+        mate = torch.where((flags & FLAG_MATE) != 0, rec[:, REC_ACTION], torch.full_like(flags, -1))
+        return mate, rec[:, REC_NCHECKS], ((flags & FLAG_TRUNCATED) != 0).to(torch.int64)
+
+    def mate_records(self, max_checks: int = 32) -> torch.Tensor:
+        """The (N, 4 + max_checks) int32 records of the last `mate_in_one(max_checks)` (csrc/mate.hip: flags, number of
+        checking moves, slot, action, the checking actions forked)."""
+        ms = self._mate.get(int(max_checks))
+        if ms is None:
+            raise ValueError(f"mate_in_one(max_checks={max_checks}) has not been called on this env")
+        return ms[0].records()
 
     def get_sfen(self, game_id: int) -> str:
         """vec_env.rs:873-882 / sfen.rs:93-171."""

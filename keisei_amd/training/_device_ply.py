@@ -24,6 +24,7 @@ from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS, OBS_CHANNELS, VecEnv
 from .game_log import GameLog, RecordedGame
 from .katago_ppo import KataGoRolloutBuffer, _check_step_inputs
 from .lookahead import Lookahead
+from .mate_search import MateSearch
 from .policy_insight import InsightRecorder
 from .sampling import GAME_PLY_BYTE
 from .tree_search import TreeSearch
@@ -85,15 +86,17 @@ class DevicePly:
     candidates.  ``controls`` (a table of ``sampling.py``) puts ``ka_policy_sample_ctl`` in the place of
     ``ka_policy_sample_play``; ``lookahead_table`` / ``lookahead_width`` (``lookahead.py``) add the one-ply value lookahead
     between the sampler and the insight, ``lookahead_reply_width > 0`` its reply search (three more stages).  ``search_table`` / ``search_width`` /
-    ``search_expansions`` (``tree_search.py``) put the tree search where the lookahead stands (not both).  An option left at
-    0 / None adds no launch and allocates nothing."""
+    ``search_expansions`` (``tree_search.py``) put the tree search where the lookahead stands (not both).  ``mate_table`` /
+    ``mate_cap`` (``mate_search.py``) add the mate-in-one check behind the lookahead or the search and before the insight
+    (``ka_mate_fork``, the env step over the child rows, ``ka_mate_choose``; no forward): it overrides their choice, and the
+    insight describes the move actually played.  An option left at 0 / None adds no launch and allocates nothing."""
 
     def __init__(self, group, num_envs: int, max_ply: int, *, start_pool_capacity: int = 0, game_log: int = 0,
                  envs_per_slot: Optional[int] = None, move_history: bool = False, insight: int = 0,
                  insight_temperature: float = 1.0, controls: Optional[np.ndarray] = None,
                  lookahead_table: Optional[np.ndarray] = None, lookahead_width: int = 0,
                  lookahead_reply_width: int = 0, search_table: Optional[np.ndarray] = None, search_width: int = 0,
-                 search_expansions: int = 0) -> None:
+                 search_expansions: int = 0, mate_table: Optional[np.ndarray] = None, mate_cap: int = 0) -> None:
         if search_table is not None and lookahead_table is not None:
             raise ValueError("search_table cannot be combined with lookahead_table: the search stands where the lookahead stands")
         N, dev = int(num_envs), group.device
@@ -118,6 +121,11 @@ class DevicePly:
             self.search: Optional[TreeSearch] = None
             if search_table is not None and search_width > 0:
                 self.search = TreeSearch(self.env, group, search_width, max(int(search_expansions), 1))
+            # the mate check's table and its child rows, likewise
+            self.mate_table: Optional[torch.Tensor] = None if mate_table is None else torch.from_numpy(mate_table).to(dev)
+            self.mate: Optional[MateSearch] = None
+            if mate_table is not None and mate_cap > 0:
+                self.mate = MateSearch(self.env, int(mate_cap))
             self.seat(group, controls)
 
     def seat(self, group, controls: Optional[np.ndarray]) -> None:
@@ -139,9 +147,11 @@ class DevicePly:
             self.lookahead.clear()
         if self.search is not None:
             self.search.clear()
+        if self.mate is not None:
+            self.mate.clear()
 
     def move(self, model_of: torch.Tensor, num_models: int, state: int, flags: int):
-        """forward -> sampler -> lookahead -> insight on the current stream.  ``state``: the device pointer of the loop's
+        """forward -> sampler -> lookahead -> mate check -> insight on the current stream.  ``state``: the device pointer of the loop's
         state array (the sampler reads the seed at its head), ``flags``: of the two sampler-flag words in it.  Returns
         ``(cur, pre, value, score, stream)``: the env's current buffers, the players to move, the value logits and the
         score lead of the forward, and the stream's pointer for the launches that follow."""
@@ -160,6 +170,8 @@ class DevicePly:
             self.lookahead.step(logits, cur.legal_mask_bits, self.actions, model_of, self.lookahead_table, st)
         if self.search is not None:                       # likewise the search's
             self.search.step(logits, cur.legal_mask_bits, self.actions, model_of, self.search_table, st)
+        if self.mate is not None:                         # a mate in one overrides whatever was chosen so far
+            self.mate.step(cur.legal_mask_bits, self.actions, model_of, self.mate_table, st)
         if self.insight is not None:                      # while the logits exist, before the step moves the history count
             self.insight.step(logits, cur.legal_mask_bits, self.actions, value, pre, model_of, num_models, flags, st)
         return cur, pre, value, score, st

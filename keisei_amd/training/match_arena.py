@@ -21,6 +21,10 @@ synchronisation:
                                                  grandchild rows and ka_lookahead_choose_replies -- csrc/lookahead.hip,
                                                  lookahead.py: the models with a
                                                  width play the best of their top moves by their own value head)
+    mate in one                                 (only with mate=: ka_mate_fork, ka_shogi_env_step over the child rows,
+                                                 ka_mate_choose -- csrc/mate.hip, mate_search.py: a model with
+                                                 max_checks > 0 plays a mate in one when the rules say there is one,
+                                                 whatever the sampler, the lookahead or the search chose)
     ka_shogi_env_step                           (csrc/shogi_env.hip)
     ka_arena_features_step                      (csrc/arena.hip, only with features=True: the reference's per-slot
                                                  GameFeatureTracker, one record per finished game)
@@ -60,6 +64,7 @@ from .dynamic_trainer import MatchRollout
 from .game_feature_tracker import GameFeatureTracker
 from .game_log import RecordedGame
 from .lookahead import LookaheadStats, arena_lookahead, arena_reply_width, lookahead_table
+from .mate_search import MateStats, arena_mate, mate_table
 from .model_group import SEResNetGroup
 from .sampling import GAME_PLY_BYTE, arena_controls, controls_table
 from .tree_search import SearchStats, arena_search, search_table
@@ -109,6 +114,7 @@ class RoundStats:
     games_dropped: int = 0              # finished games that did not fit the game log between two sync points
     lookahead: Optional[LookaheadStats] = None      # the round's lookahead counters (arenas built with lookahead=)
     search: Optional[SearchStats] = None            # the round's tree-search counters (arenas built with search=)
+    mate: Optional[MateStats] = None                # the round's mate-in-one counters (arenas built with mate=)
 
 
 def _side_bits(trainable, pairings: Sequence[Tuple[int, int]]) -> List[int]:
@@ -302,13 +308,19 @@ class MatchArena:
     variation, values backed up by max and negation.  The node pool is sized by the largest ``width`` and ``expansions``
     given; ``set_search`` rewrites the table between rounds without a new capture, up to those.  ``RoundStats.search``
     carries the counters.  With None nothing is allocated and the launches are what they were.  Not together with
-    ``lookahead=`` and not with ``collect=True``."""
+    ``lookahead=`` and not with ``collect=True``.
+    ``mate=`` (a ``MateControls`` for every model, one per model, or a dict by model index; ``mate_search.py``) adds a
+    rules-only mate-in-one check behind the lookahead or the search and before the insight: the legal moves that give check
+    are forked (at most ``max_checks`` of them, in ascending action order), the env's own step decides them, and a move that
+    mates is played in the place of whatever was chosen.  The child rows are sized by the largest ``max_checks`` given;
+    ``set_mate`` rewrites the table between rounds without a new capture, up to it.  ``RoundStats.mate`` carries the
+    counters.  With None nothing is allocated and the launches are what they were.  Not with ``collect=True``."""
 
     def __init__(self, group: SEResNetGroup, num_envs: int = 512, envs_per_match: int = 64, max_ply: int = 512, *,
                  sync_every: int = 32, graph: bool = True, seed: Optional[int] = None, record: bool = False,
                  collect: bool = False, features: bool = False, start_pool_capacity: int = 0,
                  game_log: int = 0, move_history: bool = False, insight: int = 0,
-                 insight_temperature: float = 1.0, sampling=None, lookahead=None, search=None) -> None:
+                 insight_temperature: float = 1.0, sampling=None, lookahead=None, search=None, mate=None) -> None:
         if len(group) == 0:
             raise ValueError("MatchArena needs a group with at least one model")
         if num_envs <= 0 or envs_per_match <= 0 or num_envs % envs_per_match != 0:
@@ -323,6 +335,7 @@ class MatchArena:
         la_table, la_width = arena_lookahead(lookahead, len(group), bool(collect))
         la_reply = arena_reply_width(lookahead, len(group))
         se_table, se_width, se_expansions = arena_search(search, len(group), bool(collect), lookahead)
+        mt_table, mt_cap = arena_mate(mate, len(group), bool(collect))
         self.group = group
         self.device = group.device
         self.num_envs, self.envs_per_match, self.max_ply = int(num_envs), int(envs_per_match), int(max_ply)
@@ -337,11 +350,13 @@ class MatchArena:
                                    envs_per_slot=self.envs_per_match, move_history=move_history, insight=insight,
                                    insight_temperature=insight_temperature, controls=table, lookahead_table=la_table,
                                    lookahead_width=la_width, lookahead_reply_width=la_reply, search_table=se_table,
-                                   search_width=se_width, search_expansions=se_expansions)
+                                   search_width=se_width, search_expansions=se_expansions, mate_table=mt_table,
+                                   mate_cap=mt_cap)
         self.env, self.game_log, self.insight = ply.env, ply.game_log, ply.insight
         self._actions, self._logp, self._nlegal = ply.actions, ply.log_probs, ply.n_legal
         self._ctl, self._la_table, self._la = ply.ctl, ply.lookahead_table, ply.lookahead
         self._se_table, self._se = ply.search_table, ply.search
+        self._mt_table, self._mt = ply.mate_table, ply.mate
         with torch.cuda.device(dev):
             self._state = torch.zeros(_lib.query("ka_arena_state_words", self.num_slots), dtype=torch.int32, device=dev)
             self._state_host = torch.zeros(self._state.shape, dtype=torch.int32).pin_memory()
@@ -402,6 +417,23 @@ class MatchArena:
                              "the grandchild rows are allocated once, by the largest reply_width given to the constructor")
         with torch.cuda.device(self.device):
             self._la_table.copy_(torch.from_numpy(table))
+
+    def set_mate(self, mate) -> None:
+        """New mate-in-one controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
+        writes rows that are off.  A ``max_checks`` above the largest the arena was built with is refused (the child rows are
+        sized by it), and so is an arena built without ``mate=``: its ply holds no mate check."""
+        if self._mt_table is None:
+            raise ValueError("this arena was built without mate=: its ply (and its captured graph) holds no mate check; "
+                             "build the arena with mate controls to change them later")
+        table, cap = arena_mate(mate, len(self.group), self.collect)
+        if table is None:
+            table = mate_table(None, len(self.group))
+        built = 0 if self._mt is None else self._mt.cap
+        if cap > built:
+            raise ValueError(f"mate max_checks {cap} is above the largest this arena was built with ({built}): the child "
+                             "rows are allocated once, by the largest max_checks given to the constructor")
+        with torch.cuda.device(self.device):
+            self._mt_table.copy_(torch.from_numpy(table))
 
     def set_search(self, search) -> None:
         """New search controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
@@ -494,6 +526,8 @@ class MatchArena:
                        node_rewards=se.rewards.cpu().reshape(shape), node_done=(se.terminated | se.truncated).cpu().reshape(shape),
                        node_logits=se.logits.cpu().reshape(-1, ACTION_SPACE), node_mask_bits=se.mask_bits.cpu(),
                        node_model_of=se.model_of.cpu().reshape(shape))
+        if self._mt is not None:
+            rec.update(mate_records=self._mt.records().cpu())
         rec.update(actions=self._actions.cpu(), log_probs=self._logp.cpu(), n_legal=self._nlegal.cpu(),
                    rewards=self.env._rewards[self.env._cur].cpu(), terminated=self.env._terminated[self.env._cur].cpu(),
                    truncated=self.env._truncated[self.env._cur].cpu())
@@ -632,6 +666,8 @@ class MatchArena:
             stats.lookahead = LookaheadStats()
         if self._se_table is not None:
             stats.search = SearchStats()
+        if self._mt_table is not None:
+            stats.mate = MateStats()
         if not pairings:
             return [], stats
         with torch.cuda.device(self.device), torch.no_grad():
@@ -681,6 +717,8 @@ class MatchArena:
                 stats.lookahead = self._la.read()
             if self._se is not None:
                 stats.search = self._se.read()
+            if self._mt is not None:
+                stats.mate = self._mt.read()
             stats.host_syncs += 1
             slot = st[_HDR:].reshape(self.num_slots, _SLOT)
             if self.collect:
