@@ -982,6 +982,63 @@ int ka_mate_fork(const void* legal, int legal_words, const long long* actions, c
 int ka_mate_choose(void* records, int cap, const float* child_rewards, const void* child_terminated, const void* child_reason,
                    const void* child_err, long long* actions, int* stats, int* err, int N, void* stream);
 
+/* ---- mate in three (csrc/mate3.hip), behind the three stages of the mate in one and reusing them for the third ply.  On
+ * the same stream, kernel launches only, caller-owned buffers, no workgroup waits for another:
+ *   ka_mate_fork, ka_shogi_env_step, ka_mate_choose          the root, as above
+ *   ka_mate3_fork(...)                                       the budget walk; the grandchild rows, one per evasion
+ *   ka_shogi_env_step over the N * G grandchild rows         its own err, stats and output buffers
+ *   ka_mate3_gate(...)                                       grand_model_of and a filler action per grandchild row
+ *   ka_mate_fork, ka_shogi_env_step, ka_mate_choose          the third ply: the N * G grandchild rows as the envs, cap3 rows
+ *                                                            each, grand_model_of, a second K x 4 table (word 0
+ *                                                            reply_checks, word 1 zero), grand_filler as the action array
+ *   ka_mate3_choose(...)                                     the proving set, actions[e], the record, the counters
+ * table: the table of the mate in one; word 2 int32 evasion_rows (0 = mate in one only, 1..128), word 3 int32 reply_checks
+ *   (0..64).  A row whose words 2 / 3 lie outside these ranges has depth three off, not its mate in one.
+ * Env e is active at depth three when its mate-in-one record has bit 0 set and bit 1 clear and evasion_rows > 0.  Child i
+ *   (root slot i) is open when its step neither terminated nor truncated it; n_i = the set bits of its new packed mask, the
+ *   defender's evasions.  Budget walk in slot order, left = min(evasion_rows, G): an open child with 1 <= n_i <= left gets
+ *   the next n_i grandchild rows of the env (one per evasion, ascending) and left -= n_i; an open child with n_i > left is
+ *   skipped and the walk goes on.  A grandchild its step terminated or truncated refutes its check, whatever ended it and
+ *   whatever the restarted row shows.  Child i proves when it got rows and every grandchild of it is open and its third-ply
+ *   record has a mate.  A proving incoming action stays; otherwise the proving check with the lowest action replaces
+ *   actions[e]; without one the action stands.
+ * Record of an env, ka_mate3_words(0, cap) = 6 + 2 * cap int32 words:
+ *   0 flags (bit 0 active at depth three, 1 mate in three found, 2 the action was changed, 3 a child was skipped by the
+ *   budget, 4 a refuting grandchild's third-ply fork was truncated)   1 grandchild rows used   2 slot played, -1
+ *   3 action played (the incoming action unless bit 2)   4, 5 the proving set as a 64-bit mask over the slots, low word
+ *   first   6.. cap words n_i (-1: slot unused or not open)   6 + cap.. cap words first grandchild row of the slot within the
+ *   env (-1: without rows)
+ * ka_mate3_words(which, cap): 0 record words, 1 table words per model (4), 2 counter words (7: positions active at depth
+ *   three, grandchild rows used, third-ply rows used, mates in three, actions changed, children skipped, then the error
+ *   word), 3 the maximum G (128), 4 the maximum cap (64); -1 otherwise.
+ * ka_mate3_fork: legal / actions / model_of / table / state as ka_mate_fork reads them (actions after ka_mate_choose);
+ *   root_records and the child_* rows as the root's stages left them, child_mask_bits the child step's NEW masks; all only
+ *   read.  Written: records (N, words); grandchild rows g = e * G + r: grand_state, grand_keys / grand_checks (entries
+ *   [0, ply + 1) of the child's rows, rows in use only; same row stride), grand_mask_bits (the child's new mask: the step
+ *   validates against it), grand_actions (the evasion; for an unused row the root env's state, mask and incoming action).
+ * ka_mate3_gate: grand_mask_bits / grand_terminated / grand_truncated as the grandchild step wrote them.  Written:
+ *   grand_model_of (N * G) int32 = model_of[e] for a used, open row, -1 otherwise; grand_filler (N * G) int64 = the first
+ *   set bit of the row's new mask.
+ * ka_mate3_choose: third_records (N * G, 4 + cap3) of the third ply; child_err / grand_err / third_err the two 64-bit error
+ *   words of the three child steps: a non-zero one sets err bit 1 / 2 / 3 and nothing is replaced.  actions (N) int64 is
+ *   overwritten where a mate in three replaces it; stats (6 int32) is added to with atomics, err (1 int32) is ORed; the
+ *   caller clears both.
+ * Refused: null tensors, another action space or mask width, cap outside [1, 64], G outside [1, 128], cap3 outside [1, 64],
+ *   K < 1, misaligned rows. */
+int ka_mate3_words(int which, int cap);
+int ka_mate3_fork(const void* legal, int legal_words, const long long* actions, const int* model_of, int K, const void* table,
+                  const void* state, const void* root_records, int cap, const void* child_state, const void* child_keys,
+                  const void* child_checks, const void* child_mask_bits, const void* child_terminated,
+                  const void* child_truncated, int max_ply, int G, void* records, void* grand_state, void* grand_keys,
+                  void* grand_checks, void* grand_mask_bits, long long* grand_actions, int N, int A, void* stream);
+int ka_mate3_gate(const void* records, int cap, int G, const int* model_of, const void* grand_mask_bits, int legal_words,
+                  const void* grand_terminated, const void* grand_truncated, int* grand_model_of, long long* grand_filler,
+                  int N, void* stream);
+int ka_mate3_choose(void* records, const void* root_records, int cap, int G, const void* third_records, int cap3,
+                    const void* grand_terminated, const void* grand_truncated, const int* model_of, int K,
+                    const void* third_table, const void* child_err, const void* grand_err, const void* third_err,
+                    long long* actions, int* stats, int* err, int N, void* stream);
+
 /* ---- SL shard preparation (csrc/sl_prepare.hip; the replay keisei/sl/prepare.py:151-161 leaves out).  A batch of E game
  * records, game g in env g, stepped in lockstep from ka_shogi_env_reset.  One ply = ka_sl_replay_plan, ka_shogi_env_step
  * (unchanged), ka_sl_replay_record on one stream.

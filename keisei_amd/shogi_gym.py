@@ -558,7 +558,7 @@ class VecEnv:
         self._stats = z(4, dtype=torch.int64)
         self._err = z(2, dtype=torch.int64)                   # [this step's refusal, the latch raise_if_refused reads and clears]
         self._actions = z(n, dtype=torch.int64)
-        self._mate: dict = {}                                 # mate_in_one's scratch rows by cap, allocated at the first call
+        self._mate: dict = {}                                 # mate_in_one's / mate_in_three's scratch rows by caps, allocated at the first call
         # start positions (set_start_positions): allocated once, so that a captured graph keeps valid pointers; the
         # header {count, 0, seed lo, seed hi} is read by every launch.  Capacity 0: no pool, the entry points without one.
         self._pool_capacity = int(start_pool_capacity)
@@ -890,6 +890,60 @@ class VecEnv:
         if ms is None:
             raise ValueError(f"mate_in_one(max_checks={max_checks}) has not been called on this env")
         return ms[0].records()
+
+    def _mate3_search(self, max_checks, evasion_rows, reply_checks):
+        from keisei_amd.training.mate_search import Mate3Search, MateControls, mate3_reply_table, mate_table
+        if self._omode != 1 or self._amode != 1:
+            raise ValueError("mate_in_three covers the katago observation and the spatial action mode only")
+        ctl = MateControls(max_checks, 0, evasion_rows, reply_checks)
+        if ctl.max_checks < 1 or ctl.evasion_rows < 1:
+            raise ValueError(f"max_checks, evasion_rows and reply_checks must be positive, got {max_checks!r}, "
+                             f"{evasion_rows!r} and {reply_checks!r}")
+        key = (ctl.max_checks, ctl.evasion_rows, ctl.reply_checks)
+        ms = self._mate.get(key)
+        if ms is None:                                        # the scratch rows of these caps, allocated at the first call
+            table = mate_table(ctl, 1)
+            ms = self._mate[key] = (Mate3Search(weakref.proxy(self), *key), torch.from_numpy(table).to(self.device),
+                                    torch.from_numpy(mate3_reply_table(table)).to(self.device),
+                                    torch.zeros(self._n, dtype=torch.int32, device=self.device))
+        return ms
+
+    def mate_in_three(self, max_checks: int = 16, evasion_rows: int = 32, reply_checks: int = 8):
+        """Does the side to move have a mate in one, or a forced mate in three?  `(actions, depth, cut)`, (N,) int64
+        tensors on the env's device for the positions now to move: the mating move or -1; 1 for a mate in one (the move
+        `mate_in_one` gives), 3 for a mate in three (the lowest checking move after which every reply runs into a mate in
+        one), 0 for neither; and 1 where a cap cut the search -- more than `max_checks` (1..64) checking moves, a check
+        whose evasions did not fit what was left of the `evasion_rows` (1..128) grandchild rows, or a reply without a
+        mate among its first `reply_checks` (1..64) checking moves when it has more -- so a 0 beside a 1 is no proof.  A
+        mate that is found is always one.  The stages are those of `training/mate_search.py` (csrc/mate.hip,
+        csrc/mate3.hip); the env is only read.  For katago / spatial envs; any other mode raises `ValueError`."""
+        from keisei_amd.training.mate_search import FLAG3_MATE, FLAG3_REPLY_TRUNCATED, FLAG3_SKIPPED, FLAG_MATE, \
+            FLAG_TRUNCATED, REC3_ACTION, REC3_FLAGS, REC_ACTION, REC_FLAGS
+        with torch.cuda.device(self.device):
+            search, table, reply_table, model_of = self._mate3_search(max_checks, evasion_rows, reply_checks)
+            # the unused slots replay a legal move of the position: its first
+            actions = self._mask[self._cur].to(torch.uint8).argmax(dim=1)
+            search.clear()
+            search.step(self._bits[self._cur], actions, model_of, table, reply_table, _lib.stream_ptr())
+            search.root.read()                                # raise on the error words
+            search.read()
+            rec1, rec3 = search.root.records().to(torch.int64), search.records().to(torch.int64)
+        f1, f3 = rec1[:, REC_FLAGS], rec3[:, REC3_FLAGS]
+        one, three = (f1 & FLAG_MATE) != 0, (f3 & FLAG3_MATE) != 0
+        none = torch.full_like(f1, -1)
+        move = torch.where(one, rec1[:, REC_ACTION], torch.where(three, rec3[:, REC3_ACTION], none))
+        depth = torch.where(one, torch.ones_like(f1), torch.where(three, torch.full_like(f1, 3), torch.zeros_like(f1)))
+        cut = ((f1 & FLAG_TRUNCATED) != 0) | ((f3 & (FLAG3_SKIPPED | FLAG3_REPLY_TRUNCATED)) != 0)
+        return move, depth, cut.to(torch.int64)
+
+    def mate3_records(self, max_checks: int = 16, evasion_rows: int = 32, reply_checks: int = 8):
+        """`(root, deep)` of the last `mate_in_three` with these caps: the (N, 4 + max_checks) int32 mate-in-one records
+        (csrc/mate.hip) and the (N, 6 + 2 * max_checks) int32 mate-in-three records (csrc/mate3.hip: flags, grandchild
+        rows used, slot, action, the proving set, every slot's evasion count and first row)."""
+        ms = self._mate.get((int(max_checks), int(evasion_rows), int(reply_checks)))
+        if ms is None:
+            raise ValueError(f"mate_in_three({max_checks}, {evasion_rows}, {reply_checks}) has not been called on this env")
+        return ms[0].root.records(), ms[0].records()
 
     def get_sfen(self, game_id: int) -> str:
         """vec_env.rs:873-882 / sfen.rs:93-171."""

@@ -7,7 +7,7 @@ from .league_rollout import LeagueRollout, LeagueRolloutStats  # noqa: F401
 from .lookahead import (Lookahead, LookaheadChoice, LookaheadControls, LookaheadReplyChoice, LookaheadStats,  # noqa: F401
                         lookahead_active, lookahead_candidates, lookahead_choose, lookahead_choose_replies,
                         lookahead_reply_widths, lookahead_table)
-from .mate_search import MateControls, MateSearch, MateStats, mate_table  # noqa: F401
+from .mate_search import Mate3Search, Mate3Stats, MateControls, MateSearch, MateStats, mate_table  # noqa: F401
 from .match_arena import MatchArena, MatchResult, RoundStats  # noqa: F401
 from .policy_insight import InsightRecorder, PolicyInsight, action_usi, insight_dict, policy_insight  # noqa: F401
 from .sampling import ControlledSample, SamplingControls, controls_table, sample_controlled  # noqa: F401

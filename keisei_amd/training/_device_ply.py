@@ -24,7 +24,7 @@ from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS, OBS_CHANNELS, VecEnv
 from .game_log import GameLog, RecordedGame
 from .katago_ppo import KataGoRolloutBuffer, _check_step_inputs
 from .lookahead import Lookahead
-from .mate_search import MateSearch
+from .mate_search import Mate3Search, MateSearch, mate3_reply_table
 from .policy_insight import InsightRecorder
 from .sampling import GAME_PLY_BYTE
 from .tree_search import TreeSearch
@@ -89,14 +89,17 @@ class DevicePly:
     ``search_expansions`` (``tree_search.py``) put the tree search where the lookahead stands (not both).  ``mate_table`` /
     ``mate_cap`` (``mate_search.py``) add the mate-in-one check behind the lookahead or the search and before the insight
     (``ka_mate_fork``, the env step over the child rows, ``ka_mate_choose``; no forward): it overrides their choice, and the
-    insight describes the move actually played.  An option left at 0 / None adds no launch and allocates nothing."""
+    insight describes the move actually played; ``mate_rows`` / ``mate_reply_cap`` > 0 put the mate in three behind it
+    (``Mate3Search``: the grandchild rows per env and the third ply's rows per grandchild; seven more launches, no forward).
+    An option left at 0 / None adds no launch and allocates nothing."""
 
     def __init__(self, group, num_envs: int, max_ply: int, *, start_pool_capacity: int = 0, game_log: int = 0,
                  envs_per_slot: Optional[int] = None, move_history: bool = False, insight: int = 0,
                  insight_temperature: float = 1.0, controls: Optional[np.ndarray] = None,
                  lookahead_table: Optional[np.ndarray] = None, lookahead_width: int = 0,
                  lookahead_reply_width: int = 0, search_table: Optional[np.ndarray] = None, search_width: int = 0,
-                 search_expansions: int = 0, mate_table: Optional[np.ndarray] = None, mate_cap: int = 0) -> None:
+                 search_expansions: int = 0, mate_table: Optional[np.ndarray] = None, mate_cap: int = 0, mate_rows: int = 0,
+                 mate_reply_cap: int = 0) -> None:
         if search_table is not None and lookahead_table is not None:
             raise ValueError("search_table cannot be combined with lookahead_table: the search stands where the lookahead stands")
         N, dev = int(num_envs), group.device
@@ -124,7 +127,13 @@ class DevicePly:
             # the mate check's table and its child rows, likewise
             self.mate_table: Optional[torch.Tensor] = None if mate_table is None else torch.from_numpy(mate_table).to(dev)
             self.mate: Optional[MateSearch] = None
-            if mate_table is not None and mate_cap > 0:
+            self.mate3: Optional[Mate3Search] = None      # (its root is self.mate; its third ply reads mate_reply_table)
+            self.mate_reply_table: Optional[torch.Tensor] = None
+            if mate_table is not None and mate_cap > 0 and mate_rows > 0 and mate_reply_cap > 0:
+                self.mate3 = Mate3Search(self.env, int(mate_cap), int(mate_rows), int(mate_reply_cap))
+                self.mate = self.mate3.root
+                self.mate_reply_table = torch.from_numpy(mate3_reply_table(mate_table)).to(dev)
+            elif mate_table is not None and mate_cap > 0:
                 self.mate = MateSearch(self.env, int(mate_cap))
             self.seat(group, controls)
 
@@ -147,7 +156,9 @@ class DevicePly:
             self.lookahead.clear()
         if self.search is not None:
             self.search.clear()
-        if self.mate is not None:
+        if self.mate3 is not None:
+            self.mate3.clear()
+        elif self.mate is not None:
             self.mate.clear()
 
     def move(self, model_of: torch.Tensor, num_models: int, state: int, flags: int):
@@ -170,7 +181,9 @@ class DevicePly:
             self.lookahead.step(logits, cur.legal_mask_bits, self.actions, model_of, self.lookahead_table, st)
         if self.search is not None:                       # likewise the search's
             self.search.step(logits, cur.legal_mask_bits, self.actions, model_of, self.search_table, st)
-        if self.mate is not None:                         # a mate in one overrides whatever was chosen so far
+        if self.mate3 is not None:                        # a mate in one or in three overrides whatever was chosen so far
+            self.mate3.step(cur.legal_mask_bits, self.actions, model_of, self.mate_table, self.mate_reply_table, st)
+        elif self.mate is not None:                       # a mate in one does
             self.mate.step(cur.legal_mask_bits, self.actions, model_of, self.mate_table, st)
         if self.insight is not None:                      # while the logits exist, before the step moves the history count
             self.insight.step(logits, cur.legal_mask_bits, self.actions, value, pre, model_of, num_models, flags, st)

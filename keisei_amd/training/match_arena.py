@@ -25,6 +25,10 @@ synchronisation:
                                                  ka_mate_choose -- csrc/mate.hip, mate_search.py: a model with
                                                  max_checks > 0 plays a mate in one when the rules say there is one,
                                                  whatever the sampler, the lookahead or the search chose)
+    mate in three                               (only with mate= and an evasion_rows > 0: ka_mate3_fork, ka_shogi_env_step
+                                                 over the grandchild rows, ka_mate3_gate, the three mate-in-one stages
+                                                 over the grandchild rows, ka_mate3_choose -- csrc/mate3.hip: the lowest
+                                                 check after which every reply runs into a mate in one)
     ka_shogi_env_step                           (csrc/shogi_env.hip)
     ka_arena_features_step                      (csrc/arena.hip, only with features=True: the reference's per-slot
                                                  GameFeatureTracker, one record per finished game)
@@ -64,7 +68,7 @@ from .dynamic_trainer import MatchRollout
 from .game_feature_tracker import GameFeatureTracker
 from .game_log import RecordedGame
 from .lookahead import LookaheadStats, arena_lookahead, arena_reply_width, lookahead_table
-from .mate_search import MateStats, arena_mate, mate_table
+from .mate_search import Mate3Stats, MateStats, arena_mate, arena_mate3, mate3_reply_table, mate_table
 from .model_group import SEResNetGroup
 from .sampling import GAME_PLY_BYTE, arena_controls, controls_table
 from .tree_search import SearchStats, arena_search, search_table
@@ -115,6 +119,7 @@ class RoundStats:
     lookahead: Optional[LookaheadStats] = None      # the round's lookahead counters (arenas built with lookahead=)
     search: Optional[SearchStats] = None            # the round's tree-search counters (arenas built with search=)
     mate: Optional[MateStats] = None                # the round's mate-in-one counters (arenas built with mate=)
+    mate3: Optional[Mate3Stats] = None              # the round's mate-in-three counters (mate= with evasion_rows > 0)
 
 
 def _side_bits(trainable, pairings: Sequence[Tuple[int, int]]) -> List[int]:
@@ -314,7 +319,12 @@ class MatchArena:
     are forked (at most ``max_checks`` of them, in ascending action order), the env's own step decides them, and a move that
     mates is played in the place of whatever was chosen.  The child rows are sized by the largest ``max_checks`` given;
     ``set_mate`` rewrites the table between rounds without a new capture, up to it.  ``RoundStats.mate`` carries the
-    counters.  With None nothing is allocated and the launches are what they were.  Not with ``collect=True``."""
+    counters.  With None nothing is allocated and the launches are what they were.  Not with ``collect=True``.  Controls
+    with ``evasion_rows`` / ``reply_checks`` > 0 put the mate in three behind it (``Mate3Search``): an env with checking
+    moves and no mate in one forks the defender's evasions of every check into at most ``evasion_rows`` grandchild rows,
+    looks for a mate in one behind each among ``reply_checks`` checking moves, and plays the lowest check that every reply
+    loses to.  The rows are sized by the largest values given, ``set_mate`` switches it per model under the same capture,
+    ``RoundStats.mate3`` carries its counters; without such controls the launches are the mate in one's."""
 
     def __init__(self, group: SEResNetGroup, num_envs: int = 512, envs_per_match: int = 64, max_ply: int = 512, *,
                  sync_every: int = 32, graph: bool = True, seed: Optional[int] = None, record: bool = False,
@@ -336,6 +346,7 @@ class MatchArena:
         la_reply = arena_reply_width(lookahead, len(group))
         se_table, se_width, se_expansions = arena_search(search, len(group), bool(collect), lookahead)
         mt_table, mt_cap = arena_mate(mate, len(group), bool(collect))
+        mt_rows, mt_reply = arena_mate3(mate, len(group))
         self.group = group
         self.device = group.device
         self.num_envs, self.envs_per_match, self.max_ply = int(num_envs), int(envs_per_match), int(max_ply)
@@ -351,12 +362,13 @@ class MatchArena:
                                    insight_temperature=insight_temperature, controls=table, lookahead_table=la_table,
                                    lookahead_width=la_width, lookahead_reply_width=la_reply, search_table=se_table,
                                    search_width=se_width, search_expansions=se_expansions, mate_table=mt_table,
-                                   mate_cap=mt_cap)
+                                   mate_cap=mt_cap, mate_rows=mt_rows, mate_reply_cap=mt_reply)
         self.env, self.game_log, self.insight = ply.env, ply.game_log, ply.insight
         self._actions, self._logp, self._nlegal = ply.actions, ply.log_probs, ply.n_legal
         self._ctl, self._la_table, self._la = ply.ctl, ply.lookahead_table, ply.lookahead
         self._se_table, self._se = ply.search_table, ply.search
         self._mt_table, self._mt = ply.mate_table, ply.mate
+        self._mt3, self._mt3_table = ply.mate3, ply.mate_reply_table
         with torch.cuda.device(dev):
             self._state = torch.zeros(_lib.query("ka_arena_state_words", self.num_slots), dtype=torch.int32, device=dev)
             self._state_host = torch.zeros(self._state.shape, dtype=torch.int32).pin_memory()
@@ -419,9 +431,10 @@ class MatchArena:
             self._la_table.copy_(torch.from_numpy(table))
 
     def set_mate(self, mate) -> None:
-        """New mate-in-one controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
-        writes rows that are off.  A ``max_checks`` above the largest the arena was built with is refused (the child rows are
-        sized by it), and so is an arena built without ``mate=``: its ply holds no mate check."""
+        """New mate controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
+        writes rows that are off.  A ``max_checks``, ``evasion_rows`` or ``reply_checks`` above the largest the arena was
+        built with is refused (the child, grandchild and third-ply rows are sized by them), and so is an arena built
+        without ``mate=``: its ply holds no mate check."""
         if self._mt_table is None:
             raise ValueError("this arena was built without mate=: its ply (and its captured graph) holds no mate check; "
                              "build the arena with mate controls to change them later")
@@ -432,8 +445,18 @@ class MatchArena:
         if cap > built:
             raise ValueError(f"mate max_checks {cap} is above the largest this arena was built with ({built}): the child "
                              "rows are allocated once, by the largest max_checks given to the constructor")
+        rows, reply = arena_mate3(mate, len(self.group))
+        built_rows, built_reply = (0, 0) if self._mt3 is None else (self._mt3.rows, self._mt3.reply_cap)
+        if rows > built_rows:
+            raise ValueError(f"mate evasion_rows {rows} is above the largest this arena was built with ({built_rows}): the "
+                             "grandchild rows are allocated once, by the largest evasion_rows given to the constructor")
+        if reply > built_reply:
+            raise ValueError(f"mate reply_checks {reply} is above the largest this arena was built with ({built_reply}): "
+                             "the third ply's rows are allocated once, by the largest reply_checks given to the constructor")
         with torch.cuda.device(self.device):
             self._mt_table.copy_(torch.from_numpy(table))
+            if self._mt3_table is not None:
+                self._mt3_table.copy_(torch.from_numpy(mate3_reply_table(table)))
 
     def set_search(self, search) -> None:
         """New search controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
@@ -528,6 +551,8 @@ class MatchArena:
                        node_model_of=se.model_of.cpu().reshape(shape))
         if self._mt is not None:
             rec.update(mate_records=self._mt.records().cpu())
+        if self._mt3 is not None:
+            rec.update(mate3_records=self._mt3.records().cpu())
         rec.update(actions=self._actions.cpu(), log_probs=self._logp.cpu(), n_legal=self._nlegal.cpu(),
                    rewards=self.env._rewards[self.env._cur].cpu(), terminated=self.env._terminated[self.env._cur].cpu(),
                    truncated=self.env._truncated[self.env._cur].cpu())
@@ -668,6 +693,8 @@ class MatchArena:
             stats.search = SearchStats()
         if self._mt_table is not None:
             stats.mate = MateStats()
+        if self._mt3 is not None:
+            stats.mate3 = Mate3Stats()
         if not pairings:
             return [], stats
         with torch.cuda.device(self.device), torch.no_grad():
@@ -719,6 +746,8 @@ class MatchArena:
                 stats.search = self._se.read()
             if self._mt is not None:
                 stats.mate = self._mt.read()
+            if self._mt3 is not None:
+                stats.mate3 = self._mt3.read()
             stats.host_syncs += 1
             slot = st[_HDR:].reshape(self.num_slots, _SLOT)
             if self.collect:

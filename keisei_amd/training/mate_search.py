@@ -16,6 +16,16 @@ a *mate* when the env step terminated it by checkmate with a positive reward for
 definition, so a checking move that ends the game by repetition, perpetual check or the move limit is not one.  An incoming
 action that is itself a mate stays; otherwise the mate with the lowest action index is played; an env without a mate keeps
 its action, and nothing else about the ply changes.
+
+Mate in three (``Mate3Search``, csrc/mate3.hip) stands behind it for the models whose row has ``evasion_rows`` > 0.  An env
+that is active above and has no mate in one is *active at depth three*.  A child the step neither terminated nor truncated
+is *open*; its evasions are the set bits of its new mask.  A budget of ``min(evasion_rows, G)`` grandchild rows is walked
+over the children in slot order: an open child whose evasions fit gets one row per evasion, ascending; one whose evasions do
+not fit is skipped and the walk goes on.  The env step steps the grandchild rows; one that it terminated or truncated
+refutes its check.  The three stages above then run with the grandchild rows as their envs and ``reply_checks`` as their
+``max_checks``.  A child *proves* when it got rows and every grandchild of it is open and has a mate in one; a proving
+incoming action stays, otherwise the proving check with the lowest action is played.  Caps and the budget only ever turn a
+mate into "not proven"; the records say when one cut.
 """
 from __future__ import annotations
 
@@ -29,14 +39,21 @@ from keisei_amd import _lib
 from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS
 
 __all__ = ["MateControls", "MateStats", "MateSearch", "mate_table", "mate_words", "arena_mate", "MAX_CHECKS",
-           "MAX_SKIP_PLIES"]
+           "MAX_SKIP_PLIES", "MAX_EVASION_ROWS", "Mate3Stats", "Mate3Search", "mate3_words", "mate3_reply_table",
+           "arena_mate3"]
 
 MAX_CHECKS = 64
 MAX_SKIP_PLIES = 65535
+MAX_EVASION_ROWS = 128
 # record words (csrc/mate.hip; ka_mate_words reports the sizes)
 REC_FLAGS, REC_NCHECKS, REC_SLOT, REC_ACTION, REC_LIST = 0, 1, 2, 3, 4
 FLAG_ACTIVE, FLAG_MATE, FLAG_CHANGED, FLAG_TRUNCATED = 1, 2, 4, 8
 ERR_CHILD_STEP = 2
+# the record of the mate in three (csrc/mate3.hip; ka_mate3_words reports the sizes): the n_i follow at REC3_N, the slots'
+# first rows behind them
+REC3_FLAGS, REC3_ROWS, REC3_SLOT, REC3_ACTION, REC3_PROVING, REC3_N = 0, 1, 2, 3, 4, 6
+FLAG3_ACTIVE, FLAG3_MATE, FLAG3_CHANGED, FLAG3_SKIPPED, FLAG3_REPLY_TRUNCATED = 1, 2, 4, 8, 16
+ERR3_CHILD_STEP, ERR3_GRAND_STEP, ERR3_THIRD_STEP = 2, 4, 8
 
 
 def mate_words(cap: int) -> int:
@@ -46,22 +63,30 @@ def mate_words(cap: int) -> int:
 
 @dataclass(frozen=True)
 class MateControls:
-    """One model's mate-in-one controls.  ``max_checks`` 0 is off."""
+    """One model's mate controls.  ``max_checks`` 0 is off.  ``evasion_rows`` > 0 (with ``reply_checks`` > 0) adds the mate
+    in three behind the mate in one: the budget of grandchild rows per position, one per evasion of a check, and the
+    checking moves tried at the third ply."""
     max_checks: int = 16
     skip_plies: int = 0
+    evasion_rows: int = 0
+    reply_checks: int = 0
 
     OFF: ClassVar["MateControls"]
 
     def __post_init__(self) -> None:
-        for name, hi in (("max_checks", MAX_CHECKS), ("skip_plies", MAX_SKIP_PLIES)):
+        for name, hi in (("max_checks", MAX_CHECKS), ("skip_plies", MAX_SKIP_PLIES), ("evasion_rows", MAX_EVASION_ROWS),
+                         ("reply_checks", MAX_CHECKS)):
             v = getattr(self, name)
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= hi:
                 raise ValueError(f"{name} must be an integer in [0, {hi}], got {v!r}")
             object.__setattr__(self, name, int(v))
+        if (self.evasion_rows > 0) != (self.reply_checks > 0):
+            raise ValueError(f"evasion_rows and reply_checks must be both zero or both positive, got {self.evasion_rows} "
+                             f"and {self.reply_checks}")
 
     def row(self) -> np.ndarray:
-        """The table row: int32 max_checks, int32 skip_plies, two reserved zero words."""
-        return np.array([self.max_checks, self.skip_plies, 0, 0], dtype=np.int32)
+        """The table row: int32 max_checks, skip_plies, evasion_rows, reply_checks (csrc/mate.hip reads the first two)."""
+        return np.array([self.max_checks, self.skip_plies, self.evasion_rows, self.reply_checks], dtype=np.int32)
 
 
 MateControls.OFF = MateControls(0)
@@ -121,6 +146,27 @@ def arena_mate(mate, num_models: int, collect: bool) -> Tuple[Optional[np.ndarra
                          "from the entry's own policy, and the logged log-prob would not be the played move's")
     rows = _rows(mate, num_models)
     return mate_table(rows, num_models), max(r.max_checks for r in rows)
+
+
+def mate3_reply_table(table: np.ndarray) -> np.ndarray:
+    """The third ply's ``(K, 4)`` table of a controls table: word 0 ``reply_checks`` of the rows with depth three on (0
+    otherwise), the other words zero -- what the unchanged ``ka_mate_fork`` reads as ``max_checks`` / ``skip_plies``."""
+    table = np.asarray(table, dtype=np.int32)
+    out = np.zeros_like(table)
+    er, rc = table[:, 2], table[:, 3]
+    on = (er > 0) & (er <= MAX_EVASION_ROWS) & (rc >= 0) & (rc <= MAX_CHECKS)
+    out[:, 0] = np.where(on, rc, 0)
+    return out
+
+
+def arena_mate3(mate, num_models: int) -> Tuple[int, int]:
+    """``(G, cap3)`` of ``MatchArena``'s ``mate=``: the largest ``evasion_rows`` and ``reply_checks`` given, the grandchild
+    rows per env and the third ply's rows per grandchild; ``(0, 0)`` when no model asks for depth three (or ``mate`` is
+    None): the ply is then the mate in one's."""
+    if mate is None:
+        return 0, 0
+    rows = _rows(mate, num_models)
+    return max(r.evasion_rows for r in rows), max(r.reply_checks for r in rows)
 
 
 def _check_cap(cap) -> int:
@@ -216,4 +262,135 @@ class MateSearch:
 
     def records(self) -> torch.Tensor:
         """The per-env records of the last ``step`` (a copy on the device)."""
+        return self._records.clone()
+
+
+def mate3_words(cap: int) -> int:
+    """32-bit words of one mate-in-three record."""
+    return REC3_N + 2 * int(cap)
+
+
+@dataclass
+class Mate3Stats:
+    """The counters ``ka_mate3_choose`` adds to."""
+    positions: int = 0     # envs active at depth three (checking moves, no mate in one), summed over the plies
+    rows: int = 0          # grandchild rows in use: the evasions stepped
+    reply_rows: int = 0    # third-ply rows in use: the checking moves stepped behind the evasions
+    mates: int = 0         # positions with a mate in three
+    changed: int = 0       # of these, the ones whose incoming action did not prove already
+    skipped: int = 0       # open children the budget walk left without rows
+
+
+class _Rows:
+    """What ``MateSearch`` reads of an env, for rows that are no env's: the grandchild rows as the third ply's positions."""
+
+    def __init__(self, env, n: int, state, keys, checks) -> None:
+        self.num_envs, self.device = n, env.device
+        self._amode, self._omode, self._C, self._max_ply = env._amode, env._omode, env._C, env._max_ply
+        self._state, self._keys, self._checks = state, keys, checks
+
+
+class Mate3Search:
+    """The mate in three of a device ``VecEnv``: a ``MateSearch`` for the root (``cap`` child rows per env), ``rows``
+    grandchild rows per env -- one per evasion of the checks the budget walk takes -- and a third-ply ``MateSearch`` over
+    the grandchild rows (``reply_cap`` rows each).  Everything is allocated here, once.  ``step`` runs the root's three
+    stages as they are and, behind them, ``ka_mate3_fork``, the env step over the grandchild rows, ``ka_mate3_gate``, the
+    third ply's three stages and ``ka_mate3_choose`` (csrc/mate3.hip)."""
+
+    def __init__(self, env, cap: int, rows: int, reply_cap: int) -> None:
+        if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or not 1 <= rows <= MAX_EVASION_ROWS:
+            raise ValueError(f"rows must be an integer in [1, {MAX_EVASION_ROWS}], got {rows!r}")
+        self.root = MateSearch(env, cap)
+        self.env, self.cap, self.rows, self.reply_cap = env, self.root.cap, int(rows), _check_cap(reply_cap)
+        n, dev, hist = env.num_envs, env.device, env._keys.shape[1]
+        self.words = _lib.query("ka_mate3_words", 0, self.cap)
+        assert self.words == mate3_words(self.cap) and _lib.query("ka_mate3_words", 3, 0) == MAX_EVASION_ROWS
+        self.M = M = n * self.rows
+        with torch.cuda.device(dev):
+            z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)  # noqa: E731
+            self._records = z(n, self.words, dtype=torch.int32)
+            self.grand_state = z(M, 128, dtype=torch.uint8)
+            self.grand_keys = z(M, hist, dtype=torch.int64)
+            self.grand_checks = z(M, hist, dtype=torch.uint8)
+            self.grand_bits_in = z(M, MASK_WORDS, dtype=torch.int32)       # the children's new masks: the step validates against them
+            self.grand_actions = z(M, dtype=torch.int64)
+            self.grand_obs = z(M, env._C, 9, 9, dtype=torch.float32)
+            self.grand_mask_bits = z(M, MASK_WORDS, dtype=torch.int32)
+            self.grand_rewards = z(M, dtype=torch.float32)
+            self.grand_terminated = z(M, dtype=torch.bool)
+            self.grand_truncated = z(M, dtype=torch.bool)
+            self.grand_players = z(M, dtype=torch.uint8)
+            self.grand_reason = z(M, dtype=torch.uint8)
+            self._terminal_obs = z(M, env._C, 9, 9, dtype=torch.float32)
+            self._captured = z(M, dtype=torch.uint8)
+            self._ply = z(M, dtype=torch.int16)
+            self._material = z(M, dtype=torch.int32)
+            self._env_stats = z(4, dtype=torch.int64)
+            self._grand_err = z(2, dtype=torch.int64)
+            self.grand_model_of = z(M, dtype=torch.int32)
+            self.grand_filler = z(M, dtype=torch.int64)                    # the third ply's action array: a scratch one
+            self._counters = z(_lib.query("ka_mate3_words", 2, self.cap), dtype=torch.int32)      # stats, then the error word
+            self._counters_host = torch.zeros(self._counters.shape, dtype=torch.int32).pin_memory()
+            self.third = MateSearch(_Rows(env, M, self.grand_state, self.grand_keys, self.grand_checks), self.reply_cap)
+        self._nstats = self._counters.shape[0] - 1
+
+    def clear(self) -> None:
+        """Zero the counters, the error words and the refusal latches of the three child steps (a round's start)."""
+        self.root.clear()
+        self.third.clear()
+        self._counters.zero_()
+        self._grand_err.zero_()
+
+    def fork(self, mask_bits, actions, model_of, table, stream) -> None:
+        env, root = self.env, self.root
+        _lib.call("ka_mate3_fork", mask_bits, MASK_WORDS, actions, model_of, int(table.shape[0]), table, env._state,
+                  root._records, self.cap, root.child_state, root.child_keys, root.child_checks, root.child_mask_bits,
+                  root.child_terminated, root.child_truncated, env._max_ply, self.rows, self._records, self.grand_state,
+                  self.grand_keys, self.grand_checks, self.grand_bits_in, self.grand_actions, env.num_envs, ACTION_SPACE,
+                  stream)
+
+    def step_grandchildren(self, stream) -> None:
+        env = self.env
+        _lib.call("ka_shogi_env_step", self.grand_state, self.grand_keys, self.grand_checks, self.grand_actions, self.M,
+                  env._max_ply, env._omode, env._amode, None, self.grand_bits_in, self._grand_err, self.grand_obs, None,
+                  self.grand_mask_bits, self.grand_rewards, self.grand_terminated, self.grand_truncated, self._terminal_obs,
+                  self.grand_players, self._captured, self.grand_reason, self._ply, self._material, self._env_stats, stream)
+
+    def gate(self, model_of, stream) -> None:
+        _lib.call("ka_mate3_gate", self._records, self.cap, self.rows, model_of, self.grand_mask_bits, MASK_WORDS,
+                  self.grand_terminated, self.grand_truncated, self.grand_model_of, self.grand_filler, self.env.num_envs,
+                  stream)
+
+    def choose(self, actions, model_of, reply_table, stream) -> None:
+        _lib.call("ka_mate3_choose", self._records, self.root._records, self.cap, self.rows, self.third._records,
+                  self.reply_cap, self.grand_terminated, self.grand_truncated, model_of, int(reply_table.shape[0]),
+                  reply_table, self.root._child_err, self._grand_err, self.third._child_err, actions, self._counters,
+                  self._counters.data_ptr() + 4 * self._nstats, self.env.num_envs, stream)
+
+    def step(self, mask_bits, actions, model_of, table, reply_table, stream) -> None:
+        """The root's three stages and the deeper ones behind them on the current stream (``stream``: its pointer), where
+        ``MateSearch.step`` stands: ``actions`` (envs,) int64 is overwritten where a mate in one or in three replaces it.
+        ``table`` the (K, 4) int32 controls table on the device, ``reply_table`` its ``mate3_reply_table``."""
+        self.root.step(mask_bits, actions, model_of, table, stream)
+        self.fork(mask_bits, actions, model_of, table, stream)
+        self.step_grandchildren(stream)
+        self.gate(model_of, stream)
+        self.third.step(self.grand_mask_bits, self.grand_filler, self.grand_model_of, reply_table, stream)
+        self.choose(actions, model_of, reply_table, stream)
+
+    def read(self) -> Mate3Stats:
+        """At a sync point: the counters since ``clear()`` (one small device -> host copy).  Raises on the error word."""
+        self._counters_host.copy_(self._counters)
+        c = self._counters_host.numpy()
+        err = int(c[self._nstats])
+        if err:
+            which = [name for bit, name in ((ERR3_CHILD_STEP, "child"), (ERR3_GRAND_STEP, "grandchild"),
+                                            (ERR3_THIRD_STEP, "third-ply")) if err & bit]
+            raise RuntimeError(f"the mate search's {' and '.join(which)} step refused an action: a forked row does not "
+                               "match the mask it was forked with")
+        return Mate3Stats(*(int(v) for v in c[:self._nstats]))
+
+    def records(self) -> torch.Tensor:
+        """The per-env mate-in-three records of the last ``step`` (a copy on the device); ``root.records()`` are the
+        mate-in-one records beside them, ``third.records()`` the third ply's, one per grandchild row."""
         return self._records.clone()
