@@ -773,7 +773,7 @@ int ka_policy_insight(const void* logits, int logits_bf16, const void* legal, in
  *   next ply of a captured graph; the same contract as the start pool's header):
  *     word 0 fp32 temperature   1 fp32 opening_temperature   2 int32 opening_plies   3 int32 top_k
  * plies / ply_stride: the u32 game ply of row b at plies + b * ply_stride (both multiples of 4); NULL = ply "infinite".
- *   The game ply is the u32 at byte 100 of the env's state row: the ply of the position to move in, 0 at the start of every
+ *   The game ply is the u32 at byte 100 of the env's state row (kPlyByte of csrc/shogi_rules.h, the owner of the layout): the ply of the position to move in, 0 at the start of every
  *   game, restarted games included (owners pass state + 100 with stride ka_shogi_env_state_bytes()).  The ply_count output
  *   of the step is NOT it: for a finished game that holds the finished game's length.
  * A seated row (m = model_of[b] in [0, K)) with game ply p:

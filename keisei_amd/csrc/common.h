@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 
 #define KA_OK 0
 #define KA_ERR_ARG (-1)
@@ -25,6 +26,11 @@ struct bf16_t { uint16_t v; };   // storage type for bf16 tensors
 void ka_set_error(const char* fmt, ...);
 int ka_check_launch(const char* what);
 #define KA_REQUIRE(cond, ...) do { if (!(cond)) { ka_set_error(__VA_ARGS__); return KA_ERR_ARG; } } while (0)
+// every pointer of the list is a multiple of n bytes (NULL is)
+inline bool ka_aligned(size_t n, std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs) if ((uintptr_t)p % n != 0) return false;
+    return true;
+}
 
 // Kernels that need more than 64 KiB of dynamic LDS: hipFuncAttributeMaxDynamicSharedMemorySize is a per-device
 // property of the function, so it is set once per (kernel instantiation, device) -- `done` is that instantiation's
@@ -228,6 +234,17 @@ __device__ __forceinline__ float ka_blended_value(const float* vl, const float* 
     const float e0 = expf(l0 - m), e1 = expf(l1 - m), e2 = expf(l2 - m);
     float v = (e0 - e2) / (e0 + e1 + e2);
     if (score && alpha != 0.f) v = (1.f - alpha) * v + alpha * fminf(fmaxf(*score, -1.f), 1.f);
+    return v;
+}
+
+// Inclusive prefix sum of v over the 64 lanes of a wave, in lane order.
+__device__ __forceinline__ int ka_wave_scan(int v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(v, o);
+        if (lane >= o) v += t;
+    }
     return v;
 }
 

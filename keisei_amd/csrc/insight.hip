@@ -16,16 +16,15 @@
 // A row whose model_of lies outside [0, K) or that has no legal action is written as all zeros (record and heat).
 // Ranks and the candidate order compare raw logits, so they do not depend on rounding; a legal logit that is -inf or NaN is
 // never a candidate.  Kernel nodes only, caller-owned buffers, no workgroup waits for another.
-#include "common.h"
+#include "ply_rows.h"
 
 #include <climits>
 
 namespace {
 
 constexpr int kInThreads = 256, kInWaves = kInThreads / 64;
-constexpr int kInSlots = 139, kInA = 81 * kInSlots, kInHeat = 132, kInMaxTop = 8;
-constexpr int kInWords = (kInA + 31) / 32;
-constexpr uint32_t kInTailBits = (1u << (kInA - 32 * (kInWords - 1))) - 1u;       // the bits of the last word that are actions
+constexpr int kInSlots = kPlySlots, kInA = kPlyA, kInWords = kPlyWords;           // csrc/ply_rows.h
+constexpr int kInHeat = 132, kInMaxTop = 8;
 constexpr int kInFlags = 0, kInAction = 1, kInNLegal = 2, kInRank = 3, kInProb = 4, kInEntropy = 5, kInWin = 6, kInTop = 8;
 
 __host__ __device__ constexpr int in_words(int top_k) { return kInTop + 2 * top_k; }
@@ -83,8 +82,7 @@ __global__ __launch_bounds__(kInThreads) void policy_insight_kernel(InsightArgs 
     float mx = -INFINITY, nl = 0.f;
     int nan_seen = 0;
     if (seated) {
-        for (int w = tid; w < kInWords; w += kInThreads)       // (bits past the action space are dropped: no index reaches A)
-            msk[w] = w == kInWords - 1 ? lw[w] & kInTailBits : lw[w];
+        for (int w = tid; w < kInWords; w += kInThreads) msk[w] = mask_word(lw, w);
         in_for_legal(msk, [&](int j) {                         // (a thread reads back the words it wrote itself)
             const float v = a.logits_bf16 ? bf2f(static_cast<const uint16_t*>(a.logits)[(size_t)b * kInA + j])
                                           : static_cast<const float*>(a.logits)[(size_t)b * kInA + j];

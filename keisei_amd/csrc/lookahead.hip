@@ -15,7 +15,7 @@
 // graph) belongs to model m:   word 0 int32 width   1 fp32 prior_weight   2 int32 skip_plies   3 int32 reply_width
 // A row with width outside [0, 8], a negative or non-finite weight or a negative skip_plies reads as "off"; a width above
 // the launch's width is cut to it.  An env is active when its model lies in [0, K), the row's width is positive, its game
-// ply (the u32 at byte 100 of its state row) is at least skip_plies and it has a candidate.
+// ply (the ply word of its state row, csrc/shogi_rules.h) is at least skip_plies and it has a candidate.
 //
 // Record of an env, 4 + 3 width 32-bit words:
 //   0 flags (bit 0 active, bit 1 the choice differs from the sampler's action, bit 2 the chosen move won the game)
@@ -23,7 +23,7 @@
 //   4.. candidate actions (int32, -1 = unused)   4 + width.. priors (fp32)   4 + 2 width.. q (fp32)
 //
 // The fork is one workgroup per env and walks the set bits of the packed mask row, never the action space; the copies are
-// what it is for, and every thread takes part in them, 16 bytes per lane where the rows allow it.  Unused and inactive child
+// what it is for: the ply's one fork copy (csrc/ply_rows.h), shared with the mate searches.  Unused and inactive child
 // slots get the state, the mask and the env's own sampled action (legal whenever the main step's is: one refused action
 // makes the env step hold every row of its launch) and model -1; their history is not copied -- the env kernel only counts
 // repetitions in it, and nothing reads such a child's outcome.  The parent's rows are only read.  Kernel nodes only,
@@ -50,21 +50,16 @@
 //
 //   ka_search_expand      the fork kernel with a row of the pool as "env", named per env by parent_row / active
 //   ka_search_advance     one thread per env: leaf q, the backup by max and negation, the next leaf, at the end the choice
-#include "common.h"
+#include "ply_rows.h"
 
 #include <climits>
 
 namespace {
 
 constexpr int kLaThreads = 256, kLaWaves = kLaThreads / 64;
-constexpr int kLaSlots = 139, kLaA = 81 * kLaSlots, kLaMaxWidth = 8;
-constexpr int kLaWords = (kLaA + 31) / 32;
-constexpr uint32_t kLaTailBits = (1u << (kLaA - 32 * (kLaWords - 1))) - 1u;       // the bits of the last word that are actions
-constexpr int kLaStateBytes = 128, kLaPlyByte = 100;                              // csrc/shogi_env.hip, kStateBytes
+constexpr int kLaMaxWidth = 8;
 constexpr int kLaFlags = 0, kLaSlot = 1, kLaNCand = 2, kLaAction = 3, kLaCand = 4;
 constexpr int kLaTableWords = 4, kLaStatsWords = 4;
-constexpr int kLaStateUnits = kLaStateBytes / 16, kLaMaskUnits = kLaWords * 4 / 16;     // 16-byte pieces of a state / mask row
-static_assert(kLaWords * 4 % 16 == 0 && kLaStateBytes % 16 == 0, "state and mask rows are copied in 16-byte pieces");
 
 __host__ __device__ constexpr int la_words(int width) { return kLaCand + 3 * width; }
 
@@ -107,7 +102,7 @@ __device__ __forceinline__ float la_reduce(float v, float* red, bool is_max) {
 // f(j) for every legal action j of this thread's mask words, in ascending j
 template <class F>
 __device__ __forceinline__ void la_for_legal(const uint32_t* msk, F f) {
-    for (int w = threadIdx.x; w < kLaWords; w += kLaThreads) {
+    for (int w = threadIdx.x; w < kPlyWords; w += kLaThreads) {
         uint32_t m = msk[w];
         while (m) {
             f((w << 5) + __builtin_ctz(m));
@@ -154,8 +149,8 @@ __device__ __forceinline__ float la_loss_minus_win(const float* vl, size_t c, bo
 // or inactive slot is the lowest legal action of the row's own mask (there is no sampled action to fall back on).
 template <bool kReply>
 __global__ __launch_bounds__(kLaThreads) void lookahead_fork_kernel(ForkArgs a) {
-    __shared__ float row[kLaA];
-    __shared__ uint32_t msk[kLaWords];
+    __shared__ float row[kPlyA];
+    __shared__ uint32_t msk[kPlyWords];
     __shared__ float red[kLaWaves];
     __shared__ int red_i[kLaWaves];
     __shared__ int s_cand[kLaMaxWidth];
@@ -172,9 +167,9 @@ __global__ __launch_bounds__(kLaThreads) void lookahead_fork_kernel(ForkArgs a) 
             src = off ? e * width : p;                         // (row e * width of expansion 0 lies below n_parent >= N * width)
         }
     }
-    const uint32_t* lw = a.legal + (size_t)src * kLaWords;
+    const uint32_t* lw = a.legal + (size_t)src * kPlyWords;
     const int m = a.model_of[src];
-    const uint32_t ply = a.state ? *reinterpret_cast<const uint32_t*>(a.state + (size_t)src * kLaStateBytes + kLaPlyByte) : UINT_MAX;
+    const uint32_t ply = a.state ? *reinterpret_cast<const uint32_t*>(a.state + (size_t)src * kStateBytes + kPlyByte) : UINT_MAX;
     int want;                                                  // (uniform over the workgroup, as every branch below)
     if constexpr (kReply) {
         if (tree) {                                            // the width of the model, not its reply width
@@ -193,12 +188,11 @@ __global__ __launch_bounds__(kLaThreads) void lookahead_fork_kernel(ForkArgs a) 
 
     int n_cand = 0;
     if (want > 0) {
-        for (int w = tid; w < kLaWords; w += kLaThreads)       // (bits past the action space are dropped: no index reaches A)
-            msk[w] = w == kLaWords - 1 ? lw[w] & kLaTailBits : lw[w];
+        for (int w = tid; w < kPlyWords; w += kLaThreads) msk[w] = mask_word(lw, w);
         float mx = -INFINITY;
         la_for_legal(msk, [&](int j) {                         // (a thread reads back the words it wrote itself)
-            const float v = a.logits_bf16 ? bf2f(static_cast<const uint16_t*>(a.logits)[(size_t)src * kLaA + j])
-                                          : static_cast<const float*>(a.logits)[(size_t)src * kLaA + j];
+            const float v = a.logits_bf16 ? bf2f(static_cast<const uint16_t*>(a.logits)[(size_t)src * kPlyA + j])
+                                          : static_cast<const float*>(a.logits)[(size_t)src * kPlyA + j];
             row[j] = v;
             mx = fmaxf(mx, v);                                 // (a NaN is passed over)
         });
@@ -242,8 +236,8 @@ __global__ __launch_bounds__(kLaThreads) void lookahead_fork_kernel(ForkArgs a) 
     long long sampled;
     if constexpr (kReply) {                                    // a block min over the first set bits
         int lo = INT_MAX;
-        for (int w = tid; w < kLaWords; w += kLaThreads) {
-            const uint32_t mw = w == kLaWords - 1 ? lw[w] & kLaTailBits : lw[w];
+        for (int w = tid; w < kPlyWords; w += kLaThreads) {
+            const uint32_t mw = mask_word(lw, w);
             if (mw) lo = min(lo, (w << 5) + __builtin_ctz(mw));
         }
 #pragma unroll
@@ -260,62 +254,23 @@ __global__ __launch_bounds__(kLaThreads) void lookahead_fork_kernel(ForkArgs a) 
         uint32_t word = 0u;
         if (tid == kLaFlags) word = n_cand > 0 ? 1u : 0u;
         else if (tid == kLaNCand) word = (uint32_t)n_cand;
-        else if (tid == kLaAction) word = (uint32_t)(int)(sampled < -1 ? -1 : sampled > kLaA ? kLaA : sampled);
+        else if (tid == kLaAction) word = (uint32_t)(int)(sampled < -1 ? -1 : sampled > kPlyA ? kPlyA : sampled);
         else if (part == 0) word = (uint32_t)(r < n_cand ? s_cand[r] : -1);
         else if (part == 1) word = __float_as_uint(r < n_cand ? s_prior[r] : 0.f);
         a.rec[(size_t)e * W + tid] = word;
     }
     if (!a.c_state) return;                                    // candidates and priors only
 
-    // ---- the child rows e * width + j: state and mask for every slot, the history for the slots in use
-    {
-        const uint4* s_src = reinterpret_cast<const uint4*>(a.state + (size_t)src * kLaStateBytes);
-        const uint4* m_src = reinterpret_cast<const uint4*>(lw);
-        constexpr int kUnits = kLaStateUnits + kLaMaskUnits;
-        for (int u = tid; u < kUnits * width; u += kLaThreads) {
-            const int j = u / kUnits, r = u % kUnits;
-            const size_t c = (size_t)e * width + j;
-            if (r < kLaStateUnits) reinterpret_cast<uint4*>(a.c_state + c * kLaStateBytes)[r] = s_src[r];
-            else reinterpret_cast<uint4*>(a.c_bits + c * kLaWords)[r - kLaStateUnits] = m_src[r - kLaStateUnits];
-        }
-    }
-    const int hist = a.hist, n = (int)min(ply, (uint32_t)hist);            // entries [0, ply) of the env's history rows
-    if (n_cand > 0 && n > 0) {
-        const unsigned long long* k_src = a.keys + (size_t)src * hist;
-        if ((hist & 1) == 0) {                                 // rows of an even number of keys start at 16-byte boundaries
-            const int units = (n + 1) >> 1;                    // (an odd count takes one stale key along: it stays inside the row)
-            for (int u = tid; u < units * n_cand; u += kLaThreads) {
-                const int j = u / units, r = u % units;
-                reinterpret_cast<uint4*>(a.c_keys + ((size_t)e * width + j) * hist)[r] = reinterpret_cast<const uint4*>(k_src)[r];
-            }
-        } else {
-            for (int u = tid; u < n * n_cand; u += kLaThreads) {
-                const int j = u / n, r = u % n;
-                a.c_keys[((size_t)e * width + j) * hist + r] = k_src[r];
-            }
-        }
-        const uint8_t* c_src = a.checks + (size_t)src * hist;
-        if ((hist & 15) == 0) {
-            const int units = (n + 15) >> 4;
-            for (int u = tid; u < units * n_cand; u += kLaThreads) {
-                const int j = u / units, r = u % units;
-                reinterpret_cast<uint4*>(a.c_checks + ((size_t)e * width + j) * hist)[r] = reinterpret_cast<const uint4*>(c_src)[r];
-            }
-        } else if ((hist & 3) == 0) {
-            const int units = (n + 3) >> 2;
-            for (int u = tid; u < units * n_cand; u += kLaThreads) {
-                const int j = u / units, r = u % units;
-                reinterpret_cast<uint32_t*>(a.c_checks + ((size_t)e * width + j) * hist)[r] = reinterpret_cast<const uint32_t*>(c_src)[r];
-            }
-        } else {
-            for (int u = tid; u < n * n_cand; u += kLaThreads) {
-                const int j = u / n, r = u % n;
-                a.c_checks[((size_t)e * width + j) * hist + r] = c_src[r];
-            }
-        }
-    }
+    // ---- the child rows e * width + j: the row's state and mask for every slot, entries [0, ply) of its history for the
+    // slots in use
+    const int hist = a.hist;
+    const size_t c0 = (size_t)e * width;
+    const PlyRow parent{a.state + (size_t)src * kStateBytes, lw, a.keys + (size_t)src * hist, a.checks + (size_t)src * hist};
+    ply_fork_rows<kLaThreads>(PlyRows{a.c_state + c0 * kStateBytes, a.c_bits + c0 * kPlyWords, a.c_keys + c0 * hist,
+                                      a.c_checks + c0 * hist},
+                              width, n_cand, hist, (int)min(ply, (uint32_t)hist), [&](int) { return parent; });
     if (tid < width) {
-        const size_t c = (size_t)e * width + tid;
+        const size_t c = c0 + tid;
         const bool used = tid < n_cand;
         a.c_actions[c] = used ? (long long)s_cand[tid] : sampled;
         a.c_model_of[c] = used ? m : -1;
@@ -588,8 +543,7 @@ extern "C" int ka_lookahead_fork(const void* logits, int logits_bf16, const void
                                  void* child_checks, void* child_mask_bits, long long* child_actions, int* child_model_of, int N,
                                  int A, void* stream) {
     KA_REQUIRE(logits && legal && actions && model_of && table && records && N > 0, "lookahead_fork: null tensor");
-    KA_REQUIRE(A == kLaA, "lookahead_fork: the spatial action space only (A = %d), got %d", kLaA, A);
-    KA_REQUIRE(legal_words == kLaWords, "lookahead_fork: packed mask rows of %d words", kLaWords);
+    KA_REQUIRE_PLY_SPACE("lookahead_fork", A, legal_words);
     KA_REQUIRE(width >= 1 && width <= kLaMaxWidth, "lookahead_fork: width must lie in [1, %d], got %d", kLaMaxWidth, width);
     KA_REQUIRE(K >= 1, "lookahead_fork: the controls table needs at least one row, got K = %d", K);
     const bool rows = state || keys || checks || child_state || child_keys || child_checks || child_mask_bits || child_actions ||
@@ -597,13 +551,11 @@ extern "C" int ka_lookahead_fork(const void* logits, int logits_bf16, const void
     KA_REQUIRE(!rows || (state && keys && checks && child_state && child_keys && child_checks && child_mask_bits &&
                          child_actions && child_model_of),
                "lookahead_fork: the env rows and the child rows are all given or all NULL");
-    KA_REQUIRE(max_ply >= 0 && max_ply <= 65535, "lookahead_fork: max_ply must lie in [0, 65535], got %d", max_ply);
+    KA_REQUIRE_MAX_PLY("lookahead_fork", max_ply);
     KA_REQUIRE((long long)N * width <= INT_MAX, "lookahead_fork: %d envs of width %d are too many child rows", N, width);
-    KA_REQUIRE((uintptr_t)logits % (logits_bf16 ? 2 : 4) == 0 && (uintptr_t)legal % 16 == 0 && (uintptr_t)actions % 8 == 0 &&
-               (uintptr_t)model_of % 4 == 0 && (uintptr_t)table % 4 == 0 && (uintptr_t)records % 4 == 0 &&
-               (uintptr_t)state % 16 == 0 && (uintptr_t)keys % 16 == 0 && (uintptr_t)checks % 16 == 0 &&
-               (uintptr_t)child_state % 16 == 0 && (uintptr_t)child_keys % 16 == 0 && (uintptr_t)child_checks % 16 == 0 &&
-               (uintptr_t)child_mask_bits % 16 == 0 && (uintptr_t)child_actions % 8 == 0 && (uintptr_t)child_model_of % 4 == 0,
+    KA_REQUIRE(ka_aligned(logits_bf16 ? 2 : 4, {logits}) &&
+               ka_aligned(16, {legal, state, keys, checks, child_state, child_keys, child_checks, child_mask_bits}) &&
+               ka_aligned(8, {actions, child_actions}) && ka_aligned(4, {model_of, table, records, child_model_of}),
                "lookahead_fork: state, history and mask rows are 16-byte aligned, every other tensor to its element size");
     ForkArgs a{logits, logits_bf16, static_cast<const uint32_t*>(legal), actions, model_of, K, static_cast<const uint32_t*>(table),
                static_cast<const uint8_t*>(state), static_cast<const unsigned long long*>(keys),
@@ -645,19 +597,17 @@ extern "C" int ka_lookahead_fork_replies(const void* child_logits, int logits_bf
     KA_REQUIRE(child_logits && child_mask_bits && child_model_of && table && child_state && child_keys && child_checks &&
                child_terminated && child_truncated && reply_records && grand_state && grand_keys && grand_checks &&
                grand_mask_bits && grand_actions && grand_model_of && M > 0, "lookahead_fork_replies: null tensor");
-    KA_REQUIRE(A == kLaA, "lookahead_fork_replies: the spatial action space only (A = %d), got %d", kLaA, A);
-    KA_REQUIRE(legal_words == kLaWords, "lookahead_fork_replies: packed mask rows of %d words", kLaWords);
+    KA_REQUIRE_PLY_SPACE("lookahead_fork_replies", A, legal_words);
     KA_REQUIRE(reply_width >= 1 && reply_width <= kLaMaxWidth, "lookahead_fork_replies: reply_width must lie in [1, %d], got %d",
                kLaMaxWidth, reply_width);
     KA_REQUIRE(K >= 1, "lookahead_fork_replies: the controls table needs at least one row, got K = %d", K);
-    KA_REQUIRE(max_ply >= 0 && max_ply <= 65535, "lookahead_fork_replies: max_ply must lie in [0, 65535], got %d", max_ply);
+    KA_REQUIRE_MAX_PLY("lookahead_fork_replies", max_ply);
     KA_REQUIRE((long long)M * reply_width <= INT_MAX, "lookahead_fork_replies: %d children of reply width %d are too many rows", M,
                reply_width);
-    KA_REQUIRE((uintptr_t)child_logits % (logits_bf16 ? 2 : 4) == 0 && (uintptr_t)child_mask_bits % 16 == 0 &&
-               (uintptr_t)child_model_of % 4 == 0 && (uintptr_t)table % 4 == 0 && (uintptr_t)reply_records % 4 == 0 &&
-               (uintptr_t)child_state % 16 == 0 && (uintptr_t)child_keys % 16 == 0 && (uintptr_t)child_checks % 16 == 0 &&
-               (uintptr_t)grand_state % 16 == 0 && (uintptr_t)grand_keys % 16 == 0 && (uintptr_t)grand_checks % 16 == 0 &&
-               (uintptr_t)grand_mask_bits % 16 == 0 && (uintptr_t)grand_actions % 8 == 0 && (uintptr_t)grand_model_of % 4 == 0,
+    KA_REQUIRE(ka_aligned(logits_bf16 ? 2 : 4, {child_logits}) &&
+               ka_aligned(16, {child_mask_bits, child_state, child_keys, child_checks, grand_state, grand_keys, grand_checks,
+                               grand_mask_bits}) &&
+               ka_aligned(8, {grand_actions}) && ka_aligned(4, {child_model_of, table, reply_records, grand_model_of}),
                "lookahead_fork_replies: state, history and mask rows are 16-byte aligned, every other tensor to its element size");
     ForkArgs a{child_logits, logits_bf16, static_cast<const uint32_t*>(child_mask_bits), nullptr, child_model_of, K,
                static_cast<const uint32_t*>(table), static_cast<const uint8_t*>(child_state),
@@ -715,24 +665,21 @@ extern "C" int ka_search_expand(const void* pool_logits, int logits_bf16, const 
     KA_REQUIRE(pool_logits && pool_mask_bits && pool_model_of && table && pool_state && pool_keys && pool_checks &&
                pool_terminated && pool_truncated && parent_row && active && records && node_state && node_keys && node_checks &&
                node_mask_bits && node_actions && node_model_of && N > 0, "search_expand: null tensor");
-    KA_REQUIRE(A == kLaA, "search_expand: the spatial action space only (A = %d), got %d", kLaA, A);
-    KA_REQUIRE(legal_words == kLaWords, "search_expand: packed mask rows of %d words", kLaWords);
+    KA_REQUIRE_PLY_SPACE("search_expand", A, legal_words);
     KA_REQUIRE(width >= 1 && width <= kLaMaxWidth, "search_expand: width must lie in [1, %d], got %d", kLaMaxWidth, width);
     KA_REQUIRE(t >= 1 && t < kLaMaxExpansions, "search_expand: the expansion must lie in [1, %d), got %d", kLaMaxExpansions, t);
     KA_REQUIRE(K >= 1, "search_expand: the controls table needs at least one row, got K = %d", K);
-    KA_REQUIRE(max_ply >= 0 && max_ply <= 65535, "search_expand: max_ply must lie in [0, 65535], got %d", max_ply);
+    KA_REQUIRE_MAX_PLY("search_expand", max_ply);
     KA_REQUIRE((long long)N * width * (t + 1) <= INT_MAX, "search_expand: %d envs of width %d are too many rows at expansion %d", N,
                width, t);
     const size_t below = (size_t)t * N * width;                // the rows of the expansions before this one
-    KA_REQUIRE(static_cast<const uint8_t*>(node_state) == static_cast<const uint8_t*>(pool_state) + below * kLaStateBytes &&
+    KA_REQUIRE(static_cast<const uint8_t*>(node_state) == static_cast<const uint8_t*>(pool_state) + below * kStateBytes &&
                static_cast<const int*>(node_model_of) == pool_model_of + below,
                "search_expand: the rows written are slice %d of the pool: they start %zu rows behind it", t, below);
-    KA_REQUIRE((uintptr_t)pool_logits % (logits_bf16 ? 2 : 4) == 0 && (uintptr_t)pool_mask_bits % 16 == 0 &&
-               (uintptr_t)pool_model_of % 4 == 0 && (uintptr_t)table % 4 == 0 && (uintptr_t)records % 4 == 0 &&
-               (uintptr_t)parent_row % 4 == 0 && (uintptr_t)active % 4 == 0 &&
-               (uintptr_t)pool_state % 16 == 0 && (uintptr_t)pool_keys % 16 == 0 && (uintptr_t)pool_checks % 16 == 0 &&
-               (uintptr_t)node_state % 16 == 0 && (uintptr_t)node_mask_bits % 16 == 0 && (uintptr_t)node_actions % 8 == 0 &&
-               (uintptr_t)node_model_of % 4 == 0,
+    KA_REQUIRE(ka_aligned(logits_bf16 ? 2 : 4, {pool_logits}) &&
+               ka_aligned(16, {pool_mask_bits, pool_state, pool_keys, pool_checks, node_state, node_mask_bits}) &&
+               ka_aligned(8, {node_actions}) &&
+               ka_aligned(4, {pool_model_of, table, records, parent_row, active, node_model_of}),
                "search_expand: state, history and mask rows are 16-byte aligned, every other tensor to its element size");
     // a slice of the pool starts a whole number of history rows behind it: aligned to the pieces its rows are copied in
     const int hist = max_ply > 0 ? max_ply : 1;

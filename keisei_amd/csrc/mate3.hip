@@ -40,32 +40,25 @@
 // The fork is one workgroup per env.  One wave owns one child at a time: its lanes count the child's mask row, and -- after
 // one thread has walked the budget -- take six consecutive mask words each, so a wave scan of the lanes' counts places every
 // evasion in ascending action order; a child's rows are written by one wave alone, so no order is lost between waves.  The
-// copies then run over the whole workgroup, 16 bytes per lane where the rows allow it.  Unused rows get the root env's
+// copies then run over the whole workgroup: the ply's one fork copy (csrc/ply_rows.h).  Unused rows get the root env's
 // state, mask and incoming action (legal whenever the main step's is: one refused action makes the env step hold every
 // row of its launch); their history is not copied and nothing reads their outcome.  Kernel nodes only, caller-owned
 // buffers, no workgroup waits for another.
-#include "common.h"
+#include "mate_record.h"
+#include "ply_rows.h"
 
 #include <climits>
 
 namespace {
 
 constexpr int kM3Threads = 256, kM3Waves = kM3Threads / 64;
-constexpr int kM3A = 81 * 139, kM3MaxCap = 64, kM3MaxRows = 128;
-constexpr int kM3Words = (kM3A + 31) / 32;
-constexpr uint32_t kM3TailBits = (1u << (kM3A - 32 * (kM3Words - 1))) - 1u;       // the bits of the last word that are actions
-constexpr int kM3LaneWords = (kM3Words + 63) / 64;                                // consecutive mask words of one lane
-constexpr int kM3StateBytes = 128, kM3PlyByte = 100;                              // csrc/shogi_env.hip, kStateBytes
-constexpr int kM3StateUnits = kM3StateBytes / 16, kM3MaskUnits = kM3Words * 4 / 16;
-static_assert(kM3Words * 4 % 16 == 0 && kM3StateBytes % 16 == 0, "state and mask rows are copied in 16-byte pieces");
+constexpr int kM3MaxCap = 64, kM3MaxRows = 128;
+constexpr int kM3LaneWords = (kPlyWords + 63) / 64;                               // consecutive mask words of one lane
 constexpr int kM3TableWords = 4, kM3StatsWords = 6;                               // (the error word follows the stats)
-// the record of csrc/mate.hip
-constexpr int kMtFlags = 0, kMtNChecks = 1, kMtList = 4;
-// this file's record
+// this file's record (the root's and the third ply's are csrc/mate_record.h's)
 constexpr int kM3Flags = 0, kM3Rows = 1, kM3Slot = 2, kM3Action = 3, kM3Proving = 4, kM3N = 6;
 constexpr uint32_t kM3Active = 1u, kM3Mate = 2u, kM3Changed = 4u, kM3Skipped = 8u, kM3Cut3 = 16u;
 
-__host__ __device__ constexpr int mt_words(int cap) { return kMtList + cap; }
 __host__ __device__ constexpr int m3_words(int cap) { return kM3N + 2 * cap; }
 
 // evasion_rows of model m as the kernels read it (0 = depth three off)
@@ -75,10 +68,6 @@ __device__ __forceinline__ int m3_controls(const uint32_t* table, int m, int K) 
     const int er = (int)c[2], rc = (int)c[3];
     if (!(er >= 0 && er <= kM3MaxRows && rc >= 0 && rc <= kM3MaxCap)) return 0;
     return er;
-}
-
-__device__ __forceinline__ uint32_t m3_mask_word(const uint32_t* row, int w) {
-    return w == kM3Words - 1 ? row[w] & kM3TailBits : row[w];                   // (bits past the action space are dropped)
 }
 
 struct Mate3ForkArgs {
@@ -107,11 +96,11 @@ __global__ __launch_bounds__(kM3Threads) void mate3_fork_kernel(Mate3ForkArgs a)
     const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cap = a.cap, G = a.G, W1 = mt_words(cap), W = m3_words(cap);
     const uint32_t* rec1 = a.rec1 + (size_t)e * W1;
-    const uint32_t* lw = a.legal + (size_t)e * kM3Words;
-    const uint8_t* st = a.state + (size_t)e * kM3StateBytes;
+    const uint32_t* lw = a.legal + (size_t)e * kPlyWords;
+    const uint8_t* st = a.state + (size_t)e * kStateBytes;
     const uint32_t flags1 = rec1[kMtFlags];
     const int rows = min(m3_controls(a.table, a.model_of[e], a.K), G);
-    const bool active = (flags1 & 1u) && !(flags1 & 2u) && rows > 0;       // (uniform over the workgroup, as every branch below)
+    const bool active = (flags1 & kMtActive) && !(flags1 & kMtMate) && rows > 0;       // (uniform over the workgroup, as every branch below)
 
     if (tid < kM3MaxCap) { s_n[tid] = -1; s_first[tid] = -1; }
     if (tid < kM3MaxRows) { s_act[tid] = 0; s_src[tid] = 0; }  // (no row ever names a child outside the env's own)
@@ -123,9 +112,9 @@ __global__ __launch_bounds__(kM3Threads) void mate3_fork_kernel(Mate3ForkArgs a)
             if ((int)rec1[kMtList + j] < 0) break;             // the slots in use come first
             const size_t c = (size_t)e * cap + j;
             if (a.c_term[c] | a.c_trunc[c]) continue;
-            const uint32_t* row = a.c_bits + c * kM3Words;
+            const uint32_t* row = a.c_bits + c * kPlyWords;
             int cnt = 0;
-            for (int w = lane; w < kM3Words; w += 64) cnt += __popc(m3_mask_word(row, w));
+            for (int w = lane; w < kPlyWords; w += 64) cnt += __popc(mask_word(row, w));
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
             if (lane == 0) s_n[j] = cnt;
@@ -147,22 +136,16 @@ __global__ __launch_bounds__(kM3Threads) void mate3_fork_kernel(Mate3ForkArgs a)
             const int first = s_first[j];
             if (first < 0) continue;
             const int n = s_n[j];
-            const uint32_t* row = a.c_bits + ((size_t)e * cap + j) * kM3Words;
+            const uint32_t* row = a.c_bits + ((size_t)e * cap + j) * kPlyWords;
             uint32_t m[kM3LaneWords];
             int cnt = 0;
 #pragma unroll
             for (int x = 0; x < kM3LaneWords; ++x) {
                 const int w = lane * kM3LaneWords + x;
-                m[x] = w < kM3Words ? m3_mask_word(row, w) : 0u;
+                m[x] = w < kPlyWords ? mask_word(row, w) : 0u;
                 cnt += __popc(m[x]);
             }
-            int inc = cnt;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(inc, o);
-                if (lane >= o) inc += t;
-            }
-            int pos = inc - cnt;
+            int pos = ka_wave_scan(cnt) - cnt;
 #pragma unroll
             for (int x = 0; x < kM3LaneWords; ++x) {
                 uint32_t b = m[x];
@@ -184,67 +167,25 @@ __global__ __launch_bounds__(kM3Threads) void mate3_fork_kernel(Mate3ForkArgs a)
         if (tid == kM3Flags) word = (active ? kM3Active : 0u) | (s_skipped > 0 ? kM3Skipped : 0u);
         else if (tid == kM3Rows) word = (uint32_t)used;
         else if (tid == kM3Slot) word = (uint32_t)-1;
-        else if (tid == kM3Action) word = (uint32_t)(int)(incoming < -1 ? -1 : incoming > kM3A ? kM3A : incoming);
+        else if (tid == kM3Action) word = (uint32_t)(int)(incoming < -1 ? -1 : incoming > kPlyA ? kPlyA : incoming);
         else if (tid >= kM3N + cap) word = (uint32_t)s_first[tid - kM3N - cap];
         else if (tid >= kM3N) word = (uint32_t)s_n[tid - kM3N];
         a.rec[(size_t)e * W + tid] = word;
     }
 
     // ---- the grandchild rows e * G + r: the child's state and new mask for the rows in use, the root's for the others
-    {
-        constexpr int kUnits = kM3StateUnits + kM3MaskUnits;
-        for (int u = tid; u < kUnits * G; u += kM3Threads) {
-            const int r = u / kUnits, p = u % kUnits;
-            const size_t g = (size_t)e * G + r;
-            const uint4 *s_src4 = reinterpret_cast<const uint4*>(st), *m_src4 = reinterpret_cast<const uint4*>(lw);
-            if (r < used) {
-                const size_t c = (size_t)e * cap + s_src[r];
-                s_src4 = reinterpret_cast<const uint4*>(a.c_state + c * kM3StateBytes);
-                m_src4 = reinterpret_cast<const uint4*>(a.c_bits + c * kM3Words);
-            }
-            if (p < kM3StateUnits) reinterpret_cast<uint4*>(a.g_state + g * kM3StateBytes)[p] = s_src4[p];
-            else reinterpret_cast<uint4*>(a.g_bits + g * kM3Words)[p - kM3StateUnits] = m_src4[p - kM3StateUnits];
-        }
-    }
-    // entries [0, ply + 1) of the child's history rows: an open child is one ply behind its root
-    const uint32_t ply = *reinterpret_cast<const uint32_t*>(st + kM3PlyByte);
-    const int hist = a.hist, n = (int)min(ply, (uint32_t)hist - 1u) + 1;
-    if (used > 0) {
-        if ((hist & 1) == 0) {                                 // rows of an even number of keys start at 16-byte boundaries
-            const int units = (n + 1) >> 1;                    // (an odd count takes one stale key along: it stays inside the row)
-            for (int u = tid; u < units * used; u += kM3Threads) {
-                const int r = u / units, p = u % units;
-                const size_t c = (size_t)e * cap + s_src[r];
-                reinterpret_cast<uint4*>(a.g_keys + ((size_t)e * G + r) * hist)[p] = reinterpret_cast<const uint4*>(a.c_keys + c * hist)[p];
-            }
-        } else {
-            for (int u = tid; u < n * used; u += kM3Threads) {
-                const int r = u / n, p = u % n;
-                a.g_keys[((size_t)e * G + r) * hist + p] = a.c_keys[((size_t)e * cap + s_src[r]) * hist + p];
-            }
-        }
-        if ((hist & 15) == 0) {
-            const int units = (n + 15) >> 4;
-            for (int u = tid; u < units * used; u += kM3Threads) {
-                const int r = u / units, p = u % units;
-                const size_t c = (size_t)e * cap + s_src[r];
-                reinterpret_cast<uint4*>(a.g_checks + ((size_t)e * G + r) * hist)[p] = reinterpret_cast<const uint4*>(a.c_checks + c * hist)[p];
-            }
-        } else if ((hist & 3) == 0) {
-            const int units = (n + 3) >> 2;
-            for (int u = tid; u < units * used; u += kM3Threads) {
-                const int r = u / units, p = u % units;
-                const size_t c = (size_t)e * cap + s_src[r];
-                reinterpret_cast<uint32_t*>(a.g_checks + ((size_t)e * G + r) * hist)[p] = reinterpret_cast<const uint32_t*>(a.c_checks + c * hist)[p];
-            }
-        } else {
-            for (int u = tid; u < n * used; u += kM3Threads) {
-                const int r = u / n, p = u % n;
-                a.g_checks[((size_t)e * G + r) * hist + p] = a.c_checks[((size_t)e * cap + s_src[r]) * hist + p];
-            }
-        }
-    }
-    if (tid < G) a.g_actions[(size_t)e * G + tid] = tid < used ? (long long)s_act[tid] : incoming;
+    // and entries [0, ply + 1) of the child's history rows: an open child is one ply behind its root
+    const uint32_t ply = *reinterpret_cast<const uint32_t*>(st + kPlyByte);
+    const int hist = a.hist;
+    const size_t g0 = (size_t)e * G;
+    ply_fork_rows<kM3Threads>(PlyRows{a.g_state + g0 * kStateBytes, a.g_bits + g0 * kPlyWords, a.g_keys + g0 * hist,
+                                      a.g_checks + g0 * hist},
+                              G, used, hist, (int)min(ply, (uint32_t)hist - 1u) + 1, [&](int r) {
+        if (r >= used) return PlyRow{st, lw, nullptr, nullptr};
+        const size_t c = (size_t)e * cap + s_src[r];
+        return PlyRow{a.c_state + c * kStateBytes, a.c_bits + c * kPlyWords, a.c_keys + c * hist, a.c_checks + c * hist};
+    });
+    if (tid < G) a.g_actions[g0 + tid] = tid < used ? (long long)s_act[tid] : incoming;
 }
 
 // one wave per grandchild row: the first set bit of its new mask, and whether the third ply looks at it
@@ -255,11 +196,11 @@ __global__ __launch_bounds__(kM3Threads) void mate3_gate_kernel(Mate3GateArgs a)
     const int e = (int)(r / a.G), i = (int)(r % a.G);
     const uint32_t* rec = a.rec + (size_t)e * m3_words(a.cap);
     const bool on = (rec[kM3Flags] & kM3Active) && i < (int)rec[kM3Rows] && !(a.g_term[r] | a.g_trunc[r]);
-    const uint32_t* row = a.g_bits + (size_t)r * kM3Words;
+    const uint32_t* row = a.g_bits + (size_t)r * kPlyWords;
     int filler = 0;
-    for (int w0 = 0; w0 < kM3Words; w0 += 64) {
+    for (int w0 = 0; w0 < kPlyWords; w0 += 64) {
         const int w = w0 + lane;
-        const uint32_t m = w < kM3Words ? m3_mask_word(row, w) : 0u;
+        const uint32_t m = w < kPlyWords ? mask_word(row, w) : 0u;
         const unsigned long long b = __ballot(m != 0u);
         if (b) {
             const int src = __builtin_ctzll(b);
@@ -310,10 +251,10 @@ __global__ __launch_bounds__(kM3Threads) void mate3_choose_kernel(Mate3ChooseArg
                     if (a.g_term[g] | a.g_trunc[g]) { proves = false; continue; }       // refutes, whatever the row now shows
                     const uint32_t* r3 = a.rec3 + g * W3;
                     const uint32_t f3 = r3[kMtFlags];
-                    if (f3 & 1u) rows3 += (f3 & 8u) ? want3 : (int)r3[kMtNChecks];
-                    if (!(f3 & 2u)) {
+                    if (f3 & kMtActive) rows3 += (f3 & kMtTruncated) ? want3 : (int)r3[kMtNChecks];
+                    if (!(f3 & kMtMate)) {
                         proves = false;
-                        if (f3 & 8u) flags |= kM3Cut3;
+                        if (f3 & kMtTruncated) flags |= kM3Cut3;
                     }
                 }
                 if (proves) {
@@ -374,20 +315,16 @@ extern "C" int ka_mate3_fork(const void* legal, int legal_words, const long long
     KA_REQUIRE(legal && actions && model_of && table && state && root_records && child_state && child_keys && child_checks &&
                child_mask_bits && child_terminated && child_truncated && records && grand_state && grand_keys &&
                grand_checks && grand_mask_bits && grand_actions && N > 0, "mate3_fork: null tensor");
-    KA_REQUIRE(A == kM3A, "mate3_fork: the spatial action space only (A = %d), got %d", kM3A, A);
-    KA_REQUIRE(legal_words == kM3Words, "mate3_fork: packed mask rows of %d words", kM3Words);
+    KA_REQUIRE_PLY_SPACE("mate3_fork", A, legal_words);
     KA_REQUIRE(m3_sizes_ok(cap, G), "mate3_fork: cap must lie in [1, %d] and G in [1, %d], got %d and %d", kM3MaxCap,
                kM3MaxRows, cap, G);
     KA_REQUIRE(K >= 1, "mate3_fork: the controls table needs at least one row, got K = %d", K);
-    KA_REQUIRE(max_ply >= 0 && max_ply <= 65535, "mate3_fork: max_ply must lie in [0, 65535], got %d", max_ply);
+    KA_REQUIRE_MAX_PLY("mate3_fork", max_ply);
     KA_REQUIRE((long long)N * cap <= INT_MAX && (long long)N * G <= INT_MAX, "mate3_fork: %d envs of %d child and %d "
                "grandchild rows are too many rows", N, cap, G);
-    KA_REQUIRE((uintptr_t)legal % 16 == 0 && (uintptr_t)actions % 8 == 0 && (uintptr_t)model_of % 4 == 0 &&
-               (uintptr_t)table % 4 == 0 && (uintptr_t)root_records % 4 == 0 && (uintptr_t)records % 4 == 0 &&
-               (uintptr_t)state % 16 == 0 && (uintptr_t)child_state % 16 == 0 && (uintptr_t)child_keys % 16 == 0 &&
-               (uintptr_t)child_checks % 16 == 0 && (uintptr_t)child_mask_bits % 16 == 0 && (uintptr_t)grand_state % 16 == 0 &&
-               (uintptr_t)grand_keys % 16 == 0 && (uintptr_t)grand_checks % 16 == 0 && (uintptr_t)grand_mask_bits % 16 == 0 &&
-               (uintptr_t)grand_actions % 8 == 0,
+    KA_REQUIRE(ka_aligned(16, {legal, state, child_state, child_keys, child_checks, child_mask_bits, grand_state, grand_keys,
+                               grand_checks, grand_mask_bits}) &&
+               ka_aligned(8, {actions, grand_actions}) && ka_aligned(4, {model_of, table, root_records, records}),
                "mate3_fork: state, history and mask rows are 16-byte aligned, every other tensor to its element size");
     Mate3ForkArgs a{static_cast<const uint32_t*>(legal), actions, model_of, K, static_cast<const uint32_t*>(table),
                     static_cast<const uint8_t*>(state), static_cast<const uint32_t*>(root_records), cap,
@@ -406,12 +343,11 @@ extern "C" int ka_mate3_gate(const void* records, int cap, int G, const int* mod
                              long long* grand_filler, int N, void* stream) {
     KA_REQUIRE(records && model_of && grand_mask_bits && grand_terminated && grand_truncated && grand_model_of &&
                grand_filler && N > 0, "mate3_gate: null tensor");
-    KA_REQUIRE(legal_words == kM3Words, "mate3_gate: packed mask rows of %d words", kM3Words);
+    KA_REQUIRE(legal_words == kPlyWords, "mate3_gate: packed mask rows of %d words", kPlyWords);
     KA_REQUIRE(m3_sizes_ok(cap, G), "mate3_gate: cap must lie in [1, %d] and G in [1, %d], got %d and %d", kM3MaxCap,
                kM3MaxRows, cap, G);
     KA_REQUIRE((long long)N * G <= INT_MAX, "mate3_gate: %d envs of %d grandchild rows are too many rows", N, G);
-    KA_REQUIRE((uintptr_t)records % 4 == 0 && (uintptr_t)model_of % 4 == 0 && (uintptr_t)grand_mask_bits % 4 == 0 &&
-               (uintptr_t)grand_model_of % 4 == 0 && (uintptr_t)grand_filler % 8 == 0,
+    KA_REQUIRE(ka_aligned(4, {records, model_of, grand_mask_bits, grand_model_of}) && ka_aligned(8, {grand_filler}),
                "mate3_gate: every tensor is aligned to its element size");
     const int rows = N * G;
     Mate3GateArgs a{static_cast<const uint32_t*>(records), cap, G, model_of, static_cast<const uint32_t*>(grand_mask_bits),
@@ -433,10 +369,8 @@ extern "C" int ka_mate3_choose(void* records, const void* root_records, int cap,
     KA_REQUIRE(cap3 >= 1 && cap3 <= kM3MaxCap, "mate3_choose: cap3 must lie in [1, %d], got %d", kM3MaxCap, cap3);
     KA_REQUIRE(K >= 1, "mate3_choose: the controls table needs at least one row, got K = %d", K);
     KA_REQUIRE((long long)N * G <= INT_MAX, "mate3_choose: %d envs of %d grandchild rows are too many rows", N, G);
-    KA_REQUIRE((uintptr_t)records % 4 == 0 && (uintptr_t)root_records % 4 == 0 && (uintptr_t)third_records % 4 == 0 &&
-               (uintptr_t)model_of % 4 == 0 && (uintptr_t)third_table % 4 == 0 && (uintptr_t)child_err % 8 == 0 &&
-               (uintptr_t)grand_err % 8 == 0 && (uintptr_t)third_err % 8 == 0 && (uintptr_t)actions % 8 == 0 &&
-               (uintptr_t)stats % 4 == 0 && (uintptr_t)err % 4 == 0,
+    KA_REQUIRE(ka_aligned(8, {child_err, grand_err, third_err, actions}) &&
+               ka_aligned(4, {records, root_records, third_records, model_of, third_table, stats, err}),
                "mate3_choose: actions and the error words are 8-byte aligned, every other tensor to its element size");
     Mate3ChooseArgs a{static_cast<uint32_t*>(records), static_cast<const uint32_t*>(root_records), cap, G,
                       static_cast<const uint32_t*>(third_records), cap3, static_cast<const uint8_t*>(grand_terminated),

@@ -13,7 +13,7 @@
 // -- and every candidate is tested by looking OUTWARD from the king over a two-square overlay of the board in LDS.  The
 // results are the same set of moves; tests/test_hip_shogi_env.py holds the kernels to the oracle bit for bit.
 // Repetition uses a 64-bit mixed key of (board, hands, side) kept per ply, where the reference keeps Zobrist keys.
-#include "common.h"
+#include "shogi_rules.h"
 
 namespace {
 
@@ -22,40 +22,8 @@ constexpr int kTypes = 139, kBoardMoves = 81 * 80 * 2;
 // observation planes: katago 50 (katago_observation.rs), default 46 (observation.rs: planes 44-45 reserved)
 constexpr int kMaxWords = (13527 + 31) / 32, kMaxCand = 1024;
 __host__ __device__ constexpr int action_space(int amode) { return amode ? 81 * kTypes : kBoardMoves + 81 * 7; }
-constexpr int kStateBytes = 128;      // board[81] hands[14] side in_check pad[3] | ply u32 @100 | key u64 @104 | reps u32 @112 | games u32 @116
 constexpr int kPoolRowBytes = 96;     // a start-pool row: board[81] hands[14] side, the first 96 bytes of a state row
 constexpr unsigned long long kSaltPool = 0x706F6F6Cull;
-enum { PAWN = 1, LANCE, KNIGHT, SILVER, GOLD, BISHOP, ROOK, KING };
-constexpr int WHITE_BIT = 0x10, PROM_BIT = 0x20;
-enum { R_PROGRESS = 0, R_CHECKMATE, R_REPETITION, R_PERPETUAL, R_IMPASSE, R_MAXMOVES };   // step_result.rs:9-16
-
-// directions: N NE E SE S SW W NW (spatial_action_mapper.rs:31-40); "N" is toward row 0
-// (row, column) steps as 2-bit fields of two immediates: the tables are on dependent-load chains of the ray walks
-__device__ __forceinline__ int dir_dr(int d) { return ((0x1A90 >> (2 * d)) & 3) - 1; }      // -1 -1 0 1 1 1 0 -1
-__device__ __forceinline__ int dir_dc(int d) { return ((0x01A9 >> (2 * d)) & 3) - 1; }      //  0  1 1 1 0 -1 -1 -1
-
-// step (low byte) and slide (high byte) direction sets of every piece byte, in board directions (attack.rs:56-113)
-__host__ __device__ constexpr unsigned dirs_of(int pc) {
-    const unsigned N = 1, NE = 2, E = 4, SE = 8, S = 16, SW = 32, W = 64, NW = 128, gold = N | NE | NW | E | W | S;
-    const int t = pc & 15;
-    const bool pr = pc & PROM_BIT, wh = pc & WHITE_BIT;
-    unsigned st = 0, sl = 0;
-    if (pr) {
-        if (t == PAWN || t == LANCE || t == KNIGHT || t == SILVER) st = gold;
-        else if (t == BISHOP) { st = N | E | S | W; sl = NE | SE | SW | NW; }
-        else if (t == ROOK) { st = NE | SE | SW | NW; sl = N | E | S | W; }
-    } else {
-        if (t == PAWN) st = N;
-        else if (t == LANCE) sl = N;
-        else if (t == SILVER) st = N | NE | NW | SE | SW;
-        else if (t == GOLD) st = gold;
-        else if (t == BISHOP) sl = NE | SE | SW | NW;
-        else if (t == ROOK) sl = N | E | S | W;
-        else if (t == KING) st = 255;
-    }
-    if (wh) { st = ((st << 4) | (st >> 4)) & 255; sl = ((sl << 4) | (sl >> 4)) & 255; }
-    return st | (sl << 8);
-}
 
 struct EnvArgs {
     uint8_t* state; unsigned long long* keys; uint8_t* checks;
@@ -68,35 +36,6 @@ struct EnvArgs {
     const uint8_t* pool; const int* pool_hdr;     // start positions (kPool kernels only): rows of kPoolRowBytes, header {count, 0, seed lo, seed hi}
 };
 
-// the board in LDS (explicit address space: these helpers are not always inlined) with up to two squares replaced
-typedef const __attribute__((address_space(3))) uint8_t* lds_board;
-typedef const __attribute__((address_space(3))) uint16_t* lds_dirs;      // dirs_of() of every piece byte, in LDS
-struct View { lds_board b; lds_dirs dirs; int o1, p1, o2, p2; };
-__device__ __forceinline__ int at(const View& v, int sq) { return sq == v.o1 ? v.p1 : sq == v.o2 ? v.p2 : v.b[sq]; }
-
-// is `sq` attacked by a piece of colour `by`?  Looks outward from the square: the first piece met along each of the
-// eight lines attacks it if it steps (distance 1) or slides back along that line; plus the two knight origins.
-// One probe = one line (d < 8) or one knight origin (d = 8, 9), so that ten lanes can share a test.
-__device__ __forceinline__ bool attacked_from(const View& v, int sq, int by, int d) {
-    const int r = sq / 9, c = sq % 9;
-    if (d < 8) {
-        const int dr = dir_dr(d), dc = dir_dc(d);
-        const unsigned need = 1u << ((d + 4) & 7);
-        int rr = r + dr, cc = c + dc, k = 1;
-        while ((unsigned)rr < 9u && (unsigned)cc < 9u) {
-            const int p = at(v, rr * 9 + cc);
-            if (p) {
-                if (((p >> 4) & 1) != by) return false;
-                const unsigned m = v.dirs[p & 63];
-                return (k == 1 && (m & need)) || ((m >> 8) & need);
-            }
-            rr += dr; cc += dc; ++k;
-        }
-        return false;
-    }
-    const int kr = by ? r - 2 : r + 2, kc = c + (d == 8 ? -1 : 1);
-    return (unsigned)kr < 9u && (unsigned)kc < 9u && at(v, kr * 9 + kc) == (KNIGHT | (by ? WHITE_BIT : 0));
-}
 // (kPool on the helpers that are not inlined by force: each kernel form owns its copies, as the one kernel did before)
 template <bool kPool>
 __device__ bool attacked(const View& v, int sq, int by) {
@@ -266,7 +205,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
             for (int i = lane; i < 81; i += 64) s_board[i] = row[i];
             if (lane < 14) s_hands[lane] = row[81 + lane];
             __syncthreads();
-            side = row[95] & 1; in_check = side_in_check(side);
+            side = row[kSideByte] & 1; in_check = side_in_check(side);
         } else {
             set_start(); side = 0; in_check = 0;
         }
@@ -278,19 +217,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     if (a.mode == 0) {
         begin_game();
     } else if (a.mode == 2) {
-        load_board(); side = st[95]; ply = 0; reps = 1; in_check = side_in_check(side); key = position_key();
+        load_board(); side = st[kSideByte]; ply = 0; reps = 1; in_check = side_in_check(side); key = position_key();
     } else if (hold) {
         load_board();
-        side = st[95]; in_check = st[96];
-        ply = *reinterpret_cast<const uint32_t*>(st + 100);
-        key = *reinterpret_cast<const unsigned long long*>(st + 104);
+        side = st[kSideByte]; in_check = st[kCheckByte];
+        ply = *reinterpret_cast<const uint32_t*>(st + kPlyByte);
+        key = *reinterpret_cast<const unsigned long long*>(st + kKeyByte);
         reps = (int)*reinterpret_cast<const uint32_t*>(st + 112);
         last_mover = side ^ 1;
     } else {
         load_board();
-        side = st[95]; in_check = st[96];
-        ply = *reinterpret_cast<const uint32_t*>(st + 100);
-        key = *reinterpret_cast<const unsigned long long*>(st + 104);
+        side = st[kSideByte]; in_check = st[kCheckByte];
+        ply = *reinterpret_cast<const uint32_t*>(st + kPlyByte);
+        key = *reinterpret_cast<const unsigned long long*>(st + kKeyByte);
         // ---- make_move (game.rs:107-188); the position before the move and whether its mover stood in check are history
         if (lane == 0) { keys[ply] = key; checks[ply] = (uint8_t)in_check; }
         const int act = (int)a.actions[env];
@@ -547,9 +486,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
 
     // ---- state back to HBM, observation, masks
     if (lane == 0) {
-        st[95] = (uint8_t)side; st[96] = (uint8_t)in_check;
-        *reinterpret_cast<uint32_t*>(st + 100) = (uint32_t)ply;
-        *reinterpret_cast<unsigned long long*>(st + 104) = key;
+        st[kSideByte] = (uint8_t)side; st[kCheckByte] = (uint8_t)in_check;
+        *reinterpret_cast<uint32_t*>(st + kPlyByte) = (uint32_t)ply;
+        *reinterpret_cast<unsigned long long*>(st + kKeyByte) = key;
         *reinterpret_cast<uint32_t*>(st + 112) = (uint32_t)reps;
         if constexpr (kPool) *reinterpret_cast<uint32_t*>(st + 116) = games;
         if (a.current_players) a.current_players[env] = (uint8_t)side;

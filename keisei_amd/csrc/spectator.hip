@@ -16,7 +16,7 @@
 // spectator_commit_kernel runs AFTER the env step: nothing happens when the step was refused (err[0] != 0); otherwise the
 // pending note is appended to the env's row and the rows of the envs that finished are emptied (their count becomes 0).
 // Kernel nodes only, caller-owned buffers, no atomics, no workgroup waits for another.
-#include "common.h"
+#include "shogi_rules.h"
 
 namespace {
 
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(kSpThreads) void spectator_note_kernel(const uint8_
     const long long act64 = actions[e];
     uint32_t note = 0;
     if (act64 >= 0 && act64 < A) {                             // every branch on the action is uniform over the wave
-        const int act = (int)act64, side = st[95] & 1;
+        const int act = (int)act64, side = st[kSideByte] & 1;
         // decode in the mover's perspective (spatial_action_mapper.rs:188-279 / action_mapper.rs:79-110)
         int from_p = 0, to_p = 0, promote = 0, drop = -1;
         bool on_board = true;

@@ -1,0 +1,123 @@
+"""What the searches of the device ply share on the Python side: the rows beneath an env (``ForkedRows``), the parser of a
+per-model controls argument (``controls_rows``) and the check of the env and the group a search is built over
+(``check_search_env``).  ``Lookahead``, ``MateSearch`` and ``Mate3Search`` hold their child and grandchild rows as
+``ForkedRows``; ``TreeSearch`` keeps its pool-plus-scratch allocation and shares the check alone.  The device side of the same
+rows is csrc/ply_rows.h."""
+from __future__ import annotations
+
+from typing import Mapping
+
+import numpy as np
+import torch
+
+from keisei_amd import _lib
+from keisei_amd.shogi_gym import MASK_WORDS
+
+__all__ = ["ForkedRows", "controls_rows", "check_search_env"]
+
+
+def check_search_env(env, group, what: str) -> None:
+    """``what`` ("the lookahead", "the search", "the mate search") runs over a katago / spatial env with 128-byte state rows
+    and, when it evaluates rows (``group`` not None), on a GPU group on the env's device."""
+    if env._amode != 1 or env._omode != 1:
+        raise ValueError(f"{what} covers the katago observation and the spatial action mode only")
+    if group is not None:
+        index = lambda d: torch.cuda.current_device() if d.index is None else d.index  # noqa: E731
+        if getattr(group, "_tables", None) is None or group.device.type != "cuda" or index(group.device) != index(env.device):
+            raise ValueError(f"{what} runs on a GPU group on the env's device ({env.device}); this group is on {group.device}")
+    if env._state.shape[1] != 128:
+        raise ValueError(f"{what} copies state rows of 128 bytes, the env's have {env._state.shape[1]}")
+
+
+def controls_rows(controls, K, cls, what: str, by_index: bool = False) -> list:
+    """K controls objects of class ``cls`` from ``controls``: None (K times ``cls.OFF``), one ``cls`` (every model), a
+    sequence of exactly K or, with ``by_index``, a dict from model index to ``cls`` (a model not named is off).  ``what``
+    names the argument in the errors ("lookahead", "search", "mate")."""
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1:
+        raise ValueError(f"a {what} table needs at least one row, got K = {K!r}")
+    K, name = int(K), cls.__name__
+    if controls is None:
+        return [cls.OFF] * K
+    if isinstance(controls, cls):
+        return [controls] * K
+    if by_index and isinstance(controls, Mapping):
+        extra = [k for k in controls if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < K]
+        if extra:
+            raise ValueError(f"{what} names model indices {extra} outside [0, {K})")
+        rows = [controls.get(m, cls.OFF) for m in range(K)]
+    elif isinstance(controls, (list, tuple)):
+        rows = list(controls)
+        if len(rows) != K:
+            raise ValueError(f"expected {K} {name} (one per model), got {len(rows)}")
+    else:
+        forms = f"a {name}, a sequence of {K} or a dict by model index" if by_index else f"a {name} or a sequence of {K}"
+        raise ValueError(f"{what} must be None, {forms}, got {type(controls).__name__}")
+    for r in rows:
+        if not isinstance(r, cls):
+            raise ValueError(f"every entry must be a {name}, got {type(r).__name__}")
+    return rows
+
+
+class ForkedRows:
+    """``per_row`` rows beneath every row of ``parent`` (a device ``VecEnv`` or another ``ForkedRows``), allocated once: what
+    ``ka_shogi_env_step`` reads and writes for them -- a state row, a key / check history row, the mask they are stepped
+    against (``bits_in``), the action, and the step's outputs -- and, with a ``group``, a ``model_of`` column and a forward
+    workspace.  A fork kernel fills ``state`` .. ``actions`` from ``parent_state`` .. ``parent_checks``; ``step`` steps them."""
+
+    _NAMES = ("state", "keys", "checks", "bits_in", "actions", "obs", "mask_bits", "rewards", "terminated", "truncated",
+              "players", "reason")
+
+    def __init__(self, parent, per_row: int, group=None) -> None:
+        above = isinstance(parent, ForkedRows)
+        self.env = env = parent.env if above else parent
+        self.parents = parent.M if above else env.num_envs
+        self.parent_state, self.parent_keys, self.parent_checks = \
+            (parent.state, parent.keys, parent.checks) if above else (env._state, env._keys, env._checks)
+        self.M = M = self.parents * per_row
+        dev, hist = env.device, env._keys.shape[1]
+        with torch.cuda.device(dev):
+            z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)  # noqa: E731
+            self.state = z(M, 128, dtype=torch.uint8)
+            self.keys = z(M, hist, dtype=torch.int64)
+            self.checks = z(M, hist, dtype=torch.uint8)
+            self.bits_in = z(M, MASK_WORDS, dtype=torch.int32)         # the parents' masks: the step validates against them
+            self.actions = z(M, dtype=torch.int64)
+            self.obs = z(M, env._C, 9, 9, dtype=torch.float32)
+            self.mask_bits = z(M, MASK_WORDS, dtype=torch.int32)
+            self.rewards = z(M, dtype=torch.float32)
+            self.terminated = z(M, dtype=torch.bool)
+            self.truncated = z(M, dtype=torch.bool)
+            self.players = z(M, dtype=torch.uint8)
+            self.reason = z(M, dtype=torch.uint8)
+            self.terminal_obs = z(M, env._C, 9, 9, dtype=torch.float32)
+            self.captured = z(M, dtype=torch.uint8)
+            self.ply = z(M, dtype=torch.int16)
+            self.material = z(M, dtype=torch.int32)
+            self.env_stats = z(4, dtype=torch.int64)
+            self.err = z(2, dtype=torch.int64)
+            self.model_of = self.ws = None
+            if group is not None:
+                self.model_of = torch.full((M,), -1, dtype=torch.int32, device=dev)
+                self.ws = group._tables.workspace(M)
+
+    def step(self, stream) -> None:
+        env = self.env
+        _lib.call("ka_shogi_env_step", self.state, self.keys, self.checks, self.actions, self.M, env._max_ply, env._omode,
+                  env._amode, None, self.bits_in, self.err, self.obs, None, self.mask_bits, self.rewards, self.terminated,
+                  self.truncated, self.terminal_obs, self.players, self.captured, self.reason, self.ply, self.material,
+                  self.env_stats, stream)
+
+    def clear(self) -> None:
+        """Zero the refusal latch of the step."""
+        self.err.zero_()
+
+    def alias(self, owner, prefix: str) -> None:
+        """``owner.<prefix>_state`` .. ``owner.<prefix>_reason`` and ``owner._<prefix>_err``: the tensors under the names the
+        searches have always shown them by; with a group also ``<prefix>_model_of``, ``_value_logits`` and ``_logits``."""
+        for name in self._NAMES:
+            setattr(owner, f"{prefix}_{name}", getattr(self, name))
+        setattr(owner, f"_{prefix}_err", self.err)
+        if self.ws is not None:
+            setattr(owner, f"{prefix}_model_of", self.model_of)
+            setattr(owner, f"{prefix}_value_logits", self.ws["value"])
+            setattr(owner, f"{prefix}_logits", self.ws["logits"])

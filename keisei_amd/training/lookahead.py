@@ -49,6 +49,8 @@ import torch
 from keisei_amd import _lib
 from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS
 
+from ._forked_rows import ForkedRows, check_search_env, controls_rows
+
 __all__ = ["LookaheadControls", "LookaheadStats", "LookaheadChoice", "LookaheadReplyChoice", "Lookahead", "lookahead_table",
            "lookahead_active", "lookahead_reply_widths", "lookahead_candidates", "lookahead_choose", "lookahead_choose_replies",
            "lookahead_words", "arena_lookahead", "arena_reply_width", "MAX_WIDTH", "MAX_SKIP_PLIES"]
@@ -110,22 +112,7 @@ class LookaheadStats:
 
 
 def _rows(controls, K: int):
-    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1:
-        raise ValueError(f"a lookahead table needs at least one row, got K = {K!r}")
-    K = int(K)
-    if controls is None:
-        return [LookaheadControls.OFF] * K
-    if isinstance(controls, LookaheadControls):
-        return [controls] * K
-    if isinstance(controls, (list, tuple)):
-        rows = list(controls)
-        if len(rows) != K:
-            raise ValueError(f"expected {K} LookaheadControls (one per model), got {len(rows)}")
-        for r in rows:
-            if not isinstance(r, LookaheadControls):
-                raise ValueError(f"every entry must be a LookaheadControls, got {type(r).__name__}")
-        return rows
-    raise ValueError(f"lookahead must be None, a LookaheadControls or a sequence of {K}, got {type(controls).__name__}")
+    return controls_rows(controls, K, LookaheadControls, "lookahead")
 
 
 def lookahead_table(controls, K: int) -> np.ndarray:
@@ -517,42 +504,6 @@ def _choose_replies_device(priors, n_cand, vlogits, rewards, done, n_reply, gvl,
 
 
 # ---------------------------------------------------------------------------------------------- in the ply
-class _Rows:
-    """The rows of one level below the env: what ``ka_shogi_env_step`` and the grouped forward read and write for ``M``
-    forked rows, allocated once."""
-
-    def __init__(self, env, group, M: int) -> None:
-        dev, hist = env.device, env._keys.shape[1]
-        z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)  # noqa: E731
-        self.M = M
-        self.state = z(M, 128, dtype=torch.uint8)
-        self.keys = z(M, hist, dtype=torch.int64)
-        self.checks = z(M, hist, dtype=torch.uint8)
-        self.bits_in = z(M, MASK_WORDS, dtype=torch.int32)             # the parents' masks: the step validates against them
-        self.actions = z(M, dtype=torch.int64)
-        self.model_of = torch.full((M,), -1, dtype=torch.int32, device=dev)
-        self.obs = z(M, env._C, 9, 9, dtype=torch.float32)
-        self.mask_bits = z(M, MASK_WORDS, dtype=torch.int32)
-        self.rewards = z(M, dtype=torch.float32)
-        self.terminated = z(M, dtype=torch.bool)
-        self.truncated = z(M, dtype=torch.bool)
-        self.players = z(M, dtype=torch.uint8)
-        self.reason = z(M, dtype=torch.uint8)
-        self.terminal_obs = z(M, env._C, 9, 9, dtype=torch.float32)
-        self.captured = z(M, dtype=torch.uint8)
-        self.ply = z(M, dtype=torch.int16)
-        self.material = z(M, dtype=torch.int32)
-        self.env_stats = z(4, dtype=torch.int64)
-        self.err = z(2, dtype=torch.int64)
-        self.ws = group._tables.workspace(M)
-
-    def step(self, env, stream) -> None:
-        _lib.call("ka_shogi_env_step", self.state, self.keys, self.checks, self.actions, self.M, env._max_ply, env._omode,
-                  env._amode, None, self.bits_in, self.err, self.obs, None, self.mask_bits, self.rewards, self.terminated,
-                  self.truncated, self.terminal_obs, self.players, self.captured, self.reason, self.ply, self.material,
-                  self.env_stats, stream)
-
-
 class Lookahead:
     """The child rows of a device ``VecEnv``, the second forward workspace and the stages of the lookahead.  Everything is
     allocated here, once: ``width`` child rows per env, each a state row, a key / check history row, two packed mask rows,
@@ -563,13 +514,7 @@ class Lookahead:
     def __init__(self, env, group, width: int, reply_width: int = 0) -> None:
         width = _check_width(width)
         reply_width = _check_width(reply_width, "reply_width", 0)
-        if env._amode != 1 or env._omode != 1:
-            raise ValueError("the lookahead covers the katago observation and the spatial action mode only")
-        index = lambda d: torch.cuda.current_device() if d.index is None else d.index  # noqa: E731
-        if getattr(group, "_tables", None) is None or group.device.type != "cuda" or index(group.device) != index(env.device):
-            raise ValueError(f"the lookahead runs on a GPU group on the env's device ({env.device}); this group is on {group.device}")
-        if env._state.shape[1] != 128:
-            raise ValueError(f"the lookahead copies state rows of 128 bytes, the env's have {env._state.shape[1]}")
+        check_search_env(env, group, "the lookahead")
         self.env, self.group, self.width, self.reply_width = env, group, width, reply_width
         n, dev = env.num_envs, env.device
         self.words = _lib.query("ka_lookahead_words", 0, width)
@@ -579,21 +524,15 @@ class Lookahead:
         with torch.cuda.device(dev):
             z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)  # noqa: E731
             self._records = z(n, self.words, dtype=torch.int32)
-            self._child = c = _Rows(env, group, M)
-            self.child_state, self.child_keys, self.child_checks, self.child_bits_in = c.state, c.keys, c.checks, c.bits_in
-            self.child_actions, self.child_model_of, self.child_obs, self.child_mask_bits = c.actions, c.model_of, c.obs, c.mask_bits
-            self.child_rewards, self.child_terminated, self.child_truncated = c.rewards, c.terminated, c.truncated
-            self.child_players, self.child_reason, self._child_err, self._ws = c.players, c.reason, c.err, c.ws
-            self.child_value_logits, self.child_logits = c.ws["value"], c.ws["logits"]
-            self._grand: Optional[_Rows] = None
+            self._child = c = ForkedRows(env, width, group)
+            c.alias(self, "child")                         # child_state .. child_reason, child_model_of, child_logits, _child_err
+            self._ws = c.ws
+            self._grand: Optional[ForkedRows] = None
             if reply_width:
                 self.reply_words = _lib.query("ka_lookahead_words", 0, reply_width)
                 self._reply_records = z(M, self.reply_words, dtype=torch.int32)
-                self._grand = g = _Rows(env, group, M * reply_width)
-                self.grand_actions, self.grand_model_of, self.grand_obs, self.grand_mask_bits = g.actions, g.model_of, g.obs, g.mask_bits
-                self.grand_rewards, self.grand_terminated, self.grand_truncated = g.rewards, g.terminated, g.truncated
-                self.grand_players, self.grand_reason, self._grand_err = g.players, g.reason, g.err
-                self.grand_value_logits = g.ws["value"]
+                self._grand = ForkedRows(c, reply_width, group)
+                self._grand.alias(self, "grand")
             self._counters = z(_lib.query("ka_lookahead_words", 2, width) + 1, dtype=torch.int32)     # stats, then the error word
             self._counters_host = torch.zeros(self._counters.shape, dtype=torch.int32).pin_memory()
         self._nstats = self._counters.shape[0] - 1
@@ -613,7 +552,7 @@ class Lookahead:
                   env.num_envs, ACTION_SPACE, stream)
 
     def step_children(self, stream) -> None:
-        self._child.step(self.env, stream)
+        self._child.step(stream)
 
     def evaluate(self) -> None:
         self.group._tables.forward(self.child_obs, self.child_model_of, ws=self._ws)
@@ -623,7 +562,7 @@ class Lookahead:
                   self.child_value_logits, self.child_rewards, self.child_terminated, self.child_truncated, self._child_err,
                   actions, self._counters, self._counters.data_ptr() + 4 * self._nstats, self.env.num_envs, stream)
 
-    def _need_replies(self) -> _Rows:
+    def _need_replies(self) -> ForkedRows:
         if self._grand is None:
             raise ValueError("this Lookahead was built with reply_width=0: it holds no grandchild rows")
         return self._grand
@@ -636,7 +575,7 @@ class Lookahead:
                   self._reply_records, g.state, g.keys, g.checks, g.bits_in, g.actions, g.model_of, c.M, ACTION_SPACE, stream)
 
     def step_grandchildren(self, stream) -> None:
-        self._need_replies().step(self.env, stream)
+        self._need_replies().step(stream)
 
     def evaluate_grandchildren(self) -> None:
         g = self._need_replies()

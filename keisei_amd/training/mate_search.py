@@ -30,13 +30,15 @@ mate into "not proven"; the records say when one cut.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import ClassVar, Mapping, Optional, Tuple
+from typing import ClassVar, Optional, Tuple
 
 import numpy as np
 import torch
 
 from keisei_amd import _lib
 from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS
+
+from ._forked_rows import ForkedRows, check_search_env, controls_rows
 
 __all__ = ["MateControls", "MateStats", "MateSearch", "mate_table", "mate_words", "arena_mate", "MAX_CHECKS",
            "MAX_SKIP_PLIES", "MAX_EVASION_ROWS", "Mate3Stats", "Mate3Search", "mate3_words", "mate3_reply_table",
@@ -103,29 +105,7 @@ class MateStats:
 
 
 def _rows(controls, K: int):
-    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1:
-        raise ValueError(f"a mate table needs at least one row, got K = {K!r}")
-    K = int(K)
-    if controls is None:
-        return [MateControls.OFF] * K
-    if isinstance(controls, MateControls):
-        return [controls] * K
-    if isinstance(controls, Mapping):                  # model index -> controls; a model not named is off
-        extra = [k for k in controls if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < K]
-        if extra:
-            raise ValueError(f"mate names model indices {extra} outside [0, {K})")
-        rows = [controls.get(m, MateControls.OFF) for m in range(K)]
-    elif isinstance(controls, (list, tuple)):
-        rows = list(controls)
-        if len(rows) != K:
-            raise ValueError(f"expected {K} MateControls (one per model), got {len(rows)}")
-    else:
-        raise ValueError(f"mate must be None, a MateControls, a sequence of {K} or a dict by model index, "
-                         f"got {type(controls).__name__}")
-    for r in rows:
-        if not isinstance(r, MateControls):
-            raise ValueError(f"every entry must be a MateControls, got {type(r).__name__}")
-    return rows
+    return controls_rows(controls, K, MateControls, "mate", by_index=True)
 
 
 def mate_table(controls, K: int) -> np.ndarray:
@@ -182,63 +162,39 @@ class MateSearch:
     (envs, 4 + cap) int32 are the envs' records of the last ``step``."""
 
     def __init__(self, env, cap: int) -> None:
+        """``env``: the device ``VecEnv``, or the ``ForkedRows`` whose rows are this search's positions (the third ply of
+        the mate in three)."""
         cap = _check_cap(cap)
-        if env._amode != 1 or env._omode != 1:
-            raise ValueError("the mate search covers the katago observation and the spatial action mode only")
-        if env._state.shape[1] != 128:
-            raise ValueError(f"the mate search copies state rows of 128 bytes, the env's have {env._state.shape[1]}")
-        self.env, self.cap = env, cap
-        n, dev, hist = env.num_envs, env.device, env._keys.shape[1]
+        check_search_env(env.env if isinstance(env, ForkedRows) else env, None, "the mate search")
+        self._child = c = ForkedRows(env, cap)
+        c.alias(self, "child")                             # child_state .. child_reason, _child_err
+        self.env, self.cap, self.M = c.env, cap, c.M
         self.words = _lib.query("ka_mate_words", 0, cap)
         assert self.words == mate_words(cap) and cap <= _lib.query("ka_mate_words", 3, 0) == MAX_CHECKS
-        self.M = M = n * cap
-        with torch.cuda.device(dev):
-            z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)  # noqa: E731
-            self._records = z(n, self.words, dtype=torch.int32)
-            self.child_state = z(M, 128, dtype=torch.uint8)
-            self.child_keys = z(M, hist, dtype=torch.int64)
-            self.child_checks = z(M, hist, dtype=torch.uint8)
-            self.child_bits_in = z(M, MASK_WORDS, dtype=torch.int32)       # the parents' masks: the step validates against them
-            self.child_actions = z(M, dtype=torch.int64)
-            self.child_obs = z(M, env._C, 9, 9, dtype=torch.float32)
-            self.child_mask_bits = z(M, MASK_WORDS, dtype=torch.int32)
-            self.child_rewards = z(M, dtype=torch.float32)
-            self.child_terminated = z(M, dtype=torch.bool)
-            self.child_truncated = z(M, dtype=torch.bool)
-            self.child_players = z(M, dtype=torch.uint8)
-            self.child_reason = z(M, dtype=torch.uint8)
-            self._terminal_obs = z(M, env._C, 9, 9, dtype=torch.float32)
-            self._captured = z(M, dtype=torch.uint8)
-            self._ply = z(M, dtype=torch.int16)
-            self._material = z(M, dtype=torch.int32)
-            self._env_stats = z(4, dtype=torch.int64)
-            self._child_err = z(2, dtype=torch.int64)
-            self._counters = z(_lib.query("ka_mate_words", 2, cap), dtype=torch.int32)       # stats, then the error word
-            self._counters_host = torch.zeros(self._counters.shape, dtype=torch.int32).pin_memory()
+        with torch.cuda.device(c.env.device):
+            self._records = torch.zeros(c.parents, self.words, dtype=torch.int32, device=c.env.device)
+            self._counters = torch.zeros(_lib.query("ka_mate_words", 2, cap), dtype=torch.int32, device=c.env.device)
+            self._counters_host = torch.zeros(self._counters.shape, dtype=torch.int32).pin_memory()       # stats, then the error word
         self._nstats = self._counters.shape[0] - 1
 
     def clear(self) -> None:
         """Zero the counters, the error word and the refusal latch of the child step (a round's start)."""
         self._counters.zero_()
-        self._child_err.zero_()
+        self._child.clear()
 
     def fork(self, mask_bits, actions, model_of, table, stream) -> None:
-        env = self.env
-        _lib.call("ka_mate_fork", mask_bits, MASK_WORDS, actions, model_of, int(table.shape[0]), table, env._state, env._keys,
-                  env._checks, env._max_ply, self.cap, self._records, self.child_state, self.child_keys, self.child_checks,
-                  self.child_bits_in, self.child_actions, env.num_envs, ACTION_SPACE, stream)
+        c = self._child
+        _lib.call("ka_mate_fork", mask_bits, MASK_WORDS, actions, model_of, int(table.shape[0]), table, c.parent_state,
+                  c.parent_keys, c.parent_checks, self.env._max_ply, self.cap, self._records, c.state, c.keys, c.checks,
+                  c.bits_in, c.actions, c.parents, ACTION_SPACE, stream)
 
     def step_children(self, stream) -> None:
-        env = self.env
-        _lib.call("ka_shogi_env_step", self.child_state, self.child_keys, self.child_checks, self.child_actions, self.M,
-                  env._max_ply, env._omode, env._amode, None, self.child_bits_in, self._child_err, self.child_obs, None,
-                  self.child_mask_bits, self.child_rewards, self.child_terminated, self.child_truncated, self._terminal_obs,
-                  self.child_players, self._captured, self.child_reason, self._ply, self._material, self._env_stats, stream)
+        self._child.step(stream)
 
     def choose(self, actions, stream) -> None:
-        _lib.call("ka_mate_choose", self._records, self.cap, self.child_rewards, self.child_terminated, self.child_reason,
-                  self._child_err, actions, self._counters, self._counters.data_ptr() + 4 * self._nstats, self.env.num_envs,
-                  stream)
+        c = self._child
+        _lib.call("ka_mate_choose", self._records, self.cap, c.rewards, c.terminated, c.reason, c.err, actions,
+                  self._counters, self._counters.data_ptr() + 4 * self._nstats, c.parents, stream)
 
     def step(self, mask_bits, actions, model_of, table, stream) -> None:
         """The three stages on the current stream (``stream``: its pointer), after the sampler (and the lookahead or the
@@ -281,15 +237,6 @@ class Mate3Stats:
     skipped: int = 0       # open children the budget walk left without rows
 
 
-class _Rows:
-    """What ``MateSearch`` reads of an env, for rows that are no env's: the grandchild rows as the third ply's positions."""
-
-    def __init__(self, env, n: int, state, keys, checks) -> None:
-        self.num_envs, self.device = n, env.device
-        self._amode, self._omode, self._C, self._max_ply = env._amode, env._omode, env._C, env._max_ply
-        self._state, self._keys, self._checks = state, keys, checks
-
-
 class Mate3Search:
     """The mate in three of a device ``VecEnv``: a ``MateSearch`` for the root (``cap`` child rows per env), ``rows``
     grandchild rows per env -- one per evasion of the checks the budget walk takes -- and a third-ply ``MateSearch`` over
@@ -302,36 +249,21 @@ class Mate3Search:
             raise ValueError(f"rows must be an integer in [1, {MAX_EVASION_ROWS}], got {rows!r}")
         self.root = MateSearch(env, cap)
         self.env, self.cap, self.rows, self.reply_cap = env, self.root.cap, int(rows), _check_cap(reply_cap)
-        n, dev, hist = env.num_envs, env.device, env._keys.shape[1]
+        n, dev = env.num_envs, env.device
         self.words = _lib.query("ka_mate3_words", 0, self.cap)
         assert self.words == mate3_words(self.cap) and _lib.query("ka_mate3_words", 3, 0) == MAX_EVASION_ROWS
-        self.M = M = n * self.rows
+        # the grandchild rows lie beneath the env, `rows` per env: which child a row continues is the fork's choice
+        self._grand = g = ForkedRows(env, self.rows)
+        g.alias(self, "grand")                             # grand_state .. grand_reason, _grand_err
+        self.M = M = g.M
         with torch.cuda.device(dev):
             z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)  # noqa: E731
             self._records = z(n, self.words, dtype=torch.int32)
-            self.grand_state = z(M, 128, dtype=torch.uint8)
-            self.grand_keys = z(M, hist, dtype=torch.int64)
-            self.grand_checks = z(M, hist, dtype=torch.uint8)
-            self.grand_bits_in = z(M, MASK_WORDS, dtype=torch.int32)       # the children's new masks: the step validates against them
-            self.grand_actions = z(M, dtype=torch.int64)
-            self.grand_obs = z(M, env._C, 9, 9, dtype=torch.float32)
-            self.grand_mask_bits = z(M, MASK_WORDS, dtype=torch.int32)
-            self.grand_rewards = z(M, dtype=torch.float32)
-            self.grand_terminated = z(M, dtype=torch.bool)
-            self.grand_truncated = z(M, dtype=torch.bool)
-            self.grand_players = z(M, dtype=torch.uint8)
-            self.grand_reason = z(M, dtype=torch.uint8)
-            self._terminal_obs = z(M, env._C, 9, 9, dtype=torch.float32)
-            self._captured = z(M, dtype=torch.uint8)
-            self._ply = z(M, dtype=torch.int16)
-            self._material = z(M, dtype=torch.int32)
-            self._env_stats = z(4, dtype=torch.int64)
-            self._grand_err = z(2, dtype=torch.int64)
             self.grand_model_of = z(M, dtype=torch.int32)
             self.grand_filler = z(M, dtype=torch.int64)                    # the third ply's action array: a scratch one
             self._counters = z(_lib.query("ka_mate3_words", 2, self.cap), dtype=torch.int32)      # stats, then the error word
             self._counters_host = torch.zeros(self._counters.shape, dtype=torch.int32).pin_memory()
-            self.third = MateSearch(_Rows(env, M, self.grand_state, self.grand_keys, self.grand_checks), self.reply_cap)
+        self.third = MateSearch(g, self.reply_cap)
         self._nstats = self._counters.shape[0] - 1
 
     def clear(self) -> None:
@@ -339,22 +271,17 @@ class Mate3Search:
         self.root.clear()
         self.third.clear()
         self._counters.zero_()
-        self._grand_err.zero_()
+        self._grand.clear()
 
     def fork(self, mask_bits, actions, model_of, table, stream) -> None:
-        env, root = self.env, self.root
+        env, root, g = self.env, self.root, self._grand
         _lib.call("ka_mate3_fork", mask_bits, MASK_WORDS, actions, model_of, int(table.shape[0]), table, env._state,
                   root._records, self.cap, root.child_state, root.child_keys, root.child_checks, root.child_mask_bits,
-                  root.child_terminated, root.child_truncated, env._max_ply, self.rows, self._records, self.grand_state,
-                  self.grand_keys, self.grand_checks, self.grand_bits_in, self.grand_actions, env.num_envs, ACTION_SPACE,
-                  stream)
+                  root.child_terminated, root.child_truncated, env._max_ply, self.rows, self._records, g.state, g.keys,
+                  g.checks, g.bits_in, g.actions, env.num_envs, ACTION_SPACE, stream)
 
     def step_grandchildren(self, stream) -> None:
-        env = self.env
-        _lib.call("ka_shogi_env_step", self.grand_state, self.grand_keys, self.grand_checks, self.grand_actions, self.M,
-                  env._max_ply, env._omode, env._amode, None, self.grand_bits_in, self._grand_err, self.grand_obs, None,
-                  self.grand_mask_bits, self.grand_rewards, self.grand_terminated, self.grand_truncated, self._terminal_obs,
-                  self.grand_players, self._captured, self.grand_reason, self._ply, self._material, self._env_stats, stream)
+        self._grand.step(stream)
 
     def gate(self, model_of, stream) -> None:
         _lib.call("ka_mate3_gate", self._records, self.cap, self.rows, model_of, self.grand_mask_bits, MASK_WORDS,

@@ -38,6 +38,7 @@ import torch
 from keisei_amd import _lib
 from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS
 
+from ._forked_rows import check_search_env, controls_rows
 from .lookahead import (FLAG_ACTIVE, MAX_SKIP_PLIES, MAX_WIDTH, REC_CAND, REC_FLAGS, REC_NCAND, _check_width,
                         _loss_minus_win, _row_controls, lookahead_words)
 
@@ -101,22 +102,7 @@ class SearchStats:
 
 
 def _rows(controls, K) -> List[SearchControls]:
-    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1:
-        raise ValueError(f"a search table needs at least one row, got K = {K!r}")
-    K = int(K)
-    if controls is None:
-        return [SearchControls.OFF] * K
-    if isinstance(controls, SearchControls):
-        return [controls] * K
-    if isinstance(controls, (list, tuple)):
-        rows = list(controls)
-        if len(rows) != K:
-            raise ValueError(f"expected {K} SearchControls (one per model), got {len(rows)}")
-        for r in rows:
-            if not isinstance(r, SearchControls):
-                raise ValueError(f"every entry must be a SearchControls, got {type(r).__name__}")
-        return rows
-    raise ValueError(f"search must be None, a SearchControls or a sequence of {K}, got {type(controls).__name__}")
+    return controls_rows(controls, K, SearchControls, "search")
 
 
 def search_table(controls, K: int) -> np.ndarray:
@@ -319,13 +305,7 @@ class TreeSearch:
     def __init__(self, env, group, width: int, expansions: int) -> None:
         width = _check_width(width)
         expansions = _check_expansions(expansions)
-        if env._amode != 1 or env._omode != 1:
-            raise ValueError("the search covers the katago observation and the spatial action mode only")
-        index = lambda d: torch.cuda.current_device() if d.index is None else d.index  # noqa: E731
-        if getattr(group, "_tables", None) is None or group.device.type != "cuda" or index(group.device) != index(env.device):
-            raise ValueError(f"the search runs on a GPU group on the env's device ({env.device}); this group is on {group.device}")
-        if env._state.shape[1] != 128:
-            raise ValueError(f"the search copies state rows of 128 bytes, the env's have {env._state.shape[1]}")
+        check_search_env(env, group, "the search")
         self.env, self.group, self.width, self.expansions = env, group, width, expansions
         n, dev, hist = env.num_envs, env.device, env._keys.shape[1]
         self.words = _lib.query("ka_search_words", 0, width, expansions)

@@ -95,6 +95,39 @@ def expected(name: str):
     return tuple(checks), tuple(mates)
 
 
+# Two scripted lines from the start position, as (from, to) squares (row, column; row 0 is White's back rank), that end
+# with a bishop's capture with check on the board: 1. P-7f 2. P-8d 3. P-2f 4. P-8e 5. P-2e and a quiet sixth move (Black's
+# bishop takes 3c with check, ply 6), and 1. P-2f 2. P-3d 3. P-2e 4. P-9d and a quiet fifth move (White's bishop takes 7g
+# with check, ply 5).  The last move differs per env, so the envs' rows differ.
+LINES = {
+    "even": ([((6, 2), (5, 2)), ((2, 1), (3, 1)), ((6, 7), (5, 7)), ((3, 1), (4, 1)), ((5, 7), (4, 7))],
+             [((2, 0), (3, 0)), ((2, 8), (3, 8)), ((2, 2), (3, 2)), ((2, 3), (3, 3)), ((2, 4), (3, 4))]),
+    "odd": ([((6, 7), (5, 7)), ((2, 6), (3, 6)), ((5, 7), (4, 7)), ((2, 0), (3, 0))],
+            [((6, 8), (5, 8)), ((6, 0), (5, 0)), ((6, 6), (5, 6)), ((6, 5), (5, 5)), ((6, 4), (5, 4))]),
+}
+
+
+@lru_cache(maxsize=None)
+def line(which: str):
+    """``(actions (plies, envs) int64, expect)`` of a scripted line, played on the oracle in lockstep (every move is legal
+    by its mask): ``expect`` is per env ``(checks, mates)`` of ``oracle_checks`` at the end, where every env stands at ply
+    ``plies``."""
+    common, last = LINES[which]
+    n = len(last)
+    ref = OracleVecEnv(n, 500)
+    _, mask = ref.reset()
+    acts = []
+    for k in range(len(common) + 1):
+        moves = [common[k]] * n if k < len(common) else last
+        a = np.array([S.encode(S.sq(*f), S.sq(*t), white=bool(k & 1)) for f, t in moves], np.int64)
+        assert all(mask[i][a[i]] for i in range(n)), (which, k, a)
+        mask = ref.step(a)["legal_masks"]
+        acts.append(a)
+    ends = [ref.state(i) for i in range(n)]
+    assert all(ply == len(acts) for *_, ply in ends)
+    return np.stack(acts), [oracle_checks(b, h, s)[:2] for b, h, s, _ in ends]
+
+
 def expected_record(checks, mates, cap: int):
     """What a cap allows: ``(forked list, truncated, mate action or -1)`` -- the first ``cap`` checking moves, whether more
     exist, and the lowest mate among the forked ones."""

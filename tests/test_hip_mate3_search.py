@@ -161,6 +161,64 @@ def test_a_playout_in_lockstep_with_the_oracle():
     assert active >= 50 and rows >= 50, (active, rows)
 
 
+@pytest.mark.parametrize("which", ["even", "odd"])
+@pytest.mark.parametrize("max_ply", [24, 23, 16])          # (history rows copied in 16-byte, 8-byte and single-byte pieces)
+def test_grandchild_rows_at_every_history_width_are_the_replayed_games(max_ply, which):
+    """``Mate3Search.step`` behind a scripted line (ply 6 or 5; the children stand at ply 7 or 6 and stay open under every
+    ceiling): every grandchild row in use is the replay of line + check + evasion -- the state, the first ply + 2 history
+    entries, the mask, the reward and the done bytes."""
+    from keisei_amd.training.mate_search import REC3_N, REC3_ROWS, Mate3Search, MateControls, mate3_reply_table, mate_table
+    acts, expect = H.line(which)
+    plies, n = acts.shape
+    assert plies >= 5 and plies + 2 < max_ply and all(len(checks) >= 1 and not mates for checks, mates in expect)
+    cap, rows, cap3 = 4, 32, 4
+    env = VecEnv(n, max_ply, "katago", "spatial")
+    env.reset()
+    for a in acts:
+        env.step(a)
+    search, st = Mate3Search(env, cap, rows, cap3), _lib.stream_ptr(torch.device(DEV))
+    table = mate_table(MateControls(cap, 0, rows, cap3), 1)
+    incoming = env._mask[env._cur].to(torch.uint8).argmax(dim=1)
+    actions = incoming.clone()
+    search.clear()
+    search.step(env._bits[env._cur], actions, torch.zeros(n, dtype=torch.int32, device=DEV), torch.from_numpy(table).to(DEV),
+                torch.from_numpy(mate3_reply_table(table)).to(DEV), st)
+    search.read()
+    root, deep = search.root.records().cpu().numpy(), search.records().cpu().numpy()
+    # per grandchild row: the check and the evasion that lead to it; a row not in use replays two fillers and is not compared
+    check = incoming.cpu().numpy().repeat(rows)
+    used = np.zeros(n * rows, bool)
+    for e in range(n):
+        assert deep[e, REC3_FLAGS] & FLAG3_ACTIVE and deep[e, REC3_ROWS] >= 1, e
+        for j in range(cap):
+            n_j, first = int(deep[e, REC3_N + j]), int(deep[e, REC3_N + cap + j])
+            if first >= 0:
+                check[e * rows + first:e * rows + first + n_j] = root[e, REC_LIST + j]
+                used[e * rows + first:e * rows + first + n_j] = True
+        assert used[e * rows:(e + 1) * rows].sum() == deep[e, REC3_ROWS], e
+    rep = VecEnv(n * rows, max_ply, "katago", "spatial", output="torch", check_actions=True)
+    rep.reset()
+    for a in acts:
+        rep.step(torch.from_numpy(a).to(DEV).repeat_interleave(rows))
+    r = rep.step(torch.from_numpy(check).to(DEV))
+    use = torch.from_numpy(used).to(DEV)
+    assert not bool((r.terminated | r.truncated)[use].any())               # the children are open
+    evasion = torch.where(use, search.grand_actions, r.legal_masks.to(torch.uint8).argmax(dim=1))
+    # the rows in use of one check are its evasions: the set bits of the child's new mask, ascending
+    for e in range(n):
+        for j in range(cap):
+            n_j, first = int(deep[e, REC3_N + j]), int(deep[e, REC3_N + cap + j])
+            if first >= 0:
+                legal = torch.nonzero(r.legal_masks[e * rows + first]).reshape(-1)
+                assert torch.equal(search.grand_actions[e * rows + first:e * rows + first + n_j], legal), (e, j)
+    r = rep.step(evasion)
+    for name, got, want in (("state", search.grand_state, rep._state), ("keys", search.grand_keys[:, :plies + 2], rep._keys[:, :plies + 2]),
+                            ("checks", search.grand_checks[:, :plies + 2], rep._checks[:, :plies + 2]),
+                            ("packed mask", search.grand_mask_bits, r.legal_mask_bits), ("reward", search.grand_rewards, r.rewards),
+                            ("terminated", search.grand_terminated, r.terminated), ("truncated", search.grand_truncated, r.truncated)):
+        assert got.dtype == want.dtype and torch.equal(got[use], want[use]), name
+
+
 # ---------------------------------------------------------------------------------------------- ka_mate3_choose alone
 CAP, G, CAP3 = 4, 8, 2
 

@@ -168,6 +168,54 @@ def test_a_playout_in_lockstep_with_the_oracle():
     assert int(dev._state[:, 100:104].contiguous().view(torch.int32).max()) >= 40              # long histories were copied
 
 
+@pytest.mark.parametrize("which", ["even", "odd"])
+@pytest.mark.parametrize("max_ply", [24, 23, 16])          # (history rows copied in 16-byte, 8-byte and single-byte pieces)
+def test_forked_rows_at_every_history_width_are_the_replayed_games(max_ply, which):
+    """The fork copy with a history behind every env: a scripted line ends at ply 6 (even) or 5 (odd) with at least one
+    checking move, and the key rows go in 16-byte (24, 16) or 8-byte (23) pieces, the check rows in 4-byte (24), single-byte (23) or
+    16-byte (16) pieces."""
+    acts, expect = H.line(which)
+    plies, n = acts.shape
+    assert plies >= 5 and plies % 2 == (which == "odd") and all(len(checks) >= 1 for checks, _ in expect)
+    cap = 4
+    env = VecEnv(n, max_ply, "katago", "spatial")
+    env.reset()
+    for a in acts:
+        env.step(a)
+    search, st = _search(env, cap)
+    bits = env._bits[env._cur]
+    incoming = env._mask[env._cur].to(torch.uint8).argmax(dim=1)
+    search.fork(bits, incoming.clone(), torch.zeros(n, dtype=torch.int32, device=DEV), _table(MateControls(cap)), st)
+    torch.cuda.synchronize()
+    lists = search._records[:, REC_LIST:].cpu().numpy()
+    used = torch.from_numpy((lists >= 0).reshape(-1)).to(DEV)
+    assert lists.tolist() == [list(checks[:cap]) + [-1] * (cap - len(checks[:cap])) for checks, _ in expect]
+    rows = lambda t: t.repeat_interleave(cap, dim=0)  # noqa: E731
+    assert int(env._state[:, 100:104].contiguous().view(torch.int32).min()) == plies
+    assert torch.equal(search.child_state, rows(env._state)) and torch.equal(search.child_bits_in, rows(bits))
+    assert torch.equal(search.child_keys[used, :plies], rows(env._keys)[used, :plies])
+    assert torch.equal(search.child_checks[used, :plies], rows(env._checks)[used, :plies])
+    assert bool(env._keys[:, :plies].ne(0).all()) and torch.equal(search.child_actions[used].cpu(),
+                                                                  torch.from_numpy(lists.reshape(-1)[lists.reshape(-1) >= 0]))
+    search.step_children(st)
+    torch.cuda.synchronize()
+    assert not bool(search._child_err.any())
+    # a second VecEnv of n * cap rows: row e * cap + j replays env e's line, then plays what slot j plays
+    rep = VecEnv(n * cap, max_ply, "katago", "spatial", output="torch", check_actions=True)
+    rep.reset()
+    for a in acts:
+        rep.step(torch.from_numpy(a).to(DEV).repeat_interleave(cap))
+    r = rep.step(search.child_actions.clone())
+    for name, got, want in (("state", search.child_state, rep._state), ("keys", search.child_keys[:, :plies + 1], rep._keys[:, :plies + 1]),
+                            ("checks", search.child_checks[:, :plies + 1], rep._checks[:, :plies + 1]),
+                            ("observation", search.child_obs, r.observations), ("packed mask", search.child_mask_bits, r.legal_mask_bits),
+                            ("reward", search.child_rewards, r.rewards), ("terminated", search.child_terminated, r.terminated),
+                            ("truncated", search.child_truncated, r.truncated),
+                            ("termination reason", search.child_reason, r.step_metadata.termination_reason),
+                            ("current player", search.child_players, r.current_players)):
+        assert got.dtype == want.dtype and torch.equal(got[used], want[used]), name
+
+
 def test_refused_calls():
     env, _ = _loaded()
     search, st = _search(env, 4)
