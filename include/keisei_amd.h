@@ -198,6 +198,11 @@ int ka_block_dx(const void* dxc, const void* dout, const void* out, const void* 
  * of 9).  dx is rounded to the activation dtype before it is used: every output equals the two-launch sequence bit for bit.
  * dxc may be NULL; dout_up and out_up are both NULL where the gradient enters the tower from the heads (se_resnet.py:147-157). */
 int ka_block_dx_tail_bwd_supported(int C, int H, int dtype);
+/* The kernel form the board launches take for a shape; launches nothing (the tests assert the form they ran).  kernel 0:
+ * ka_block_tail_fwd / ka_pool_fwd, 1: ka_block_dx, 2: ka_tail_bwd_fused, 3: ka_block_dx_tail_bwd[_du], 4: ..._du_gate (H is read
+ * by 2..4).  0 = not covered; else threads + 1024 * squares per thread + 65536 * flags (1: 16-byte pieces -- clear: channel
+ * pairs, passes in bits 20.. --, 2: FC weights pre-loaded, 4: loads batched when dxc and du_up are given, 8: half-width pieces). */
+int ka_board_form(int kernel, int C, int H, int dtype);
 int ka_block_dx_tail_bwd(const void* dxc, const void* dout_up, const void* out_up, const void* x, const float* xpool,
                          const float* dpool, void* dx, const void* y, const float* scale, const float* shift, const float* se,
                          const float* se1, const float* W2, const float* W1, const float* mean, const float* invstd, void* dz,

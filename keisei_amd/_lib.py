@@ -56,6 +56,7 @@ _SIGS = {
     "ka_relu_bn_bwd_reduce": "pppppp ppp ii i p",
     "ka_block_dx": "pppppp p ii i p",
     "ka_block_dx_tail_bwd_supported": "iii",
+    "ka_board_form": "iiii",
     "ka_block_dx_tail_bwd": "pppppp p ppppppppp p pppp iii i p",
     "ka_block_dx_tail_bwd_du": "ppppp p ppppppppp p pppp iii i p",
     "ka_block_dx_tail_bwd_du_gate": "ppppp p ppppppppp pp pppp iii i p",

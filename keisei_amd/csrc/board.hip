@@ -1550,6 +1550,38 @@ extern "C" int ka_block_dx_tail_bwd_supported(int C, int H, int dtype) {
     return n > 0 && (dtype == KA_DTYPE_F32 ? n <= 11 : n <= 6);
 }
 
+// Which kernel form a launch of this file takes for a shape (read-only: launches nothing; the tests assert the form they ran).
+//   kernel 0: ka_block_tail_fwd / ka_pool_fwd, 1: ka_block_dx, 2: ka_tail_bwd_fused, 3: ka_block_dx_tail_bwd[_du],
+//          4: ka_block_dx_tail_bwd_du_gate (H is read by 2..4 only)
+// 0 = no form covers the shape (the launch returns an error); otherwise threads + 1024 * squares per thread + 65536 * flags with
+//   flags 1: 16-byte pieces (clear: channel pairs, and bits 20.. hold the passes over the channel pairs), 2: FC weights
+//   pre-loaded (clear: rolled loops), 4: loads batched when dxc and du_up are given, 8: half-width pieces (KA_TAIL_GATE_P4).
+extern "C" int ka_board_form(int kernel, int C, int H, int dtype) {
+    if (dtype != KA_DTYPE_BF16 && dtype != KA_DTYPE_F32) return 0;
+    int nt = 0;
+    if (kernel == 0 || kernel == 1) {
+        const int nsq = ka_opt_set(KA_OPT_BOARD_PAIRS) ? 0 : board16_plan(C, dtype, &nt);
+        if (kernel == 1 && nsq > 0) return nt + 1024 * nsq + 65536;
+        if (kernel == 0 && nsq > 0 && nsq <= 11) {
+            const int groups = C / (dtype == KA_DTYPE_BF16 ? 8 : 4), nrow = nt / (groups > 64 ? groups : 64);
+            if ((size_t)4 * nrow * C * sizeof(float) <= 64 * 1024) return nt + 1024 * (nsq <= 6 ? 6 : 11) + 65536;
+        }
+        if (!(C >= 2 && C % 2 == 0 && (C / 2 >= 128 ? (C / 2) % 128 == 0 : 256 / (C / 2) >= 2))) return 0;      // KA_BOARD_CHECK
+        const int pairs = C >> 1, cpw = pairs < 128 ? pairs : 128;
+        int ph = kThreads / cpw; if (ph > KA_BOARD) ph = KA_BOARD;
+        return kThreads + 1024 * ((KA_BOARD + ph - 1) / ph) + (pairs / cpw << 20);
+    }
+    if (kernel < 2 || kernel > 4) return 0;
+    const int nsq = tail_fused_plan(C, H, dtype, &nt);
+    if (nsq <= 0 || nsq > (kernel == 2 || dtype == KA_DTYPE_F32 ? 11 : 6)) return 0;
+    int flags = 1, maxsq = nsq <= 6 ? 6 : 11;
+    if (kernel == 4 && ka_opt(KA_OPT_TAIL_GATE_P4, 1) != 0 && dtype == KA_DTYPE_BF16 && nt == 512 && C % 4 == 0 && C / 4 <= 512 &&
+        512 % (C / 4) == 0 && (KA_BOARD + 512 / (C / 4) - 1) / (512 / (C / 4)) <= 11 && 512 % H == 0) { flags |= 8; maxsq = 11; }
+    if ((2 * C + nt / H - 1) / (nt / H) <= 16 && H <= 16) flags |= 2;
+    if (kernel == 4 && H % 4 == 0) flags |= 4;
+    return nt + 1024 * maxsq + 65536 * flags;
+}
+
 static int tail_bwd_launch(const void* dout, const void* out, const void* y, const float* scale, const float* shift,
                            const float* se, const float* se1, const float* W2, const float* W1, const float* mean,
                            const float* invstd, void* dz, float* dse, float* dh, float* s1p, float* s2p, int B, int C,
@@ -1635,7 +1667,9 @@ extern "C" int ka_block_dx_tail_bwd_du(const void* dxc, const void* du_up, const
 // (board, channel)) has one reader, the conv2 data gradient, whose input transform is already an affine map per channel:
 // ka_conv3x3_dgrad_fused_gated takes du_out, gate_out and add_out instead of dz.  One activation write less per block
 // (4 reads + 1 write); bf16(fmaf(du_out, gate_out, add_out)) is bit for bit the dz of ka_block_dx_tail_bwd_du, and du_out /
-// dse / dh / s1 / s2 are the same bits.
+// dse / dh / s1 / s2 are the same bits.  (With the half-width pieces of KA_TAIL_GATE_P4 -- the default at bf16 C = 256 -- a thread
+// owns other squares, so the per-board sums are taken in another order: du_out is the same bits, dse / dh / s1 / s2 / add are
+// equal to rounding.)
 extern "C" int ka_block_dx_tail_bwd_du_gate(const void* dxc, const void* du_up, const void* x, const float* xpool,
                                             const float* dpool, void* du_out, const void* y, const float* scale,
                                             const float* shift, const float* se, const float* se1, const float* W2,
