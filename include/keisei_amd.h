@@ -1044,6 +1044,54 @@ int ka_mate3_choose(void* records, const void* root_records, int cap, int G, con
                     const void* third_table, const void* child_err, const void* grand_err, const void* third_err,
                     long long* actions, int* stats, int* err, int N, void* stream);
 
+/* ---- perft (csrc/perft.hip; the reference's is shogi-core's, game.rs:1206-1222).  The full-width fork: every legal move of
+ * a frontier of positions becomes a complete env row, the rows are stepped by ka_shogi_env_step as it is, and counted.  The
+ * host walks the tree depth-first over chunks (keisei_amd/perft.py); per chunk, on one stream, kernel launches only,
+ * caller-owned buffers, no workgroup waits for another:
+ *   ka_perft_plan(moves of level k, cursor, ...)             offset[p], header {taken, children, blocking row}; the host
+ *                                                            reads the header
+ *   ka_perft_fork(level k rows [cursor, cursor + taken))     the `children` rows of level k + 1
+ *   ka_shogi_env_step(child_state, child_keys, child_checks, child_actions, children, max_ply, 1, 1, NULL,
+ *                     child_mask_bits, ...)                  writes the children's new masks; its own err and outputs
+ *   ka_perft_tally(level k + 1 rows [0, children))           moves of level k + 1, the counters
+ * This is perft under the env's game rules: a row whose game ended has no successors -- the step has restarted it, so its
+ * state and mask are a fresh game's, and moves[row] = 0 is what keeps it from being forked.
+ * ka_perft_words(which): 0 counter columns per (tag, level) (4: nodes, ended by checkmate, ended otherwise, side to move in
+ *   check), 1 header words (3), 2 the most moves a legal position has (593), 3 the largest cap (2^20), 4 the largest depth
+ *   (8); -1 otherwise.
+ * ka_perft_tally: n rows as a step left them -- state (n, 128), mask_bits (n, legal_words) the NEW packed masks, terminated /
+ *   truncated / reason (n) u8 -- or, with the three NULL, rows nothing ended (the env's own).  tag (n) int32.  Written:
+ *   moves[row] = 0 where terminated | truncated, else the set bits of the mask row below the action space.  With level in
+ *   [0, depth): tally (tags, depth, 4) u64, row [tag][level] gets +1 node per row, +1 in column 1 where the row ended with
+ *   reason checkmate (1), in column 2 where it ended otherwise, in column 3 where byte 96 of its state row (the side to move
+ *   is in check; of the restarted game where the row ended) is set; level -1 counts none of these.  With leaf != 0:
+ *   leaves[tag] (tags) u64 += moves[row].  Atomics, one per run of equal tags in a wave; the caller clears the tables.  A
+ *   tag outside [0, tags) counts nowhere.
+ * ka_perft_plan: one workgroup.  moves (n) int32, negative reads as 0.  taken = the largest t such that the moves of the
+ *   parents [cursor, cursor + t) sum to at most cap; offset[p] = the sum of the moves of [cursor, p) for these parents
+ *   (other entries are not written); header = {taken, children = their sum, s = cursor + taken if s < n and moves[s] > cap,
+ *   else -1}.  A first parent with more than cap moves therefore gives taken = 0 and header[2] = cursor: the caller stops.
+ * ka_perft_fork: one workgroup per parent p in [cursor, cursor + taken), of n parent rows: state / keys / checks as
+ *   ka_mate_fork reads them, mask_bits the parents' current packed masks, moves / offset / tag (n) int32 as tally and plan
+ *   left them.  A parent with moves[p] <= 0 forks nothing.  Otherwise child row c = offset[p] + r for the r-th set bit of
+ *   the mask in ascending action order, r < moves[p]: child_state, child_keys / child_checks (entries [0, ply) of the
+ *   parent's; same row stride), child_mask_bits (the parent's mask: the child step validates against it), child_actions[c]
+ *   = the action, child_tag[c] = tag[p], or divide_base + c when divide_base >= 0 (the child's ordinal: perft_divide's
+ *   first level).  err (1 int32) is ORed, the caller clears it: bit 0 the children of a parent would leave the cap rows
+ *   (nothing of it is written), bit 1 a mask whose set bits are not moves[p] (no row outside offset[p] + [0, moves[p]) is
+ *   written).
+ * Refused: null tensors, another action space or mask width, cap outside [1, 2^20], parents outside [0, n), misaligned rows
+ *   (state, history and mask rows are copied in 16-byte pieces), parent rows that overlap the child rows. */
+int ka_perft_words(int which);
+int ka_perft_tally(const void* state, const void* mask_bits, int legal_words, const void* terminated, const void* truncated,
+                   const void* reason, const int* tag, int n, int level, int depth, int leaf, int tags, int* moves, void* tally,
+                   void* leaves, void* stream);
+int ka_perft_plan(const int* moves, int cursor, int n, int cap, int* offset, int* header, void* stream);
+int ka_perft_fork(const void* state, const void* mask_bits, int legal_words, const void* keys, const void* checks,
+                  const int* moves, const int* offset, const int* tag, int cursor, int taken, int n, int max_ply, int cap,
+                  int divide_base, void* child_state, void* child_keys, void* child_checks, void* child_mask_bits,
+                  long long* child_actions, int* child_tag, int* err, int A, void* stream);
+
 /* ---- SL shard preparation (csrc/sl_prepare.hip; the replay keisei/sl/prepare.py:151-161 leaves out).  A batch of E game
  * records, game g in env g, stepped in lockstep from ka_shogi_env_reset.  One ply = ka_sl_replay_plan, ka_shogi_env_step
  * (unchanged), ka_sl_replay_record on one stream.

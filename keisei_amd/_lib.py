@@ -151,6 +151,10 @@ _SIGS = {
     "ka_mate3_fork": "pi pp i p pp i pppppp ii pppppp ii p",
     "ka_mate3_gate": "p ii pp i pp pp i p",
     "ka_mate3_choose": "pp ii p i pp p i p ppp ppp i p",
+    "ka_perft_words": "i",
+    "ka_perft_tally": "pp i pppp iiiii ppp p",
+    "ka_perft_plan": "p iii pp p",
+    "ka_perft_fork": "pp i pp ppp iiiiii ppppppp i p",
     "ka_sl_replay_state_words": "i",
     "ka_sl_replay_plan": "p i p i p p i pp p",
     "ka_sl_replay_record": "p i ppp i ppppppp p i p",

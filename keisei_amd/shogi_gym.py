@@ -559,6 +559,7 @@ class VecEnv:
         self._err = z(2, dtype=torch.int64)                   # [this step's refusal, the latch raise_if_refused reads and clears]
         self._actions = z(n, dtype=torch.int64)
         self._mate: dict = {}                                 # mate_in_one's / mate_in_three's scratch rows by caps, allocated at the first call
+        self._perft: dict = {}                                # perft's rows by (depth, rows), allocated at the first call
         # start positions (set_start_positions): allocated once, so that a captured graph keeps valid pointers; the
         # header {count, 0, seed lo, seed hi} is read by every launch.  Capacity 0: no pool, the entry points without one.
         self._pool_capacity = int(start_pool_capacity)
@@ -944,6 +945,36 @@ class VecEnv:
         if ms is None:
             raise ValueError(f"mate_in_three({max_checks}, {evasion_rows}, {reply_checks}) has not been called on this env")
         return ms[0].root.records(), ms[0].records()
+
+    def _perft_walk(self, depth, rows):
+        from keisei_amd.perft import PerftWalk, check_perft_args
+        if self._omode != 1 or self._amode != 1:
+            raise ValueError("perft covers the katago observation and the spatial action mode only")
+        key = check_perft_args(depth, rows)
+        walk = self._perft.get(key)
+        if walk is None:                                      # the rows of this (depth, rows), allocated at the first call
+            walk = self._perft[key] = PerftWalk(weakref.proxy(self), *key)
+        return walk
+
+    def perft(self, depth: int, rows: int = 16384, bulk: bool = True):
+        """Count the game tree beneath the N positions now to move, to `depth` (1..8) plies: a `PerftResult` of host
+        `np.uint64` arrays -- `nodes` (N,) the leaves per env, `by_depth` (N, depth, 4) per depth the nodes, the nodes ended
+        by checkmate, the nodes ended otherwise and the nodes whose side to move is in check, `chunks` the number of fork
+        launches.  Every legal move of a frontier of positions is forked into a scratch row and stepped by the env's own
+        step kernel (keisei_amd/perft.py, csrc/perft.hip); a level of the walk holds at most `rows` rows (1..2^20, and at
+        least the most moves any position in the tree has -- 593 always suffices -- or a `ValueError` names the row), so a
+        small `rows` only splits the work into more chunks.  With `bulk=True` the last depth is counted from the masks of
+        the depth before it and carries nodes only (zeros in the other columns); with `bulk=False` it is forked and
+        stepped too.  This is perft under the env's game rules: a position in which the game has ended has no successors
+        (the step restarts such a row).  It equals the move-generation perft of a rules engine (the oracle's `so_perft`)
+        wherever no game in the tree ends other than by checkmate; the "ended otherwise" column says when that fails.  The
+        env is only read.  For katago / spatial envs; any other mode, `depth` or `rows` raises `ValueError`."""
+        return self._perft_walk(depth, rows).perft(int(depth), bool(bulk))
+
+    def perft_divide(self, depth: int, rows: int = 16384) -> List[dict]:
+        """Per env a dict from each legal action to the leaf count beneath it at `depth`: the values of env e sum to
+        `perft(depth).nodes[e]`, which is what narrows a wrong count down to a position.  Arguments and meaning as `perft`."""
+        return self._perft_walk(depth, rows).divide(int(depth))
 
     def get_sfen(self, game_id: int) -> str:
         """vec_env.rs:873-882 / sfen.rs:93-171."""
