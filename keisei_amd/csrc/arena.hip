@@ -14,7 +14,7 @@
 // status bits: 1 = a pairing is seated, 2 = done, 4 = partial (ply ceiling), 8 = stalled (a seated env had no legal action)
 //
 // ka_arena_referee: one workgroup per slot, so the per-slot counters need no atomics.
-#include "common.h"
+#include "rollout_rows.h"
 
 namespace {
 
@@ -35,10 +35,8 @@ __global__ __launch_bounds__(kArenaThreads) void arena_referee_kernel(RefereeArg
     const int e0 = s * a.E, e1 = e0 + a.E;
     int* st = a.state + kHdrWords + s * kSlotWords;
     if (s == 0 && tid == 0) {
-        auto* seed = reinterpret_cast<unsigned long long*>(a.state);
-        *seed += kKaWeyl;                                      // next ply's seed (a Weyl step; the sampler mixes it)
+        ply_tail(a.state, 6, a.refusal);
         a.state[2] += 1;
-        if (a.refusal) *reinterpret_cast<long long*>(a.state + 6) = *a.refusal;
     }
     const int status = st[7];
     if ((status & kSeated) && !(status & kDone)) {              // uniform over the workgroup
@@ -176,17 +174,12 @@ __global__ __launch_bounds__(kArenaThreads) void arena_record_pre_kernel(RecordP
             a.cursors[s * kCursorWords + 2] += max(0, running - room);
         }
     }
-    const int n2 = a.obs_elems >> 1;                           // an observation row is 16 200 bytes: 8-byte vectors
     for (int k = blockIdx.y; k < a.E; k += gridDim.y) {
         const int r = s_rank[k];
         if (r < 0 || r >= room) continue;
         const size_t row = (size_t)s * a.cap + first + r, e = (size_t)(e0 + k);
-        const float2* src = reinterpret_cast<const float2*>(a.obs + e * a.obs_elems);
-        float2* dst = reinterpret_cast<float2*>(a.st_obs + row * a.obs_elems);
-        for (int i = tid; i < n2; i += kArenaThreads) dst[i] = src[i];
-        const uint32_t* ms = a.mask + e * a.mask_words;
-        uint32_t* md = a.st_mask + row * a.mask_words;
-        for (int i = tid; i < a.mask_words; i += kArenaThreads) md[i] = ms[i];
+        // (the launcher holds the rows to an even length and 8-byte alignment, so the copy goes in 8-byte vectors)
+        copy_transition<kArenaThreads>(a.st_obs, a.st_mask, row, a.obs, a.mask, e, a.obs_elems, a.mask_words);
         if (tid == 0) {
             a.st_actions[row] = a.actions[e];
             a.st_persp[row] = a.pre_player[e];
@@ -330,7 +323,7 @@ __global__ void dynamic_targets_kernel(const float* rewards, const float* dones,
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float r = rewards[i], d = dones[i];
-    long long c = -1;
+    long long c = -1;                                          // (rollout_rows.h's label gives a NaN reward 3; here it is -1)
     if (d != 0.f) c = r > 0.f ? 0 : (r == 0.f ? 1 : (r < 0.f ? 2 : -1));
     cats[i] = c;
     adv[i] = r * d;

@@ -226,8 +226,10 @@ __device__ __forceinline__ unsigned long long ka_mix64(unsigned long long x) {
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // The rollout's scalar value (katago_ppo.py:536-541 / value_adapter.py:56-65): P(W) - P(L) of the three value logits at
-// vl, blended with clamp(score_lead, -1, 1) by alpha when there is a score.  ONE body for ka_policy_sample,
-// ka_scalar_value, ka_league_step and ka_selfplay_step: the rows of a rollout and the sampler's values agree bit for bit.
+// vl, blended with clamp(score_lead, -1, 1) by alpha when there is a score.  ONE body for ka_policy_sample and
+// ka_policy_sample_play (loss.hip's policy_sample_kernel), ka_scalar_value and the plan kernels of ka_league_step and
+// ka_selfplay_step, which hand it to rollout_rows.h's write_row: the rows of a rollout and the sampler's values agree bit
+// for bit.
 __device__ __forceinline__ float ka_blended_value(const float* vl, const float* score, float alpha) {
     const float l0 = vl[0], l1 = vl[1], l2 = vl[2];
     const float m = fmaxf(l0, fmaxf(l1, l2));
@@ -251,7 +253,8 @@ __device__ __forceinline__ int ka_wave_scan(int v) {
 // Ranks of the flagged threads of one 256-thread tile, in thread order, behind the `running` flagged threads of the tiles
 // before it: *rank = running + (flagged threads below this one), -1 for a thread that is not flagged.  Returns the tile's
 // count.  One ballot per wave and a sum over the four waves (wsum: 4 ints of LDS): no atomics, so the order is the thread
-// order.  Every thread of the workgroup calls it.  Shared by the arena's record_pre / features_step and the league's plan.
+// order.  Every thread of the workgroup calls it.  Shared by the arena's record_pre / features_step, the league's and the
+// self-play step's plan kernels and the game log's step.
 __device__ __forceinline__ int ka_tile_rank(bool want, int running, int* wsum, int* rank) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned long long b = __ballot(want);

@@ -14,20 +14,11 @@
 //                       slot).
 // No atomics anywhere: counters are block sums, ranks are ballot scans in thread order.
 //
-// State: ka_league_state_words(K) int32, read by the host in one copy.
-//   0-1   seed (int64) ka_policy_sample_play reads this ply; advanced by a Weyl step per ply
+// State: ka_league_state_words(K) int32, read by the host in one copy.  The words shared with the self-play step are
+// tabulated in rollout_rows.h (the tallies are in the learner's frame); the league's own:
 //   2     plies stepped since the last reset
-//   3     rows written behind the descriptor's base row (a collect's rows so far)
 //   4     non-empty blocks written (the reference's add() calls)
-//   5     rows that did not fit the reserved capacity
-//   6-7   the sampler's flags [NaN logits, a row without a legal action]
-//   8-9   copy of the VecEnv refusal latch (int64)
 //   10-11 draw seed (int64), fixed between resets
-//   12    truncation slots used since the host last cleared it
-//   13    truncation records that found no slot
-//   14-20 wins, losses, draws (learner frame), black wins, white wins, terminated, truncated-only
-//   21-24 the rollout store's input guards over the rows written: terminated without done, value category outside
-//         {-1, 0, 1, 2}, NaN score target, bits of max |score target|  (ka_rollout_append's four flags)
 //   25    a pending slot was opened while still taken
 //   26    bit 0: a learner row had no legal action, bit 1: an opponent row (the envs are latched in `stall`)
 //   27-31 unused
@@ -38,16 +29,13 @@
 //   opponent = first k with (h(0x6F70706F, env, n) >> 33) < cum[k]   (cum: K uint32 thresholds on a 31-bit scale, the last 2^31)
 //   side     = h(0x73696465, env, n) >> 63
 // A function of (seed, env, n) alone: the same whatever sync_every, graph capture or launch geometry.
-#include "common.h"
+#include "rollout_rows.h"
 
 namespace {
 
 constexpr int kLgThreads = 256;
-constexpr int kLgHdr = 32, kLgPlan = 6, kLgDesc = 14;
-constexpr int kLgMaxEnvs = 4096;
-enum { kSeed = 0, kPly = 2, kRows = 3, kBlocks = 4, kDropped = 5, kSamp = 6, kRefusal = 8, kDrawSeed = 10, kTrunc = 12,
-       kTruncDropped = 13, kWins = 14, kLosses = 15, kDraws = 16, kBlack = 17, kWhite = 18, kTerminated = 19,
-       kTruncated = 20, kGuards = 21, kConflict = 25, kStall = 26 };
+constexpr int kLgHdr = 32, kLgPlan = 6;
+enum { kPly = 2, kBlocks = 4, kDrawSeed = 10, kConflict = 25, kStall = 26 };      // the league's own state words
 // pending scalars: kPendCols columns of E words {action, log-prob, value, reward, score target, valid}
 enum { kPAction = 0, kPLogp = 1, kPValue = 2, kPReward = 3, kPScore = 4, kPValid = 5, kPendCols = 6 };
 constexpr unsigned long long kSaltOpp = 0x6F70706Full, kSaltSide = 0x73696465ull;
@@ -75,38 +63,6 @@ struct LeagueArgs {
                                                //      either, keep-pending flag, unused}: store rows are absolute, -1 = none
     int obs_elems, words;
 };
-
-struct Columns {
-    float* obs; uint32_t* bits; long long* actions; float* logp; float* values; float* rewards; uint8_t* dones;
-    uint8_t* terminated; long long* cats; float* score; long long* env_ids; float* override_;
-    long long base, cap;
-};
-__device__ __forceinline__ Columns load_columns(const long long* d) {
-    Columns c;
-    c.obs = reinterpret_cast<float*>(d[0]); c.bits = reinterpret_cast<uint32_t*>(d[1]);
-    c.actions = reinterpret_cast<long long*>(d[2]); c.logp = reinterpret_cast<float*>(d[3]);
-    c.values = reinterpret_cast<float*>(d[4]); c.rewards = reinterpret_cast<float*>(d[5]);
-    c.dones = reinterpret_cast<uint8_t*>(d[6]); c.terminated = reinterpret_cast<uint8_t*>(d[7]);
-    c.cats = reinterpret_cast<long long*>(d[8]); c.score = reinterpret_cast<float*>(d[9]);
-    c.env_ids = reinterpret_cast<long long*>(d[10]); c.override_ = reinterpret_cast<float*>(d[11]);
-    c.base = d[12]; c.cap = d[13];
-    return c;
-}
-
-struct RowGuards { int term_not_done, bad_cat, nan_score, peak; };
-
-// one settled transition's scalar columns (katago_loop.py:1299-1316 / :1347-1365; label: _compute_value_cats, :75-92)
-__device__ __forceinline__ void write_row(const Columns& c, long long row, int env, long long action, float logp, float value,
-                                          float reward, bool done, bool term, float score, bool label, RowGuards* g) {
-    const long long cat = (!label || !term) ? -1 : (reward > 0.f ? 0 : (reward == 0.f ? 1 : (reward < 0.f ? 2 : 3)));
-    c.actions[row] = action; c.logp[row] = logp; c.values[row] = value; c.rewards[row] = reward;
-    c.dones[row] = done; c.terminated[row] = term; c.cats[row] = cat; c.score[row] = score; c.env_ids[row] = env;
-    c.override_[row] = __uint_as_float(0x7fc00000u);           // NaN: the host fills the truncated rows at the sync point
-    g->term_not_done |= term && !done;
-    g->bad_cat |= cat < -1 || cat > 2;
-    if (score != score) g->nan_score = 1;
-    else g->peak = max(g->peak, __float_as_int(fabsf(score)));
-}
 
 __global__ __launch_bounds__(kLgThreads) void league_plan_kernel(LeagueArgs a) {
     extern __shared__ short s_code[];                          // E: opponent * 3 + outcome of a terminated game, -1 = none
@@ -151,8 +107,8 @@ __global__ __launch_bounds__(kLgThreads) void league_plan_kernel(LeagueArgs a) {
     nt1 = ka_block_sum<kLgThreads>(nt1, red);
 
     int run1 = 0, run2 = 0, runt1 = 0, runt2 = 0;
-    int wins = 0, losses = 0, draws = 0, black = 0, white = 0, nterm = 0, ntrunc = 0, conflicts = 0, stall = 0;
-    int dropped = 0, tdropped = 0;
+    int conflicts = 0, stall = 0, dropped = 0, tdropped = 0;
+    Tallies tl{};
     RowGuards g{0, 0, 0, 0};
     for (int base = 0; base < E; base += kLgThreads) {
         const int k = base + tid;
@@ -175,12 +131,7 @@ __global__ __launch_bounds__(kLgThreads) void league_plan_kernel(LeagueArgs a) {
         int ts1 = -1, ts2 = -1;
         // 1. tallies (:1219-1248)
         if (step) {
-            nterm += tm; ntrunc += trunc_only;
-            if (tm) {
-                wins += lr > 0.f; losses += lr < 0.f; draws += lr == 0.f;
-                black += (r > 0.f && pre == 0) || (r < 0.f && pre == 1);
-                white += (r > 0.f && pre == 1) || (r < 0.f && pre == 0);
-            }
+            tally_add(tl, tm, trunc_only, lr, r, pre);
             conflicts += conflict;
             if (a.nlegal[k] == 0) { const int bit = lm ? 1 : 2; stall |= bit; a.stall[k] |= bit; }
         }
@@ -262,13 +213,9 @@ __global__ __launch_bounds__(kLgThreads) void league_plan_kernel(LeagueArgs a) {
         a.model_of[k] = (a.players[k] & 1) == sd ? 0 : o + 1;
     }
     constexpr int T = kLgThreads;
-    wins = ka_block_sum<T>(wins, red); losses = ka_block_sum<T>(losses, red); draws = ka_block_sum<T>(draws, red);
-    black = ka_block_sum<T>(black, red); white = ka_block_sum<T>(white, red);
-    nterm = ka_block_sum<T>(nterm, red); ntrunc = ka_block_sum<T>(ntrunc, red);
+    commit_tallies_and_guards<T>(tl, g, st, red);              // (a flush tallies nothing: it adds zeros)
     conflicts = ka_block_sum<T>(conflicts, red); stall = ka_block_max<T>(stall & 1, red) | (ka_block_max<T>(stall & 2, red));
     dropped = ka_block_sum<T>(dropped, red); tdropped = ka_block_sum<T>(tdropped, red);
-    const int g0 = ka_block_max<T>(g.term_not_done, red), g1 = ka_block_max<T>(g.bad_cat, red), g2 = ka_block_max<T>(g.nan_score, red);
-    const int g3 = ka_block_max<T>(g.peak, red);
     if (tid == 0) {
         const int offered = run1 + run2;
         st[kRows] = first + (int)min((long long)offered, room);
@@ -276,15 +223,9 @@ __global__ __launch_bounds__(kLgThreads) void league_plan_kernel(LeagueArgs a) {
         st[kDropped] += dropped;
         st[kTrunc] = min(E, tfirst + runt1 + runt2);
         st[kTruncDropped] += tdropped;
-        st[kGuards + 0] |= g0; st[kGuards + 1] |= g1; st[kGuards + 2] |= g2;
-        st[kGuards + 3] = max(st[kGuards + 3], g3);
         if (step) {
-            auto* seed = reinterpret_cast<unsigned long long*>(st);
-            *seed += kKaWeyl;                                  // next ply's sampler seed, as the arena's referee steps it
+            ply_tail(st, kRefusal, a.refusal);
             st[kPly] += 1;
-            if (a.refusal) *reinterpret_cast<long long*>(st + kRefusal) = *a.refusal;
-            st[kWins] += wins; st[kLosses] += losses; st[kDraws] += draws; st[kBlack] += black; st[kWhite] += white;
-            st[kTerminated] += nterm; st[kTruncated] += ntrunc;
             st[kConflict] |= conflicts > 0; st[kStall] |= stall;
         }
     }
@@ -308,21 +249,15 @@ __global__ __launch_bounds__(kLgThreads) void league_copy_kernel(LeagueArgs a) {
     const int row1 = plan[0], row2 = plan[1], ts1 = plan[2], ts2 = plan[3], keep = plan[4];
     if (row1 < 0 && row2 < 0 && !keep) return;                  // (a truncation slot always comes with a row)
     const Columns c = load_columns(a.desc);
-    const size_t n = a.obs_elems, w = a.words;
-    if (row1 >= 0) {                                            // the pending slot leaves before this ply's move takes it
-        ka_copy_row<kLgThreads>(c.obs + row1 * n, a.p_obs + e * n, a.obs_elems, tid);
-        for (int i = tid; i < a.words; i += kLgThreads) c.bits[row1 * w + i] = a.p_bits[e * w + i];
-    }
+    const size_t n = a.obs_elems;
+    // the pending slot leaves before this ply's move takes it
+    if (row1 >= 0) copy_transition<kLgThreads>(c.obs, c.bits, row1, a.p_obs, a.p_bits, e, a.obs_elems, a.words);
     if (ts1 >= 0) ka_copy_row<kLgThreads>(a.t_obs + ts1 * n, a.term_obs + e * n, a.obs_elems, tid);
     if (ts2 >= 0) ka_copy_row<kLgThreads>(a.t_obs + ts2 * n, a.term_obs + e * n, a.obs_elems, tid);
-    if (row2 >= 0) {
-        ka_copy_row<kLgThreads>(c.obs + row2 * n, a.obs + e * n, a.obs_elems, tid);
-        for (int i = tid; i < a.words; i += kLgThreads) c.bits[row2 * w + i] = a.bits[e * w + i];
-    }
+    if (row2 >= 0) copy_transition<kLgThreads>(c.obs, c.bits, row2, a.obs, a.bits, e, a.obs_elems, a.words);
     if (keep) {
         __syncthreads();                                        // row1's reads of the slot are done
-        ka_copy_row<kLgThreads>(a.p_obs + e * n, a.obs + e * n, a.obs_elems, tid);
-        for (int i = tid; i < a.words; i += kLgThreads) a.p_bits[e * w + i] = a.bits[e * w + i];
+        copy_transition<kLgThreads>(a.p_obs, a.p_bits, e, a.obs, a.bits, e, a.obs_elems, a.words);
     }
 }
 
@@ -332,7 +267,7 @@ extern "C" int ka_league_state_words(int opponents) { return opponents < 0 ? -1 
 // which: 0 = int32 words of one env's plan, 1 = int64 words of the store descriptor, 2 = int32 words of one env's pending
 // scalars, 3 = int32 words of one truncation record, 4 = the largest number of envs
 extern "C" int ka_league_layout(int which) {
-    return which == 0 ? kLgPlan : which == 1 ? kLgDesc : which == 2 ? kPendCols : which == 3 ? 3 : which == 4 ? kLgMaxEnvs : -1;
+    return which == 0 ? kLgPlan : which == 1 ? kRolloutDesc : which == 2 ? kPendCols : which == 3 ? 3 : which == 4 ? kRolloutMaxEnvs : -1;
 }
 
 extern "C" int ka_league_step(int* state, int envs, int opponents, int flush, const float* obs, const void* mask_bits,
@@ -344,14 +279,12 @@ extern "C" int ka_league_step(int* state, int envs, int opponents, int flush, co
                               float* p_obs, void* p_bits, int* p_scal, float* t_obs, int* t_list, const long long* desc,
                               int* plan, int obs_elems, int mask_words, void* stream) {
     KA_REQUIRE(state && p_obs && p_bits && p_scal && desc && plan, "league_step: null state, pending slots, descriptor or plan");
-    KA_REQUIRE(envs > 0 && envs <= kLgMaxEnvs, "league_step: envs %d (1..%d)", envs, kLgMaxEnvs);
-    KA_REQUIRE(obs_elems > 0 && mask_words > 0, "league_step: obs_elems %d, mask_words %d", obs_elems, mask_words);
+    KA_REQUIRE_ROLLOUT_STEP("league_step", envs, obs_elems, mask_words, flush ? 1.f : score_norm);     // a flush reads no score_norm
     if (!flush) {
         KA_REQUIRE(obs && mask_bits && actions && logp && vlogits && nlegal && pre_player && rewards && terminated &&
                    truncated && players && material && term_obs && side && opp && games && cum && model_of && stall &&
                    values && t_obs && t_list, "league_step: null tensor");
         KA_REQUIRE(opponents > 0 && opponents <= 10000, "league_step: opponents %d (1..10000)", opponents);
-        KA_REQUIRE(score_norm == score_norm && score_norm != 0.f, "league_step: score_norm %f", (double)score_norm);
     }
     LeagueArgs a{state, envs, opponents, flush ? 1 : 0, obs, static_cast<const uint32_t*>(mask_bits), actions, logp, vlogits,
                  score_lead, alpha, nlegal, static_cast<const uint8_t*>(pre_player), rewards,

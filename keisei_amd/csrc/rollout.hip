@@ -201,6 +201,7 @@ __global__ __launch_bounds__(256) void pending_settle_kernel(PendingArgs a) {
         a.o_dones[row] = dn ? 1.f : 0.f; a.o_terminated[row] = tm ? 1.f : 0.f;
         a.o_env_ids[row] = g;
         // value-head label of the settled transition (katago_loop.py:75-92): only genuinely terminal positions get one
+        // (rollout_rows.h's label gives a NaN reward 3; here it is 2)
         a.o_cats[row] = !tm ? -1 : (rw > 0.f ? 0 : (rw == 0.f ? 1 : 2));
         a.valid_out[g] = 0; a.rewards[g] = 0.f;
     }

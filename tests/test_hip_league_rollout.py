@@ -144,7 +144,7 @@ class _Rig:
         self.stall = torch.zeros(E, dtype=torch.uint8, device=DEV)
         self.values = torch.zeros(E, device=DEV)
 
-    def step(self, rec, flush=0):
+    def step(self, rec, flush=0, nlegal=None):
         E = self.E
         d = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(DEV)  # noqa: E731
         if flush:
@@ -153,7 +153,7 @@ class _Rig:
             bits = torch.zeros(E, self.words, dtype=torch.int32, device=DEV)
             _lib.call("ka_pack_mask_bits", d(rec["legal_masks"]), bits, E, SMALL_A, _stream())
             self.keep = [d(rec[k]) for k in ("obs", "actions", "log_probs", "vlogits", "score_lead")]
-            self.keep += [bits, torch.ones(E, dtype=torch.int32, device=DEV)]
+            self.keep += [bits, torch.ones(E, dtype=torch.int32, device=DEV) if nlegal is None else d(nlegal)]
             self.keep += [d(rec[k]) for k in ("pre_players", "rewards", "terminated", "truncated", "current_players", "material", "term_obs")]
             o, a, lp, vl, sc, bits, nl, pre, rw, tm, tr, cur, mat, tob = self.keep
             args = [o, bits, a, lp, vl, sc if self.alpha else None, self.alpha, nl, pre, rw, tm, tr, cur, mat, self.score_norm, tob,
@@ -274,6 +274,45 @@ def test_league_step_odd_row_length_no_blend_fixed_colour():
 def test_league_step_writes_nothing_past_the_reserved_rows():
     _run_kernel_case(64, 2, cap=37)
     _run_kernel_case(300, 1, cap=5)
+
+
+def test_league_step_raises_the_input_guards_and_the_zero_legal_latches():
+    """the twin of the self-play step's test, on the league's three ways to a row.  Fixed colour, so the learner is player 0.
+    Ply 0, every env a learner move: env 3 terminates with a NaN reward, a label outside {-1, 0, 1, 2} on its immediate row;
+    env 0 has no legal action (a learner row).  Ply 1, the opponent's reply in envs 0, 1, 2, 4 settles their rows; env 2 has
+    no legal action (an opponent row); env 3, a new game, opens a slot with a material beyond 3.5 score_norm, and the flush
+    settles it: the peak word shows that the flush reaches the same commit."""
+    E, norm = 5, 76.0
+    p0, p1 = _facts(E, 2, 11, SMALL_OBS)
+    calm = dict(rewards=np.zeros(E, np.float32), terminated=np.zeros(E, bool), truncated=np.zeros(E, bool))
+    p0.update({k: v.copy() for k, v in calm.items()}, pre_players=np.zeros(E, np.uint8),
+              current_players=np.array([1, 1, 1, 0, 1], np.uint8))
+    p0["terminated"][3], p0["rewards"][3] = True, np.nan
+    p1.update({k: v.copy() for k, v in calm.items()}, pre_players=p0["current_players"].copy(),
+              current_players=np.array([0, 0, 0, 1, 0], np.uint8))
+    p1["material"][3] = 400
+    rig = _Rig(E, 1, SMALL_OBS, 8, 77, cum_thresholds(None, 1), np.zeros(E, np.uint8), np.zeros(E, np.int32), False, 0.25, norm)
+    peak = lambda st: float(st[24:25].view(np.float32)[0])  # noqa: E731
+    score = lambda m: np.float32(m) / np.float32(norm)  # noqa: E731
+
+    rig.step(p0, nlegal=np.array([0, 1, 1, 1, 1], np.int32))
+    st = rig.state.cpu().numpy()
+    assert int(st[_ROWS]) == 1 and int(rig.cols["value_categories"][0]) == 3 and int(rig.cols["env_ids"][0]) == 3
+    assert st[21] == 0 and st[22] == 1 and st[23] == 0 and peak(st) == abs(score(p0["material"][3]))
+    assert st[26] == 1 and rig.stall.tolist() == [1, 0, 0, 0, 0]
+
+    rig.step(p1, nlegal=np.array([1, 1, 0, 1, 1], np.int32))
+    st = rig.state.cpu().numpy()
+    assert int(st[_ROWS]) == 5 and rig.cols["env_ids"][1:5].tolist() == [0, 1, 2, 4]
+    assert st[21] == 0 and st[22] == 1 and st[23] == 0 and peak(st) == score(np.abs(p0["material"]).max())
+    assert st[25] == 0 and st[26] == 3 and rig.stall.tolist() == [1, 0, 2, 0, 0]
+
+    rig.step(None, flush=1)
+    st = rig.state.cpu().numpy()
+    assert int(st[_ROWS]) == 6 and int(rig.cols["env_ids"][5]) == 3 and int(rig.cols["value_categories"][5]) == -1
+    assert st[21] == 0 and st[22] == 1 and st[23] == 0 and peak(st) == score(400)
+    assert st[25] == 0 and st[26] == 3 and rig.stall.tolist() == [1, 0, 2, 0, 0]      # latches: the flush clears neither
+    rig.guards_intact(6)
 
 
 # ------------------------------------------------------------------ whole epochs
