@@ -1874,6 +1874,11 @@ int conv_dispatch(ConvArgs a, hipStream_t st) {
     // tuning overrides (experiments only): channels per LDS chunk, n-tiles per wave
     if (const int v = ka_opt(KA_OPT_CONV_KC, 0); v > 0 && a.Cin % v == 0 && v % CPK == 0 && v <= kc) kc = v;
     if (const int v = ka_opt(KA_OPT_CONV_NTW, 0); v == 1 || v == 2 || v == 4) ntw = v;
+    // an odd number of 16-channel tiles (Cout = 80, 144, ...) leaves the last tile without a partner, and the bf16 epilogue of two or
+    // more tiles per wave works on tile PAIRS: its 16-byte store (and the masked form's 16-byte y read and 8 coefficients) of the lone
+    // tile ran 4 channels past the row's end -- into the next square, past the tensor behind the last one -- and its lanes
+    // overlapped.  One tile per wave has 8-byte pieces of a single tile; the fp32 epilogue is per tile anyway.
+    if (E::kSize == 2 && ((a.Cout >> 4) & 1)) ntw = 1;
     a.tune_stagger = ka_opt(KA_OPT_CONV_STAGGER, a.tune_stagger);
     a.tune_prio = ka_opt(KA_OPT_CONV_PRIO, a.tune_prio);
     KA_REQUIRE(256 % (kc * E::kSize / 16) == 0, "conv3x3: chunk of %d channels does not tile the workgroup", kc);
