@@ -940,6 +940,49 @@ int ka_search_advance(void* records, void* tree, int width, int expansions, int 
                       const void* pool_truncated, const void* step_err, long long* actions, int* parent_row, int* active,
                       int* pv, int* stats, int* err, int N, void* stream);
 
+/* ---- visit-count (PUCT) search (csrc/mcts.hip), in the place of the lookahead or the tree search in the ply.  The node
+ * pool, its slices, the records and every stage that moves rows are the tree search's; the tree policy is new.  Per ply:
+ *   ka_lookahead_fork, step and forward over slice 0, ka_mcts_advance(t = 0)
+ *   for t = 1 .. simulations - 1:  ka_search_expand(t), step and forward over slice t, ka_mcts_advance(t)
+ * table: K x 4 words, row m for model m: int32 width (0..8, 0 = off), fp32 c_puct (finite, >= 0), int32 skip_plies, int32
+ *   simulations (1..64; a word outside reads as 1; a value above the launch's is cut to it).  Words 0-2 are read as
+ *   ka_lookahead_fork reads them and an env is active by its rule.
+ * Node (t, j) is candidate j of simulation t, local node t * width + j, pool row (t * N + e) * width + j.  Per node: N
+ *   (int32 visits), S (fp32 value sum for the player who moved into the node), P (fp32, the prior the fork that created the
+ *   node wrote: priors are used at every depth), by (the simulation that forked it, -1 = never).  Per simulation: parent,
+ *   the local node it selected (-1: simulation 0, or it did not run).  The root holds no statistics.
+ * q(t, j) is the tree search's leaf value (the step's reward where the game ended there, else P(L) - P(W) of the value
+ *   head); a non-finite value logit of a live node is err bit 0 and its q is 0, in the record and in every sum.
+ * Simulation 0 is the lookahead's fork: every child gets N = 1, S = q.
+ * Selection of simulation t >= 1 (t < simulations_m), from the root: at a node with children k, Npar = sum_k N_k,
+ *   s_k = S_k / N_k, plus c * P_k * sqrtf(Npar) / (1 + N_k) when c > 0, all fp32 in that written order; the first maximum
+ *   is chosen (ties keep the lower slot) and written as slot and action of the record whose candidates the children are.
+ *   A chosen child that is live and was never forked is the leaf: it forks into slice t through ka_search_expand
+ *   (by = t).  A chosen child that is done, or was forked without a candidate, is a revisit: nothing forks (active = 0).
+ * Backup of simulation t, after its forward: every new child gets N = 1, S = q_k; v = max_k q_k, the first maximum; the
+ *   leaf gets N += 1, S += 0 - v, its parent N += 1, S += v, the signs alternating up to the root's child.  A revisit -- and
+ *   a fork that found no candidate -- adds the node's own q to it instead, the signs alternating above it.  One thread adds,
+ *   in simulation order.
+ * Choice, in the last launch: the root candidate of most visits (ties keep the lower slot: the higher logit) replaces
+ *   actions[e]; flag bit 3 = it differs from the arg-max of q(0, j).  pv (N, simulations) int32: the chosen action, then
+ *   the most visited child at each level (ties the lower slot) down to the first node never forked or done, padded with
+ *   -1.  root_visits (N, width) int32 and root_values (N, width) fp32 (S / N, 0 for an unused slot or an inactive env).
+ * Tree of an env, ka_mcts_words(1, ..) = E + 4 E width words: parent[E], N[E * width], S[E * width], P[E * width],
+ *   by[E * width].
+ * ka_mcts_words(which, width, simulations): 0 record words, 1 tree words per env, 2 stats words (6: positions searched,
+ *   choices that differ from the sampler's, chosen moves that won, choices that differ from the one-ply choice, simulations
+ *   run and revisits, both summed over the envs), 3 the maximum width (8), 4 the maximum simulations (64), 5 table words per
+ *   model; else -1.
+ * ka_mcts_advance: one thread per env after the forward of simulation t, in this order: leaf q of slice t, backup,
+ *   selection for t + 1 (parent_row / active for ka_search_expand), and at t = simulations - 1 the choice.  step_err:
+ *   (simulations, 2) 64-bit words, the error words of every slice's step; a non-zero word of slices 0..t is err bit 1, and
+ *   then nothing is selected, chosen or replaced.  stats is added to with atomics, err is ORed; the caller clears both. */
+int ka_mcts_words(int which, int width, int simulations);
+int ka_mcts_advance(void* records, void* tree, int width, int simulations, int t, const void* table, const int* model_of,
+                    int K, const float* pool_vlogits, const float* pool_rewards, const void* pool_terminated,
+                    const void* pool_truncated, const void* step_err, long long* actions, int* parent_row, int* active,
+                    int* pv, int* root_visits, float* root_values, int* stats, int* err, int N, void* stream);
+
 /* ---- mate in one (csrc/mate.hip; the reference never searches).  A rules-only mate check inside the ply, behind the
  * lookahead or the search and before the insight, per model: fork the env rows into one child row per checking move, step
  * the children with ka_shogi_env_step as it is, and play a child that ended by checkmate.  No forward runs.  Three stages on

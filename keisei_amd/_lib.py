@@ -144,6 +144,8 @@ _SIGS = {
     "ka_search_words": "iii",
     "ka_search_expand": "pi pi pi p ppp pp iii pp p pppp pp ii p",
     "ka_search_advance": "pp iii pp i pppp p pppp pp i p",
+    "ka_mcts_words": "iii",
+    "ka_mcts_advance": "pp iii pp i pppp p pppp pp pp i p",
     "ka_mate_words": "ii",
     "ka_mate_fork": "pi pp i p ppp ii p pppp p ii p",
     "ka_mate_choose": "pi pppp ppp i p",

@@ -50,18 +50,14 @@
 //
 //   ka_search_expand      the fork kernel with a row of the pool as "env", named per env by parent_row / active
 //   ka_search_advance     one thread per env: leaf q, the backup by max and negation, the next leaf, at the end the choice
-#include "ply_rows.h"
+#include "lookahead_record.h"
 
 #include <climits>
 
 namespace {
 
 constexpr int kLaThreads = 256, kLaWaves = kLaThreads / 64;
-constexpr int kLaMaxWidth = 8;
-constexpr int kLaFlags = 0, kLaSlot = 1, kLaNCand = 2, kLaAction = 3, kLaCand = 4;
-constexpr int kLaTableWords = 4, kLaStatsWords = 4;
-
-__host__ __device__ constexpr int la_words(int width) { return kLaCand + 3 * width; }
+constexpr int kLaStatsWords = 4;
 
 struct ForkArgs {
     const void* logits; int logits_bf16; const uint32_t* legal; const long long* actions; const int* model_of; int K;
@@ -114,18 +110,6 @@ __device__ __forceinline__ void la_for_legal(const uint32_t* msk, F f) {
 // (v, i) comes before (bv, bi) in the candidate order: greater logit, equal logits by lower action
 __device__ __forceinline__ bool la_before(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
-// the controls of model m as the kernels read them: the width (0 = off) and the prior weight
-__device__ __forceinline__ int la_controls(const uint32_t* table, int m, int K, float* pw, int* skip) {
-    *pw = 0.f; *skip = 0;
-    if (m < 0 || m >= K) return 0;
-    const uint32_t* c = table + (size_t)m * kLaTableWords;
-    const int w = (int)c[0], s = (int)c[2];
-    const float p = __uint_as_float(c[1]);
-    if (!(w >= 0 && w <= kLaMaxWidth && p >= 0.f && p <= 3.0e38f && s >= 0)) return 0;
-    *pw = p; *skip = s;
-    return w;
-}
-
 // the reply width of model m: word 3 of a row that is on; a word outside [0, 8] reads as 0
 __device__ __forceinline__ int la_reply_width(const uint32_t* table, int m, int K) {
     float pw;
@@ -133,15 +117,6 @@ __device__ __forceinline__ int la_reply_width(const uint32_t* table, int m, int 
     if (la_controls(table, m, K, &pw, &skip) <= 0) return 0;
     const int r = (int)table[(size_t)m * kLaTableWords + 3];
     return r >= 0 && r <= kLaMaxWidth ? r : 0;
-}
-
-// P(L) - P(W) of the value logits of row c; a non-finite logit sets *bad
-__device__ __forceinline__ float la_loss_minus_win(const float* vl, size_t c, bool* bad) {
-    const float l0 = vl[c * 3], l1 = vl[c * 3 + 1], l2 = vl[c * 3 + 2];
-    const float mx = fmaxf(l0, fmaxf(l1, l2));
-    const float e0 = expf(l0 - mx), e1 = expf(l1 - mx), e2 = expf(l2 - mx);
-    *bad = !(fabsf(l0) <= 3.4e38f && fabsf(l1) <= 3.4e38f && fabsf(l2) <= 3.4e38f);
-    return (e2 - e0) / (e0 + e1 + e2);
 }
 
 // kReply = false: the envs fork into their children.  kReply = true: the "envs" are the child rows after their step -- a done
@@ -667,7 +642,7 @@ extern "C" int ka_search_expand(const void* pool_logits, int logits_bf16, const 
                node_mask_bits && node_actions && node_model_of && N > 0, "search_expand: null tensor");
     KA_REQUIRE_PLY_SPACE("search_expand", A, legal_words);
     KA_REQUIRE(width >= 1 && width <= kLaMaxWidth, "search_expand: width must lie in [1, %d], got %d", kLaMaxWidth, width);
-    KA_REQUIRE(t >= 1 && t < kLaMaxExpansions, "search_expand: the expansion must lie in [1, %d), got %d", kLaMaxExpansions, t);
+    KA_REQUIRE(t >= 1 && t < kPoolMaxSlices, "search_expand: the expansion must lie in [1, %d), got %d", kPoolMaxSlices, t);
     KA_REQUIRE(K >= 1, "search_expand: the controls table needs at least one row, got K = %d", K);
     KA_REQUIRE_MAX_PLY("search_expand", max_ply);
     KA_REQUIRE((long long)N * width * (t + 1) <= INT_MAX, "search_expand: %d envs of width %d are too many rows at expansion %d", N,

@@ -25,6 +25,7 @@ from .game_log import GameLog, RecordedGame
 from .katago_ppo import KataGoRolloutBuffer, _check_step_inputs
 from .lookahead import Lookahead
 from .mate_search import Mate3Search, MateSearch, mate3_reply_table
+from .mcts_search import MctsSearch
 from .policy_insight import InsightRecorder
 from .sampling import GAME_PLY_BYTE
 from .tree_search import TreeSearch
@@ -86,8 +87,9 @@ class DevicePly:
     candidates.  ``controls`` (a table of ``sampling.py``) puts ``ka_policy_sample_ctl`` in the place of
     ``ka_policy_sample_play``; ``lookahead_table`` / ``lookahead_width`` (``lookahead.py``) add the one-ply value lookahead
     between the sampler and the insight, ``lookahead_reply_width > 0`` its reply search (three more stages).  ``search_table`` / ``search_width`` /
-    ``search_expansions`` (``tree_search.py``) put the tree search where the lookahead stands (not both).  ``mate_table`` /
-    ``mate_cap`` (``mate_search.py``) add the mate-in-one check behind the lookahead or the search and before the insight
+    ``search_expansions`` (``tree_search.py``) put the tree search where the lookahead stands (not both); ``mcts_table`` /
+    ``mcts_width`` / ``mcts_simulations`` (``mcts_search.py``) put the visit-count search there (none of the others).
+    ``mate_table`` / ``mate_cap`` (``mate_search.py``) add the mate-in-one check behind the lookahead or the search and before the insight
     (``ka_mate_fork``, the env step over the child rows, ``ka_mate_choose``; no forward): it overrides their choice, and the
     insight describes the move actually played; ``mate_rows`` / ``mate_reply_cap`` > 0 put the mate in three behind it
     (``Mate3Search``: the grandchild rows per env and the third ply's rows per grandchild; seven more launches, no forward).
@@ -99,9 +101,13 @@ class DevicePly:
                  lookahead_table: Optional[np.ndarray] = None, lookahead_width: int = 0,
                  lookahead_reply_width: int = 0, search_table: Optional[np.ndarray] = None, search_width: int = 0,
                  search_expansions: int = 0, mate_table: Optional[np.ndarray] = None, mate_cap: int = 0, mate_rows: int = 0,
-                 mate_reply_cap: int = 0) -> None:
+                 mate_reply_cap: int = 0, mcts_table: Optional[np.ndarray] = None, mcts_width: int = 0,
+                 mcts_simulations: int = 0) -> None:
         if search_table is not None and lookahead_table is not None:
             raise ValueError("search_table cannot be combined with lookahead_table: the search stands where the lookahead stands")
+        if mcts_table is not None and (lookahead_table is not None or search_table is not None):
+            raise ValueError("mcts_table cannot be combined with lookahead_table or search_table: the visit-count search "
+                             "stands where they stand")
         N, dev = int(num_envs), group.device
         self.device, self.num_envs = dev, N
         with torch.cuda.device(dev):
@@ -124,6 +130,11 @@ class DevicePly:
             self.search: Optional[TreeSearch] = None
             if search_table is not None and search_width > 0:
                 self.search = TreeSearch(self.env, group, search_width, max(int(search_expansions), 1))
+            # the visit-count search's table and its node pool, likewise
+            self.mcts_table: Optional[torch.Tensor] = None if mcts_table is None else torch.from_numpy(mcts_table).to(dev)
+            self.mcts: Optional[MctsSearch] = None
+            if mcts_table is not None and mcts_width > 0:
+                self.mcts = MctsSearch(self.env, group, mcts_width, max(int(mcts_simulations), 1))
             # the mate check's table and its child rows, likewise
             self.mate_table: Optional[torch.Tensor] = None if mate_table is None else torch.from_numpy(mate_table).to(dev)
             self.mate: Optional[MateSearch] = None
@@ -156,6 +167,8 @@ class DevicePly:
             self.lookahead.clear()
         if self.search is not None:
             self.search.clear()
+        if self.mcts is not None:
+            self.mcts.clear()
         if self.mate3 is not None:
             self.mate3.clear()
         elif self.mate is not None:
@@ -181,6 +194,8 @@ class DevicePly:
             self.lookahead.step(logits, cur.legal_mask_bits, self.actions, model_of, self.lookahead_table, st)
         if self.search is not None:                       # likewise the search's
             self.search.step(logits, cur.legal_mask_bits, self.actions, model_of, self.search_table, st)
+        if self.mcts is not None:                         # or the visit-count search's
+            self.mcts.step(logits, cur.legal_mask_bits, self.actions, model_of, self.mcts_table, st)
         if self.mate3 is not None:                        # a mate in one or in three overrides whatever was chosen so far
             self.mate3.step(cur.legal_mask_bits, self.actions, model_of, self.mate_table, self.mate_reply_table, st)
         elif self.mate is not None:                       # a mate in one does

@@ -1,8 +1,8 @@
 """What the searches of the device ply share on the Python side: the rows beneath an env (``ForkedRows``), the parser of a
 per-model controls argument (``controls_rows``) and the check of the env and the group a search is built over
 (``check_search_env``).  ``Lookahead``, ``MateSearch`` and ``Mate3Search`` hold their child and grandchild rows as
-``ForkedRows``; ``TreeSearch`` keeps its pool-plus-scratch allocation and shares the check alone.  The device side of the same
-rows is csrc/ply_rows.h."""
+``ForkedRows``; ``TreeSearch`` and ``MctsSearch`` search in a ``NodePool``, a pool of slices plus one scratch.  The device
+side of the same rows is csrc/ply_rows.h."""
 from __future__ import annotations
 
 from typing import Mapping
@@ -11,9 +11,9 @@ import numpy as np
 import torch
 
 from keisei_amd import _lib
-from keisei_amd.shogi_gym import MASK_WORDS
+from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS
 
-__all__ = ["ForkedRows", "controls_rows", "check_search_env"]
+__all__ = ["ForkedRows", "NodePool", "controls_rows", "check_search_env"]
 
 
 def check_search_env(env, group, what: str) -> None:
@@ -56,6 +56,111 @@ def controls_rows(controls, K, cls, what: str, by_index: bool = False) -> list:
         if not isinstance(r, cls):
             raise ValueError(f"every entry must be a {name}, got {type(r).__name__}")
     return rows
+
+
+class NodePool:
+    """The node pool of a device ``VecEnv`` that ``TreeSearch`` and ``MctsSearch`` search in, and the stages that move rows.
+    Everything is allocated here, once: ``slices * envs * width`` node rows -- state, key and check history, both packed mask
+    rows, action, model, policy logits, value logits and the step's scalars -- and one scratch of ``envs * width`` rows that
+    every slice's step and forward write and nothing else reads: observations, terminal observations and the forward's
+    activation maps.  Slice ``t`` of the pool is rows ``[t * envs * width, (t + 1) * envs * width)``; node ``(t, j)`` of env
+    ``e`` is row ``(t * envs + e) * width + j``.  ``words``: 32-bit words of a record (the lookahead's layout)."""
+
+    _SLICE = "slice"                                        # what a subclass calls a slice in its errors
+
+    def __init__(self, env, group, width: int, slices: int, words: int) -> None:
+        self.env, self.group, self.width, self.slices, self.words = env, group, width, slices, words
+        n, dev, hist = env.num_envs, env.device, env._keys.shape[1]
+        self.M = M = n * width
+        P = slices * M
+        with torch.cuda.device(dev):
+            z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)  # noqa: E731
+            self.state = z(P, 128, dtype=torch.uint8)
+            self.keys = z(P, hist, dtype=torch.int64)
+            self.checks = z(P, hist, dtype=torch.uint8)
+            self.bits_in = z(P, MASK_WORDS, dtype=torch.int32)         # the parents' masks: the step validates against them
+            self.mask_bits = z(P, MASK_WORDS, dtype=torch.int32)
+            self.actions = z(P, dtype=torch.int64)
+            self.model_of = torch.full((P,), -1, dtype=torch.int32, device=dev)
+            self.logits = z(P, 9, 9, ACTION_SPACE // 81, dtype=torch.float32)
+            self.value_logits = z(P, 3, dtype=torch.float32)
+            self.rewards = z(P, dtype=torch.float32)
+            self.terminated = z(P, dtype=torch.bool)
+            self.truncated = z(P, dtype=torch.bool)
+            self.players = z(P, dtype=torch.uint8)
+            self.reason = z(P, dtype=torch.uint8)
+            self.captured = z(P, dtype=torch.uint8)
+            self.ply = z(P, dtype=torch.int16)
+            self.material = z(P, dtype=torch.int32)
+            # the scratch of one slice, shared by all
+            self.obs = z(M, env._C, 9, 9, dtype=torch.float32)
+            self.terminal_obs = z(M, env._C, 9, 9, dtype=torch.float32)
+            scratch = group._tables.workspace(M)
+            self._ws = [dict(scratch, logits=self.logits[t * M:(t + 1) * M], value=self.value_logits[t * M:(t + 1) * M])
+                        for t in range(slices)]
+            self._env_stats = z(4, dtype=torch.int64)
+            self._step_err = z(slices, 2, dtype=torch.int64)
+            self._records = z(slices, n, words, dtype=torch.int32)
+            self.parent_row = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            self.active = z(n, dtype=torch.int32)
+
+    def rows(self, t: int) -> slice:
+        """The pool rows of slice ``t``."""
+        if not 0 <= t < self.slices:
+            raise ValueError(f"{self._SLICE} {t} lies outside [0, {self.slices})")
+        return slice(t * self.M, (t + 1) * self.M)
+
+    def node_row(self, e, node):
+        """The pool row of local node ``node`` (``t * width + j``) of env ``e``."""
+        return (node // self.width * self.env.num_envs + e) * self.width + node % self.width
+
+    # ------------------------------------------------------------------ the stages that move rows
+    def fork(self, logits, mask_bits, actions, model_of, table, stream) -> None:
+        """Slice 0: the lookahead's fork of the envs."""
+        env, s = self.env, self.rows(0)
+        _lib.call("ka_lookahead_fork", logits, int(logits.dtype == torch.bfloat16), mask_bits, MASK_WORDS, actions, model_of,
+                  int(table.shape[0]), table, env._state, env._keys, env._checks, env._max_ply, self.width, self._records[0],
+                  self.state[s], self.keys[s], self.checks[s], self.bits_in[s], self.actions[s], self.model_of[s],
+                  env.num_envs, ACTION_SPACE, stream)
+
+    def expand(self, t: int, table, stream) -> None:
+        """Slice ``t >= 1``, after ``advance(t - 1)``: the leaves named by ``parent_row`` / ``active`` fork into it."""
+        env, s = self.env, self.rows(t)
+        _lib.call("ka_search_expand", self.logits, 0, self.mask_bits, MASK_WORDS, self.model_of, int(table.shape[0]), table,
+                  self.state, self.keys, self.checks, self.terminated, self.truncated, env._max_ply, self.width, t,
+                  self.parent_row, self.active, self._records[t], self.state[s], self.keys[s], self.checks[s], self.bits_in[s],
+                  self.actions[s], self.model_of[s], env.num_envs, ACTION_SPACE, stream)
+
+    def step_nodes(self, t: int, stream) -> None:
+        env, s = self.env, self.rows(t)
+        _lib.call("ka_shogi_env_step", self.state[s], self.keys[s], self.checks[s], self.actions[s], self.M, env._max_ply,
+                  env._omode, env._amode, None, self.bits_in[s], self._step_err[t], self.obs, None, self.mask_bits[s],
+                  self.rewards[s], self.terminated[s], self.truncated[s], self.terminal_obs, self.players[s], self.captured[s],
+                  self.reason[s], self.ply[s], self.material[s], self._env_stats, stream)
+
+    def evaluate(self, t: int) -> None:
+        self.group._tables.forward(self.obs, self.model_of[self.rows(t)], ws=self._ws[t])
+
+    def step(self, logits, mask_bits, actions, model_of, table, stream) -> None:
+        """Every stage on the current stream (``stream``: its pointer), after the sampler and before ``env.step``:
+        ``actions`` (envs,) int64 is overwritten for the active envs.  Arguments as ``Lookahead.step``; ``table`` is the
+        (K, 4) int32 table of the search on the device."""
+        for t in range(self.slices):
+            if t == 0:
+                self.fork(logits, mask_bits, actions, model_of, table, stream)
+            else:
+                self.expand(t, table, stream)
+            self.step_nodes(t, stream)
+            self.evaluate(t)
+            self.advance(t, actions, model_of, table, stream)
+
+    def records(self, t=None) -> torch.Tensor:
+        """The records of the last ``step`` (a copy on the device): (envs, 4 + 3 width) of slice ``t``, or all
+        (slices, envs, 4 + 3 width)."""
+        if t is None:
+            return self._records.clone()
+        self.rows(t)
+        return self._records[t].clone()
 
 
 class ForkedRows:

@@ -15,6 +15,8 @@ synchronisation:
                                                  (ka_lookahead_fork, then ka_search_expand), ka_shogi_env_step and the
                                                  grouped forward over its slice of the node pool, ka_search_advance --
                                                  csrc/lookahead.hip, tree_search.py)
+    visit-count search                          (only with mcts=, in the same place: the same stages per simulation with
+                                                 ka_mcts_advance as the tree policy -- csrc/mcts.hip, mcts_search.py)
     lookahead                                   (only with lookahead=: ka_lookahead_fork, ka_shogi_env_step over the child
                                                  rows, the grouped forward over the child observations,
                                                  ka_lookahead_choose -- or, with a reply_width, three more stages over the
@@ -69,6 +71,7 @@ from .game_feature_tracker import GameFeatureTracker
 from .game_log import RecordedGame
 from .lookahead import LookaheadStats, arena_lookahead, arena_reply_width, lookahead_table
 from .mate_search import Mate3Stats, MateStats, arena_mate, arena_mate3, mate3_reply_table, mate_table
+from .mcts_search import MctsStats, arena_mcts, mcts_table
 from .model_group import SEResNetGroup
 from .sampling import GAME_PLY_BYTE, arena_controls, controls_table
 from .tree_search import SearchStats, arena_search, search_table
@@ -118,6 +121,7 @@ class RoundStats:
     games_dropped: int = 0              # finished games that did not fit the game log between two sync points
     lookahead: Optional[LookaheadStats] = None      # the round's lookahead counters (arenas built with lookahead=)
     search: Optional[SearchStats] = None            # the round's tree-search counters (arenas built with search=)
+    mcts: Optional[MctsStats] = None                # the round's visit-count search counters (arenas built with mcts=)
     mate: Optional[MateStats] = None                # the round's mate-in-one counters (arenas built with mate=)
     mate3: Optional[Mate3Stats] = None              # the round's mate-in-three counters (mate= with evasion_rows > 0)
 
@@ -314,6 +318,13 @@ class MatchArena:
     given; ``set_search`` rewrites the table between rounds without a new capture, up to those.  ``RoundStats.search``
     carries the counters.  With None nothing is allocated and the launches are what they were.  Not together with
     ``lookahead=`` and not with ``collect=True``.
+    ``mcts=`` (an ``MctsControls`` for every model, or one per model; ``mcts_search.py``) puts a visit-count (PUCT) search
+    where the lookahead stands: ``simulations`` forks of ``width`` rows per env, spread by ``Q + c_puct P sqrt(N) / (1 + n)``,
+    values backed up as means, the most visited root candidate played.  ``self.mcts.root_visits()`` between two plies gives the
+    visit distribution of every searched position (``visit_policy`` makes a dense target of it).  The node pool is sized by the
+    largest ``width`` and ``simulations`` given; ``set_mcts`` rewrites the table between rounds without a new capture, up to
+    those.  ``RoundStats.mcts`` carries the counters.  With None nothing is allocated and the launches are what they were.
+    Not together with ``lookahead=`` or ``search=`` and not with ``collect=True``.
     ``mate=`` (a ``MateControls`` for every model, one per model, or a dict by model index; ``mate_search.py``) adds a
     rules-only mate-in-one check behind the lookahead or the search and before the insight: the legal moves that give check
     are forked (at most ``max_checks`` of them, in ascending action order), the env's own step decides them, and a move that
@@ -330,7 +341,8 @@ class MatchArena:
                  sync_every: int = 32, graph: bool = True, seed: Optional[int] = None, record: bool = False,
                  collect: bool = False, features: bool = False, start_pool_capacity: int = 0,
                  game_log: int = 0, move_history: bool = False, insight: int = 0,
-                 insight_temperature: float = 1.0, sampling=None, lookahead=None, search=None, mate=None) -> None:
+                 insight_temperature: float = 1.0, sampling=None, lookahead=None, search=None, mate=None,
+                 mcts=None) -> None:
         if len(group) == 0:
             raise ValueError("MatchArena needs a group with at least one model")
         if num_envs <= 0 or envs_per_match <= 0 or num_envs % envs_per_match != 0:
@@ -345,6 +357,7 @@ class MatchArena:
         la_table, la_width = arena_lookahead(lookahead, len(group), bool(collect))
         la_reply = arena_reply_width(lookahead, len(group))
         se_table, se_width, se_expansions = arena_search(search, len(group), bool(collect), lookahead)
+        mc_table, mc_width, mc_sims = arena_mcts(mcts, len(group), bool(collect), lookahead, search)
         mt_table, mt_cap = arena_mate(mate, len(group), bool(collect))
         mt_rows, mt_reply = arena_mate3(mate, len(group))
         self.group = group
@@ -362,11 +375,13 @@ class MatchArena:
                                    insight_temperature=insight_temperature, controls=table, lookahead_table=la_table,
                                    lookahead_width=la_width, lookahead_reply_width=la_reply, search_table=se_table,
                                    search_width=se_width, search_expansions=se_expansions, mate_table=mt_table,
-                                   mate_cap=mt_cap, mate_rows=mt_rows, mate_reply_cap=mt_reply)
+                                   mate_cap=mt_cap, mate_rows=mt_rows, mate_reply_cap=mt_reply, mcts_table=mc_table,
+                                   mcts_width=mc_width, mcts_simulations=mc_sims)
         self.env, self.game_log, self.insight = ply.env, ply.game_log, ply.insight
         self._actions, self._logp, self._nlegal = ply.actions, ply.log_probs, ply.n_legal
         self._ctl, self._la_table, self._la = ply.ctl, ply.lookahead_table, ply.lookahead
         self._se_table, self._se = ply.search_table, ply.search
+        self._mc_table, self.mcts = ply.mcts_table, ply.mcts
         self._mt_table, self._mt = ply.mate_table, ply.mate
         self._mt3, self._mt3_table = ply.mate3, ply.mate_reply_table
         with torch.cuda.device(dev):
@@ -479,6 +494,27 @@ class MatchArena:
         with torch.cuda.device(self.device):
             self._se_table.copy_(torch.from_numpy(table))
 
+    def set_mcts(self, mcts) -> None:
+        """New visit-count search controls from the next ply on (between two ``run_round`` calls); nothing is captured
+        again.  None writes rows that are off.  A width or ``simulations`` above what the arena was built with is refused (the
+        node pool is sized by them), and so is an arena built without ``mcts=``: its ply holds no such search."""
+        if self._mc_table is None:
+            raise ValueError("this arena was built without mcts=: its ply (and its captured graph) holds no visit-count "
+                             "search; build the arena with mcts controls to change them later")
+        table, width, simulations = arena_mcts(mcts, len(self.group), self.collect)
+        if table is None:
+            table = mcts_table(None, len(self.group))
+        built = 0 if self.mcts is None else self.mcts.width
+        if width > built:
+            raise ValueError(f"mcts width {width} is above the width this arena was built with ({built}): the node pool "
+                             "is allocated once, by the largest width given to the constructor")
+        built = 1 if self.mcts is None else self.mcts.simulations
+        if simulations > built:
+            raise ValueError(f"mcts simulations {simulations} is above the simulations this arena was built with ({built}): "
+                             "the node pool is allocated once, by the largest simulations given to the constructor")
+        with torch.cuda.device(self.device):
+            self._mc_table.copy_(torch.from_numpy(table))
+
     def set_sampling(self, sampling) -> None:
         """New sampling controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
         writes neutral rows.  An arena built without ``sampling=`` holds the play sampler in its ply and refuses."""
@@ -549,6 +585,15 @@ class MatchArena:
                        node_rewards=se.rewards.cpu().reshape(shape), node_done=(se.terminated | se.truncated).cpu().reshape(shape),
                        node_logits=se.logits.cpu().reshape(-1, ACTION_SPACE), node_mask_bits=se.mask_bits.cpu(),
                        node_model_of=se.model_of.cpu().reshape(shape))
+        if self.mcts is not None:
+            mc = self.mcts
+            shape = (mc.simulations, self.num_envs, mc.width)
+            rec.update(mcts_records=mc.records().cpu(), mcts_tree={k: v.cpu() for k, v in mc.tree().items()},
+                       mcts_pv=mc.principal_variations().cpu(), mcts_root_visits=tuple(x.cpu() for x in mc.root_visits()),
+                       node_value_logits=mc.value_logits.cpu().reshape(*shape, 3), node_rewards=mc.rewards.cpu().reshape(shape),
+                       node_done=(mc.terminated | mc.truncated).cpu().reshape(shape),
+                       node_logits=mc.logits.cpu().reshape(-1, ACTION_SPACE), node_mask_bits=mc.mask_bits.cpu(),
+                       node_model_of=mc.model_of.cpu().reshape(shape))
         if self._mt is not None:
             rec.update(mate_records=self._mt.records().cpu())
         if self._mt3 is not None:
@@ -691,6 +736,8 @@ class MatchArena:
             stats.lookahead = LookaheadStats()
         if self._se_table is not None:
             stats.search = SearchStats()
+        if self._mc_table is not None:
+            stats.mcts = MctsStats()
         if self._mt_table is not None:
             stats.mate = MateStats()
         if self._mt3 is not None:
@@ -744,6 +791,8 @@ class MatchArena:
                 stats.lookahead = self._la.read()
             if self._se is not None:
                 stats.search = self._se.read()
+            if self.mcts is not None:
+                stats.mcts = self.mcts.read()
             if self._mt is not None:
                 stats.mate = self._mt.read()
             if self._mt3 is not None:

@@ -36,9 +36,8 @@ import numpy as np
 import torch
 
 from keisei_amd import _lib
-from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS
 
-from ._forked_rows import check_search_env, controls_rows
+from ._forked_rows import NodePool, check_search_env, controls_rows
 from .lookahead import (FLAG_ACTIVE, MAX_SKIP_PLIES, MAX_WIDTH, REC_CAND, REC_FLAGS, REC_NCAND, _check_width,
                         _loss_minus_win, _row_controls, lookahead_words)
 
@@ -295,71 +294,31 @@ def search_backup_select(records, done, parent, controls, model_of=None, *, q=No
 
 
 # ---------------------------------------------------------------------------------------------- in the ply
-class TreeSearch:
-    """The node pool of a device ``VecEnv`` and the stages of the search.  Everything is allocated here, once: ``expansions *
-    envs * width`` node rows -- state, key and check history, both packed mask rows, action, model, policy logits, value
-    logits and the step's scalars -- and one scratch of ``envs * width`` rows that every expansion's step and forward write
-    and nothing else reads: observations, terminal observations and the forward's activation maps.  Slice ``t`` of the pool is
-    rows ``[t * envs * width, (t + 1) * envs * width)``; node ``(t, j)`` of env ``e`` is row ``(t * envs + e) * width + j``."""
+class TreeSearch(NodePool):
+    """The node pool of a device ``VecEnv`` (``NodePool``: ``expansions`` slices of ``envs * width`` rows and one scratch) and
+    the stages of the search.  Everything is allocated once.  Slice ``t`` of the pool is rows ``[t * envs * width, (t + 1) *
+    envs * width)``; node ``(t, j)`` of env ``e`` is row ``(t * envs + e) * width + j``."""
+
+    _SLICE = "expansion"
 
     def __init__(self, env, group, width: int, expansions: int) -> None:
         width = _check_width(width)
         expansions = _check_expansions(expansions)
         check_search_env(env, group, "the search")
-        self.env, self.group, self.width, self.expansions = env, group, width, expansions
-        n, dev, hist = env.num_envs, env.device, env._keys.shape[1]
-        self.words = _lib.query("ka_search_words", 0, width, expansions)
+        self.expansions = expansions
+        words = _lib.query("ka_search_words", 0, width, expansions)
         self.tree_words = _lib.query("ka_search_words", 1, width, expansions)
-        assert self.words == lookahead_words(width) and self.tree_words == expansions + 2 * expansions * width
+        assert words == lookahead_words(width) and self.tree_words == expansions + 2 * expansions * width
         assert width <= _lib.query("ka_search_words", 3, 0, 0) == MAX_WIDTH
         assert expansions <= _lib.query("ka_search_words", 4, 0, 0) == MAX_EXPANSIONS
-        self.M = M = n * width
-        P = expansions * M
+        super().__init__(env, group, width, expansions, words)
+        n, dev = env.num_envs, env.device
         with torch.cuda.device(dev):
-            z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)  # noqa: E731
-            self.state = z(P, 128, dtype=torch.uint8)
-            self.keys = z(P, hist, dtype=torch.int64)
-            self.checks = z(P, hist, dtype=torch.uint8)
-            self.bits_in = z(P, MASK_WORDS, dtype=torch.int32)         # the parents' masks: the step validates against them
-            self.mask_bits = z(P, MASK_WORDS, dtype=torch.int32)
-            self.actions = z(P, dtype=torch.int64)
-            self.model_of = torch.full((P,), -1, dtype=torch.int32, device=dev)
-            self.logits = z(P, 9, 9, ACTION_SPACE // 81, dtype=torch.float32)
-            self.value_logits = z(P, 3, dtype=torch.float32)
-            self.rewards = z(P, dtype=torch.float32)
-            self.terminated = z(P, dtype=torch.bool)
-            self.truncated = z(P, dtype=torch.bool)
-            self.players = z(P, dtype=torch.uint8)
-            self.reason = z(P, dtype=torch.uint8)
-            self.captured = z(P, dtype=torch.uint8)
-            self.ply = z(P, dtype=torch.int16)
-            self.material = z(P, dtype=torch.int32)
-            # the scratch of one expansion, shared by all
-            self.obs = z(M, env._C, 9, 9, dtype=torch.float32)
-            self.terminal_obs = z(M, env._C, 9, 9, dtype=torch.float32)
-            scratch = group._tables.workspace(M)
-            self._ws = [dict(scratch, logits=self.logits[t * M:(t + 1) * M], value=self.value_logits[t * M:(t + 1) * M])
-                        for t in range(expansions)]
-            self._env_stats = z(4, dtype=torch.int64)
-            self._step_err = z(expansions, 2, dtype=torch.int64)
-            self._records = z(expansions, n, self.words, dtype=torch.int32)
-            self._tree = z(n, self.tree_words, dtype=torch.int32)
-            self.parent_row = torch.full((n,), -1, dtype=torch.int32, device=dev)
-            self.active = z(n, dtype=torch.int32)
+            self._tree = torch.zeros(n, self.tree_words, dtype=torch.int32, device=dev)
             self._pv = torch.full((n, expansions), -1, dtype=torch.int32, device=dev)
             self._nstats = _lib.query("ka_search_words", 2, width, expansions)
-            self._counters = z(self._nstats + 1, dtype=torch.int32)    # stats, then the error word
+            self._counters = torch.zeros(self._nstats + 1, dtype=torch.int32, device=dev)    # stats, then the error word
             self._counters_host = torch.zeros(self._counters.shape, dtype=torch.int32).pin_memory()
-
-    def rows(self, t: int) -> slice:
-        """The pool rows of expansion ``t``."""
-        if not 0 <= t < self.expansions:
-            raise ValueError(f"expansion {t} lies outside [0, {self.expansions})")
-        return slice(t * self.M, (t + 1) * self.M)
-
-    def node_row(self, e, node):
-        """The pool row of local node ``node`` (``t * width + j``) of env ``e``."""
-        return (node // self.width * self.env.num_envs + e) * self.width + node % self.width
 
     def clear(self) -> None:
         """Zero the counters, the error word and the refusal latches of every slice's step (a round's start)."""
@@ -367,32 +326,6 @@ class TreeSearch:
         self._step_err.zero_()
 
     # ------------------------------------------------------------------ the stages
-    def fork(self, logits, mask_bits, actions, model_of, table, stream) -> None:
-        """Expansion 0: the lookahead's fork of the envs into slice 0."""
-        env, s = self.env, self.rows(0)
-        _lib.call("ka_lookahead_fork", logits, int(logits.dtype == torch.bfloat16), mask_bits, MASK_WORDS, actions, model_of,
-                  int(table.shape[0]), table, env._state, env._keys, env._checks, env._max_ply, self.width, self._records[0],
-                  self.state[s], self.keys[s], self.checks[s], self.bits_in[s], self.actions[s], self.model_of[s],
-                  env.num_envs, ACTION_SPACE, stream)
-
-    def expand(self, t: int, table, stream) -> None:
-        """Expansion ``t >= 1``, after ``advance(t - 1)``: the leaves named by ``parent_row`` / ``active`` fork into slice t."""
-        env, s = self.env, self.rows(t)
-        _lib.call("ka_search_expand", self.logits, 0, self.mask_bits, MASK_WORDS, self.model_of, int(table.shape[0]), table,
-                  self.state, self.keys, self.checks, self.terminated, self.truncated, env._max_ply, self.width, t,
-                  self.parent_row, self.active, self._records[t], self.state[s], self.keys[s], self.checks[s], self.bits_in[s],
-                  self.actions[s], self.model_of[s], env.num_envs, ACTION_SPACE, stream)
-
-    def step_nodes(self, t: int, stream) -> None:
-        env, s = self.env, self.rows(t)
-        _lib.call("ka_shogi_env_step", self.state[s], self.keys[s], self.checks[s], self.actions[s], self.M, env._max_ply,
-                  env._omode, env._amode, None, self.bits_in[s], self._step_err[t], self.obs, None, self.mask_bits[s],
-                  self.rewards[s], self.terminated[s], self.truncated[s], self.terminal_obs, self.players[s], self.captured[s],
-                  self.reason[s], self.ply[s], self.material[s], self._env_stats, stream)
-
-    def evaluate(self, t: int) -> None:
-        self.group._tables.forward(self.obs, self.model_of[self.rows(t)], ws=self._ws[t])
-
     def advance(self, t: int, actions, model_of, table, stream) -> None:
         """After ``evaluate(t)``: leaf q, backup, the leaf of expansion t + 1; at the last expansion the choice."""
         self.rows(t)
@@ -400,19 +333,6 @@ class TreeSearch:
                   int(table.shape[0]), self.value_logits, self.rewards, self.terminated, self.truncated, self._step_err,
                   actions, self.parent_row, self.active, self._pv, self._counters,
                   self._counters.data_ptr() + 4 * self._nstats, self.env.num_envs, stream)
-
-    def step(self, logits, mask_bits, actions, model_of, table, stream) -> None:
-        """Every stage on the current stream (``stream``: its pointer), after the sampler and before ``env.step``:
-        ``actions`` (envs,) int64 is overwritten for the active envs.  Arguments as ``Lookahead.step``; ``table`` is the
-        (K, 4) int32 search table on the device."""
-        for t in range(self.expansions):
-            if t == 0:
-                self.fork(logits, mask_bits, actions, model_of, table, stream)
-            else:
-                self.expand(t, table, stream)
-            self.step_nodes(t, stream)
-            self.evaluate(t)
-            self.advance(t, actions, model_of, table, stream)
 
     # ------------------------------------------------------------------ host side
     def read(self) -> SearchStats:
@@ -429,14 +349,6 @@ class TreeSearch:
         if err & ERR_VALUE:
             raise RuntimeError("non-finite value logits in the search (a model has diverged)")
         return SearchStats(*(int(v) for v in c[:5]))
-
-    def records(self, t: Optional[int] = None) -> torch.Tensor:
-        """The records of the last ``step`` (a copy on the device): (envs, 4 + 3 width) of expansion ``t``, or all
-        (expansions, envs, 4 + 3 width)."""
-        if t is None:
-            return self._records.clone()
-        self.rows(t)
-        return self._records[t].clone()
 
     def tree(self) -> dict:
         """The trees of the last ``step`` (copies on the device): ``parent`` (envs, expansions) int32, ``val`` (envs,
