@@ -313,6 +313,18 @@ int ka_policy_sample_play(const void* logits, int logits_bf16, const void* legal
  * (rowent = zeros, entropy_coeff = 0). */
 int ka_policy_ce(const float* logits, const long long* targets, const long long* idx, float* dlogits, float* rowloss,
                  int* flags, const float* gscale, float w_policy, int B, int A, void* stream);
+/* The policy cross-entropy against a distribution over at most 64 actions per row (the visit counts of a search): row b has
+ * K slots (actions[b][k] int32, weights[b][k] fp32), 1 <= K <= 64.  A slot is used iff its weight is > 0; a slot of weight
+ * 0 is ignored whatever its action.  One workgroup per row on ka_policy_ce's row pass (the row staged in LDS, the same
+ * maximum, sum and lse).  With s = w_policy [* *gscale]:
+ *   rowloss[b]    = sum_k w_k (lse - z[a_k])                       over the used slots, in slot order
+ *   dlogits[b][j] = s (sum_k w_k) exp(z_j - lse) - s sum_{k: a_k = j} w_k      (optional; duplicate actions add in slot
+ *                   order; an element some used slot names is fma(s W, exp(z_j - lse), -(s * its weights)))
+ * flags[0] |= NaN in the logits.  flags[1] |= a used slot whose action lies outside [0, A), a weight that is negative or
+ * not finite, or a row without a used slot: such a row gives rowloss 0 and a zero gradient row.  A row whose only used
+ * slot has weight 1.0 gives, to the bit, the rowloss and the dlogits of ka_policy_ce with that action as its target. */
+int ka_policy_ce_soft(const float* logits, const int* actions, const float* weights, int K, float* dlogits, float* rowloss,
+                      int* flags, const float* gscale, float w_policy, int B, int A, void* stream);
 int ka_value_loss(const float* vlogits, const float* score, const long long* cats, const float* targets,
                   const long long* idx, const float* rowloss, const float* rowent, float* dvlogits, float* dscore,
                   float* out, float* acc, const float* gscale, float lambda_policy, float lambda_value, float lambda_score,
@@ -1197,6 +1209,48 @@ int ka_sl_gather(const void* packed, long long n, const long long* idx, int B, f
  * idx[b] outside [0, n) gives a zero row with targets 0 and adds 1 to flags[0] in every mode. */
 int ka_sl_gather_aug(const void* packed, long long n, const long long* idx, int B, float* obs_out, long long* policy_out,
                      long long* value_out, float* score_out, int* flags, int mode, long long seed, int epoch, void* stream);
+/* Visit rows: a dataset may hold, beside every packed position, KA_SL_VISIT_WORDS visit words and KA_SL_INFO_WORDS info
+ * words (for every position or for none).  Visit word k = action | visits << 16 (action < 11259, visits 0 = the slot is
+ * unused); info = {model | mover << 16, index of the move in its game, env, game number}.
+ * gather_visits: batch row b < B from visit row idx[b]: actions_out[b][k] (int32) = the action of a used slot, -1 of an
+ * unused one; weights_out[b][k] (fp32) = (float)N_k / (float)(sum of the row's N), one IEEE division, 0 for an unused slot.
+ * mode, seed, epoch as ka_sl_gather_aug: the rows it reflects have every used slot's action replaced by mirror(a), the
+ * same draw of (seed, epoch, idx[b]).  An idx[b] outside [0, n) gives an all-unused row (the observation gather counts
+ * it); flags (int32[1], may be null) counts the used words whose action lies outside [0, 11259), handed on as stored. */
+#define KA_SL_VISIT_WORDS 8
+#define KA_SL_INFO_WORDS 4
+int ka_sl_gather_visits(const void* visits, long long n, const long long* idx, int B, int mode, long long seed, int epoch,
+                        int* actions_out, float* weights_out, int* flags, void* stream);
+
+/* ---- search samples (csrc/search_samples.hip; keisei_amd/training/search_samples.py): the positions a visit-count search
+ * looked at, written as training rows inside the ply.  Per env a region of rows_per_env sample rows of
+ * KA_SEARCH_SAMPLE_WORDS = 204 + 8 + 4 dwords (864 bytes): the packed position (above), the visit words, the info words.
+ * Per-env meta, int32[5]: {write cursor, first row of the game in progress, samples dropped, moves played in the game in
+ * progress, games finished}; the host zeroes it (and the error word) when the envs are reset.
+ * step: one launch per ply, one workgroup per env, behind ka_shogi_env_step and before the loop's bookkeeping launch
+ *   rewrites model_of.  obs_prev / players_prev are the env's PREVIOUS result buffers (the position before the move and
+ *   its player to move, intact until the step after the next one); records (envs, rec_words) are the search's records of
+ *   simulation 0 (word 0 bit 0 = active, word 2 = n_cand, words 4.. = the candidates' actions), root_visits (envs, width)
+ *   the root candidates' visits, width <= 8; actions the actions stepped; material, rewards, terminated, truncated the
+ *   step's results.
+ * Write rule: a sample is written iff record 0 is active, n_cand >= 1 and model_of[e] >= 0.  The observation is packed as
+ *   ka_sl_pack packs it; policy = actions[e] (the move played, after any mate override: not necessarily the most visited);
+ *   value = -1 (unlabelled); score = the bits of (float)material[e] / 76.0f; word 203 = 0; visit word j = candidate j's
+ *   action | visits << 16 for j < n_cand (0 where the visits are 0); info = {model_of[e] | mover << 16, moves, e, games}.
+ *   A full region drops the sample and counts it in the meta; an observation that cannot be held packed ORs 1 into *err.
+ *   The move counter (and, at a game's end, the game counter) advances for every env on every ply, written or not.
+ * Label rule: where terminated | truncated, the winner is the game log's: the mover if rewards[e] > 0, the other side if
+ *   < 0, nobody otherwise (a NaN included).  Every row of the region from the game's first row to the cursor, the new one
+ *   included, gets value 0 where its mover is the winner, 2 where it is the loser, 1 for a draw; the game's first row moves
+ *   to the cursor.
+ * No env reads another env's words; the one atomic is the OR into *err.  which: 0 = words of a sample row, 1 = meta words
+ * per env, 2 = visit words, 3 = info words, 4 = the largest number of envs. */
+#define KA_SEARCH_SAMPLE_WORDS 216
+int ka_search_sample_words(int which);
+int ka_search_sample_step(const float* obs_prev, int obs_elems, const void* players_prev, const int* records, int rec_words,
+                          const int* root_visits, int width, const int* model_of, const long long* actions,
+                          const int* material, const float* rewards, const void* terminated, const void* truncated,
+                          void* rows, int rows_per_env, int* meta, int* err, int envs, void* stream);
 
 /* ---- transformer encoder path (BASELINE config 5; keisei/training/models/transformer.py:37-95: nn.Linear(50, d),
  * row/col nn.Embedding, nn.TransformerEncoder(nn.TransformerEncoderLayer(d, nhead, 4d, batch_first, norm_first), L),

@@ -75,6 +75,7 @@ _SIGS = {
     "ka_policy_sample": "pi pi q pp f ppp pp ii p",
     "ka_policy_sample_play": "pi pi pp i pp pp ii p",
     "ka_policy_ce": "ppp ppp p f ii p",
+    "ka_policy_ce_soft": "ppp i ppp p f ii p",
     "ka_value_loss": "ppppp pp pp pp p ffff i i p",
     "ka_scalar_value": "pp f p i p",
     "ka_adam_chunk": "",
@@ -164,7 +165,10 @@ _SIGS = {
     "ka_sl_pack": "pp i pp p",
     "ka_sl_gather": "p q p i ppppp p",
     "ka_sl_gather_aug": "p q p i ppppp i q i p",
+    "ka_sl_gather_visits": "p q p ii q i ppp p",
     "ka_sl_eval": "pppppp iii pp p p p",
+    "ka_search_sample_words": "i",
+    "ka_search_sample_step": "p i p p i p i pp ppp p p i pp i p",
     "ka_tf_gemm_nt": "ppppp iii iii iii f q p",
     "ka_tf_gemm_nt_slabs": "ii",
     "ka_tf_gemm_nt_masked": "pppp iii iii f q p",

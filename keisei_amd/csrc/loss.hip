@@ -190,27 +190,34 @@ struct PolicyCeArgs {
     const float* gscale; float w_policy; int A;
 };
 
-__global__ __launch_bounds__(kPolThreads) void policy_ce_kernel(PolicyCeArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* row = reinterpret_cast<float*>(smem);
-    __shared__ float red[kPolThreads / 64];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const long long src = a.idx ? a.idx[b] : b;
-    const float* lg = a.logits + (size_t)b * a.A;
+// The row pass of the supervised policy head, shared by policy_ce_kernel and policy_ce_soft_kernel: the A logits at lg staged
+// in LDS, their maximum, the sum of exp(z - mx) and lse = mx + log(sum); *nan_count > 0 where the row holds a NaN.
+__device__ __forceinline__ float policy_ce_row_pass(const float* __restrict__ lg, int A, float* row, float* red, float* nan_count) {
+    const int tid = threadIdx.x;
     float mx = -INFINITY;
     int nan_seen = 0;
-    for (int j = tid; j < a.A; j += kPolThreads) {
+    for (int j = tid; j < A; j += kPolThreads) {
         const float v = lg[j];
         row[j] = v;
         nan_seen |= (v != v);
         mx = fmaxf(mx, v);
     }
     mx = block_reduce(mx, red, true);
-    const float nanf_ = block_reduce((float)nan_seen, red, false);
+    *nan_count = block_reduce((float)nan_seen, red, false);
     float s = 0.f;
-    for (int j = tid; j < a.A; j += kPolThreads) s += expf(row[j] - mx);
+    for (int j = tid; j < A; j += kPolThreads) s += expf(row[j] - mx);
     s = block_reduce(s, red, false);
-    const float lse = mx + logf(s);
+    return mx + logf(s);
+}
+
+__global__ __launch_bounds__(kPolThreads) void policy_ce_kernel(PolicyCeArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* row = reinterpret_cast<float*>(smem);
+    __shared__ float red[kPolThreads / 64];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const long long src = a.idx ? a.idx[b] : b;
+    float nanf_;
+    const float lse = policy_ce_row_pass(a.logits + (size_t)b * a.A, a.A, row, red, &nanf_);
     const long long tgt = a.targets[src];
     const bool ok = tgt >= 0 && tgt < a.A;
     if (tid == 0) {
@@ -226,6 +233,86 @@ __global__ __launch_bounds__(kPolThreads) void policy_ce_kernel(PolicyCeArgs a) 
             if (j == tgt) g -= w;
             dl[j] = g;
         }
+    }
+}
+
+// The policy head against a distribution over at most kSoftSlots actions per row (visit counts of a search): row b has K
+// slots (actions[b][k], weights[b][k]); a slot is used where its weight is > 0, and a slot of weight 0 is ignored whatever
+// its action.  With W = sum of the used weights, in slot order,
+//   rowloss[b]    = sum_k w_k (lse - z[a_k])                                   thread 0, in slot order
+//   dlogits[b][j] = s W exp(z_j - lse) - s sum_{k: a_k = j} w_k,  s = w_policy * gscale
+// The gradient is written in two steps: every element as (s W) * exp(z_j - lse), then, behind a barrier, the lowest slot of
+// every distinct used action rewrites its element as fma(s W, exp(z_a - lse), -(s * sum of that action's weights in slot
+// order)) -- the form policy_ce_kernel's element takes at its target, so a row whose only used slot has weight 1 gives
+// ka_policy_ce's bits.  flags[1]: a used slot's action outside [0, A), a weight that is negative or not finite, or no used
+// slot at all; such a row gives rowloss 0 and a zero gradient row.
+constexpr int kSoftSlots = 64;
+
+struct PolicyCeSoftArgs {
+    const float* logits; const int* actions; const float* weights; int K; float* dlogits; float* rowloss; int* flags;
+    const float* gscale; float w_policy; int A;
+};
+
+__global__ __launch_bounds__(kPolThreads) void policy_ce_soft_kernel(PolicyCeSoftArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* row = reinterpret_cast<float*>(smem);
+    __shared__ float red[kPolThreads / 64];
+    __shared__ int s_act[kSoftSlots];
+    __shared__ float s_w[kSoftSlots];
+    __shared__ int s_state[2];                                 // a slot that is an error; a slot that is used
+    __shared__ float s_total;
+    const int b = blockIdx.x, tid = threadIdx.x, K = a.K;
+    float nanf_;
+    const float lse = policy_ce_row_pass(a.logits + (size_t)b * a.A, a.A, row, red, &nanf_);
+    if (tid < 64) {                                            // wave 0, every lane: the ballots are over the whole wave
+        int act = -1;
+        float w = 0.f;
+        bool bad = false;
+        if (tid < K) {
+            act = a.actions[(size_t)b * K + tid];
+            w = a.weights[(size_t)b * K + tid];
+            const bool finite = fabsf(w) <= 3.4028234663852886e38f;     // false for a NaN and for an infinity
+            bad = !finite || w < 0.f || (w > 0.f && (act < 0 || act >= a.A));
+            if (!(w > 0.f) || bad) { w = 0.f; act = -1; }
+        }
+        s_act[tid] = act;
+        s_w[tid] = w;
+        const unsigned long long any_bad = __ballot(bad), any_used = __ballot(w > 0.f);
+        if (tid == 0) { s_state[0] = any_bad != 0ull; s_state[1] = any_used != 0ull; }
+    }
+    __syncthreads();
+    const bool valid = !s_state[0] && s_state[1];
+    if (tid == 0) {
+        float total = 0.f, loss = 0.f;
+        if (valid)
+            for (int k = 0; k < K; ++k)
+                if (s_w[k] > 0.f) { total += s_w[k]; loss += s_w[k] * (lse - row[s_act[k]]); }
+        s_total = total;
+        if (nanf_ > 0.f) atomicOr(&a.flags[0], 1);
+        if (!valid) atomicOr(&a.flags[1], 1);
+        a.rowloss[b] = loss;
+    }
+    if (!a.dlogits) return;
+    __syncthreads();
+    const float s = a.w_policy * (a.gscale ? *a.gscale : 1.f);
+    const float sw = s * s_total;
+    float* dl = a.dlogits + (size_t)b * a.A;
+    if (!valid) {
+        for (int j = tid; j < a.A; j += kPolThreads) dl[j] = 0.f;
+        return;
+    }
+    for (int j = tid; j < a.A; j += kPolThreads) dl[j] = sw * expf(row[j] - lse);
+    __syncthreads();                                           // the owners below rewrite elements other threads wrote
+    if (tid < K && s_w[tid] > 0.f) {
+        const int act = s_act[tid];
+        bool owner = true;
+        float mine = 0.f;
+        for (int k = 0; k < K; ++k)
+            if (s_w[k] > 0.f && s_act[k] == act) {
+                if (k < tid) owner = false;
+                mine += s_w[k];
+            }
+        if (owner) dl[act] = __fmaf_rn(sw, expf(row[act] - lse), -(s * mine));
     }
 }
 
@@ -607,6 +694,17 @@ extern "C" int ka_policy_ce(const float* logits, const long long* targets, const
     KA_REQUIRE(lds <= 64 * 1024, "policy_ce: action space %d too large for the LDS row", A);
     hipLaunchKernelGGL(policy_ce_kernel, dim3(B), dim3(kPolThreads), lds, static_cast<hipStream_t>(stream), a);
     return ka_check_launch("policy_ce");
+}
+
+extern "C" int ka_policy_ce_soft(const float* logits, const int* actions, const float* weights, int K, float* dlogits,
+                                 float* rowloss, int* flags, const float* gscale, float w_policy, int B, int A, void* stream) {
+    KA_REQUIRE(logits && actions && weights && rowloss && flags && B > 0 && A > 0, "policy_ce_soft: null tensor");
+    KA_REQUIRE(K >= 1 && K <= kSoftSlots, "policy_ce_soft: K %d (1..%d)", K, kSoftSlots);
+    PolicyCeSoftArgs a{logits, actions, weights, K, dlogits, rowloss, flags, gscale, w_policy, A};
+    const size_t lds = ((size_t)A * 4 + 15) / 16 * 16;
+    KA_REQUIRE(lds <= 63 * 1024, "policy_ce_soft: action space %d too large for the LDS row", A);
+    hipLaunchKernelGGL(policy_ce_soft_kernel, dim3(B), dim3(kPolThreads), lds, static_cast<hipStream_t>(stream), a);
+    return ka_check_launch("policy_ce_soft");
 }
 
 // out[9]: policy_loss, value_ce, score_mse, entropy, total, n_valid, value_accuracy, frac_win, frac_draw

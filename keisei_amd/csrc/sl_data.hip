@@ -27,23 +27,11 @@
 //                     instance, which ka_sl_gather launches, contains none of this.
 // All are memory-bound copies; nothing in them is tuned further.
 #include "common.h"
+#include "sl_packed.h"
 
 #include <limits.h>
 
 namespace {
-
-constexpr int kPkThreads = 256;
-constexpr int kPkWaves = kPkThreads / 64;
-constexpr int kPkChannels = 50;
-constexpr int kPkSquares = 81;
-constexpr int kPkObsWords = kPkChannels * kPkSquares;         // 4050
-constexpr int kPkRowWords = kPkObsWords + 5;                   // 16 220 B: obs, i64 policy, i64 value, f32 score
-constexpr int kPkValueAt = 3 * kPkChannels;                    // 150
-constexpr int kPkPolicyAt = kPkValueAt + kPkChannels;          // 200
-constexpr int kPkWords = kPkPolicyAt + 4;                      // 204
-constexpr uint32_t kPkActions = 81 * 139;
-static_assert(kPkWords * 4 % 16 == 0, "packed rows are 16-byte aligned");
-static_assert(kPkObsWords % 2 == 0, "the gather stores pairs");
 
 __global__ __launch_bounds__(kPkThreads) void sl_pack_kernel(const uint32_t* __restrict__ records,
                                                              const long long* __restrict__ src_rows, int n,
@@ -54,23 +42,7 @@ __global__ __launch_bounds__(kPkThreads) void sl_pack_kernel(const uint32_t* __r
     if (i >= n) return;
     const long long r = src_rows ? src_rows[i] : (long long)i;
     const uint32_t* src = records + (size_t)r * kPkRowWords;
-    bool bad = false;
-    for (int c = wave; c < kPkChannels; c += kPkWaves) {         // wave-uniform bounds: all 64 lanes reach every ballot
-        const uint32_t* plane = src + c * kPkSquares;
-        const uint32_t x0 = plane[lane];
-        const uint32_t x1 = lane < kPkSquares - 64 ? plane[64 + lane] : 0u;
-        const unsigned long long m0 = __ballot(x0 != 0u), m1 = __ballot(x1 != 0u);
-        const uint32_t v0 = __shfl(x0, m0 ? __ffsll(m0) - 1 : 0);
-        const uint32_t v1 = __shfl(x1, m1 ? __ffsll(m1) - 1 : 0);
-        const uint32_t value = m0 ? v0 : v1;                      // (no set lane at all: x1 of lane 0, which is 0)
-        bad |= __ballot((x0 != 0u && x0 != value) || (x1 != 0u && x1 != value)) != 0ull;
-        if (lane == 0) {
-            s_row[3 * c + 0] = (uint32_t)m0;
-            s_row[3 * c + 1] = (uint32_t)(m0 >> 32);
-            s_row[3 * c + 2] = (uint32_t)m1;
-            s_row[kPkValueAt + c] = value;
-        }
-    }
+    const bool bad = sl_pack_channels(src, s_row, lane, wave);
     if (lane == 0) s_bad[wave] = bad;
     bool bad_target = false;
     if (tid == 0) {
@@ -153,6 +125,43 @@ __global__ __launch_bounds__(kPkThreads) void sl_gather_kernel(const uint32_t* _
     }
 }
 
+// The visit rows of a batch (DeviceSLDataset with visit rows): one thread per (batch row, slot).  Visit word k of row idx[b]
+// is action | visits << 16, visits 0 = unused; the thread reads the row's eight words for the sum, so w_k is ONE division
+// (float)N_k / (float)sum whatever the geometry.  The row is reflected where sl_gather_kernel<true> reflects it: the same
+// mode and the same draw.  A used word that names no action counts in the flag word and is handed on as stored.
+constexpr int kVisitSlots = 8;
+
+__global__ __launch_bounds__(kPkThreads) void sl_gather_visits_kernel(const uint32_t* __restrict__ visits, long long n,
+                                                                      const long long* __restrict__ idx, int B, int mode,
+                                                                      unsigned long long seed, unsigned epoch,
+                                                                      int* __restrict__ actions_out,
+                                                                      float* __restrict__ weights_out, int* __restrict__ flags) {
+    const int t = blockIdx.x * kPkThreads + threadIdx.x;
+    const int b = t / kVisitSlots, k = t - b * kVisitSlots;
+    if (b >= B) return;
+    const long long r = idx[b];
+    int action = -1;
+    float weight = 0.f;
+    if (r >= 0 && r < n) {
+        const uint32_t* row = visits + (size_t)r * kVisitSlots;
+        uint32_t total = 0u;
+        for (int j = 0; j < kVisitSlots; ++j) total += row[j] >> 16;
+        const uint32_t word = row[k], count = word >> 16;
+        if (count != 0u) {
+            uint32_t a = word & 0xffffu;
+            bool reflect = mode == 1;
+            if (mode == 2)
+                reflect = (ka_mix64(seed ^ ka_mix64((((unsigned long long)epoch << 32) | (uint32_t)r) + kSaltMirror)) >> 63) != 0ull;
+            if (a >= kPkActions) { if (flags) atomicAdd(flags, 1); }
+            else if (reflect) a = sl_mirror_action(a);
+            action = (int)a;
+            weight = (float)count / (float)total;
+        }
+    }
+    actions_out[t] = action;
+    weights_out[t] = weight;
+}
+
 }  // namespace
 
 extern "C" int ka_sl_packed_words(void) { return kPkWords; }
@@ -196,4 +205,19 @@ extern "C" int ka_sl_gather_aug(const void* packed, long long n, const long long
                        value_out, reinterpret_cast<uint32_t*>(score_out), flags, mode, (unsigned long long)seed,
                        (unsigned)epoch);
     return ka_check_launch("sl_gather_aug");
+}
+
+extern "C" int ka_sl_gather_visits(const void* visits, long long n, const long long* idx, int B, int mode, long long seed,
+                                   int epoch, int* actions_out, float* weights_out, int* flags, void* stream) {
+    KA_REQUIRE(idx && actions_out && weights_out, "sl_gather_visits: null tensor");
+    KA_REQUIRE(n >= 0 && (visits || n == 0), "sl_gather_visits: n %lld without visit rows", n);
+    KA_REQUIRE(B > 0 && (long long)B * kVisitSlots < (1ll << 31), "sl_gather_visits: B %d", B);
+    KA_REQUIRE(mode >= 0 && mode <= 2, "sl_gather_visits: mode %d (0 plain, 1 every row reflected, 2 drawn per row)", mode);
+    KA_REQUIRE(epoch >= 0, "sl_gather_visits: epoch %d", epoch);
+    KA_REQUIRE((reinterpret_cast<uintptr_t>(visits) & 3) == 0, "sl_gather_visits: the visit rows must be 4-byte aligned");
+    const int threads = B * kVisitSlots;
+    hipLaunchKernelGGL(sl_gather_visits_kernel, dim3((threads + kPkThreads - 1) / kPkThreads), dim3(kPkThreads), 0,
+                       static_cast<hipStream_t>(stream), static_cast<const uint32_t*>(visits), n, idx, B, mode,
+                       (unsigned long long)seed, (unsigned)epoch, actions_out, weights_out, flags);
+    return ka_check_launch("sl_gather_visits");
 }

@@ -18,6 +18,12 @@ position with the reflected move is as valid a sample as the original.  ``gather
 (``ka_sl_gather_aug``: another mask bit per square and a closed form on the policy target; no second copy of the corpus);
 ``mirror_action`` / ``mirror_records`` / ``sl_mirror_draw`` restate it in numpy.  ``view(start, stop)`` is a read-only
 dataset over a range of the same memory: shards keep game order, so a tail range is a held-out set of whole games.
+
+A dataset may hold, beside every position, a *visit row* -- eight words ``action | visits << 16``, the visit counts a
+visit-count search left over the position's root candidates -- and an *info row* (who played the move, in which game): the
+samples ``keisei_amd.training.search_samples.SearchSamples.drain()`` appends through ``append_packed``.  It has them for every
+position or for none.  ``gather(..., visit_targets=True)`` hands the visit distribution out as ``visit_actions`` /
+``visit_weights`` (``ka_sl_gather_visits``, reflected with the position); ``visit_weights`` / ``mirror_visit_words`` restate it.
 """
 from __future__ import annotations
 
@@ -31,10 +37,11 @@ from keisei_amd import _lib
 from keisei_amd.sl.dataset import NUM_ACTIONS, OBS_SIZE, RECORD_SIZE, SLDataset, _RECORD
 
 __all__ = ["DeviceSLDataset", "pack_records", "unpack_records", "mirror_action", "mirror_records", "sl_mirror_draw",
-           "PACKED_WORDS", "PACKED_BYTES"]
+           "visit_weights", "mirror_visit_words", "PACKED_WORDS", "PACKED_BYTES", "VISIT_SLOTS", "INFO_WORDS"]
 
 PACKED_WORDS = 204                       # KA_SL_PACKED_WORDS
 PACKED_BYTES = 4 * PACKED_WORDS
+VISIT_SLOTS, INFO_WORDS = 8, 4           # a position's visit row (action | visits << 16 per slot) and its info row
 _CHANNELS, _SQUARES = 50, 81
 _VALUE_AT, _POLICY_AT = 3 * _CHANNELS, 4 * _CHANNELS
 _INT_MAX = 2 ** 31 - 1
@@ -153,6 +160,35 @@ def sl_mirror_draw(seed: int, epoch: int, indices) -> np.ndarray:
     return (h >> np.uint64(63)).astype(bool)
 
 
+def visit_weights(words) -> np.ndarray:
+    """The policy target of visit words ``(..., 8)`` (``action | visits << 16``, visits 0 = unused) as ``ka_sl_gather_visits``
+    forms it: float32 ``w_k = (float)N_k / (float)sum N``, one IEEE division, 0 in the unused slots and in a row without
+    a used slot."""
+    n = (np.asarray(words).astype(np.uint32, copy=False) >> np.uint32(16)).astype(np.float32)
+    total = n.sum(axis=-1, keepdims=True, dtype=np.float32)          # integers below 2^24: exact in any order
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(n > 0, n / total, np.float32(0)).astype(np.float32)
+
+
+def mirror_visit_words(words) -> np.ndarray:
+    """Visit words of the reflected position: every used slot's action through ``mirror_action``, the visits and the
+    unused slots as they are (``ka_sl_gather_visits`` mode 1 on the words).  An involution."""
+    w = np.asarray(words).astype(np.uint32, copy=False)
+    used = (w >> np.uint32(16)) > 0
+    act = np.where(used, w & np.uint32(0xFFFF), 0).astype(np.int64)
+    return np.where(used, (w & np.uint32(0xFFFF0000)) | mirror_action(act).astype(np.uint32), w).astype(np.uint32)
+
+
+def _refuse_mixing(n: int, has_visits: bool, adds_visits: bool, how: str) -> None:
+    """A dataset has visit rows for every position or for none."""
+    if has_visits and not adds_visits:
+        raise ValueError(f"this dataset holds visit rows: {how} would add positions without them (a dataset has visit rows "
+                         "for every position or for none)")
+    if adds_visits and not has_visits and n > 0:
+        raise ValueError(f"this dataset holds {n} positions without visit rows: {how} with visits would mix the two (a "
+                         "dataset has visit rows for every position or for none)")
+
+
 # ---------------------------------------------------------------------------------------------- the device dataset
 def _require_library() -> None:
     words = _lib.query("ka_sl_packed_words")                    # raises KeiseiHipError without the library
@@ -177,6 +213,8 @@ class DeviceSLDataset:
             raise ValueError(f"DeviceSLDataset lives on a GPU, got device {dev}")
         self._device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
         self._packed = torch.empty(0, PACKED_WORDS, dtype=torch.int32, device=self._device)
+        self._visits: Optional[torch.Tensor] = None              # int32 (capacity, 8) / (capacity, 4) beside the packed rows:
+        self._info: Optional[torch.Tensor] = None                # for every position or for none
         self._n = 0
         self._read_only = False                                  # a view(): rows of another dataset's memory
         # flags of the pack launches not read yet: (index of the launch's first position, int32[4] on the device)
@@ -200,6 +238,18 @@ class DeviceSLDataset:
         """The packed rows, int32 ``(len, 204)``: a view of the dataset's memory."""
         return self._packed[:self._n]
 
+    @property
+    def visits(self) -> Optional[torch.Tensor]:
+        """The visit rows, int32 ``(len, 8)`` (``action | visits << 16`` per slot, visits 0 = unused): a view of the
+        dataset's memory; None for a dataset without them."""
+        return None if self._visits is None else self._visits[:self._n]
+
+    @property
+    def info(self) -> Optional[torch.Tensor]:
+        """The info rows, int32 ``(len, 4)`` (``model | mover << 16``, index of the move in its game, env, game number);
+        None for a dataset without visit rows."""
+        return None if self._info is None else self._info[:self._n]
+
     # ------------------------------------------------------------------ filling
     def _reserve(self, total: int) -> None:
         """Room for ``total`` positions; growth doubles, the rows keep their order."""
@@ -209,6 +259,11 @@ class DeviceSLDataset:
         with torch.cuda.device(self._device):
             grown = torch.empty(max(total, 2 * cap, 1024), PACKED_WORDS, dtype=torch.int32, device=self._device)
             grown[:self._n].copy_(self._packed[:self._n])
+            if self._visits is not None:
+                for name, width in (("_visits", VISIT_SLOTS), ("_info", INFO_WORDS)):
+                    side = torch.zeros(grown.shape[0], width, dtype=torch.int32, device=self._device)
+                    side[:self._n].copy_(getattr(self, name)[:self._n])
+                    setattr(self, name, side)
         self._packed = grown
 
     def _pack(self, raw: torch.Tensor, src_rows: Optional[torch.Tensor], count: int, flags: torch.Tensor) -> None:
@@ -223,6 +278,7 @@ class DeviceSLDataset:
         16 220-byte records onto the end.  Nothing is read back: ``check()`` reports what could not be packed."""
         if self._read_only:
             raise ValueError("this dataset is a view of another one's memory and cannot grow: append to its parent")
+        _refuse_mixing(self._n, self._visits is not None, False, "append_raw")
         raw = raw_device_bytes
         if raw.dtype != torch.uint8 or not raw.is_contiguous() or raw.device != self._device or raw.numel() % RECORD_SIZE:
             raise ValueError(f"raw_device_bytes must be a contiguous uint8 tensor of whole {RECORD_SIZE}-byte records "
@@ -237,6 +293,49 @@ class DeviceSLDataset:
             return
         self._reserve(self._n + rows.size)
         self._pack(raw, torch.from_numpy(rows).to(self._device), int(rows.size), _fresh_flags(1, self._device)[0])
+
+    def append_packed(self, packed: torch.Tensor, visits: Optional[torch.Tensor] = None,
+                      info: Optional[torch.Tensor] = None) -> None:
+        """Append positions that are already packed -- ``packed`` int32 ``(m, 204)`` on the dataset's device -- device to
+        device; with ``visits`` int32 ``(m, 8)`` (and ``info`` int32 ``(m, 4)``, zeros when left out) the dataset holds visit
+        rows.  A dataset has them for every position or for none: mixing raises.  The rows are validated on the device
+        and nothing is read back: ``check()`` reports the lowest row whose policy lies outside [0, 11259), whose value
+        outside {0, 1, 2}, that has a used visit word naming no action, or that has no used visit word at all."""
+        if self._read_only:
+            raise ValueError("this dataset is a view of another one's memory and cannot grow: append to its parent")
+        _refuse_mixing(self._n, self._visits is not None, visits is not None, "append_packed")
+        if info is not None and visits is None:
+            raise ValueError("info rows come with visit rows: append_packed(info=) needs visits=")
+        m = int(packed.shape[0]) if packed.dim() == 2 else -1
+        for name, t, width in (("packed", packed, PACKED_WORDS), ("visits", visits, VISIT_SLOTS), ("info", info, INFO_WORDS)):
+            if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (m, width) or t.device != self._device
+                                  or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous int32 tensor ({max(m, 0)}, {width}) on {self._device}")
+        if m == 0:
+            return
+        self._reserve(self._n + m)
+        with torch.cuda.device(self._device):
+            if visits is not None and self._visits is None:
+                cap = self._packed.shape[0]
+                self._visits = torch.zeros(cap, VISIT_SLOTS, dtype=torch.int32, device=self._device)
+                self._info = torch.zeros(cap, INFO_WORDS, dtype=torch.int32, device=self._device)
+            lo = self._n
+            self._packed[lo:lo + m].copy_(packed)
+            policy, value = packed[:, _POLICY_AT], packed[:, _POLICY_AT + 1]
+            bad = (policy < 0) | (policy >= NUM_ACTIONS) | (value < 0) | (value > 2)
+            if visits is not None:
+                self._visits[lo:lo + m].copy_(visits)
+                if info is None:
+                    self._info[lo:lo + m].zero_()
+                else:
+                    self._info[lo:lo + m].copy_(info)
+                used = (visits >> 16) != 0                       # (an arithmetic shift: a count with bit 15 set is used too)
+                bad |= (used & ((visits & 0xFFFF) >= NUM_ACTIONS)).any(1) | ~used.any(1)
+            at = torch.where(bad, torch.arange(m, device=self._device), torch.full((), _INT_MAX, device=self._device)).min()
+            zero = torch.zeros((), dtype=torch.int64, device=self._device)
+            flags = torch.stack([zero, zero + _INT_MAX, bad.sum(), at]).to(torch.int32)
+        self._unread.append((lo, flags))
+        self._n += m
 
     def check(self, describe: Optional[Callable[[int, bool], None]] = None) -> None:
         """Read the flags of every pack launch since the last check -- one read -- and raise ``ValueError`` for the
@@ -260,8 +359,13 @@ class DeviceSLDataset:
             describe(index, kind == 0)
         if kind == 0:
             policy, value = self._packed[index, _POLICY_AT:_POLICY_AT + 2].cpu().tolist()
+            more = ""
+            if self._visits is not None:
+                words = [f"{w & 0xFFFFFFFF:#x}" for w in self._visits[index].cpu().tolist()]
+                more = (f"; its visit words {words} must hold a used slot, and every used slot (visits << 16 != 0) an action "
+                        f"in [0, {NUM_ACTIONS})")
             raise ValueError(f"Invalid targets (policy_target={policy}, value_target={value} as stored) at index {index}: "
-                             f"policy must be in [0, {NUM_ACTIONS}), value 0 (W), 1 (D), or 2 (L)")
+                             f"policy must be in [0, {NUM_ACTIONS}), value 0 (W), 1 (D), or 2 (L){more}")
         raise ValueError(f"Unpackable observation at index {index}: {_UNPACKABLE}")
 
     @classmethod
@@ -336,16 +440,24 @@ class DeviceSLDataset:
             raise IndexError(f"view [{start}, {stop}) out of range for dataset with {self._n} positions")
         part = DeviceSLDataset(self._device)
         part._packed = self._packed[start:stop]
+        if self._visits is not None:
+            part._visits, part._info = self._visits[start:stop], self._info[start:stop]
         part._n = stop - start
         part._read_only = True
         return part
 
     # ------------------------------------------------------------------ reading
-    def gather(self, idx: torch.Tensor, flag: torch.Tensor, *, mirror: int = MIRROR_NONE, seed: int = 0, epoch: int = 0) -> dict:
+    def gather(self, idx: torch.Tensor, flag: torch.Tensor, *, mirror: int = MIRROR_NONE, seed: int = 0, epoch: int = 0,
+               visit_targets: bool = False) -> dict:
         """The batch of the int64 device tensor ``idx`` as fresh device tensors, keys / dtypes / shapes of
         ``SLDataset.read_batch``: one launch, no host work.  An index outside the dataset adds 1 to ``flag`` (int32[1] on
         the device) and gives a zero row.  ``mirror``: 0 the rows as stored, 1 every row reflected left to right, 2 the rows
-        ``sl_mirror_draw(seed, epoch, idx)`` names."""
+        ``sl_mirror_draw(seed, epoch, idx)`` names.  ``visit_targets=True`` (a dataset with visit rows) adds
+        ``visit_actions`` (int32 ``(B, 8)``, -1 = unused) and ``visit_weights`` (fp32 ``(B, 8)``, ``visit_weights`` of the rows)
+        from a second launch, ``ka_sl_gather_visits``, which reflects the actions of the rows the first one reflects."""
+        if visit_targets and self._visits is None:
+            raise ValueError("visit_targets=True needs a dataset with visit rows (append_packed(..., visits=), or the "
+                             "dataset SearchSamples.drain() gives)")
         if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != self._device or not idx.is_contiguous():
             raise ValueError(f"idx must be a contiguous 1-d int64 tensor on {self._device}")
         if mirror not in (MIRROR_NONE, MIRROR_ALL, MIRROR_DRAWN):
@@ -366,6 +478,14 @@ class DeviceSLDataset:
                 _lib.call("ka_sl_gather_aug", self._packed, self._n, idx, B, out["observation"], out["policy_target"],
                           out["value_target"], out["score_target"], flag, int(mirror),
                           seed64 - (1 << 64) if seed64 >> 63 else seed64, int(epoch), _lib.stream_ptr(dev))
+            if visit_targets:
+                out["visit_actions"] = torch.empty(B, VISIT_SLOTS, dtype=torch.int32, device=dev)
+                out["visit_weights"] = torch.empty(B, VISIT_SLOTS, dtype=torch.float32, device=dev)
+                if B:
+                    seed64 = int(seed) & _M64
+                    _lib.call("ka_sl_gather_visits", self._visits, self._n, idx, B, int(mirror),
+                              seed64 - (1 << 64) if seed64 >> 63 else seed64, int(epoch), out["visit_actions"],
+                              out["visit_weights"], flag, _lib.stream_ptr(dev))
         return out
 
     def read_batch(self, indices) -> dict:

@@ -15,6 +15,9 @@ trained on data).  Two execution paths:
   minibatch is one ``ka_sl_gather`` launch in front of the same per-batch body -- no thread, no pinned copy, no upload
   per batch.  Asked for where the fused path cannot run, it raises instead of falling back.  ``SLConfig.mirror_augment``
   has that gather reflect, left to right, the positions a draw of (``mirror_seed``, epoch, position) names.
+  ``SLConfig.visit_targets`` (a dataset with visit rows: the samples of the arena's visit-count search,
+  ``SearchSamples.drain()``) has it hand out the visit distribution of every position too, and ``ka_policy_ce_soft`` takes
+  the place of ``ka_policy_ce``: the policy loss is the cross-entropy against that distribution.
 * **held-out evaluation** (``evaluate()``, not in the reference; the fused path only): eval-mode forwards under ``no_grad``
   over a ``DeviceSLDataset`` -- ``eval_dataset``, typically a tail ``view()`` of the corpus -- one gather and one
   ``ka_sl_eval`` per chunk, the losses as sums over positions and the top-1 / top-k / value hit counts in a 64-byte
@@ -65,6 +68,9 @@ class SLConfig:
     # field and the last positional argument); not in the reference
     mirror_augment: bool = field(default=False, kw_only=True)
     mirror_seed: int = field(default=0, kw_only=True)
+    # the policy target is the dataset's visit distribution (a DeviceSLDataset with visit rows, the samples of a visit-count
+    # search) and the policy loss ka_policy_ce_soft; keyword-only for the same reason; not in the reference
+    visit_targets: bool = field(default=False, kw_only=True)
     device_resident: bool = False          # hold the dataset packed in device memory (DeviceSLDataset); not in the reference
 
     def __post_init__(self) -> None:
@@ -137,6 +143,9 @@ class SLTrainer(FusedAdamMixin):
         if config.mirror_augment and dataset is None and not config.device_resident:
             raise ValueError("mirror_augment reflects positions inside the device-resident gather: it needs "
                              "device_resident=True or a DeviceSLDataset, there is no reflection on the shard path")
+        if config.visit_targets and dataset is None and not config.device_resident:
+            raise ValueError("visit_targets trains on the visit rows of a device-resident dataset: it needs a "
+                             "DeviceSLDataset with visit rows (device_resident=True or dataset=), the shard path has none")
         if dataset is not None or config.device_resident:
             # the positions stay packed on the device and config.data_dir is read at most once, here; there is no other
             # way to run this than the fused path, and no falling back to the shard path
@@ -148,6 +157,9 @@ class SLTrainer(FusedAdamMixin):
                                                       allow_placeholder=config.allow_placeholder)
             if dataset.device != self.device:
                 raise ValueError(f"the dataset lives on {dataset.device}, the model on {self.device}")
+            if config.visit_targets and dataset.visits is None:
+                raise ValueError("visit_targets=True needs a dataset with visit rows (SearchSamples.drain(), or "
+                                 "append_packed(..., visits=)); this dataset holds none")
             self.device_dataset = dataset
             self.dataset = self.dataloader = self._index_loader = None
             return
@@ -228,8 +240,8 @@ class SLTrainer(FusedAdamMixin):
                     out_m=torch.zeros(16, device=dev), A=None)
 
     def _fused_batch(self, ep: dict, batch: dict) -> None:
-        """One minibatch of device tensors: forward, ``ka_policy_ce``, ``ka_value_loss``, backward, ``ka_clip_adam_step``.
-        The ONE body of the shard epoch and the device-resident epoch."""
+        """One minibatch of device tensors: forward, ``ka_policy_ce`` (``ka_policy_ce_soft`` with ``visit_targets``),
+        ``ka_value_loss``, backward, ``ka_clip_adam_step``.  The ONE body of the shard epoch and the device-resident epoch."""
         cfg, dev, call = self.config, self.device, _lib.call
         st, sp, scaler_t, gscale, acc, flags = ep["st"], ep["sp"], ep["scaler_t"], ep["gscale"], ep["acc"], ep["flags"]
         group = self.optimizer.param_groups[0]
@@ -243,8 +255,12 @@ class SLTrainer(FusedAdamMixin):
         rowloss = torch.empty(B, device=dev)
         rowent = torch.zeros(B, device=dev)
         dv, ds = torch.empty(B, 3, device=dev), torch.empty(B, 1, device=dev)
-        call("ka_policy_ce", logits, batch["policy_target"], None, dlogits, rowloss, flags, gscale,
-             float(cfg.lambda_policy) / B, B, A, sp)
+        if cfg.visit_targets:                      # the cross-entropy against the batch's visit distribution
+            call("ka_policy_ce_soft", logits, batch["visit_actions"], batch["visit_weights"],
+                 int(batch["visit_actions"].shape[1]), dlogits, rowloss, flags, gscale, float(cfg.lambda_policy) / B, B, A, sp)
+        else:
+            call("ka_policy_ce", logits, batch["policy_target"], None, dlogits, rowloss, flags, gscale,
+                 float(cfg.lambda_policy) / B, B, A, sp)
         call("ka_value_loss", out.value_logits, out.score_lead, batch["value_target"], batch["score_target"], None,
              rowloss, rowent, dv, ds, ep["out_m"], acc, gscale, float(cfg.lambda_policy), float(cfg.lambda_value),
              float(cfg.lambda_score), 0.0, 0, B, sp)
@@ -271,7 +287,9 @@ class SLTrainer(FusedAdamMixin):
         if host[8]:
             raise IndexError(f"{int(host[8])} indices outside the dataset reached the gather kernel")
         if host[7]:
-            raise ValueError(f"policy_target outside [0, {ep['A']}) reached the loss kernel")
+            raise ValueError(f"policy_target outside [0, {ep['A']}) reached the loss kernel" if not self.config.visit_targets else
+                             f"a visit target outside [0, {ep['A']}), a weight that is negative or not finite, or a position "
+                             "without a visited move reached the loss kernel")
         return host[:3], batches
 
     def _epoch_fused(self):
@@ -325,6 +343,8 @@ class SLTrainer(FusedAdamMixin):
         how = {}
         if self.config.mirror_augment:                           # the draw of (mirror_seed, this epoch, position)
             how = dict(mirror=MIRROR_DRAWN, seed=self.config.mirror_seed, epoch=self.epochs_done)
+        if self.config.visit_targets:
+            how["visit_targets"] = True
         for lo in range(0, order.shape[0], self.config.batch_size):
             self._fused_batch(ep, ds.gather(order[lo:lo + self.config.batch_size], gather_flag, **how))
             batches += 1

@@ -13,6 +13,8 @@ from .mcts_search import (MctsControls, MctsRestatement, MctsSearch, MctsStats, 
                           mcts_simulations, mcts_table, visit_policy)
 from .policy_insight import InsightRecorder, PolicyInsight, action_usi, insight_dict, policy_insight  # noqa: F401
 from .sampling import ControlledSample, SamplingControls, controls_table, sample_controlled  # noqa: F401
+from .search_samples import (SearchSamples, SearchSampleStats, search_sample_step_host, unpack_visit_words,  # noqa: F401
+                             visit_words)
 from .selfplay_rollout import SelfPlayRollout, SelfPlayStats  # noqa: F401
 from .tree_search import (SearchControls, SearchStats, SearchTree, TreeSearch, search_backup_select,  # noqa: F401
                           search_expansions, search_leaf_q, search_records, search_table)

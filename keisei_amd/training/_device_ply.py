@@ -28,6 +28,7 @@ from .mate_search import Mate3Search, MateSearch, mate3_reply_table
 from .mcts_search import MctsSearch
 from .policy_insight import InsightRecorder
 from .sampling import GAME_PLY_BYTE
+from .search_samples import SearchSamples
 from .tree_search import TreeSearch
 from .value_adapter import MultiHeadValueAdapter
 
@@ -93,6 +94,9 @@ class DevicePly:
     (``ka_mate_fork``, the env step over the child rows, ``ka_mate_choose``; no forward): it overrides their choice, and the
     insight describes the move actually played; ``mate_rows`` / ``mate_reply_cap`` > 0 put the mate in three behind it
     (``Mate3Search``: the grandchild rows per env and the third ply's rows per grandchild; seven more launches, no forward).
+    ``search_samples=rows_per_env > 0`` (only with the visit-count search; ``search_samples.py``) keeps the searched
+    positions with their visit counts and, once the game has ended, its result as training rows on the device: one launch,
+    ``ka_search_sample_step``, that the loop enqueues through ``sample(...)`` between the env step and its bookkeeping launch.
     An option left at 0 / None adds no launch and allocates nothing."""
 
     def __init__(self, group, num_envs: int, max_ply: int, *, start_pool_capacity: int = 0, game_log: int = 0,
@@ -102,7 +106,7 @@ class DevicePly:
                  lookahead_reply_width: int = 0, search_table: Optional[np.ndarray] = None, search_width: int = 0,
                  search_expansions: int = 0, mate_table: Optional[np.ndarray] = None, mate_cap: int = 0, mate_rows: int = 0,
                  mate_reply_cap: int = 0, mcts_table: Optional[np.ndarray] = None, mcts_width: int = 0,
-                 mcts_simulations: int = 0) -> None:
+                 mcts_simulations: int = 0, search_samples: int = 0) -> None:
         if search_table is not None and lookahead_table is not None:
             raise ValueError("search_table cannot be combined with lookahead_table: the search stands where the lookahead stands")
         if mcts_table is not None and (lookahead_table is not None or search_table is not None):
@@ -146,6 +150,13 @@ class DevicePly:
                 self.mate_reply_table = torch.from_numpy(mate3_reply_table(mate_table)).to(dev)
             elif mate_table is not None and mate_cap > 0:
                 self.mate = MateSearch(self.env, int(mate_cap))
+            # the samples of the visit-count search: a region of rows per env, allocated once
+            self.search_samples: Optional[SearchSamples] = None
+            if search_samples:
+                if self.mcts is None:
+                    raise ValueError("search_samples needs the visit-count search (mcts_table with a width above 0): a "
+                                     "sample is a searched position with its visit counts")
+                self.search_samples = SearchSamples(self.env, self.mcts, search_samples)
             self.seat(group, controls)
 
     def seat(self, group, controls: Optional[np.ndarray]) -> None:
@@ -169,6 +180,8 @@ class DevicePly:
             self.search.clear()
         if self.mcts is not None:
             self.mcts.clear()
+        if self.search_samples is not None:
+            self.search_samples.begin()
         if self.mate3 is not None:
             self.mate3.clear()
         elif self.mate is not None:
@@ -216,6 +229,14 @@ class DevicePly:
             fn = self.game_log.step_env if "ids" in kw else self.game_log.step
             fn(self.actions, r.rewards, r.terminated, r.truncated, pre, r.step_metadata.termination_reason,
                nlegal=self.n_legal, **kw)
+
+    def sample(self, r, pre: torch.Tensor, model_of: torch.Tensor, stream) -> None:
+        """The search-sample launch behind the env step ``r``, before the loop's bookkeeping launch rewrites ``model_of``:
+        the position before the move lies in the env's previous buffers, ``pre`` are its players to move."""
+        if self.search_samples is not None:
+            env = self.env
+            self.search_samples.step(env._obs[env._cur ^ 1], pre, model_of, self.actions, r.step_metadata.material_balance,
+                                     r.rewards, r.terminated, r.truncated, stream)
 
     def live_games(self, owner: str, envs: Optional[Sequence[int]], **kw) -> List[RecordedGame]:
         if self.game_log is None:

@@ -34,6 +34,8 @@ synchronisation:
     ka_shogi_env_step                           (csrc/shogi_env.hip)
     ka_arena_features_step                      (csrc/arena.hip, only with features=True: the reference's per-slot
                                                  GameFeatureTracker, one record per finished game)
+    ka_search_sample_step                       (csrc/search_samples.hip, only with search_samples > 0: the searched
+                                                 positions with their visit counts, labelled when their game ends)
     ka_gamelog_step                             (csrc/gamelog.hip, only with game_log > 0: the finished games, move
                                                  by move, one record per game the referee tallies)
     ka_arena_referee                            (csrc/arena.hip: tally by the last-mover rule, close slots, seat the
@@ -74,6 +76,7 @@ from .mate_search import Mate3Stats, MateStats, arena_mate, arena_mate3, mate3_r
 from .mcts_search import MctsStats, arena_mcts, mcts_table
 from .model_group import SEResNetGroup
 from .sampling import GAME_PLY_BYTE, arena_controls, controls_table
+from .search_samples import arena_search_samples
 from .tree_search import SearchStats, arena_search, search_table
 
 _HDR, _SLOT = 8, 8                      # int32 words of the state header and of one slot (csrc/arena.hip)
@@ -325,6 +328,11 @@ class MatchArena:
     largest ``width`` and ``simulations`` given; ``set_mcts`` rewrites the table between rounds without a new capture, up to
     those.  ``RoundStats.mcts`` carries the counters.  With None nothing is allocated and the launches are what they were.
     Not together with ``lookahead=`` or ``search=`` and not with ``collect=True``.
+    ``search_samples=rows_per_env > 0`` (only with ``mcts=``; ``search_samples.py``) adds one launch,
+    ``ka_search_sample_step``, behind the env step: every searched position is written, packed as a ``DeviceSLDataset`` row,
+    with its visit counts into the env's region of ``rows_per_env`` rows, and a game that ends labels its rows W / D / L.
+    ``arena.search_samples.drain()`` between two rounds hands the labelled rows over as a ``DeviceSLDataset`` that
+    ``SLTrainer`` with ``visit_targets=True`` trains on.  With 0 nothing is allocated and the launches are what they were.
     ``mate=`` (a ``MateControls`` for every model, one per model, or a dict by model index; ``mate_search.py``) adds a
     rules-only mate-in-one check behind the lookahead or the search and before the insight: the legal moves that give check
     are forked (at most ``max_checks`` of them, in ascending action order), the env's own step decides them, and a move that
@@ -342,12 +350,13 @@ class MatchArena:
                  collect: bool = False, features: bool = False, start_pool_capacity: int = 0,
                  game_log: int = 0, move_history: bool = False, insight: int = 0,
                  insight_temperature: float = 1.0, sampling=None, lookahead=None, search=None, mate=None,
-                 mcts=None) -> None:
+                 mcts=None, search_samples: int = 0) -> None:
         if len(group) == 0:
             raise ValueError("MatchArena needs a group with at least one model")
         if num_envs <= 0 or envs_per_match <= 0 or num_envs % envs_per_match != 0:
             raise ValueError(f"num_envs ({num_envs}) must be a positive multiple of envs_per_match ({envs_per_match})")
         check_loop_args(max_ply, sync_every, graph, record, start_pool_capacity, game_log)
+        search_samples = arena_search_samples(search_samples, mcts, len(group))
         if features and start_pool_capacity > 0:
             raise ValueError("features=True cannot be combined with start_pool_capacity > 0: the opening and rook-square "
                              "style features are defined from the standard start position")
@@ -376,12 +385,13 @@ class MatchArena:
                                    lookahead_width=la_width, lookahead_reply_width=la_reply, search_table=se_table,
                                    search_width=se_width, search_expansions=se_expansions, mate_table=mt_table,
                                    mate_cap=mt_cap, mate_rows=mt_rows, mate_reply_cap=mt_reply, mcts_table=mc_table,
-                                   mcts_width=mc_width, mcts_simulations=mc_sims)
+                                   mcts_width=mc_width, mcts_simulations=mc_sims, search_samples=int(search_samples))
         self.env, self.game_log, self.insight = ply.env, ply.game_log, ply.insight
         self._actions, self._logp, self._nlegal = ply.actions, ply.log_probs, ply.n_legal
         self._ctl, self._la_table, self._la = ply.ctl, ply.lookahead_table, ply.lookahead
         self._se_table, self._se = ply.search_table, ply.search
         self._mc_table, self.mcts = ply.mcts_table, ply.mcts
+        self.search_samples = ply.search_samples
         self._mt_table, self._mt = ply.mate_table, ply.mate
         self._mt3, self._mt3_table = ply.mate3, ply.mate_reply_table
         with torch.cuda.device(dev):
@@ -549,6 +559,7 @@ class MatchArena:
                       self._nlegal, meta.captured_piece, meta.termination_reason, meta.ply_count, r.rewards, r.terminated,
                       r.truncated, self._facc, self._frecords, self._fcursors, self._fcap, st)
         # before the referee: it rewrites model_of and the round ply
+        ply.sample(r, pre, self._model_of, st)
         ply.log(r, pre, live=self._model_of, pairs=sp + 4 * _HDR, pair_stride=_SLOT, envs_per_pair=self.envs_per_match,
                 ply_counter=sp + 4 * _PLY)
         # env._err[1] is the VecEnv's refusal latch: the referee copies it into the state so the host sees a refused
@@ -594,6 +605,8 @@ class MatchArena:
                        node_done=(mc.terminated | mc.truncated).cpu().reshape(shape),
                        node_logits=mc.logits.cpu().reshape(-1, ACTION_SPACE), node_mask_bits=mc.mask_bits.cpu(),
                        node_model_of=mc.model_of.cpu().reshape(shape))
+        if self.search_samples is not None:
+            rec.update(material_balance=self.env._material[self.env._cur].cpu())
         if self._mt is not None:
             rec.update(mate_records=self._mt.records().cpu())
         if self._mt3 is not None:
