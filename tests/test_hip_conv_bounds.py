@@ -21,54 +21,85 @@ def st():
     return _lib.stream_ptr()
 
 
-def guarded(shape, dtype, fill):
-    """(full, mid): full has G extra rows of the leading dimension before and after; mid = full[G:-G] is contiguous.
-    fill: a float, or "pattern" for the output guard bit pattern."""
-    full_shape = (shape[0] + 2 * G, *shape[1:])
+def guarded(shape, dtype, fill, g=G, off=0, device=DEV):
+    """(full, mid): full has g extra rows of the leading dimension before and after; mid = full[g:-g] is contiguous.
+    fill: a float, or "pattern" for the output guard bit pattern.  off (one-dimensional tensors only): mid starts `off`
+    elements later, full is 8 elements longer, and the elements on both sides of mid are guards all the same."""
+    assert off == 0 or (len(shape) == 1 and 0 < off < 8)
+    full_shape = (shape[0] + 2 * g + (8 if off else 0), *shape[1:])
     if fill == "pattern":
         it, v = PATTERN[dtype]
-        full = torch.full(full_shape, v, dtype=it, device=DEV).view(dtype)
+        full = torch.full(full_shape, v, dtype=it, device=device).view(dtype)
     else:
-        full = torch.full(full_shape, fill, dtype=dtype, device=DEV)
-    return full, full[G:G + shape[0]]
+        full = torch.full(full_shape, fill, dtype=dtype, device=device)
+    return full, full[g + off:g + off + shape[0]]
 
 
 def bits(t):
     return t.view(PATTERN[t.dtype][0])
 
 
-def guards_intact(full):
+def middle(full, g=G, off=0):
+    return full[g + off:full.shape[0] - g - (8 - off if off else 0)]
+
+
+def guards_intact(full, g=G, off=0):
     it, v = PATTERN[full.dtype]
     b = full.view(it)
-    return bool((b[:G] == v).all()) and bool((b[-G:] == v).all())
+    end = full.shape[0] - g - (8 - off if off else 0)
+    return bool((b[:g + off] == v).all()) and bool((b[end:] == v).all())
 
 
-def run_guarded(call, inputs, outputs, in_fill):
-    """inputs: name -> tensor (leading dimension guarded); outputs: name -> (shape, dtype).  Returns name -> full tensor."""
+def _spec(entry, first):
+    """(what, guard rows, off) of an entry of run_guarded; first = 1: a tensor or (tensor[, g[, off]]), first = 2: (shape, dtype[,
+    g[, off]]), what = (shape, dtype).  The default is G rows and no offset."""
+    if first == 2:
+        return (entry[0], entry[1]), (entry[2] if len(entry) > 2 else G), (entry[3] if len(entry) > 3 else 0)
+    if isinstance(entry, tuple):
+        return entry[0], entry[1], (entry[2] if len(entry) > 2 else 0)
+    return entry, G, 0
+
+
+def run_guarded(call, inputs, outputs, in_fill, inout=None, device=DEV):
+    """inputs: name -> tensor (leading dimension guarded) or (tensor, guard rows[, off]); outputs: name -> (shape, dtype[, guard
+    rows[, off]]); inout: like inputs, for tensors the call updates in place (pattern guards).  Returns name -> full tensor."""
     bufs, fulls = {}, {}
-    for n, t in inputs.items():
-        full, mid = guarded(tuple(t.shape), t.dtype, in_fill)
+    for n, e in inputs.items():
+        t, g, off = _spec(e, 1)
+        full, mid = guarded(tuple(t.shape), t.dtype, in_fill, g, off, device)
         mid.copy_(t)
         bufs[n] = mid
-    for n, (shape, dt) in outputs.items():
-        fulls[n], bufs[n] = guarded(shape, dt, "pattern")
-    torch.cuda.synchronize()
+    for n, e in (inout or {}).items():
+        t, g, off = _spec(e, 1)
+        fulls[n], bufs[n] = guarded(tuple(t.shape), t.dtype, "pattern", g, off, device)
+        bufs[n].copy_(t)
+    for n, e in outputs.items():
+        (shape, dt), g, off = _spec(e, 2)
+        fulls[n], bufs[n] = guarded(shape, dt, "pattern", g, off, device)
+    sync = torch.device(device).type == "cuda"
+    if sync:
+        torch.cuda.synchronize()
     call(bufs)
-    torch.cuda.synchronize()
+    if sync:
+        torch.cuda.synchronize()
     return fulls
 
 
-def check_guarded(call, inputs, outputs, finite=None):
-    """Both runs: output guards intact; every output's middle finite (the names in `finite`, default all) and bit-identical
+def check_guarded(call, inputs, outputs, finite=None, inout=None, valid=None, device=DEV):
+    """Both runs: output guards intact; every output's middle finite (the names in `finite`, default all; valid: name -> a
+    function that cuts the region that must be finite out of the middle, for outputs with pad columns) and bit-identical
     between zero and NaN input guards.  Returns the middles of the NaN-guard run."""
-    runs = [run_guarded(call, inputs, outputs, f) for f in (0.0, float("nan"))]
+    runs = [run_guarded(call, inputs, outputs, f, inout, device) for f in (0.0, float("nan"))]
+    where = {n: _spec(e, 2)[1:] for n, e in outputs.items()}
+    where.update({n: _spec(e, 1)[1:] for n, e in (inout or {}).items()})
     for fill, res in zip(("zero", "NaN"), runs):
         for n, full in res.items():
-            assert guards_intact(full), f"{n}: guard rows overwritten ({fill} input guards)"
-    mids = [{n: full[G:-G] for n, full in res.items()} for res in runs]
-    for n in outputs:
+            assert guards_intact(full, *where[n]), f"{n}: guard rows overwritten ({fill} input guards)"
+    mids = [{n: middle(full, *where[n]) for n, full in res.items()} for res in runs]
+    for n in where:
         if finite is None or n in finite:
-            assert bool(torch.isfinite(mids[1][n].float()).all()), f"{n}: non-finite (or unwritten) element in the valid region"
+            region = (valid or {}).get(n, lambda t: t)
+            assert bool(torch.isfinite(region(mids[1][n]).float()).all()), f"{n}: non-finite (or unwritten) element in the valid region"
             assert torch.equal(bits(mids[0][n]), bits(mids[1][n])), f"{n}: depends on memory past the tensors"
     return mids[1]
 

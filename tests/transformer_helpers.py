@@ -656,6 +656,104 @@ def ulp32(t):
     return t.abs().clamp_min(2.0 ** -126) * 2.0 ** -23
 
 
+# ------------------------------------------------------------------------------------------------ guard-band cases
+# Shared by tests/test_transformer_bounds_cpu.py and tests/test_hip_transformer_bounds.py.  The tile constants of
+# csrc/transformer.hip beside BM / BN / K_TILE / TN_ROWS / SP above: kKsRows, kGM, kGN, the 128-column tiles of the TN kernel,
+# the (board, head) pairs of a register-attention workgroup.
+K256_ROWS, BIG_M, BIG_N, TN_COLS, ATTN_PAIRS = 128, 256, 256, 128, 4
+GUARD_FLAT = 4096                                # elements on each side of a tensor a flat grid-stride kernel walks
+# what one workgroup spans along the guarded (leading) dimension of its tensors, and the guard rows the tests put there
+SPAN = {"tiled": max(BM, BN), "map": max(BM, BN), "k256": K256_ROWS, "big": max(BIG_M, BIG_N), "tn": max(TN_ROWS, TN_COLS),
+        "attn": ATTN_PAIRS * SP}
+GUARD_ROWS = {"tiled": 256, "map": 256, "k256": 256, "big": 512, "tn": 256, "attn": ATTN_PAIRS * SP}
+
+
+def round8(n):
+    return ceil_div(n, 8) * 8
+
+
+def flat_rows(cols):
+    """Guard rows of a (rows, cols) tensor that a flat kernel walks: at least GUARD_FLAT elements, a multiple of 8 rows."""
+    return round8(ceil_div(GUARD_FLAT, cols))
+
+
+def lse_guard(H):
+    """Floats on each side of lse [B][H][81]: the four pairs of a workgroup, 96 padded squares each, for every head."""
+    return ATTN_PAIRS * H * SP
+
+
+def ln_block_rows(c):
+    """The most rows one workgroup of a LayerNorm kernel owns: 4 waves x (64 / L) rows x 4 iterations in the 16-byte forward
+    (4 rows in the wave-per-row one), ceil(M / parts) <= 128 in the backward."""
+    L = ln_vec_lanes(c.d, c.bf16, not c.off)
+    return max(128, 16 * (64 // L) if L else 4)
+
+
+def ln_parts(M):
+    """ka_tf_layernorm_parts restated."""
+    return min(ceil_div(M, 128), 2048)
+
+
+# ka_tf_gemm_nt on the tiled kernel: M in {1, 129}, N in {1, 130, 136}, K in {32, 96}; the scalar store (N or ldc no multiple
+# of 4), the 8-byte one (bf16, multiples of 4), the 16-byte one (fp32, multiples of 4) and the LDS epilogue (bf16, multiples of
+# 8, a full tile); the epilogue families none, bias + relu, bias + dropout + residual in fp32 and bf16; the masked entry once.
+NT_BOUNDS_TILED = (NtCase("tiled", 1, 1, 32, "none", False),
+                   NtCase("tiled", 129, 130, 96, "bias_relu", True, 8, 0, 1),
+                   NtCase("tiled", 129, 136, 32, "bias_drop_res", True, 0, 8, 4),
+                   NtCase("tiled", 1, 136, 96, "bias_drop_res", False, 8, 8, 0),
+                   NtCase("tiled", 129, 136, 96, "bias_relu", False, 0, 0, 8),
+                   NtCase("tiled", 1, 136, 32, "masked5", True, 8, 0, 0))
+NT_BOUNDS_LDS = (NtCase("tiled", 129, 136, 96, "none", True, 0, 8, 0),)
+NT_BOUNDS_SPLIT = (NT_SPLIT[0],)
+# K = 256: the tail panel alone, one full panel and the tail, full panels only; N = 64 and 192; the residual and activation
+# instantiations the C ABI reaches ((RES, ACT) = (1, 1) has no entry point)
+NT_BOUNDS_K256 = tuple(NtCase("k256", M, N, 256, epi, True, la, lb, lc) for M, N, epi, la, lb, lc in
+                       ((1, 64, "none", 0, 8, 0), (129, 192, "bias_drop_res", 8, 0, 8), (128, 64, "masked5", 0, 0, 8),
+                        (129, 64, "res", 8, 8, 0), (1, 192, "masked0", 0, 8, 8), (128, 192, "bias_relu_drop", 8, 0, 0)))
+NT_BOUNDS_BIG = (NT_BIG[2], NT_BIG[3])
+NT_BOUNDS = NT_BOUNDS_TILED + NT_BOUNDS_LDS + NT_BOUNDS_SPLIT + NT_MAP + NT_BOUNDS_K256 + NT_BOUNDS_BIG
+TN_BOUNDS = tuple(c for c in TN_CASES if (c.M, c.N, c.K) in ((1, 120, 264), (65, 264, 120), (4097, 136, 264)))
+# register forms <1> (dh <= 16) and <2> with B H % 4 in {1, 2, 3}; the LDS forms at dh = 8 (by the switch), 40 and 64
+HOT_BOUNDS_REG = (HotCase(1, 1, 8), HotCase(5, 1, 8), HotCase(3, 3, 16), HotCase(2, 5, 24), HotCase(1, 3, 32))
+HOT_BOUNDS_LDS = (HotCase(5, 1, 8), HotCase(1, 3, 40), HotCase(1, 2, 64))
+ATTN_BOUNDS_P = (0.0, 0.3, 0.5)                 # 0.5: the kept scale is exactly 2 and the one-hot oracle stays exact
+LN_BOUNDS = ((LnCase(True, 1, 256), LnCase(True, 33, 256), LnCase(True, 1025, 8))
+             + tuple(LnCase(bf, M, d) for bf in (False, True) for d, M in ((24, 1), (400, 5), (24, 129), (400, 1), (24, 5), (400, 129)))
+             + (LnCase(True, 33, 256, off=1),))
+W16_JOBS = ((8, 264), (139, 256), (70, 44))      # (N, K) of the three-job table of ka_tf_weights16_multi
+DROP_BOUNDS_NS = (1, 5, 1025)
+ROW_BOUNDS = ((1, 8), (3, 24))                   # (B, d) of add_pos, mean_pool, head_grad
+POS_GRAD_BOUNDS_B = (1, 65)
+TANH_BOUNDS_NS = (1, 257)
+
+# every entry point with a pointer argument, by the group of cases that calls it (the coverage test of the CPU twin reads this)
+BOUNDS_ENTRY_POINTS = {
+    "ka_tf_gemm_nt": NT_BOUNDS, "ka_tf_gemm_nt_masked": tuple(c for c in NT_BOUNDS if c.masked),
+    "ka_tf_gemm_tn": TN_BOUNDS, "ka_tf_gemm_tn_bias": TN_BOUNDS,
+    "ka_tf_attention_fwd": HOT_BOUNDS_REG + HOT_BOUNDS_LDS, "ka_tf_attention_bwd": HOT_BOUNDS_REG + HOT_BOUNDS_LDS,
+    "ka_tf_attention_bwd_o": HOT_BOUNDS_REG + HOT_BOUNDS_LDS,
+    "ka_tf_layernorm_fwd": LN_BOUNDS, "ka_tf_layernorm_bwd": LN_BOUNDS, "ka_tf_layernorm_bwd_drop": LN_BOUNDS,
+    "ka_tf_transpose_pad": TRANSPOSE_CASES, "ka_tf_cast_pad": CAST_CASES, "ka_tf_weights16_multi": W16_JOBS,
+    "ka_tf_drop_apply": DROP_BOUNDS_NS, "ka_tf_add_pos": ROW_BOUNDS, "ka_tf_mean_pool": ROW_BOUNDS, "ka_tf_head_grad": ROW_BOUNDS,
+    "ka_tf_colsum": COLSUM_CASES, "ka_tf_pos_grad": POS_GRAD_BOUNDS_B, "ka_tf_tanh": TANH_BOUNDS_NS, "ka_tf_tanh_bwd": TANH_BOUNDS_NS,
+}
+BOUNDS_NO_POINTERS_TO_GUARD = ("ka_tf_route_counts", "ka_tf_gemm_tn_slabs", "ka_tf_gemm_nt_slabs", "ka_tf_layernorm_parts")
+
+
+def w16_ld(n):
+    """Row length of the bf16 weight cache: the next multiple of 32 (hip/transformer.py)."""
+    return ceil_div(n, 32) * 32
+
+
+@functools.lru_cache(maxsize=None)
+def w16_data(N, K):
+    """(W fp32 (N, K), out (N, ldo) bf16, outT (K, ldt) bf16): the weight, its bf16 copy and the transposed copy, zero padded."""
+    W = torch.randn(N, K, generator=torch.Generator().manual_seed(N * 1000 + K))
+    out, outT = torch.zeros(N, w16_ld(K), dtype=torch.bfloat16), torch.zeros(K, w16_ld(N), dtype=torch.bfloat16)
+    out[:, :K], outT[:, :N] = W.bfloat16(), W.t().bfloat16()
+    return W, out, outT
+
+
 # ------------------------------------------------------------------------------------------------ mutants of the references
 def same(a, b):
     return all(torch.equal(x, y) for x, y in zip(a, b))
