@@ -984,7 +984,7 @@ int ka_search_advance(void* records, void* tree, int width, int expansions, int 
  * ka_mcts_words(which, width, simulations): 0 record words, 1 tree words per env, 2 stats words (6: positions searched,
  *   choices that differ from the sampler's, chosen moves that won, choices that differ from the one-ply choice, simulations
  *   run and revisits, both summed over the envs), 3 the maximum width (8), 4 the maximum simulations (64), 5 table words per
- *   model; else -1.
+ *   model, 7 the exploration's counter words (below); else -1.
  * ka_mcts_advance: one thread per env after the forward of simulation t, in this order: leaf q of slice t, backup,
  *   selection for t + 1 (parent_row / active for ka_search_expand), and at t = simulations - 1 the choice.  step_err:
  *   (simulations, 2) 64-bit words, the error words of every slice's step; a non-zero word of slices 0..t is err bit 1, and
@@ -994,6 +994,47 @@ int ka_mcts_advance(void* records, void* tree, int width, int simulations, int t
                     int K, const float* pool_vlogits, const float* pool_rewards, const void* pool_terminated,
                     const void* pool_truncated, const void* step_err, long long* actions, int* parent_row, int* active,
                     int* pv, int* root_visits, float* root_values, int* stats, int* err, int N, void* stream);
+
+/* ---- exploration for the visit-count search (csrc/mcts_explore.hip, csrc/mcts_explore.h, the choice in csrc/mcts.hip):
+ * Dirichlet noise mixed into the root priors, and for the first plies of a game the move drawn in proportion to the root
+ * visits.  Per ply, with both on:
+ *   ka_lookahead_fork, ka_mcts_root_noise, step and forward over slice 0, ka_mcts_advance_explore(t = 0), ...
+ * explore_table: K rows of 4 32-bit words in device memory, row m for model m, read by every launch (a new table applies from
+ *   the next ply of a captured graph):   0 fp32 noise_fraction epsilon in [0, 1]   1 fp32 noise_alpha in [0.01, 100] (not
+ *   looked at when epsilon is 0)   2 int32 sample_plies in [0, 65535]   3 reserved, zero.  A row with a word out of range
+ *   reads as off (all zero), and so does a model outside [0, K).
+ * Random numbers: seed_dev points at the int64 the ply's sampler reads.  The stream of env e for purpose C is
+ *   h = mix(seed ^ mix(e + C)) with mix = the splitmix64 finaliser behind every draw of the library, draw i of it
+ *   r_i = mix(h + i * 0x9E3779B97F4A7C15), a uniform in (0, 1) is ((r >> 12) + 0.5) * 2^-52.  C = 0x2545F4914F6CDD1D for the
+ *   noise and 0xD1342543DE82EF95 for the choice; the sampler's uniform uses 0x5851F42D4C957F2D.
+ * ka_mcts_root_noise, behind ka_lookahead_fork and before ka_mcts_advance(t = 0): for every env whose record 0 has flag bit 0
+ *   and whose model has epsilon > 0, with n = clamp(n_cand, 1, width): eta ~ Dirichlet(alpha) over the n candidates,
+ *   s = p_0 + .. + p_{n-1} in slot order, p'_k = (1 - epsilon) p_k + epsilon s eta_k in fp64, rounded once to fp32 into the
+ *   record's prior words (the prior mass of the candidates is kept).  Gamma(alpha) of slot k by Marsaglia-Tsang in fp64:
+ *   a' = alpha < 1 ? alpha + 1 : alpha, d = a' - 1/3, c = 1 / sqrt(9 d); try j = 0..15 takes draws 64 k + 3 j + {0, 1, 2}:
+ *   x = sqrt(-2 ln u0) cos(2 pi u1), v = (1 + c x)^3, rejected if v <= 0, accepted if ln u2 < 0.5 x^2 + d - d v + d ln v;
+ *   g = d v, or d after 16 rejections; for alpha < 1 times exp(ln(u_b) / alpha), u_b draw 64 k + 48.  eta_k = g_k / sum g,
+ *   the sum in slot order; 1 / n where the sum is not above 0 or not finite.  Written for a noised env only: the n prior words
+ *   of the record, raw_priors (N, width) fp32 (the priors before, 0 in the unused slots) and eta (N, width) fp64 (0 in the
+ *   unused slots); explore_stats[0] += the envs noised.  Nothing is written for any other env, and no slot >= n of a record.
+ * ka_mcts_advance_explore: ka_mcts_advance (the same kernel; explore_table == NULL is ka_mcts_advance exactly, and the other
+ *   four arguments are then not looked at).  With a table, behind the last simulation: best is the most visited root slot as
+ *   before; p = the u32 at plies + e * ply_stride (the env's game ply: byte 100 of its state row).  Where p < sample_plies of
+ *   the env's model the played slot is drawn: total = sum_{k<n} N_k, x = ((r_0 >> 32) * total) >> 32 on the choice stream,
+ *   the first k whose running sum of N exceeds x (a slot without visits is never drawn); else it is best.  The played slot
+ *   takes best's place in actions[e], slot and action of record 0, the changed / won bits and counters and the head of pv
+ *   (the line beneath it: the most visited child at each level).  deepened, root_visits and root_values are unchanged.
+ *   Record 0 flag bit 4 = the move was drawn, bit 5 = the drawn slot differs from best.
+ * explore_stats, ka_mcts_words(7, ..) = 4 words (which = 6 stays unanswered, -1): envs noised, moves drawn, drawn moves that differ from best, reserved;
+ *   added to with atomics, the caller clears them. */
+int ka_mcts_root_noise(void* records, int width, const void* explore_table, const int* model_of, int K,
+                       const long long* seed_dev, float* raw_priors, double* eta, int* explore_stats, int N, void* stream);
+int ka_mcts_advance_explore(void* records, void* tree, int width, int simulations, int t, const void* table,
+                            const int* model_of, int K, const float* pool_vlogits, const float* pool_rewards,
+                            const void* pool_terminated, const void* pool_truncated, const void* step_err, long long* actions,
+                            int* parent_row, int* active, int* pv, int* root_visits, float* root_values, int* stats, int* err,
+                            const void* explore_table, const long long* seed_dev, const void* plies, int ply_stride,
+                            int* explore_stats, int N, void* stream);
 
 /* ---- mate in one (csrc/mate.hip; the reference never searches).  A rules-only mate check inside the ply, behind the
  * lookahead or the search and before the insight, per model: fork the env rows into one child row per checking move, step

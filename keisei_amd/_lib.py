@@ -147,6 +147,8 @@ _SIGS = {
     "ka_search_advance": "pp iii pp i pppp p pppp pp i p",
     "ka_mcts_words": "iii",
     "ka_mcts_advance": "pp iii pp i pppp p pppp pp pp i p",
+    "ka_mcts_advance_explore": "pp iii pp i pppp p pppp pp pp ppp i p i p",
+    "ka_mcts_root_noise": "p i pp i p pp p i p",
     "ka_mate_words": "ii",
     "ka_mate_fork": "pi pp i p ppp ii p pppp p ii p",
     "ka_mate_choose": "pi pppp ppp i p",

@@ -16,13 +16,14 @@ from pathlib import Path
 CSRC = Path(__file__).resolve().parent / "csrc"
 DIAG = bool(os.environ.get("KA_DIAG"))      # diagnostic build: ablation switches compiled in (common.h ka_diag_env), separate .so
 OUT = Path(__file__).resolve().parent / ("libkeisei_amd_diag.so" if DIAG else "libkeisei_amd.so")
-SOURCES = ["capi.hip", "conv3x3.hip", "wgrad.hip", "board.hip", "gemm.hip", "loss.hip", "optim.hip", "gae.hip", "rollout.hip", "transformer.hip", "tower.hip", "shogi_env.hip", "arena.hip", "league.hip", "selfplay.hip", "gamelog.hip", "spectator.hip", "insight.hip", "sampling.hip", "lookahead.hip", "mcts.hip", "mate.hip", "mate3.hip", "perft.hip", "sl_prepare.hip", "sl_data.hip", "search_samples.hip"]
+SOURCES = ["capi.hip", "conv3x3.hip", "wgrad.hip", "board.hip", "gemm.hip", "loss.hip", "optim.hip", "gae.hip", "rollout.hip", "transformer.hip", "tower.hip", "shogi_env.hip", "arena.hip", "league.hip", "selfplay.hip", "gamelog.hip", "spectator.hip", "insight.hip", "sampling.hip", "lookahead.hip", "mcts.hip", "mcts_explore.hip", "mate.hip", "mate3.hip", "perft.hip", "sl_prepare.hip", "sl_data.hip", "search_samples.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-Wno-unknown-pragmas", "-Wno-sometimes-uninitialized"]
 # conv3x3.hip: no SLP vectorisation -- v_pk_fma_f32 / v_pk_add_f32 beside MFMAs cost more than the scalar pair they replace
 # (MI355X_MICROARCH.md, filler prices) and the packed temporaries spilled the masked epilogue (profiles/NOTES_r04.md)
-PER_FILE = {"gae.hip": ["-ffp-contract=off"], "conv3x3.hip": ["-fno-slp-vectorize"]}
+# mcts_explore.hip: no fp contraction -- its fp64 +, *, / are the numpy restatement's to the bit (see its header comment)
+PER_FILE = {"gae.hip": ["-ffp-contract=off"], "conv3x3.hip": ["-fno-slp-vectorize"], "mcts_explore.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -7,6 +7,8 @@
 //   ka_mcts_advance     one thread per env, after the forward of simulation t: the leaf q of the new nodes, the backup of
 //                       simulation t, the selection for simulation t + 1 (parent_row / active for ka_search_expand), and
 //                       behind the last launch the choice, the flags, the principal variation and the counters
+//   ka_mcts_advance_explore   the same kernel with an exploration table (csrc/mcts_explore.h): where the env's game ply lies
+//                       below its model's sample_plies the played move is drawn in proportion to the root visits
 //
 // The header above ka_mcts_words in include/keisei_amd.h states the semantics.  Node (t, j) of env e is local node
 // t * width + j and row (t * N + e) * width + j of the node pool; record (t, e) is row t * N + e of the records (the
@@ -22,7 +24,7 @@
 // step depending on the one before, and the order of the fp32 adds into S is part of the contract -- there is nothing in it
 // for a second lane to do.  The launch is bound by the latency of those dependent loads (a few per level, the tree lies in
 // L2 between the launches of a ply), not by bandwidth or arithmetic.
-#include "lookahead_record.h"
+#include "mcts_explore.h"
 
 #include <climits>
 
@@ -38,6 +40,8 @@ struct MctsArgs {
     uint32_t* rec; uint32_t* tree; int width; int sims; int t; const uint32_t* table; const int* model_of; int K;
     const float* vl; const float* rewards; const uint8_t* term; const uint8_t* trunc; const unsigned long long* step_err;
     long long* actions; int* parent_row; int* active; int* pv; int* root_visits; float* root_values; int* stats; int* err; int n;
+    // the exploration of ka_mcts_advance_explore; xtable == nullptr is ka_mcts_advance
+    const uint32_t* xtable; const long long* seed_dev; const uint8_t* plies; int ply_stride; int* xstats;
 };
 
 // the simulations of model m: word 3 of its row, outside [1, 64] reads as 1
@@ -54,6 +58,7 @@ __global__ __launch_bounds__(kMcThreads) void mcts_advance_kernel(MctsArgs a) {
     for (int x = 0; x <= t; ++x) held |= (a.step_err[2 * x] | a.step_err[2 * x + 1]) != 0ull;
     const bool last = t == E - 1;
     bool ran = false, revisit = false, bad = false, searched = false, changed = false, won = false, deepened = false;
+    bool sampled = false, diverged = false;
     if (e < N) {
         uint32_t* tree = a.tree + (size_t)e * mcts_tree_words(width, E);
         int* parent = reinterpret_cast<int*>(tree);
@@ -166,17 +171,37 @@ __global__ __launch_bounds__(kMcThreads) void mcts_advance_kernel(MctsArgs a) {
                     if (visits[k] > visits[best]) best = k;
                     if (leaf_q(k) > leaf_q(best1)) best1 = k;
                 }
-                const size_t cb = row_of(best);
-                const int act = (int)rec0[kLaCand + best];
+                int play = best;                               // the played slot: best, or drawn in proportion to the visits
+                if (a.xtable) {
+                    float eps, alpha;
+                    int sample_plies;
+                    xp_controls(a.xtable, m, a.K, &eps, &alpha, &sample_plies);
+                    const uint32_t ply = *reinterpret_cast<const uint32_t*>(a.plies + (size_t)e * a.ply_stride);
+                    if (ply < (uint32_t)sample_plies) {
+                        unsigned long long total = 0ull, run = 0ull;
+                        for (int k = 0; k < n; ++k) total += (unsigned long long)visits[k];
+                        const unsigned long long r0 = xp_draw(xp_stream((unsigned long long)*a.seed_dev, e, kXpChoice), 0);
+                        const unsigned long long x = ((r0 >> 32) * total) >> 32;      // in [0, total)
+                        for (int k = 0; k < n; ++k) {              // the first slot whose running sum exceeds x
+                            run += (unsigned long long)visits[k];
+                            if (run > x) { play = k; break; }
+                        }
+                        sampled = true;
+                        diverged = play != best;
+                    }
+                }
+                const size_t cb = row_of(play);
+                const int act = (int)rec0[kLaCand + play];
                 changed = (long long)act != a.actions[e];
                 won = a.term[cb] && a.rewards[cb] > 0.f;
                 searched = true;
                 deepened = best != best1;
-                rec0[kLaSlot] = (uint32_t)best;
+                rec0[kLaSlot] = (uint32_t)play;
                 rec0[kLaAction] = (uint32_t)act;
-                rec0[kLaFlags] = 1u | ((uint32_t)changed << 1) | ((uint32_t)won << 2) | ((uint32_t)deepened << 3);
+                rec0[kLaFlags] = 1u | ((uint32_t)changed << 1) | ((uint32_t)won << 2) | ((uint32_t)deepened << 3) |
+                                 ((uint32_t)sampled << 4) | ((uint32_t)diverged << 5);
                 a.actions[e] = act;
-                int node = best, len = 0;
+                int node = play, len = 0;
                 pv[len++] = act;
                 while (len < E && !done_at(row_of(node))) {    // the most visited children down the line
                     const int x = by[node];
@@ -206,6 +231,11 @@ __global__ __launch_bounds__(kMcThreads) void mcts_advance_kernel(MctsArgs a) {
         if (any_bad) atomicOr(&a.err[0], 1);
         if (held && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&a.err[0], 2);
     }
+    if (a.xtable && last) {                                    // (wave-uniform: the ballots are whole)
+        const int nsm = __popcll(__ballot(sampled)), ndv = __popcll(__ballot(diverged));
+        if (lane == 0 && nsm) atomicAdd(&a.xstats[1], nsm);
+        if (lane == 0 && ndv) atomicAdd(&a.xstats[2], ndv);
+    }
 }
 
 }  // namespace
@@ -213,14 +243,17 @@ __global__ __launch_bounds__(kMcThreads) void mcts_advance_kernel(MctsArgs a) {
 extern "C" int ka_mcts_words(int which, int width, int simulations) {
     if (width < 0 || width > kLaMaxWidth || simulations < 0 || simulations > kMcMaxSimulations) return -1;
     return which == 0 ? la_words(width) : which == 1 ? mcts_tree_words(width, simulations) : which == 2 ? kMcStatsWords :
-           which == 3 ? kLaMaxWidth : which == 4 ? kMcMaxSimulations : which == 5 ? kLaTableWords : -1;
+           which == 3 ? kLaMaxWidth : which == 4 ? kMcMaxSimulations : which == 5 ? kLaTableWords :
+           which == 7 ? kXpStatsWords : -1;
 }
 
-extern "C" int ka_mcts_advance(void* records, void* tree, int width, int simulations, int t, const void* table,
-                               const int* model_of, int K, const float* pool_vlogits, const float* pool_rewards,
-                               const void* pool_terminated, const void* pool_truncated, const void* step_err,
-                               long long* actions, int* parent_row, int* active, int* pv, int* root_visits, float* root_values,
-                               int* stats, int* err, int N, void* stream) {
+extern "C" int ka_mcts_advance_explore(void* records, void* tree, int width, int simulations, int t, const void* table,
+                                       const int* model_of, int K, const float* pool_vlogits, const float* pool_rewards,
+                                       const void* pool_terminated, const void* pool_truncated, const void* step_err,
+                                       long long* actions, int* parent_row, int* active, int* pv, int* root_visits,
+                                       float* root_values, int* stats, int* err, const void* explore_table,
+                                       const long long* seed_dev, const void* plies, int ply_stride, int* explore_stats, int N,
+                                       void* stream) {
     KA_REQUIRE(records && tree && table && model_of && pool_vlogits && pool_rewards && pool_terminated && pool_truncated &&
                step_err && actions && parent_row && active && pv && root_visits && root_values && stats && err && N > 0,
                "mcts_advance: null tensor");
@@ -236,12 +269,30 @@ extern "C" int ka_mcts_advance(void* records, void* tree, int width, int simulat
                (uintptr_t)pv % 4 == 0 && (uintptr_t)root_visits % 4 == 0 && (uintptr_t)root_values % 4 == 0 &&
                (uintptr_t)stats % 4 == 0 && (uintptr_t)err % 4 == 0,
                "mcts_advance: actions and the step error words are 8-byte aligned, every other tensor to its element size");
+    if (explore_table) {
+        KA_REQUIRE(seed_dev && plies && explore_stats, "mcts_advance: an exploration table needs the seed, the game plies and its counters");
+        KA_REQUIRE(ply_stride >= 4, "mcts_advance: ply_stride must be at least 4 bytes, got %d", ply_stride);
+        KA_REQUIRE((uintptr_t)explore_table % 4 == 0 && (uintptr_t)seed_dev % 8 == 0 && (uintptr_t)plies % 4 == 0 &&
+                   ply_stride % 4 == 0 && (uintptr_t)explore_stats % 4 == 0,
+                   "mcts_advance: the seed is 8-byte aligned, the exploration table, the game plies and the counters to 4 bytes");
+    }
     MctsArgs a{static_cast<uint32_t*>(records), static_cast<uint32_t*>(tree), width, simulations, t,
                static_cast<const uint32_t*>(table), model_of, K, pool_vlogits, pool_rewards,
                static_cast<const uint8_t*>(pool_terminated), static_cast<const uint8_t*>(pool_truncated),
                static_cast<const unsigned long long*>(step_err), actions, parent_row, active, pv, root_visits, root_values,
-               stats, err, N};
+               stats, err, N, static_cast<const uint32_t*>(explore_table), seed_dev, static_cast<const uint8_t*>(plies),
+               ply_stride, explore_stats};
     hipLaunchKernelGGL(mcts_advance_kernel, dim3((N + kMcThreads - 1) / kMcThreads), dim3(kMcThreads), 0,
                        static_cast<hipStream_t>(stream), a);
     return ka_check_launch("mcts_advance");
+}
+
+extern "C" int ka_mcts_advance(void* records, void* tree, int width, int simulations, int t, const void* table,
+                               const int* model_of, int K, const float* pool_vlogits, const float* pool_rewards,
+                               const void* pool_terminated, const void* pool_truncated, const void* step_err,
+                               long long* actions, int* parent_row, int* active, int* pv, int* root_visits, float* root_values,
+                               int* stats, int* err, int N, void* stream) {
+    return ka_mcts_advance_explore(records, tree, width, simulations, t, table, model_of, K, pool_vlogits, pool_rewards,
+                                   pool_terminated, pool_truncated, step_err, actions, parent_row, active, pv, root_visits,
+                                   root_values, stats, err, nullptr, nullptr, nullptr, 0, nullptr, N, stream);
 }

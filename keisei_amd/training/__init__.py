@@ -9,6 +9,7 @@ from .lookahead import (Lookahead, LookaheadChoice, LookaheadControls, Lookahead
                         lookahead_reply_widths, lookahead_table)
 from .mate_search import Mate3Search, Mate3Stats, MateControls, MateSearch, MateStats, mate_table  # noqa: F401
 from .match_arena import MatchArena, MatchResult, RoundStats  # noqa: F401
+from .mcts_explore import MctsExploration, explore_table, root_noise_host, visit_choice_host  # noqa: F401
 from .mcts_search import (MctsControls, MctsRestatement, MctsSearch, MctsStats, MctsTree, mcts_backup_select,  # noqa: F401
                           mcts_simulations, mcts_table, visit_policy)
 from .policy_insight import InsightRecorder, PolicyInsight, action_usi, insight_dict, policy_insight  # noqa: F401

@@ -89,7 +89,9 @@ class DevicePly:
     ``ka_policy_sample_play``; ``lookahead_table`` / ``lookahead_width`` (``lookahead.py``) add the one-ply value lookahead
     between the sampler and the insight, ``lookahead_reply_width > 0`` its reply search (three more stages).  ``search_table`` / ``search_width`` /
     ``search_expansions`` (``tree_search.py``) put the tree search where the lookahead stands (not both); ``mcts_table`` /
-    ``mcts_width`` / ``mcts_simulations`` (``mcts_search.py``) put the visit-count search there (none of the others).
+    ``mcts_width`` / ``mcts_simulations`` (``mcts_search.py``) put the visit-count search there (none of the others), and
+    ``mcts_explore_table`` (``mcts_explore.py``; only with ``mcts_table``) adds its exploration: one launch,
+    ``ka_mcts_root_noise``, behind the fork of simulation 0, and ``ka_mcts_advance_explore`` in the place of ``ka_mcts_advance``.
     ``mate_table`` / ``mate_cap`` (``mate_search.py``) add the mate-in-one check behind the lookahead or the search and before the insight
     (``ka_mate_fork``, the env step over the child rows, ``ka_mate_choose``; no forward): it overrides their choice, and the
     insight describes the move actually played; ``mate_rows`` / ``mate_reply_cap`` > 0 put the mate in three behind it
@@ -106,12 +108,15 @@ class DevicePly:
                  lookahead_reply_width: int = 0, search_table: Optional[np.ndarray] = None, search_width: int = 0,
                  search_expansions: int = 0, mate_table: Optional[np.ndarray] = None, mate_cap: int = 0, mate_rows: int = 0,
                  mate_reply_cap: int = 0, mcts_table: Optional[np.ndarray] = None, mcts_width: int = 0,
-                 mcts_simulations: int = 0, search_samples: int = 0) -> None:
+                 mcts_simulations: int = 0, search_samples: int = 0,
+                 mcts_explore_table: Optional[np.ndarray] = None) -> None:
         if search_table is not None and lookahead_table is not None:
             raise ValueError("search_table cannot be combined with lookahead_table: the search stands where the lookahead stands")
         if mcts_table is not None and (lookahead_table is not None or search_table is not None):
             raise ValueError("mcts_table cannot be combined with lookahead_table or search_table: the visit-count search "
                              "stands where they stand")
+        if mcts_explore_table is not None and mcts_table is None:
+            raise ValueError("mcts_explore_table needs mcts_table: it is the visit-count search that is explored")
         N, dev = int(num_envs), group.device
         self.device, self.num_envs = dev, N
         with torch.cuda.device(dev):
@@ -138,7 +143,11 @@ class DevicePly:
             self.mcts_table: Optional[torch.Tensor] = None if mcts_table is None else torch.from_numpy(mcts_table).to(dev)
             self.mcts: Optional[MctsSearch] = None
             if mcts_table is not None and mcts_width > 0:
-                self.mcts = MctsSearch(self.env, group, mcts_width, max(int(mcts_simulations), 1))
+                self.mcts = MctsSearch(self.env, group, mcts_width, max(int(mcts_simulations), 1),
+                                       explore=mcts_explore_table is not None)
+            # its exploration table (read by every launch); None: the launches are those of the search alone
+            self.mcts_explore_table: Optional[torch.Tensor] = \
+                None if mcts_explore_table is None else torch.from_numpy(mcts_explore_table).to(dev)
             # the mate check's table and its child rows, likewise
             self.mate_table: Optional[torch.Tensor] = None if mate_table is None else torch.from_numpy(mate_table).to(dev)
             self.mate: Optional[MateSearch] = None
@@ -208,7 +217,11 @@ class DevicePly:
         if self.search is not None:                       # likewise the search's
             self.search.step(logits, cur.legal_mask_bits, self.actions, model_of, self.search_table, st)
         if self.mcts is not None:                         # or the visit-count search's
-            self.mcts.step(logits, cur.legal_mask_bits, self.actions, model_of, self.mcts_table, st)
+            if self.mcts_explore_table is None:
+                self.mcts.step(logits, cur.legal_mask_bits, self.actions, model_of, self.mcts_table, st)
+            else:                                         # the noise and the drawn move read the sampler's seed of this ply
+                self.mcts.step(logits, cur.legal_mask_bits, self.actions, model_of, self.mcts_table, st,
+                               explore_table=self.mcts_explore_table, seed=state)
         if self.mate3 is not None:                        # a mate in one or in three overrides whatever was chosen so far
             self.mate3.step(cur.legal_mask_bits, self.actions, model_of, self.mate_table, self.mate_reply_table, st)
         elif self.mate is not None:                       # a mate in one does

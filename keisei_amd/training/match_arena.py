@@ -73,6 +73,7 @@ from .game_feature_tracker import GameFeatureTracker
 from .game_log import RecordedGame
 from .lookahead import LookaheadStats, arena_lookahead, arena_reply_width, lookahead_table
 from .mate_search import Mate3Stats, MateStats, arena_mate, arena_mate3, mate3_reply_table, mate_table
+from .mcts_explore import arena_mcts_explore, explore_table
 from .mcts_search import MctsStats, arena_mcts, mcts_table
 from .model_group import SEResNetGroup
 from .sampling import GAME_PLY_BYTE, arena_controls, controls_table
@@ -328,6 +329,13 @@ class MatchArena:
     largest ``width`` and ``simulations`` given; ``set_mcts`` rewrites the table between rounds without a new capture, up to
     those.  ``RoundStats.mcts`` carries the counters.  With None nothing is allocated and the launches are what they were.
     Not together with ``lookahead=`` or ``search=`` and not with ``collect=True``.
+    ``mcts_explore=`` (an ``MctsExploration`` for every model, or one per model; ``mcts_explore.py``; only with ``mcts=``)
+    gives that search its two sources of variety: Dirichlet noise mixed into the root priors (one launch,
+    ``ka_mcts_root_noise``, behind the fork of simulation 0) and, while a game's ply lies below ``sample_plies``, the move
+    drawn in proportion to the root visits (a branch of the advance, ``ka_mcts_advance_explore``).  Both draw from the round's
+    seed, so two arenas with one seed play the same games.  ``set_mcts_explore`` rewrites the table between rounds without a
+    new capture; ``self.mcts.root_noise()`` gives the priors before the noise and the draw, ``RoundStats.mcts`` the counters
+    ``noised`` / ``sampled`` / ``diverged``.  With None nothing is allocated and the launches are what they were.
     ``search_samples=rows_per_env > 0`` (only with ``mcts=``; ``search_samples.py``) adds one launch,
     ``ka_search_sample_step``, behind the env step: every searched position is written, packed as a ``DeviceSLDataset`` row,
     with its visit counts into the env's region of ``rows_per_env`` rows, and a game that ends labels its rows W / D / L.
@@ -350,13 +358,14 @@ class MatchArena:
                  collect: bool = False, features: bool = False, start_pool_capacity: int = 0,
                  game_log: int = 0, move_history: bool = False, insight: int = 0,
                  insight_temperature: float = 1.0, sampling=None, lookahead=None, search=None, mate=None,
-                 mcts=None, search_samples: int = 0) -> None:
+                 mcts=None, search_samples: int = 0, mcts_explore=None) -> None:
         if len(group) == 0:
             raise ValueError("MatchArena needs a group with at least one model")
         if num_envs <= 0 or envs_per_match <= 0 or num_envs % envs_per_match != 0:
             raise ValueError(f"num_envs ({num_envs}) must be a positive multiple of envs_per_match ({envs_per_match})")
         check_loop_args(max_ply, sync_every, graph, record, start_pool_capacity, game_log)
         search_samples = arena_search_samples(search_samples, mcts, len(group))
+        xp_table = arena_mcts_explore(mcts_explore, mcts, len(group))
         if features and start_pool_capacity > 0:
             raise ValueError("features=True cannot be combined with start_pool_capacity > 0: the opening and rook-square "
                              "style features are defined from the standard start position")
@@ -385,12 +394,13 @@ class MatchArena:
                                    lookahead_width=la_width, lookahead_reply_width=la_reply, search_table=se_table,
                                    search_width=se_width, search_expansions=se_expansions, mate_table=mt_table,
                                    mate_cap=mt_cap, mate_rows=mt_rows, mate_reply_cap=mt_reply, mcts_table=mc_table,
-                                   mcts_width=mc_width, mcts_simulations=mc_sims, search_samples=int(search_samples))
+                                   mcts_width=mc_width, mcts_simulations=mc_sims, search_samples=int(search_samples),
+                                   mcts_explore_table=xp_table)
         self.env, self.game_log, self.insight = ply.env, ply.game_log, ply.insight
         self._actions, self._logp, self._nlegal = ply.actions, ply.log_probs, ply.n_legal
         self._ctl, self._la_table, self._la = ply.ctl, ply.lookahead_table, ply.lookahead
         self._se_table, self._se = ply.search_table, ply.search
-        self._mc_table, self.mcts = ply.mcts_table, ply.mcts
+        self._mc_table, self.mcts, self._xp_table = ply.mcts_table, ply.mcts, ply.mcts_explore_table
         self.search_samples = ply.search_samples
         self._mt_table, self._mt = ply.mate_table, ply.mate
         self._mt3, self._mt3_table = ply.mate3, ply.mate_reply_table
@@ -525,6 +535,16 @@ class MatchArena:
         with torch.cuda.device(self.device):
             self._mc_table.copy_(torch.from_numpy(table))
 
+    def set_mcts_explore(self, mcts_explore) -> None:
+        """New exploration controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
+        writes rows that are off: the games are then those of the search alone.  An arena built without ``mcts_explore=``
+        holds neither the noise launch nor the exploring advance in its ply and refuses."""
+        if self._xp_table is None:
+            raise ValueError("this arena was built without mcts_explore=: its ply (and its captured graph) holds no "
+                             "exploration; build the arena with exploration controls to change them later")
+        with torch.cuda.device(self.device):
+            self._xp_table.copy_(torch.from_numpy(explore_table(mcts_explore, len(self.group))))
+
     def set_sampling(self, sampling) -> None:
         """New sampling controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
         writes neutral rows.  An arena built without ``sampling=`` holds the play sampler in its ply and refuses."""
@@ -605,6 +625,8 @@ class MatchArena:
                        node_done=(mc.terminated | mc.truncated).cpu().reshape(shape),
                        node_logits=mc.logits.cpu().reshape(-1, ACTION_SPACE), node_mask_bits=mc.mask_bits.cpu(),
                        node_model_of=mc.model_of.cpu().reshape(shape))
+            if self._xp_table is not None and mc._eta is not None:
+                rec.update(mcts_root_noise=tuple(x.cpu() for x in mc.root_noise()))
         if self.search_samples is not None:
             rec.update(material_balance=self.env._material[self.env._cur].cpu())
         if self._mt is not None:

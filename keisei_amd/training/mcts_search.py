@@ -45,6 +45,7 @@ from keisei_amd.shogi_gym import ACTION_SPACE
 from ._forked_rows import NodePool, check_search_env, controls_rows
 from .lookahead import (FLAG_ACTIVE, MAX_SKIP_PLIES, MAX_WIDTH, REC_CAND, REC_FLAGS, REC_NCAND, _check_width, _row_controls,
                         _table_of, lookahead_words)
+from .sampling import GAME_PLY_BYTE
 
 __all__ = ["MctsControls", "MctsStats", "MctsTree", "MctsRestatement", "MctsSearch", "mcts_table", "mcts_simulations",
            "mcts_backup_select", "visit_policy", "arena_mcts", "MAX_SIMULATIONS"]
@@ -103,6 +104,10 @@ class MctsStats:
     deepened: int = 0      # choices that differ from the arg-max of the root candidates' leaf q
     simulations: int = 0   # simulations run, summed over the envs and plies (simulation 0 included)
     revisits: int = 0      # of them: simulations that forked nothing and backed up the selected node's own q
+    # the exploration's (``mcts_explore.py``; 0 for a search built without ``explore=True``)
+    noised: int = 0        # positions whose root priors were noised
+    sampled: int = 0       # moves drawn in proportion to the root visits
+    diverged: int = 0      # of them: draws that differ from the most visited candidate
 
 
 def _rows(controls, K) -> List[MctsControls]:
@@ -383,11 +388,12 @@ def visit_policy(candidates, visits, temperature: float = 1.0) -> torch.Tensor:
 # ---------------------------------------------------------------------------------------------- in the ply
 class MctsSearch(NodePool):
     """The node pool of a device ``VecEnv`` (``NodePool``: ``simulations`` slices of ``envs * width`` rows and one scratch),
-    the trees and the stages of the visit-count search.  Everything is allocated here, once."""
+    the trees and the stages of the visit-count search.  Everything is allocated here, once.  ``explore=True`` also allocates
+    what the exploration of ``mcts_explore.py`` writes: the raw priors, eta and three more counters."""
 
     _SLICE = "simulation"
 
-    def __init__(self, env, group, width: int, simulations: int) -> None:
+    def __init__(self, env, group, width: int, simulations: int, explore: bool = False) -> None:
         width = _check_width(width)
         simulations = _check_simulations(simulations)
         check_search_env(env, group, "the visit-count search")
@@ -405,21 +411,62 @@ class MctsSearch(NodePool):
             self._root_visits = torch.zeros(n, width, dtype=torch.int32, device=dev)
             self._root_values = torch.zeros(n, width, dtype=torch.float32, device=dev)
             self._nstats = _lib.query("ka_mcts_words", 2, width, simulations)
-            self._counters = torch.zeros(self._nstats + 1, dtype=torch.int32, device=dev)    # stats, then the error word
+            self._nexplore = _lib.query("ka_mcts_words", 7, width, simulations) if explore else 0
+            # stats, then the error word, then the exploration's counters
+            self._counters = torch.zeros(self._nstats + 1 + self._nexplore, dtype=torch.int32, device=dev)
             self._counters_host = torch.zeros(self._counters.shape, dtype=torch.int32).pin_memory()
+            self._raw_priors = self._eta = None
+            if explore:
+                self._raw_priors = torch.zeros(n, width, dtype=torch.float32, device=dev)
+                self._eta = torch.zeros(n, width, dtype=torch.float64, device=dev)
 
     def clear(self) -> None:
         """Zero the counters, the error word and the refusal latches of every slice's step (a round's start)."""
         self._counters.zero_()
         self._step_err.zero_()
 
-    def advance(self, t: int, actions, model_of, table, stream) -> None:
-        """After ``evaluate(t)``: leaf q, backup, the selection of simulation t + 1; at the last simulation the choice."""
+    def advance(self, t: int, actions, model_of, table, stream, explore_table=None, seed=None) -> None:
+        """After ``evaluate(t)``: leaf q, backup, the selection of simulation t + 1; at the last simulation the choice --
+        with ``explore_table`` and ``seed`` (``step``) the choice of ``ka_mcts_advance_explore``."""
         self.rows(t)
-        _lib.call("ka_mcts_advance", self._records, self._tree, self.width, self.simulations, t, table, model_of,
-                  int(table.shape[0]), self.value_logits, self.rewards, self.terminated, self.truncated, self._step_err,
-                  actions, self.parent_row, self.active, self._pv, self._root_visits, self._root_values, self._counters,
-                  self._counters.data_ptr() + 4 * self._nstats, self.env.num_envs, stream)
+        args = (self._records, self._tree, self.width, self.simulations, t, table, model_of, int(table.shape[0]),
+                self.value_logits, self.rewards, self.terminated, self.truncated, self._step_err, actions, self.parent_row,
+                self.active, self._pv, self._root_visits, self._root_values, self._counters,
+                self._counters.data_ptr() + 4 * self._nstats)
+        if explore_table is None:
+            _lib.call("ka_mcts_advance", *args, self.env.num_envs, stream)
+        else:
+            env = self.env
+            _lib.call("ka_mcts_advance_explore", *args, explore_table, seed, env._state.data_ptr() + GAME_PLY_BYTE,
+                      env._state.shape[1], self._explore_stats(), env.num_envs, stream)
+
+    def _explore_stats(self) -> int:
+        if not self._nexplore:
+            raise ValueError("the exploration needs an MctsSearch built with explore=True")
+        return self._counters.data_ptr() + 4 * (self._nstats + 1)
+
+    def root_noise_step(self, model_of, explore_table, seed, stream) -> None:
+        """Behind ``fork`` and before ``advance(0)``: ``ka_mcts_root_noise`` over the records of simulation 0."""
+        _lib.call("ka_mcts_root_noise", self._records[0], self.width, explore_table, model_of, int(explore_table.shape[0]),
+                  seed, self._raw_priors, self._eta, self._explore_stats(), self.env.num_envs, stream)
+
+    def step(self, logits, mask_bits, actions, model_of, table, stream, explore_table=None, seed=None) -> None:
+        """``NodePool.step``.  With ``explore_table`` (the (K, 4) int32 table of ``mcts_explore.py`` on the device) and
+        ``seed`` (the device pointer of the int64 the ply's sampler reads) the root noise is launched behind the fork of
+        simulation 0 and the advance is ``ka_mcts_advance_explore``; without them the launches are what they were."""
+        if explore_table is None:
+            return super().step(logits, mask_bits, actions, model_of, table, stream)
+        if seed is None:
+            raise ValueError("explore_table= needs seed=, the device pointer of the ply's sampler seed")
+        for t in range(self.slices):
+            if t == 0:
+                self.fork(logits, mask_bits, actions, model_of, table, stream)
+                self.root_noise_step(model_of, explore_table, seed, stream)
+            else:
+                self.expand(t, table, stream)
+            self.step_nodes(t, stream)
+            self.evaluate(t)
+            self.advance(t, actions, model_of, table, stream, explore_table, seed)
 
     # ------------------------------------------------------------------ host side
     def read(self) -> MctsStats:
@@ -435,7 +482,7 @@ class MctsSearch(NodePool):
                                "forked with")
         if err & ERR_VALUE:
             raise RuntimeError("non-finite value logits in the visit-count search (a model has diverged)")
-        return MctsStats(*(int(v) for v in c[:6]))
+        return MctsStats(*(int(v) for v in c[:6]), *(int(v) for v in c[self._nstats + 1:self._nstats + 4][:self._nexplore]))
 
     def tree(self) -> dict:
         """The trees of the last ``step`` (copies on the device): ``parent`` (envs, simulations) int32, and (envs,
@@ -449,6 +496,14 @@ class MctsSearch(NodePool):
     def principal_variations(self) -> torch.Tensor:
         """(envs, simulations) int32: per env the chosen action and the line behind it, padded with -1."""
         return self._pv.clone()
+
+    def root_noise(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(raw_priors, eta)`` of the last ``step`` with an exploration table (copies on the device), (envs, width) each:
+        the root priors before the noise (fp32) and the Dirichlet draw (float64), 0 in the unused slots.  The kernel writes
+        the rows it noises and no other: a row not noised in the last ply keeps what an earlier ply left (0 at first)."""
+        if self._eta is None:
+            raise ValueError("root_noise() needs an MctsSearch built with explore=True")
+        return self._raw_priors.clone(), self._eta.clone()
 
     def root_visits(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """``(candidates, visits, mean_values)`` of the last ``step`` (copies on the device), (envs, width) each: the root
