@@ -2,7 +2,7 @@
 two loops that write a rollout buffer.
 
 ``DevicePly`` is what one ply of any of the three does before its own bookkeeping launch: the grouped forward, the
-sampler, the optional lookahead and insight, the env step and the optional game-log launch.  A loop holds one by
+sampler, the optional searches (a list of ``PlyStage``) and insight, the env step and the optional game-log launch.  A loop holds one by
 composition and adds its state array, its ``model_of`` and its bookkeeping kernel (``ka_arena_referee``,
 ``ka_league_step``, ``ka_selfplay_step``).  ``DeviceRollout`` is the part of ``LeagueRollout`` and ``SelfPlayRollout``
 around the ply: graph capture per buffer parity, the column descriptor, the guard decoding of a sync point, the learner's
@@ -21,15 +21,12 @@ import torch
 from keisei_amd import _lib
 from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS, OBS_CHANNELS, VecEnv
 
+from ._forked_rows import PlyStage, refuse_shared_place
 from .game_log import GameLog, RecordedGame
 from .katago_ppo import KataGoRolloutBuffer, _check_step_inputs
-from .lookahead import Lookahead
-from .mate_search import Mate3Search, MateSearch, mate3_reply_table
-from .mcts_search import MctsSearch
 from .policy_insight import InsightRecorder
 from .sampling import GAME_PLY_BYTE
 from .search_samples import SearchSamples
-from .tree_search import TreeSearch
 from .value_adapter import MultiHeadValueAdapter
 
 _OBS_SHAPE = (OBS_CHANNELS, 9, 9)
@@ -86,16 +83,10 @@ class DevicePly:
     every ``spectator_data()`` dict gains ``insight``, the figures of the env's last move at ``insight_temperature``, and
     with ``move_history=True`` every history entry gains its move's probability, rank, entropy, win probability and top
     candidates.  ``controls`` (a table of ``sampling.py``) puts ``ka_policy_sample_ctl`` in the place of
-    ``ka_policy_sample_play``; ``lookahead_table`` / ``lookahead_width`` (``lookahead.py``) add the one-ply value lookahead
-    between the sampler and the insight, ``lookahead_reply_width > 0`` its reply search (three more stages).  ``search_table`` / ``search_width`` /
-    ``search_expansions`` (``tree_search.py``) put the tree search where the lookahead stands (not both); ``mcts_table`` /
-    ``mcts_width`` / ``mcts_simulations`` (``mcts_search.py``) put the visit-count search there (none of the others), and
-    ``mcts_explore_table`` (``mcts_explore.py``; only with ``mcts_table``) adds its exploration: one launch,
-    ``ka_mcts_root_noise``, behind the fork of simulation 0, and ``ka_mcts_advance_explore`` in the place of ``ka_mcts_advance``.
-    ``mate_table`` / ``mate_cap`` (``mate_search.py``) add the mate-in-one check behind the lookahead or the search and before the insight
-    (``ka_mate_fork``, the env step over the child rows, ``ka_mate_choose``; no forward): it overrides their choice, and the
-    insight describes the move actually played; ``mate_rows`` / ``mate_reply_cap`` > 0 put the mate in three behind it
-    (``Mate3Search``: the grandchild rows per env and the third ply's rows per grandchild; seven more launches, no forward).
+    ``ka_policy_sample_play``.  ``stages`` are the searches of the ply, in launch order: ``PlyStage`` objects as their
+    modules parse a loop's options (``lookahead.py``, ``tree_search.py``, ``mcts_search.py``, ``mate_search.py``; a None
+    among them is an option not given).  They are built here, launched between the sampler and the insight, cleared by
+    ``reset()`` and kept by name in ``self.stages``; at most one of them may stand in the lookahead's place.
     ``search_samples=rows_per_env > 0`` (only with the visit-count search; ``search_samples.py``) keeps the searched
     positions with their visit counts and, once the game has ended, its result as training rows on the device: one launch,
     ``ka_search_sample_step``, that the loop enqueues through ``sample(...)`` between the env step and its bookkeeping launch.
@@ -104,19 +95,9 @@ class DevicePly:
     def __init__(self, group, num_envs: int, max_ply: int, *, start_pool_capacity: int = 0, game_log: int = 0,
                  envs_per_slot: Optional[int] = None, move_history: bool = False, insight: int = 0,
                  insight_temperature: float = 1.0, controls: Optional[np.ndarray] = None,
-                 lookahead_table: Optional[np.ndarray] = None, lookahead_width: int = 0,
-                 lookahead_reply_width: int = 0, search_table: Optional[np.ndarray] = None, search_width: int = 0,
-                 search_expansions: int = 0, mate_table: Optional[np.ndarray] = None, mate_cap: int = 0, mate_rows: int = 0,
-                 mate_reply_cap: int = 0, mcts_table: Optional[np.ndarray] = None, mcts_width: int = 0,
-                 mcts_simulations: int = 0, search_samples: int = 0,
-                 mcts_explore_table: Optional[np.ndarray] = None) -> None:
-        if search_table is not None and lookahead_table is not None:
-            raise ValueError("search_table cannot be combined with lookahead_table: the search stands where the lookahead stands")
-        if mcts_table is not None and (lookahead_table is not None or search_table is not None):
-            raise ValueError("mcts_table cannot be combined with lookahead_table or search_table: the visit-count search "
-                             "stands where they stand")
-        if mcts_explore_table is not None and mcts_table is None:
-            raise ValueError("mcts_explore_table needs mcts_table: it is the visit-count search that is explored")
+                 stages: Sequence[Optional[PlyStage]] = (), search_samples: int = 0) -> None:
+        self.stages: Dict[str, PlyStage] = {s.name: s for s in stages if s is not None}
+        refuse_shared_place(**{name: s for name, s in self.stages.items() if s.shares_place})
         N, dev = int(num_envs), group.device
         self.device, self.num_envs = dev, N
         with torch.cuda.device(dev):
@@ -129,41 +110,15 @@ class DevicePly:
             if game_log:
                 self.game_log = GameLog(self.env, capacity=int(game_log), envs_per_slot=envs_per_slot)
             self.insight: Optional[InsightRecorder] = InsightRecorder(self.env, insight, insight_temperature) if insight else None
-            # the lookahead's table (read by every launch) and its child rows, allocated once
-            self.lookahead_table: Optional[torch.Tensor] = None if lookahead_table is None else torch.from_numpy(lookahead_table).to(dev)
-            self.lookahead: Optional[Lookahead] = None
-            if lookahead_width > 0:
-                self.lookahead = Lookahead(self.env, group, lookahead_width, lookahead_reply_width)
-            # the search's table and its node pool, likewise
-            self.search_table: Optional[torch.Tensor] = None if search_table is None else torch.from_numpy(search_table).to(dev)
-            self.search: Optional[TreeSearch] = None
-            if search_table is not None and search_width > 0:
-                self.search = TreeSearch(self.env, group, search_width, max(int(search_expansions), 1))
-            # the visit-count search's table and its node pool, likewise
-            self.mcts_table: Optional[torch.Tensor] = None if mcts_table is None else torch.from_numpy(mcts_table).to(dev)
-            self.mcts: Optional[MctsSearch] = None
-            if mcts_table is not None and mcts_width > 0:
-                self.mcts = MctsSearch(self.env, group, mcts_width, max(int(mcts_simulations), 1),
-                                       explore=mcts_explore_table is not None)
-            # its exploration table (read by every launch); None: the launches are those of the search alone
-            self.mcts_explore_table: Optional[torch.Tensor] = \
-                None if mcts_explore_table is None else torch.from_numpy(mcts_explore_table).to(dev)
-            # the mate check's table and its child rows, likewise
-            self.mate_table: Optional[torch.Tensor] = None if mate_table is None else torch.from_numpy(mate_table).to(dev)
-            self.mate: Optional[MateSearch] = None
-            self.mate3: Optional[Mate3Search] = None      # (its root is self.mate; its third ply reads mate_reply_table)
-            self.mate_reply_table: Optional[torch.Tensor] = None
-            if mate_table is not None and mate_cap > 0 and mate_rows > 0 and mate_reply_cap > 0:
-                self.mate3 = Mate3Search(self.env, int(mate_cap), int(mate_rows), int(mate_reply_cap))
-                self.mate = self.mate3.root
-                self.mate_reply_table = torch.from_numpy(mate3_reply_table(mate_table)).to(dev)
-            elif mate_table is not None and mate_cap > 0:
-                self.mate = MateSearch(self.env, int(mate_cap))
+            # every stage's table (read by every launch) and its rows, allocated once
+            for stage in self.stages.values():
+                stage.build(self.env, group)
+            self.mcts = getattr(self.stages.get("mcts"), "engine", None)      # the visit-count search: its visits are read
             # the samples of the visit-count search: a region of rows per env, allocated once
             self.search_samples: Optional[SearchSamples] = None
             if search_samples:
                 if self.mcts is None:
-                    raise ValueError("search_samples needs the visit-count search (mcts_table with a width above 0): a "
+                    raise ValueError("search_samples needs the visit-count search (an mcts stage with a width above 0): a "
                                      "sample is a searched position with its visit counts")
                 self.search_samples = SearchSamples(self.env, self.mcts, search_samples)
             self.seat(group, controls)
@@ -177,27 +132,19 @@ class DevicePly:
             self.ctl: Optional[torch.Tensor] = None if controls is None else torch.from_numpy(controls).to(self.device)
 
     def reset(self) -> None:
-        """Every env back to the start position; the log, the insight and the lookahead's counters begin anew."""
+        """Every env back to the start position; the log, the insight and the stages' counters begin anew."""
         self.env.reset()
         if self.game_log is not None:
             self.game_log.begin()
         if self.insight is not None:
             self.insight.clear()
-        if self.lookahead is not None:
-            self.lookahead.clear()
-        if self.search is not None:
-            self.search.clear()
-        if self.mcts is not None:
-            self.mcts.clear()
+        for stage in self.stages.values():
+            stage.clear()
         if self.search_samples is not None:
             self.search_samples.begin()
-        if self.mate3 is not None:
-            self.mate3.clear()
-        elif self.mate is not None:
-            self.mate.clear()
 
     def move(self, model_of: torch.Tensor, num_models: int, state: int, flags: int):
-        """forward -> sampler -> lookahead -> mate check -> insight on the current stream.  ``state``: the device pointer of the loop's
+        """forward -> sampler -> the stages, in their order -> insight on the current stream.  ``state``: the device pointer of the loop's
         state array (the sampler reads the seed at its head), ``flags``: of the two sampler-flag words in it.  Returns
         ``(cur, pre, value, score, stream)``: the env's current buffers, the players to move, the value logits and the
         score lead of the forward, and the stream's pointer for the launches that follow."""
@@ -212,20 +159,8 @@ class DevicePly:
             _lib.call("ka_policy_sample_ctl", logits, 0, cur.legal_mask_bits, MASK_WORDS, state, model_of, num_models,
                       self.ctl, env._state.data_ptr() + GAME_PLY_BYTE, env._state.shape[1], self.actions, self.log_probs,
                       self.n_legal, flags, N, ACTION_SPACE, st)
-        if self.lookahead is not None:                    # the active envs' actions become the lookahead's choices
-            self.lookahead.step(logits, cur.legal_mask_bits, self.actions, model_of, self.lookahead_table, st)
-        if self.search is not None:                       # likewise the search's
-            self.search.step(logits, cur.legal_mask_bits, self.actions, model_of, self.search_table, st)
-        if self.mcts is not None:                         # or the visit-count search's
-            if self.mcts_explore_table is None:
-                self.mcts.step(logits, cur.legal_mask_bits, self.actions, model_of, self.mcts_table, st)
-            else:                                         # the noise and the drawn move read the sampler's seed of this ply
-                self.mcts.step(logits, cur.legal_mask_bits, self.actions, model_of, self.mcts_table, st,
-                               explore_table=self.mcts_explore_table, seed=state)
-        if self.mate3 is not None:                        # a mate in one or in three overrides whatever was chosen so far
-            self.mate3.step(cur.legal_mask_bits, self.actions, model_of, self.mate_table, self.mate_reply_table, st)
-        elif self.mate is not None:                       # a mate in one does
-            self.mate.step(cur.legal_mask_bits, self.actions, model_of, self.mate_table, st)
+        for stage in self.stages.values():                # the active envs' actions become the search's choices; a later
+            stage.launch(logits, cur.legal_mask_bits, self.actions, model_of, state, st)      # stage overrides an earlier one
         if self.insight is not None:                      # while the logits exist, before the step moves the history count
             self.insight.step(logits, cur.legal_mask_bits, self.actions, value, pre, model_of, num_models, flags, st)
         return cur, pre, value, score, st

@@ -1,11 +1,13 @@
 """What the searches of the device ply share on the Python side: the rows beneath an env (``ForkedRows``), the parser of a
-per-model controls argument (``controls_rows``) and the check of the env and the group a search is built over
-(``check_search_env``).  ``Lookahead``, ``MateSearch`` and ``Mate3Search`` hold their child and grandchild rows as
-``ForkedRows``; ``TreeSearch`` and ``MctsSearch`` search in a ``NodePool``, a pool of slices plus one scratch.  The device
-side of the same rows is csrc/ply_rows.h."""
+per-model controls argument (``controls_rows``), the reader of a controls table (``table_of``), the field checks
+(``check_int``, ``check_weight``), the check of the env and the group a search is built over (``check_search_env``) and the
+shape in which a search is built into a ply (``PlyStage``).  ``Lookahead``, ``MateSearch`` and ``Mate3Search`` hold their
+child and grandchild rows as ``ForkedRows``; ``TreeSearch`` and ``MctsSearch`` search in a ``NodePool``, a pool of slices
+plus one scratch.  The device side of the same rows is csrc/ply_rows.h."""
 from __future__ import annotations
 
-from typing import Mapping
+import math
+from typing import Callable, Dict, Mapping, Optional
 
 import numpy as np
 import torch
@@ -13,7 +15,26 @@ import torch
 from keisei_amd import _lib
 from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS
 
-__all__ = ["ForkedRows", "NodePool", "controls_rows", "check_search_env"]
+__all__ = ["ForkedRows", "NodePool", "PlyStage", "controls_rows", "table_of", "check_int", "check_weight",
+           "check_search_env", "refuse_shared_place"]
+
+ERR_VALUE, ERR_STEP = 1, 2                              # the error word of a node pool's advance
+
+
+def check_int(name: str, v, lo: int, hi: int) -> int:
+    """``v`` as an int when it is an integer in ``[lo, hi]`` and no bool; refused under ``name`` otherwise."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+        raise ValueError(f"{name} must be an integer in [{lo}, {hi}], got {v!r}")
+    return int(v)
+
+
+def check_weight(name: str, w) -> float:
+    """``w`` as a float when it is finite, >= 0 and fits a float32; refused under ``name`` otherwise."""
+    if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w) or w < 0:
+        raise ValueError(f"{name} must be finite and >= 0, got {w!r}")
+    if float(w) > 3.0e38:
+        raise ValueError(f"{name} must fit a float32 (at most 3.0e38), got {w!r}")
+    return float(w)
 
 
 def check_search_env(env, group, what: str) -> None:
@@ -58,18 +79,131 @@ def controls_rows(controls, K, cls, what: str, by_index: bool = False) -> list:
     return rows
 
 
+def table_of(controls, K: Optional[int], make_table: Callable, what: str) -> np.ndarray:
+    """The ``(K, 4)`` int32 table of ``controls``: a controls object or a sequence of them goes through ``make_table``
+    (the module's ``*_table(controls, K)``; K None: the sequence's length, 1 for one object); an array or a tensor is a table
+    as it lies in device memory and is taken as it is.  ``what`` names the table in the errors ("lookahead", "search")."""
+    if isinstance(controls, torch.Tensor):
+        controls = controls.detach().cpu().numpy()
+    if isinstance(controls, np.ndarray):
+        if controls.dtype != np.int32 or controls.ndim != 2 or controls.shape[1] != 4 or controls.shape[0] < 1:
+            raise ValueError(f"a {what} table is a (K, 4) int32 array, got {controls.dtype} {controls.shape}")
+        if K is not None and controls.shape[0] != K:
+            raise ValueError(f"expected a table of {K} rows, got {controls.shape[0]}")
+        return np.ascontiguousarray(controls)
+    if K is None:
+        K = len(controls) if isinstance(controls, (list, tuple)) else 1
+    return make_table(controls, K)
+
+
+def refuse_shared_place(**options) -> None:
+    """The one rule between the searches: ``lookahead``, ``search`` and ``mcts`` stand in the same place in the ply (behind
+    the sampler, before the mate check), and a ply plays the choice of one.  ``options``: what was given for each, in that
+    order, None = not given; the later of two is refused."""
+    given = [name for name, option in options.items() if option is not None]
+    if len(given) > 1:
+        raise ValueError(f"{given[-1]}= cannot be combined with {given[0]}=: the lookahead, the tree search and the "
+                         "visit-count search stand in the same place in the ply, and a ply plays the choice of one")
+
+
+class PlyStage:
+    """One search as it is built into a ply: its ``name`` (the loop's keyword and the ``RoundStats`` field), its controls
+    ``table`` on the device, its ``engine`` (None when every row of the table is off: the table exists, nothing is allocated
+    and nothing is launched) and ``sizes``, what the engine's rows were sized by, by name.  A module's subclass says how the
+    option is read (``parse``), how the engine is built (``_engine``) and launched (``_launch``), which ``RoundStats`` fields
+    it fills (``fresh``, ``_read``) and what a recorded ply keeps of it (``_record``).  ``parse`` makes the stage on the
+    host; ``DevicePly`` builds it on the device (``build``) and loops over its stages in ``reset()`` and ``move()``.  What a
+    further search has to bring is such a subclass in its own module, its entry in ``MatchArena``'s stage list with a
+    ``set_*`` one-liner, and its ``RoundStats`` field."""
+
+    name = ""
+    shares_place = False                                # it stands where the lookahead stands (``refuse_shared_place``)
+    _ABOVE = "the {size}"                               # how ``rewrite`` names the built size it refuses to exceed
+    _ROWS = "rows"                                      # ... and what was allocated by it
+
+    def __init__(self, table: np.ndarray, **sizes: int) -> None:
+        self.host_table, self.sizes = table, sizes
+        self.table: Optional[torch.Tensor] = None
+        self.engine = None
+
+    @classmethod
+    def parse(cls, option, num_models: int, collect: bool) -> Optional["PlyStage"]:
+        """The stage of a loop's ``option`` on the host, through the module's ``arena_*`` reader; None for None."""
+        raise NotImplementedError
+
+    @classmethod
+    def _off(cls, num_models: int) -> "PlyStage":
+        raise NotImplementedError
+
+    def build(self, env, group) -> None:
+        """The table and, where a row is on, the engine, on the env's device; everything is allocated here, once."""
+        self.table = torch.from_numpy(self.host_table).to(env.device)
+        self.engine = self._engine(env, group)
+
+    def rewriters(self) -> Dict[str, Callable]:
+        """The loop's ``set_*`` options this stage answers, each with the method that takes ``(controls, num_models,
+        collect)``."""
+        return {self.name: self.rewrite}
+
+    def rewrite(self, controls, num_models: int, collect: bool) -> None:
+        """New controls from the next ply on; nothing is captured again.  None writes rows that are off.  Refused: what
+        ``parse`` refuses (``collect=True``, a wrong row count) and a size above the one built, whose rows are allocated."""
+        new = self.parse(controls, num_models, collect) or self._off(num_models)
+        for size, built in self.sizes.items():
+            if new.sizes[size] > built:
+                raise ValueError(f"{self.name} {size} {new.sizes[size]} is above {self._ABOVE.format(size=size)} this arena "
+                                 f"was built with ({built}): the {self._ROWS} are allocated once, by the largest {size} "
+                                 "given to the constructor")
+        with torch.cuda.device(self.table.device):
+            self._write(new)
+
+    def _write(self, new: "PlyStage") -> None:
+        self.table.copy_(torch.from_numpy(new.host_table))
+
+    def launch(self, logits, mask_bits, actions, model_of, seed: int, stream) -> None:
+        """The stage's launches on the current stream (``stream``: its pointer), behind the sampler and before the env
+        step: ``actions`` is overwritten for the envs the search decides.  ``seed``: the device pointer of the ply's seed."""
+        if self.engine is not None:
+            self._launch(logits, mask_bits, actions, model_of, seed, stream)
+
+    def clear(self) -> None:
+        if self.engine is not None:
+            self.engine.clear()
+
+    def fresh(self) -> dict:
+        """The ``RoundStats`` fields the stage fills, as a round begins."""
+        return {self.name: self.STATS()}
+
+    def read(self) -> dict:
+        """The same fields at a sync point, from the engine's counters; raises on its error word."""
+        return self.fresh() if self.engine is None else self._read()
+
+    def _read(self) -> dict:
+        return {self.name: self.engine.read()}
+
+    def record(self) -> dict:
+        """What a recorded ply keeps of the stage's last launch (host copies)."""
+        return {} if self.engine is None else self._record()
+
+
 class NodePool:
     """The node pool of a device ``VecEnv`` that ``TreeSearch`` and ``MctsSearch`` search in, and the stages that move rows.
     Everything is allocated here, once: ``slices * envs * width`` node rows -- state, key and check history, both packed mask
     rows, action, model, policy logits, value logits and the step's scalars -- and one scratch of ``envs * width`` rows that
     every slice's step and forward write and nothing else reads: observations, terminal observations and the forward's
     activation maps.  Slice ``t`` of the pool is rows ``[t * envs * width, (t + 1) * envs * width)``; node ``(t, j)`` of env
-    ``e`` is row ``(t * envs + e) * width + j``.  ``words``: 32-bit words of a record (the lookahead's layout)."""
+    ``e`` is row ``(t * envs + e) * width + j``.  The trees, the principal variations and the counters (with the error
+    word behind them, then ``extra_counters`` words of the subclass's) lie beside the pool; their sizes are the answers of the
+    subclass's words query (``_WORDS``: 0 = words of a record, the lookahead's layout, 1 = of a tree, 2 = counters)."""
 
-    _SLICE = "slice"                                        # what a subclass calls a slice in its errors
+    _WORDS = ""                                             # the subclass's words query: ka_search_words, ka_mcts_words
+    _WHAT, _SLICE = "the pool", "slice"                     # what a subclass calls itself and a slice in its errors
 
-    def __init__(self, env, group, width: int, slices: int, words: int) -> None:
-        self.env, self.group, self.width, self.slices, self.words = env, group, width, slices, words
+    def __init__(self, env, group, width: int, slices: int, extra_counters: int = 0) -> None:
+        check_search_env(env, group, self._WHAT)
+        q = lambda which: _lib.query(self._WORDS, which, width, slices)  # noqa: E731
+        self.env, self.group, self.width, self.slices = env, group, width, slices
+        self.words, self.tree_words, self._nstats = q(0), q(1), q(2)
         n, dev, hist = env.num_envs, env.device, env._keys.shape[1]
         self.M = M = n * width
         P = slices * M
@@ -100,9 +234,18 @@ class NodePool:
                         for t in range(slices)]
             self._env_stats = z(4, dtype=torch.int64)
             self._step_err = z(slices, 2, dtype=torch.int64)
-            self._records = z(slices, n, words, dtype=torch.int32)
+            self._records = z(slices, n, self.words, dtype=torch.int32)
             self.parent_row = torch.full((n,), -1, dtype=torch.int32, device=dev)
             self.active = z(n, dtype=torch.int32)
+            self._tree = z(n, self.tree_words, dtype=torch.int32)
+            self._pv = torch.full((n, slices), -1, dtype=torch.int32, device=dev)
+            self._counters = z(self._nstats + 1 + extra_counters, dtype=torch.int32)
+            self._counters_host = torch.zeros(self._counters.shape, dtype=torch.int32).pin_memory()
+
+    def clear(self) -> None:
+        """Zero the counters, the error word and the refusal latches of every slice's step (a round's start)."""
+        self._counters.zero_()
+        self._step_err.zero_()
 
     def rows(self, t: int) -> slice:
         """The pool rows of slice ``t``."""
@@ -161,6 +304,25 @@ class NodePool:
             return self._records.clone()
         self.rows(t)
         return self._records[t].clone()
+
+    def principal_variations(self) -> torch.Tensor:
+        """(envs, slices) int32: per env the chosen action and the line behind it, padded with -1."""
+        return self._pv.clone()
+
+    def _read_counters(self) -> np.ndarray:
+        """At a sync point: the counters since ``clear()`` (one small device -> host copy).  Raises on the error word."""
+        self._counters_host.copy_(self._counters)
+        c = self._counters_host.numpy()
+        err = int(c[self._nstats])
+        if err & ERR_STEP:
+            words = self._step_err.cpu()
+            t = int(torch.nonzero(words.ne(0).any(1))[0]) if bool(words.ne(0).any()) else 0
+            raise RuntimeError(f"{self._WHAT}'s step of {self._SLICE} {t} refused an action (word "
+                               f"{int(words[t, 1]) or int(words[t, 0]):#x}): a forked row does not match the mask it was "
+                               "forked with")
+        if err & ERR_VALUE:
+            raise RuntimeError(f"non-finite value logits in {self._WHAT} (a model has diverged)")
+        return c
 
 
 class ForkedRows:

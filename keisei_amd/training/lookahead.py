@@ -49,7 +49,7 @@ import torch
 from keisei_amd import _lib
 from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS
 
-from ._forked_rows import ForkedRows, check_search_env, controls_rows
+from ._forked_rows import ForkedRows, PlyStage, check_int, check_search_env, check_weight, controls_rows, table_of
 
 __all__ = ["LookaheadControls", "LookaheadStats", "LookaheadChoice", "LookaheadReplyChoice", "Lookahead", "lookahead_table",
            "lookahead_active", "lookahead_reply_widths", "lookahead_candidates", "lookahead_choose", "lookahead_choose_replies",
@@ -80,16 +80,8 @@ class LookaheadControls:
 
     def __post_init__(self) -> None:
         for name, hi in (("width", MAX_WIDTH), ("skip_plies", MAX_SKIP_PLIES), ("reply_width", MAX_WIDTH)):
-            v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= hi:
-                raise ValueError(f"{name} must be an integer in [0, {hi}], got {v!r}")
-            object.__setattr__(self, name, int(v))
-        w = self.prior_weight
-        if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w) or w < 0:
-            raise ValueError(f"prior_weight must be finite and >= 0, got {w!r}")
-        object.__setattr__(self, "prior_weight", float(w))
-        if self.prior_weight > 3.0e38:
-            raise ValueError(f"prior_weight must fit a float32 (at most 3.0e38), got {w!r}")
+            object.__setattr__(self, name, check_int(name, getattr(self, name), 0, hi))
+        object.__setattr__(self, "prior_weight", check_weight("prior_weight", self.prior_weight))
         if self.reply_width > 0 and self.width == 0:
             raise ValueError(f"reply_width {self.reply_width} needs a width above 0: there is no child to reply to")
 
@@ -139,20 +131,6 @@ def arena_reply_width(lookahead, num_models: int) -> int:
     return 0 if lookahead is None else max(r.reply_width for r in _rows(lookahead, num_models))
 
 
-def _table_of(controls, K: Optional[int]) -> np.ndarray:
-    if isinstance(controls, torch.Tensor):
-        controls = controls.detach().cpu().numpy()
-    if isinstance(controls, np.ndarray):              # a table as it lies in device memory: taken as it is
-        if controls.dtype != np.int32 or controls.ndim != 2 or controls.shape[1] != 4 or controls.shape[0] < 1:
-            raise ValueError(f"a lookahead table is a (K, 4) int32 array, got {controls.dtype} {controls.shape}")
-        if K is not None and controls.shape[0] != K:
-            raise ValueError(f"expected a table of {K} rows, got {controls.shape[0]}")
-        return np.ascontiguousarray(controls)
-    if K is None:
-        K = len(controls) if isinstance(controls, (list, tuple)) else 1
-    return lookahead_table(controls, K)
-
-
 def _row_controls(row: np.ndarray) -> Tuple[int, float, int]:
     """(width, prior_weight, skip_plies) of a table row as the kernels read it: a row with width outside [0, 8], a negative
     or non-finite weight or a negative skip_plies is off."""
@@ -168,7 +146,7 @@ def lookahead_active(controls, model_of, plies=None, *, num_models: Optional[int
     outside ``[0, K)``, whose table row is off or invalid, or whose game ply is below ``skip_plies``; a width above
     ``width`` (the launch's) is cut to it.  ``plies`` None = past every ``skip_plies``.  (A row with a positive width is
     active when it also has a candidate.)"""
-    table = _table_of(controls, num_models)
+    table = table_of(controls, num_models, lookahead_table, "lookahead")
     mo = np.asarray(torch.as_tensor(model_of).cpu().numpy(), np.int64).reshape(-1)
     pl = None if plies is None else np.asarray(torch.as_tensor(plies).cpu().numpy(), np.int64).reshape(-1)
     widths, weights = np.zeros(mo.shape[0], np.int64), np.zeros(mo.shape[0], np.float64)
@@ -186,7 +164,7 @@ def lookahead_reply_widths(controls, model_of, *, num_models: Optional[int] = No
     """Per row: the reply width as the kernels read it from the table -- 0 for a row whose model lies outside ``[0, K)`` or
     whose table row is off or invalid, word 3 outside [0, 8] reads as 0; a value above ``reply_width`` (the launch's) is cut
     to it.  ``skip_plies`` plays no part at this level."""
-    table = _table_of(controls, num_models)
+    table = table_of(controls, num_models, lookahead_table, "lookahead")
     mo = np.asarray(torch.as_tensor(model_of).cpu().numpy(), np.int64).reshape(-1)
     out = np.zeros(mo.shape[0], np.int64)
     for b, m in enumerate(mo):
@@ -198,9 +176,7 @@ def lookahead_reply_widths(controls, model_of, *, num_models: Optional[int] = No
 
 # ---------------------------------------------------------------------------------------------- candidates
 def _check_width(width, name: str = "width", lo: int = 1) -> int:
-    if isinstance(width, bool) or not isinstance(width, (int, np.integer)) or not lo <= width <= MAX_WIDTH:
-        raise ValueError(f"{name} must be an integer in [{lo}, {MAX_WIDTH}], got {width!r}")
-    return int(width)
+    return check_int(name, width, lo, MAX_WIDTH)
 
 
 def lookahead_candidates(logits: torch.Tensor, legal: torch.Tensor, width: int):
@@ -629,3 +605,41 @@ class Lookahead:
         the grandchildren's values."""
         self._need_replies()
         return self._reply_records.clone()
+
+
+class LookaheadStage(PlyStage):
+    """The lookahead as a loop builds it into its ply (``lookahead=``: a ``LookaheadControls`` for every model, or one per
+    model), between the sampler and the mate check: the insight, the game log and the spectator notes describe the move
+    actually played.  The child rows and a second forward workspace are sized by the largest ``width`` given, the grandchild
+    rows and a third workspace by the largest ``reply_width``; ``set_lookahead`` goes up to them.  With every ``reply_width``
+    0 the launches are those of the one-ply lookahead.  ``RoundStats.lookahead`` carries the counters."""
+
+    name, shares_place, STATS = "lookahead", True, LookaheadStats
+    _ROWS = "child and grandchild rows"
+
+    @classmethod
+    def parse(cls, lookahead, num_models: int, collect: bool) -> Optional["LookaheadStage"]:
+        table, width = arena_lookahead(lookahead, num_models, collect)
+        return None if table is None else cls(table, width=width, reply_width=arena_reply_width(lookahead, num_models))
+
+    @classmethod
+    def _off(cls, num_models: int) -> "LookaheadStage":
+        return cls(lookahead_table(None, num_models), width=0, reply_width=0)
+
+    def _engine(self, env, group) -> Optional[Lookahead]:
+        return Lookahead(env, group, **self.sizes) if self.sizes["width"] else None
+
+    def _launch(self, logits, mask_bits, actions, model_of, seed, stream) -> None:
+        self.engine.step(logits, mask_bits, actions, model_of, self.table, stream)
+
+    def _record(self) -> dict:
+        la, w, r = self.engine, self.engine.width, self.engine.reply_width
+        cpu = lambda t, *shape: t.cpu().reshape(-1, *shape)  # noqa: E731
+        rec = dict(lookahead_records=la.records().cpu(), child_value_logits=cpu(la.child_value_logits, w, 3),
+                   child_rewards=cpu(la.child_rewards, w), child_done=cpu(la.child_terminated | la.child_truncated, w),
+                   child_obs=la.child_obs.cpu(), child_mask_bits=la.child_mask_bits.cpu())
+        if r:
+            rec.update(lookahead_reply_records=la.reply_records().cpu(), grand_value_logits=cpu(la.grand_value_logits, w, r, 3),
+                       grand_rewards=cpu(la.grand_rewards, w, r), grand_done=cpu(la.grand_terminated | la.grand_truncated, w, r),
+                       child_logits=cpu(la.child_logits, ACTION_SPACE))
+        return rec

@@ -65,20 +65,20 @@ import numpy as np
 import torch
 
 from keisei_amd import _lib
-from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS
+from keisei_amd.shogi_gym import MASK_WORDS
 
 from ._device_ply import _OBS_ELEMS, DevicePly, check_loop_args
 from .dynamic_trainer import MatchRollout
 from .game_feature_tracker import GameFeatureTracker
 from .game_log import RecordedGame
-from .lookahead import LookaheadStats, arena_lookahead, arena_reply_width, lookahead_table
-from .mate_search import Mate3Stats, MateStats, arena_mate, arena_mate3, mate3_reply_table, mate_table
-from .mcts_explore import arena_mcts_explore, explore_table
-from .mcts_search import MctsStats, arena_mcts, mcts_table
+from .lookahead import LookaheadStage, LookaheadStats
+from .mate_search import Mate3Stats, MateStage, MateStats
+from .mcts_explore import arena_mcts_explore
+from .mcts_search import MctsStage, MctsStats
 from .model_group import SEResNetGroup
 from .sampling import GAME_PLY_BYTE, arena_controls, controls_table
 from .search_samples import arena_search_samples
-from .tree_search import SearchStats, arena_search, search_table
+from .tree_search import SearchStage, SearchStats
 
 _HDR, _SLOT = 8, 8                      # int32 words of the state header and of one slot (csrc/arena.hip)
 _PLY, _MAX_PLY, _SAMP, _REFUSAL = 2, 3, 4, 6    # header words: plies of the round, the ply ceiling's max_ply, the
@@ -298,60 +298,20 @@ class MatchArena:
     inherited it from the slot's previous pairing or the slot sat idle during it (there is no per-slot reset).
     ``collect``, ``features`` and ``game_log`` are independent.  The ``insight`` of ``spectator_data()`` is None for the
     envs of an idle slot.
-    ``sampling=`` (a ``SamplingControls`` for every model, or one per model; ``sampling.py``) replaces the play sampler of the
-    ply by ``ka_policy_sample_ctl`` -- temperature, top-k cut and opening schedule per model, read from a table on the device
-    that ``set_sampling`` rewrites between rounds without a new capture.  With None the ply is launch for launch what it
-    was.  Not with ``collect=True``.  The insight keeps its own ``insight_temperature``: under a cut or an opening
-    schedule its probabilities are those of the uncut, single-temperature softmax.
-    ``lookahead=`` (a ``LookaheadControls`` for every model, or one per model; ``lookahead.py``) adds a one-ply value
-    lookahead between the sampler and the insight: a model with ``width > 0`` plays, of its ``width`` most probable legal
-    moves, the one whose child position its own value head likes best (a move that ends the game counts by its reward), so
-    the insight, the game log and the spectator notes describe the move actually played.  The child rows and a second
-    forward workspace are sized by the largest ``width`` given; ``set_lookahead`` rewrites the table on the device between
-    rounds without a new capture, up to that width.  ``RoundStats.lookahead`` carries the counters.  With None the ply is
-    launch for launch what it was; with every width 0 nothing is allocated and nothing is launched.  Not with
-    ``collect=True``.  A model with ``reply_width = r > 0`` searches a second ply: every live child gets the model's ``r``
-    most probable replies (by the child logits the children's forward wrote anyway), the grandchildren are stepped and
-    evaluated like the children, and a candidate is worth the worst of its replies for the mover -- so a move that walks into a
-    mate in one or hangs a piece to a one-move capture is seen.  The grandchild rows and a third workspace are sized by the
-    largest ``reply_width`` given (``set_lookahead`` goes up to it); ``RoundStats.lookahead.reply_changed`` counts the choices
-    that differ from the one-ply choice.  With every ``reply_width`` 0 the launches are those of the one-ply lookahead.
-    ``search=`` (a ``SearchControls`` for every model, or one per model; ``tree_search.py``) puts a best-first minimax search
-    where the lookahead stands: ``expansions`` forks of ``width`` rows per env, each spent on the leaf of the current principal
-    variation, values backed up by max and negation.  The node pool is sized by the largest ``width`` and ``expansions``
-    given; ``set_search`` rewrites the table between rounds without a new capture, up to those.  ``RoundStats.search``
-    carries the counters.  With None nothing is allocated and the launches are what they were.  Not together with
-    ``lookahead=`` and not with ``collect=True``.
-    ``mcts=`` (an ``MctsControls`` for every model, or one per model; ``mcts_search.py``) puts a visit-count (PUCT) search
-    where the lookahead stands: ``simulations`` forks of ``width`` rows per env, spread by ``Q + c_puct P sqrt(N) / (1 + n)``,
-    values backed up as means, the most visited root candidate played.  ``self.mcts.root_visits()`` between two plies gives the
-    visit distribution of every searched position (``visit_policy`` makes a dense target of it).  The node pool is sized by the
-    largest ``width`` and ``simulations`` given; ``set_mcts`` rewrites the table between rounds without a new capture, up to
-    those.  ``RoundStats.mcts`` carries the counters.  With None nothing is allocated and the launches are what they were.
-    Not together with ``lookahead=`` or ``search=`` and not with ``collect=True``.
-    ``mcts_explore=`` (an ``MctsExploration`` for every model, or one per model; ``mcts_explore.py``; only with ``mcts=``)
-    gives that search its two sources of variety: Dirichlet noise mixed into the root priors (one launch,
-    ``ka_mcts_root_noise``, behind the fork of simulation 0) and, while a game's ply lies below ``sample_plies``, the move
-    drawn in proportion to the root visits (a branch of the advance, ``ka_mcts_advance_explore``).  Both draw from the round's
-    seed, so two arenas with one seed play the same games.  ``set_mcts_explore`` rewrites the table between rounds without a
-    new capture; ``self.mcts.root_noise()`` gives the priors before the noise and the draw, ``RoundStats.mcts`` the counters
-    ``noised`` / ``sampled`` / ``diverged``.  With None nothing is allocated and the launches are what they were.
-    ``search_samples=rows_per_env > 0`` (only with ``mcts=``; ``search_samples.py``) adds one launch,
-    ``ka_search_sample_step``, behind the env step: every searched position is written, packed as a ``DeviceSLDataset`` row,
-    with its visit counts into the env's region of ``rows_per_env`` rows, and a game that ends labels its rows W / D / L.
-    ``arena.search_samples.drain()`` between two rounds hands the labelled rows over as a ``DeviceSLDataset`` that
-    ``SLTrainer`` with ``visit_targets=True`` trains on.  With 0 nothing is allocated and the launches are what they were.
-    ``mate=`` (a ``MateControls`` for every model, one per model, or a dict by model index; ``mate_search.py``) adds a
-    rules-only mate-in-one check behind the lookahead or the search and before the insight: the legal moves that give check
-    are forked (at most ``max_checks`` of them, in ascending action order), the env's own step decides them, and a move that
-    mates is played in the place of whatever was chosen.  The child rows are sized by the largest ``max_checks`` given;
-    ``set_mate`` rewrites the table between rounds without a new capture, up to it.  ``RoundStats.mate`` carries the
-    counters.  With None nothing is allocated and the launches are what they were.  Not with ``collect=True``.  Controls
-    with ``evasion_rows`` / ``reply_checks`` > 0 put the mate in three behind it (``Mate3Search``): an env with checking
-    moves and no mate in one forks the defender's evasions of every check into at most ``evasion_rows`` grandchild rows,
-    looks for a mate in one behind each among ``reply_checks`` checking moves, and plays the lowest check that every reply
-    loses to.  The rows are sized by the largest values given, ``set_mate`` switches it per model under the same capture,
-    ``RoundStats.mate3`` carries its counters; without such controls the launches are the mate in one's."""
+    The options that change how a move is chosen are per model, each described in its module.  None leaves the ply launch
+    for launch what it was; every row off allocates nothing and launches nothing; none goes with ``collect=True``; each
+    ``set_*`` rewrites the option's table on the device between two rounds without a new capture, up to the sizes built.
+    ``sampling=`` (``sampling.py``, ``set_sampling``): temperature, top-k cut and opening schedule, ``ka_policy_sample_ctl``.
+    ``lookahead=`` (``lookahead.py``, ``set_lookahead``): the best of the top moves by the model's own value head, with a
+    ``reply_width`` over two plies.
+    ``search=`` (``tree_search.py``, ``set_search``): a best-first minimax search where the lookahead stands.
+    ``mcts=`` (``mcts_search.py``, ``set_mcts``): a visit-count (PUCT) search in the same place; ``arena.mcts`` is its engine.
+    ``mcts_explore=`` (``mcts_explore.py``, ``set_mcts_explore``; only with ``mcts=``): root noise and visit-proportional play.
+    ``search_samples=rows_per_env`` (``search_samples.py``; only with ``mcts=``): the searched positions as training rows,
+    ``arena.search_samples.drain()`` between two rounds.
+    ``mate=`` (``mate_search.py``, ``set_mate``): a rules-only mate in one, and in three, that overrides whatever was chosen.
+    At most one of ``lookahead=``, ``search=`` and ``mcts=``.  The searches are the ``PlyStage`` objects of
+    ``arena.ply.stages`` (``_forked_rows.py``), by name, in launch order; their counters are the ``RoundStats`` fields."""
 
     def __init__(self, group: SEResNetGroup, num_envs: int = 512, envs_per_match: int = 64, max_ply: int = 512, *,
                  sync_every: int = 32, graph: bool = True, seed: Optional[int] = None, record: bool = False,
@@ -364,20 +324,18 @@ class MatchArena:
         if num_envs <= 0 or envs_per_match <= 0 or num_envs % envs_per_match != 0:
             raise ValueError(f"num_envs ({num_envs}) must be a positive multiple of envs_per_match ({envs_per_match})")
         check_loop_args(max_ply, sync_every, graph, record, start_pool_capacity, game_log)
-        search_samples = arena_search_samples(search_samples, mcts, len(group))
-        xp_table = arena_mcts_explore(mcts_explore, mcts, len(group))
+        K, collect = len(group), bool(collect)
+        search_samples = arena_search_samples(search_samples, mcts, K)
+        explore = arena_mcts_explore(mcts_explore, mcts, K)
         if features and start_pool_capacity > 0:
             raise ValueError("features=True cannot be combined with start_pool_capacity > 0: the opening and rook-square "
                              "style features are defined from the standard start position")
         if group.device.type != "cuda" or group._tables is None:
             raise ValueError(f"MatchArena runs on a GPU group; this group is on {group.device} (VecEnv has no CPU path)")
-        table = arena_controls(sampling, len(group), bool(collect))
-        la_table, la_width = arena_lookahead(lookahead, len(group), bool(collect))
-        la_reply = arena_reply_width(lookahead, len(group))
-        se_table, se_width, se_expansions = arena_search(search, len(group), bool(collect), lookahead)
-        mc_table, mc_width, mc_sims = arena_mcts(mcts, len(group), bool(collect), lookahead, search)
-        mt_table, mt_cap = arena_mate(mate, len(group), bool(collect))
-        mt_rows, mt_reply = arena_mate3(mate, len(group))
+        table = arena_controls(sampling, K, collect)
+        # the searches of the ply, in launch order (None: not given); DevicePly refuses two in the lookahead's place
+        stages = (LookaheadStage.parse(lookahead, K, collect), SearchStage.parse(search, K, collect),
+                  MctsStage.parse(mcts, K, collect, explore), MateStage.parse(mate, K, collect))
         self.group = group
         self.device = group.device
         self.num_envs, self.envs_per_match, self.max_ply = int(num_envs), int(envs_per_match), int(max_ply)
@@ -386,24 +344,15 @@ class MatchArena:
         self.record_enabled = bool(record)
         self.record: List[dict] = []
         N, dev = self.num_envs, self.device
-        # the controls table of ka_policy_sample_ctl and the lookahead's table are allocated once: set_sampling and
-        # set_lookahead write into them, the ply reads them
+        # the controls table of ka_policy_sample_ctl and the stages' tables are allocated once: the set_* methods write
+        # into them, the ply reads them
         self.ply = ply = DevicePly(group, N, self.max_ply, start_pool_capacity=int(start_pool_capacity), game_log=game_log,
                                    envs_per_slot=self.envs_per_match, move_history=move_history, insight=insight,
-                                   insight_temperature=insight_temperature, controls=table, lookahead_table=la_table,
-                                   lookahead_width=la_width, lookahead_reply_width=la_reply, search_table=se_table,
-                                   search_width=se_width, search_expansions=se_expansions, mate_table=mt_table,
-                                   mate_cap=mt_cap, mate_rows=mt_rows, mate_reply_cap=mt_reply, mcts_table=mc_table,
-                                   mcts_width=mc_width, mcts_simulations=mc_sims, search_samples=int(search_samples),
-                                   mcts_explore_table=xp_table)
+                                   insight_temperature=insight_temperature, controls=table, stages=stages,
+                                   search_samples=int(search_samples))
         self.env, self.game_log, self.insight = ply.env, ply.game_log, ply.insight
         self._actions, self._logp, self._nlegal = ply.actions, ply.log_probs, ply.n_legal
-        self._ctl, self._la_table, self._la = ply.ctl, ply.lookahead_table, ply.lookahead
-        self._se_table, self._se = ply.search_table, ply.search
-        self._mc_table, self.mcts, self._xp_table = ply.mcts_table, ply.mcts, ply.mcts_explore_table
-        self.search_samples = ply.search_samples
-        self._mt_table, self._mt = ply.mate_table, ply.mate
-        self._mt3, self._mt3_table = ply.mate3, ply.mate_reply_table
+        self._ctl, self.mcts, self.search_samples = ply.ctl, ply.mcts, ply.search_samples
         with torch.cuda.device(dev):
             self._state = torch.zeros(_lib.query("ka_arena_state_words", self.num_slots), dtype=torch.int32, device=dev)
             self._state_host = torch.zeros(self._state.shape, dtype=torch.int32).pin_memory()
@@ -444,118 +393,41 @@ class MatchArena:
                 self._every_slot = every.to(dev)                  # seat jobs naming every slot: the round-start clear
         self._graph: Optional[torch.cuda.CUDAGraph] = None
 
-    def set_lookahead(self, lookahead) -> None:
-        """New lookahead controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
-        writes rows that are off.  A width above the one the arena was built with is refused (the child rows are sized by
-        it), and so is an arena built without ``lookahead=``: its ply holds no lookahead."""
-        if self._la_table is None:
-            raise ValueError("this arena was built without lookahead=: its ply (and its captured graph) holds no "
-                             "lookahead; build the arena with lookahead controls to change them later")
-        table, width = arena_lookahead(lookahead, len(self.group), self.collect)
-        if table is None:
-            table = lookahead_table(None, len(self.group))
-        built = 0 if self._la is None else self._la.width
-        if width > built:
-            raise ValueError(f"lookahead width {width} is above the width this arena was built with ({built}): the child "
-                             "rows are allocated once, by the largest width given to the constructor")
-        reply, built = arena_reply_width(lookahead, len(self.group)), 0 if self._la is None else self._la.reply_width
-        if reply > built:
-            raise ValueError(f"lookahead reply_width {reply} is above the reply_width this arena was built with ({built}): "
-                             "the grandchild rows are allocated once, by the largest reply_width given to the constructor")
-        with torch.cuda.device(self.device):
-            self._la_table.copy_(torch.from_numpy(table))
+    def _set(self, option: str, controls) -> None:
+        """New controls for ``option`` from the next ply on (between two ``run_round`` calls); nothing is captured again.
+        None writes rows that are off (neutral rows for the sampler).  Refused: an arena built without the option -- its ply
+        and its captured graph hold no launch of it --, ``collect=True``, a wrong row count and a size above the size built
+        (``PlyStage.rewrite``)."""
+        rewriters = {} if self._ctl is None else {"sampling": self._rewrite_sampling}
+        for stage in self.ply.stages.values():
+            rewriters.update(stage.rewriters())
+        if option not in rewriters:
+            raise ValueError(f"this arena was built without {option}=: its ply (and its captured graph) holds no launch of "
+                             f"it; build the arena with {option}= controls to change them later")
+        rewriters[option](controls, len(self.group), self.collect)
 
-    def set_mate(self, mate) -> None:
-        """New mate controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
-        writes rows that are off.  A ``max_checks``, ``evasion_rows`` or ``reply_checks`` above the largest the arena was
-        built with is refused (the child, grandchild and third-ply rows are sized by them), and so is an arena built
-        without ``mate=``: its ply holds no mate check."""
-        if self._mt_table is None:
-            raise ValueError("this arena was built without mate=: its ply (and its captured graph) holds no mate check; "
-                             "build the arena with mate controls to change them later")
-        table, cap = arena_mate(mate, len(self.group), self.collect)
-        if table is None:
-            table = mate_table(None, len(self.group))
-        built = 0 if self._mt is None else self._mt.cap
-        if cap > built:
-            raise ValueError(f"mate max_checks {cap} is above the largest this arena was built with ({built}): the child "
-                             "rows are allocated once, by the largest max_checks given to the constructor")
-        rows, reply = arena_mate3(mate, len(self.group))
-        built_rows, built_reply = (0, 0) if self._mt3 is None else (self._mt3.rows, self._mt3.reply_cap)
-        if rows > built_rows:
-            raise ValueError(f"mate evasion_rows {rows} is above the largest this arena was built with ({built_rows}): the "
-                             "grandchild rows are allocated once, by the largest evasion_rows given to the constructor")
-        if reply > built_reply:
-            raise ValueError(f"mate reply_checks {reply} is above the largest this arena was built with ({built_reply}): "
-                             "the third ply's rows are allocated once, by the largest reply_checks given to the constructor")
+    def _rewrite_sampling(self, sampling, num_models: int, collect: bool) -> None:
+        table = arena_controls(sampling, num_models, collect)
         with torch.cuda.device(self.device):
-            self._mt_table.copy_(torch.from_numpy(table))
-            if self._mt3_table is not None:
-                self._mt3_table.copy_(torch.from_numpy(mate3_reply_table(table)))
-
-    def set_search(self, search) -> None:
-        """New search controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
-        writes rows that are off.  A width or ``expansions`` above what the arena was built with is refused (the node pool is
-        sized by them), and so is an arena built without ``search=``: its ply holds no search."""
-        if self._se_table is None:
-            raise ValueError("this arena was built without search=: its ply (and its captured graph) holds no search; "
-                             "build the arena with search controls to change them later")
-        table, width, expansions = arena_search(search, len(self.group), self.collect)
-        if table is None:
-            table = search_table(None, len(self.group))
-        built = 0 if self._se is None else self._se.width
-        if width > built:
-            raise ValueError(f"search width {width} is above the width this arena was built with ({built}): the node pool "
-                             "is allocated once, by the largest width given to the constructor")
-        built = 1 if self._se is None else self._se.expansions
-        if expansions > built:
-            raise ValueError(f"search expansions {expansions} is above the expansions this arena was built with ({built}): "
-                             "the node pool is allocated once, by the largest expansions given to the constructor")
-        with torch.cuda.device(self.device):
-            self._se_table.copy_(torch.from_numpy(table))
-
-    def set_mcts(self, mcts) -> None:
-        """New visit-count search controls from the next ply on (between two ``run_round`` calls); nothing is captured
-        again.  None writes rows that are off.  A width or ``simulations`` above what the arena was built with is refused (the
-        node pool is sized by them), and so is an arena built without ``mcts=``: its ply holds no such search."""
-        if self._mc_table is None:
-            raise ValueError("this arena was built without mcts=: its ply (and its captured graph) holds no visit-count "
-                             "search; build the arena with mcts controls to change them later")
-        table, width, simulations = arena_mcts(mcts, len(self.group), self.collect)
-        if table is None:
-            table = mcts_table(None, len(self.group))
-        built = 0 if self.mcts is None else self.mcts.width
-        if width > built:
-            raise ValueError(f"mcts width {width} is above the width this arena was built with ({built}): the node pool "
-                             "is allocated once, by the largest width given to the constructor")
-        built = 1 if self.mcts is None else self.mcts.simulations
-        if simulations > built:
-            raise ValueError(f"mcts simulations {simulations} is above the simulations this arena was built with ({built}): "
-                             "the node pool is allocated once, by the largest simulations given to the constructor")
-        with torch.cuda.device(self.device):
-            self._mc_table.copy_(torch.from_numpy(table))
-
-    def set_mcts_explore(self, mcts_explore) -> None:
-        """New exploration controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
-        writes rows that are off: the games are then those of the search alone.  An arena built without ``mcts_explore=``
-        holds neither the noise launch nor the exploring advance in its ply and refuses."""
-        if self._xp_table is None:
-            raise ValueError("this arena was built without mcts_explore=: its ply (and its captured graph) holds no "
-                             "exploration; build the arena with exploration controls to change them later")
-        with torch.cuda.device(self.device):
-            self._xp_table.copy_(torch.from_numpy(explore_table(mcts_explore, len(self.group))))
+            self._ctl.copy_(torch.from_numpy(controls_table(None, num_models) if table is None else table))
 
     def set_sampling(self, sampling) -> None:
-        """New sampling controls from the next ply on (between two ``run_round`` calls); nothing is captured again.  None
-        writes neutral rows.  An arena built without ``sampling=`` holds the play sampler in its ply and refuses."""
-        if self._ctl is None:
-            raise ValueError("this arena was built without sampling=: its ply (and its captured graph) holds "
-                             "ka_policy_sample_play; build the arena with sampling controls to change them later")
-        table = arena_controls(sampling, len(self.group), self.collect)
-        if table is None:
-            table = controls_table(None, len(self.group))
-        with torch.cuda.device(self.device):
-            self._ctl.copy_(torch.from_numpy(table))
+        self._set("sampling", sampling)
+
+    def set_lookahead(self, lookahead) -> None:
+        self._set("lookahead", lookahead)
+
+    def set_search(self, search) -> None:
+        self._set("search", search)
+
+    def set_mcts(self, mcts) -> None:
+        self._set("mcts", mcts)
+
+    def set_mcts_explore(self, mcts_explore) -> None:
+        self._set("mcts_explore", mcts_explore)
+
+    def set_mate(self, mate) -> None:
+        self._set("mate", mate)
 
     # ------------------------------------------------------------------ one ply
     def _ply(self) -> None:
@@ -595,44 +467,10 @@ class MatchArena:
                "pre_players": self.env._players[self.env._cur].cpu(),
                "game_plies": self.env._state[:, GAME_PLY_BYTE:GAME_PLY_BYTE + 4].cpu().contiguous().view(torch.int32).reshape(-1)}
         self._ply()
-        if self._la is not None:
-            la, w = self._la, self._la.width
-            rec.update(lookahead_records=la.records().cpu(), child_value_logits=la.child_value_logits.cpu().reshape(-1, w, 3),
-                       child_rewards=la.child_rewards.cpu().reshape(-1, w),
-                       child_done=(la.child_terminated | la.child_truncated).cpu().reshape(-1, w),
-                       child_obs=la.child_obs.cpu(), child_mask_bits=la.child_mask_bits.cpu())
-            if la.reply_width:
-                r = la.reply_width
-                rec.update(lookahead_reply_records=la.reply_records().cpu(),
-                           grand_value_logits=la.grand_value_logits.cpu().reshape(-1, w, r, 3),
-                           grand_rewards=la.grand_rewards.cpu().reshape(-1, w, r),
-                           grand_done=(la.grand_terminated | la.grand_truncated).cpu().reshape(-1, w, r),
-                           child_logits=la.child_logits.cpu().reshape(-1, ACTION_SPACE))
-        if self._se is not None:
-            se = self._se
-            shape = (se.expansions, self.num_envs, se.width)
-            rec.update(search_records=se.records().cpu(), search_tree={k: v.cpu() for k, v in se.tree().items()},
-                       search_pv=se.principal_variations().cpu(), node_value_logits=se.value_logits.cpu().reshape(*shape, 3),
-                       node_rewards=se.rewards.cpu().reshape(shape), node_done=(se.terminated | se.truncated).cpu().reshape(shape),
-                       node_logits=se.logits.cpu().reshape(-1, ACTION_SPACE), node_mask_bits=se.mask_bits.cpu(),
-                       node_model_of=se.model_of.cpu().reshape(shape))
-        if self.mcts is not None:
-            mc = self.mcts
-            shape = (mc.simulations, self.num_envs, mc.width)
-            rec.update(mcts_records=mc.records().cpu(), mcts_tree={k: v.cpu() for k, v in mc.tree().items()},
-                       mcts_pv=mc.principal_variations().cpu(), mcts_root_visits=tuple(x.cpu() for x in mc.root_visits()),
-                       node_value_logits=mc.value_logits.cpu().reshape(*shape, 3), node_rewards=mc.rewards.cpu().reshape(shape),
-                       node_done=(mc.terminated | mc.truncated).cpu().reshape(shape),
-                       node_logits=mc.logits.cpu().reshape(-1, ACTION_SPACE), node_mask_bits=mc.mask_bits.cpu(),
-                       node_model_of=mc.model_of.cpu().reshape(shape))
-            if self._xp_table is not None and mc._eta is not None:
-                rec.update(mcts_root_noise=tuple(x.cpu() for x in mc.root_noise()))
+        for stage in self.ply.stages.values():
+            rec.update(stage.record())
         if self.search_samples is not None:
             rec.update(material_balance=self.env._material[self.env._cur].cpu())
-        if self._mt is not None:
-            rec.update(mate_records=self._mt.records().cpu())
-        if self._mt3 is not None:
-            rec.update(mate3_records=self._mt3.records().cpu())
         rec.update(actions=self._actions.cpu(), log_probs=self._logp.cpu(), n_legal=self._nlegal.cpu(),
                    rewards=self.env._rewards[self.env._cur].cpu(), terminated=self.env._terminated[self.env._cur].cpu(),
                    truncated=self.env._truncated[self.env._cur].cpu())
@@ -767,16 +605,8 @@ class MatchArena:
         if max_ply < 1:
             raise ValueError(f"max_ply must be positive, got {max_ply}")
         stats = RoundStats(pairings_requested=len(pairings))
-        if self._la_table is not None:                    # (every width 0: nothing is searched)
-            stats.lookahead = LookaheadStats()
-        if self._se_table is not None:
-            stats.search = SearchStats()
-        if self._mc_table is not None:
-            stats.mcts = MctsStats()
-        if self._mt_table is not None:
-            stats.mate = MateStats()
-        if self._mt3 is not None:
-            stats.mate3 = Mate3Stats()
+        for stage in self.ply.stages.values():            # (every row off: nothing is searched, the counters stay 0)
+            vars(stats).update(stage.fresh())
         if not pairings:
             return [], stats
         with torch.cuda.device(self.device), torch.no_grad():
@@ -822,16 +652,8 @@ class MatchArena:
         while active:
             self._chunk()
             st = self._read_state()
-            if self._la is not None:                      # raises on its error word
-                stats.lookahead = self._la.read()
-            if self._se is not None:
-                stats.search = self._se.read()
-            if self.mcts is not None:
-                stats.mcts = self.mcts.read()
-            if self._mt is not None:
-                stats.mate = self._mt.read()
-            if self._mt3 is not None:
-                stats.mate3 = self._mt3.read()
+            for stage in self.ply.stages.values():        # raises on its error word
+                vars(stats).update(stage.read())
             stats.host_syncs += 1
             slot = st[_HDR:].reshape(self.num_slots, _SLOT)
             if self.collect:

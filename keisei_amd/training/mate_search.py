@@ -38,7 +38,7 @@ import torch
 from keisei_amd import _lib
 from keisei_amd.shogi_gym import ACTION_SPACE, MASK_WORDS
 
-from ._forked_rows import ForkedRows, check_search_env, controls_rows
+from ._forked_rows import ForkedRows, PlyStage, check_int, check_search_env, controls_rows
 
 __all__ = ["MateControls", "MateStats", "MateSearch", "mate_table", "mate_words", "arena_mate", "MAX_CHECKS",
            "MAX_SKIP_PLIES", "MAX_EVASION_ROWS", "Mate3Stats", "Mate3Search", "mate3_words", "mate3_reply_table",
@@ -78,10 +78,7 @@ class MateControls:
     def __post_init__(self) -> None:
         for name, hi in (("max_checks", MAX_CHECKS), ("skip_plies", MAX_SKIP_PLIES), ("evasion_rows", MAX_EVASION_ROWS),
                          ("reply_checks", MAX_CHECKS)):
-            v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= hi:
-                raise ValueError(f"{name} must be an integer in [0, {hi}], got {v!r}")
-            object.__setattr__(self, name, int(v))
+            object.__setattr__(self, name, check_int(name, getattr(self, name), 0, hi))
         if (self.evasion_rows > 0) != (self.reply_checks > 0):
             raise ValueError(f"evasion_rows and reply_checks must be both zero or both positive, got {self.evasion_rows} "
                              f"and {self.reply_checks}")
@@ -150,9 +147,7 @@ def arena_mate3(mate, num_models: int) -> Tuple[int, int]:
 
 
 def _check_cap(cap) -> int:
-    if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 1 <= cap <= MAX_CHECKS:
-        raise ValueError(f"cap must be an integer in [1, {MAX_CHECKS}], got {cap!r}")
-    return int(cap)
+    return check_int("cap", cap, 1, MAX_CHECKS)
 
 
 class MateSearch:
@@ -245,10 +240,9 @@ class Mate3Search:
     third ply's three stages and ``ka_mate3_choose`` (csrc/mate3.hip)."""
 
     def __init__(self, env, cap: int, rows: int, reply_cap: int) -> None:
-        if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or not 1 <= rows <= MAX_EVASION_ROWS:
-            raise ValueError(f"rows must be an integer in [1, {MAX_EVASION_ROWS}], got {rows!r}")
+        rows = check_int("rows", rows, 1, MAX_EVASION_ROWS)
         self.root = MateSearch(env, cap)
-        self.env, self.cap, self.rows, self.reply_cap = env, self.root.cap, int(rows), _check_cap(reply_cap)
+        self.env, self.cap, self.rows, self.reply_cap = env, self.root.cap, rows, _check_cap(reply_cap)
         n, dev = env.num_envs, env.device
         self.words = _lib.query("ka_mate3_words", 0, self.cap)
         assert self.words == mate3_words(self.cap) and _lib.query("ka_mate3_words", 3, 0) == MAX_EVASION_ROWS
@@ -321,3 +315,59 @@ class Mate3Search:
         """The per-env mate-in-three records of the last ``step`` (a copy on the device); ``root.records()`` are the
         mate-in-one records beside them, ``third.records()`` the third ply's, one per grandchild row."""
         return self._records.clone()
+
+
+class MateStage(PlyStage):
+    """The mate check as a loop builds it into its ply (``mate=``: a ``MateControls`` for every model, one per model, or a
+    dict by model index), behind the lookahead or the search and before the insight: it overrides their choice, and the
+    insight describes the move actually played.  The engine is a ``MateSearch`` whose child rows are sized by the largest
+    ``max_checks`` given, or -- when a model's controls switch depth three on -- a ``Mate3Search`` (its ``root`` is that
+    ``MateSearch``) with the grandchild and third-ply rows sized by the largest ``evasion_rows`` and ``reply_checks``; the
+    stage then owns the third ply's ``reply_table`` too.  ``set_mate`` goes up to those sizes and switches depth three per
+    model under the same capture.  ``RoundStats.mate`` carries the counters, ``RoundStats.mate3`` those of depth three."""
+
+    name = "mate"
+    _ABOVE, _ROWS = "the largest", "child, grandchild and third-ply rows"
+
+    def __init__(self, table: np.ndarray, max_checks: int = 0, evasion_rows: int = 0, reply_checks: int = 0) -> None:
+        deep = max_checks > 0 and evasion_rows > 0 and reply_checks > 0
+        super().__init__(table, max_checks=int(max_checks), evasion_rows=int(evasion_rows) if deep else 0,
+                         reply_checks=int(reply_checks) if deep else 0)
+        self.reply_table: Optional[torch.Tensor] = None
+
+    @classmethod
+    def parse(cls, mate, num_models: int, collect: bool) -> Optional["MateStage"]:
+        table, cap = arena_mate(mate, num_models, collect)
+        return None if table is None else cls(table, cap, *arena_mate3(mate, num_models))
+
+    @classmethod
+    def _off(cls, num_models: int) -> "MateStage":
+        return cls(mate_table(None, num_models))
+
+    mate = property(lambda self: getattr(self.engine, "root", self.engine))             # the MateSearch, or None
+    mate3 = property(lambda self: self.engine if self.sizes["evasion_rows"] else None)  # the Mate3Search, or None
+
+    def _engine(self, env, group):
+        cap, rows, reply = self.sizes.values()
+        if rows:
+            self.reply_table = torch.from_numpy(mate3_reply_table(self.host_table)).to(env.device)
+            return Mate3Search(env, cap, rows, reply)
+        return MateSearch(env, cap) if cap else None
+
+    def _write(self, new: "MateStage") -> None:
+        super()._write(new)
+        if self.reply_table is not None:
+            self.reply_table.copy_(torch.from_numpy(mate3_reply_table(new.host_table)))
+
+    def _launch(self, logits, mask_bits, actions, model_of, seed, stream) -> None:
+        tables = (self.table,) if self.reply_table is None else (self.table, self.reply_table)
+        self.engine.step(mask_bits, actions, model_of, *tables, stream)
+
+    def fresh(self) -> dict:
+        return dict(mate=MateStats(), mate3=Mate3Stats()) if self.sizes["evasion_rows"] else dict(mate=MateStats())
+
+    def _read(self) -> dict:
+        return {field: getattr(self, field).read() for field in self.fresh()}
+
+    def _record(self) -> dict:
+        return {f"{field}_records": getattr(self, field).records().cpu() for field in self.fresh()}

@@ -41,7 +41,7 @@ from typing import ClassVar, List, Optional, Tuple
 import numpy as np
 import torch
 
-from ._forked_rows import controls_rows
+from ._forked_rows import check_int, controls_rows, table_of
 from .sampling import MAX_OPENING_PLIES, _M64, _mix
 
 __all__ = ["MctsExploration", "explore_table", "explore_controls", "arena_mcts_explore", "noise_stream",
@@ -79,10 +79,7 @@ class MctsExploration:
                              f"{self.noise_alpha!r}")
         if self.noise_fraction == 0 and not 0.0 <= self.noise_alpha <= MAX_ALPHA:
             raise ValueError(f"noise_alpha must lie in [0, {MAX_ALPHA}], got {self.noise_alpha!r}")
-        v = self.sample_plies
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= MAX_SAMPLE_PLIES:
-            raise ValueError(f"sample_plies must be an integer in [0, {MAX_SAMPLE_PLIES}], got {v!r}")
-        object.__setattr__(self, "sample_plies", int(v))
+        object.__setattr__(self, "sample_plies", check_int("sample_plies", self.sample_plies, 0, MAX_SAMPLE_PLIES))
 
     def row(self) -> np.ndarray:
         """The table row: fp32 noise_fraction, fp32 noise_alpha, int32 sample_plies, a reserved zero, as four int32."""
@@ -110,22 +107,11 @@ def arena_mcts_explore(mcts_explore, mcts, num_models: int) -> Optional[np.ndarr
     return explore_table(mcts_explore, num_models)
 
 
-def _table_of(controls) -> np.ndarray:
-    if isinstance(controls, torch.Tensor):
-        controls = controls.cpu().numpy()
-    if isinstance(controls, np.ndarray):                        # a table as it lies in device memory: taken as it is
-        t = np.ascontiguousarray(controls).view(np.int32)
-        if t.ndim != 2 or t.shape[1] != 4:
-            raise ValueError(f"an exploration table is (K, 4) int32, got {t.shape}")
-        return t
-    return explore_table(controls, len(controls) if isinstance(controls, (list, tuple)) else 1)
-
-
 def explore_controls(controls, model_of) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """Per row ``(epsilon, alpha, sample_plies)`` as the kernels read them from the table (``controls``: an
     ``MctsExploration``, a sequence of them or a (K, 4) table): the fp32 values as float64; a row with a word out of range
     and a model outside ``[0, K)`` read as off."""
-    table = _table_of(controls)
+    table = table_of(controls, None, explore_table, "mcts_explore")
     mo = np.asarray(torch.as_tensor(model_of).cpu().numpy(), np.int64).reshape(-1)
     eps, alpha, plies = np.zeros(mo.shape[0]), np.zeros(mo.shape[0]), np.zeros(mo.shape[0], np.int64)
     for b, m in enumerate(mo):

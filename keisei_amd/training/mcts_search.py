@@ -42,22 +42,21 @@ import torch
 from keisei_amd import _lib
 from keisei_amd.shogi_gym import ACTION_SPACE
 
-from ._forked_rows import NodePool, check_search_env, controls_rows
+from ._forked_rows import NodePool, PlyStage, check_int, check_weight, controls_rows, refuse_shared_place, table_of
 from .lookahead import (FLAG_ACTIVE, MAX_SKIP_PLIES, MAX_WIDTH, REC_CAND, REC_FLAGS, REC_NCAND, _check_width, _row_controls,
-                        _table_of, lookahead_words)
+                        lookahead_words)
+from .mcts_explore import explore_table
 from .sampling import GAME_PLY_BYTE
+from .tree_search import node_record
 
 __all__ = ["MctsControls", "MctsStats", "MctsTree", "MctsRestatement", "MctsSearch", "mcts_table", "mcts_simulations",
            "mcts_backup_select", "visit_policy", "arena_mcts", "MAX_SIMULATIONS"]
 
 MAX_SIMULATIONS = 64
-ERR_VALUE, ERR_STEP = 1, 2
 
 
 def _check_simulations(simulations, lo: int = 1) -> int:
-    if isinstance(simulations, bool) or not isinstance(simulations, (int, np.integer)) or not lo <= simulations <= MAX_SIMULATIONS:
-        raise ValueError(f"simulations must be an integer in [{lo}, {MAX_SIMULATIONS}], got {simulations!r}")
-    return int(simulations)
+    return check_int("simulations", simulations, lo, MAX_SIMULATIONS)
 
 
 @dataclass(frozen=True)
@@ -72,17 +71,9 @@ class MctsControls:
 
     def __post_init__(self) -> None:
         for name, hi in (("width", MAX_WIDTH), ("skip_plies", MAX_SKIP_PLIES)):
-            v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= hi:
-                raise ValueError(f"{name} must be an integer in [0, {hi}], got {v!r}")
-            object.__setattr__(self, name, int(v))
+            object.__setattr__(self, name, check_int(name, getattr(self, name), 0, hi))
         object.__setattr__(self, "simulations", _check_simulations(self.simulations))
-        c = self.c_puct
-        if isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c < 0:
-            raise ValueError(f"c_puct must be finite and >= 0, got {c!r}")
-        object.__setattr__(self, "c_puct", float(c))
-        if self.c_puct > 3.0e38:
-            raise ValueError(f"c_puct must fit a float32 (at most 3.0e38), got {c!r}")
+        object.__setattr__(self, "c_puct", check_weight("c_puct", self.c_puct))
         if self.simulations > 1 and self.width == 0:
             raise ValueError(f"simulations {self.simulations} needs a width above 0: there is no node to visit")
 
@@ -126,12 +117,7 @@ def arena_mcts(mcts, num_models: int, collect: bool, lookahead=None, search=None
     ``search=`` (it stands where they stand) and with ``collect=True`` (a searched move is no draw from the policy)."""
     if mcts is None:
         return None, 0, 0
-    if lookahead is not None:
-        raise ValueError("mcts= cannot be combined with lookahead=: the visit-count search stands where the lookahead stands "
-                         "in the ply, and its simulation 0 is the lookahead's fork")
-    if search is not None:
-        raise ValueError("mcts= cannot be combined with search=: both searches stand in the lookahead's place in the ply, "
-                         "and a ply plays the choice of one")
+    refuse_shared_place(lookahead=lookahead, search=search, mcts=mcts)
     if collect:
         raise ValueError("a search cannot be combined with collect=True: DynamicTrainer treats the recorded actions as "
                          "draws from the entry's own policy, and a move chosen by the search is not one")
@@ -139,17 +125,11 @@ def arena_mcts(mcts, num_models: int, collect: bool, lookahead=None, search=None
     return mcts_table(rows, num_models), max(r.width for r in rows), max(r.simulations for r in rows)
 
 
-def _mcts_table_of(controls) -> np.ndarray:
-    if isinstance(controls, (torch.Tensor, np.ndarray)):
-        return _table_of(controls, None)                       # a table as it lies in device memory: taken as it is
-    return mcts_table(controls, len(controls) if isinstance(controls, (list, tuple)) else 1)
-
-
 def mcts_simulations(controls, model_of, *, simulations: int = MAX_SIMULATIONS):
     """Per row: ``(c_puct, simulations)`` as ``ka_mcts_advance`` reads them from the table: ``c_puct`` of a row that is on
     (else 0), word 3 outside [1, 64] or a model outside ``[0, K)`` reads as 1, a value above ``simulations`` (the launch's) is
     cut to it."""
-    table = _mcts_table_of(controls)
+    table = table_of(controls, None, mcts_table, "mcts")
     mo = np.asarray(torch.as_tensor(model_of).cpu().numpy(), np.int64).reshape(-1)
     cs, sims = np.zeros(mo.shape[0], np.float64), np.ones(mo.shape[0], np.int64)
     for b, m in enumerate(mo):
@@ -391,39 +371,24 @@ class MctsSearch(NodePool):
     the trees and the stages of the visit-count search.  Everything is allocated here, once.  ``explore=True`` also allocates
     what the exploration of ``mcts_explore.py`` writes: the raw priors, eta and three more counters."""
 
-    _SLICE = "simulation"
+    _WORDS, _WHAT, _SLICE = "ka_mcts_words", "the visit-count search", "simulation"
 
     def __init__(self, env, group, width: int, simulations: int, explore: bool = False) -> None:
         width = _check_width(width)
-        simulations = _check_simulations(simulations)
-        check_search_env(env, group, "the visit-count search")
-        self.simulations = simulations
-        words = _lib.query("ka_mcts_words", 0, width, simulations)
-        self.tree_words = _lib.query("ka_mcts_words", 1, width, simulations)
-        assert words == lookahead_words(width) and self.tree_words == simulations + 4 * simulations * width
+        self.simulations = simulations = _check_simulations(simulations)
         assert width <= _lib.query("ka_mcts_words", 3, 0, 0) == MAX_WIDTH
         assert simulations <= _lib.query("ka_mcts_words", 4, 0, 0) == MAX_SIMULATIONS
-        super().__init__(env, group, width, simulations, words)
+        self._nexplore = _lib.query("ka_mcts_words", 7, width, simulations) if explore else 0
+        super().__init__(env, group, width, simulations, extra_counters=self._nexplore)    # the exploration's counters
+        assert self.words == lookahead_words(width) and self.tree_words == simulations + 4 * simulations * width
         n, dev = env.num_envs, env.device
         with torch.cuda.device(dev):
-            self._tree = torch.zeros(n, self.tree_words, dtype=torch.int32, device=dev)
-            self._pv = torch.full((n, simulations), -1, dtype=torch.int32, device=dev)
             self._root_visits = torch.zeros(n, width, dtype=torch.int32, device=dev)
             self._root_values = torch.zeros(n, width, dtype=torch.float32, device=dev)
-            self._nstats = _lib.query("ka_mcts_words", 2, width, simulations)
-            self._nexplore = _lib.query("ka_mcts_words", 7, width, simulations) if explore else 0
-            # stats, then the error word, then the exploration's counters
-            self._counters = torch.zeros(self._nstats + 1 + self._nexplore, dtype=torch.int32, device=dev)
-            self._counters_host = torch.zeros(self._counters.shape, dtype=torch.int32).pin_memory()
             self._raw_priors = self._eta = None
             if explore:
                 self._raw_priors = torch.zeros(n, width, dtype=torch.float32, device=dev)
                 self._eta = torch.zeros(n, width, dtype=torch.float64, device=dev)
-
-    def clear(self) -> None:
-        """Zero the counters, the error word and the refusal latches of every slice's step (a round's start)."""
-        self._counters.zero_()
-        self._step_err.zero_()
 
     def advance(self, t: int, actions, model_of, table, stream, explore_table=None, seed=None) -> None:
         """After ``evaluate(t)``: leaf q, backup, the selection of simulation t + 1; at the last simulation the choice --
@@ -471,17 +436,7 @@ class MctsSearch(NodePool):
     # ------------------------------------------------------------------ host side
     def read(self) -> MctsStats:
         """At a sync point: the counters since ``clear()`` (one small device -> host copy).  Raises on the error word."""
-        self._counters_host.copy_(self._counters)
-        c = self._counters_host.numpy()
-        err = int(c[self._nstats])
-        if err & ERR_STEP:
-            words = self._step_err.cpu()
-            t = int(torch.nonzero(words.ne(0).any(1))[0]) if bool(words.ne(0).any()) else 0
-            raise RuntimeError(f"the visit-count search's step of simulation {t} refused an action (word "
-                               f"{int(words[t, 1]) or int(words[t, 0]):#x}): a forked row does not match the mask it was "
-                               "forked with")
-        if err & ERR_VALUE:
-            raise RuntimeError("non-finite value logits in the visit-count search (a model has diverged)")
+        c = self._read_counters()
         return MctsStats(*(int(v) for v in c[:6]), *(int(v) for v in c[self._nstats + 1:self._nstats + 4][:self._nexplore]))
 
     def tree(self) -> dict:
@@ -492,10 +447,6 @@ class MctsSearch(NodePool):
         part = lambda i: t[:, E + i * E * W:E + (i + 1) * E * W]  # noqa: E731
         return {"parent": t[:, :E], "N": part(0).reshape(n, E, W), "S": part(1).view(torch.float32).reshape(n, E, W),
                 "P": part(2).view(torch.float32).reshape(n, E, W), "by": part(3).reshape(n, E, W)}
-
-    def principal_variations(self) -> torch.Tensor:
-        """(envs, simulations) int32: per env the chosen action and the line behind it, padded with -1."""
-        return self._pv.clone()
 
     def root_noise(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(raw_priors, eta)`` of the last ``step`` with an exploration table (copies on the device), (envs, width) each:
@@ -513,3 +464,63 @@ class MctsSearch(NodePool):
         active = (rec0[:, REC_FLAGS] & FLAG_ACTIVE).ne(0)[:, None]
         cand = torch.where(active, rec0[:, REC_CAND:REC_CAND + self.width], torch.full_like(rec0[:, :1], -1))
         return cand, self._root_visits.clone(), self._root_values.clone()
+
+
+class MctsStage(PlyStage):
+    """The visit-count search as a loop builds it into its ply (``mcts=``: an ``MctsControls`` for every model, or one per
+    model), where the lookahead stands.  The node pool is sized by the largest ``width`` and ``simulations`` given;
+    ``set_mcts`` goes up to them.  ``engine.root_visits()`` between two plies gives the visit distribution of every searched
+    position, ``RoundStats.mcts`` carries the counters.  The stage owns the exploration of ``mcts_explore.py``
+    (``mcts_explore=``): its table (None: nothing is allocated and the launches are those of the search alone), the
+    ``explore=`` flag of the engine and ``set_mcts_explore``; ``engine.root_noise()`` gives the priors before the noise and
+    the draw, ``RoundStats.mcts`` the counters ``noised`` / ``sampled`` / ``diverged``."""
+
+    name, shares_place, STATS = "mcts", True, MctsStats
+    _ROWS = "node pool's rows"
+
+    def __init__(self, table: np.ndarray, explore: Optional[np.ndarray] = None, **sizes: int) -> None:
+        super().__init__(table, **sizes)
+        self.host_explore_table, self.explore_table = explore, None
+
+    @classmethod
+    def parse(cls, mcts, num_models: int, collect: bool, explore: Optional[np.ndarray] = None) -> Optional["MctsStage"]:
+        """``explore``: the exploration table as ``arena_mcts_explore`` read it."""
+        table, width, simulations = arena_mcts(mcts, num_models, collect)
+        if table is None and explore is not None:
+            raise ValueError("an exploration needs mcts=: it is the visit-count search that is explored")
+        return None if table is None else cls(table, explore, width=width, simulations=simulations)
+
+    @classmethod
+    def _off(cls, num_models: int) -> "MctsStage":
+        return cls(mcts_table(None, num_models), width=0, simulations=1)
+
+    def build(self, env, group) -> None:
+        super().build(env, group)
+        if self.host_explore_table is not None:
+            self.explore_table = torch.from_numpy(self.host_explore_table).to(env.device)
+
+    def _engine(self, env, group) -> Optional[MctsSearch]:
+        if not self.sizes["width"]:
+            return None
+        return MctsSearch(env, group, **self.sizes, explore=self.host_explore_table is not None)
+
+    def _launch(self, logits, mask_bits, actions, model_of, seed, stream) -> None:
+        # (with an exploration the noise and the drawn move read the sampler's seed of this ply)
+        self.engine.step(logits, mask_bits, actions, model_of, self.table, stream, explore_table=self.explore_table, seed=seed)
+
+    def rewriters(self) -> dict:
+        explore = {} if self.explore_table is None else {"mcts_explore": self.rewrite_explore}
+        return dict(super().rewriters(), **explore)
+
+    def rewrite_explore(self, mcts_explore, num_models: int, collect: bool) -> None:
+        """New exploration controls from the next ply on; nothing is captured again.  None writes rows that are off: the
+        games are then those of the search alone."""
+        with torch.cuda.device(self.explore_table.device):
+            self.explore_table.copy_(torch.from_numpy(explore_table(mcts_explore, num_models)))
+
+    def _record(self) -> dict:
+        mc = self.engine
+        rec = dict(node_record(mc, "mcts"), mcts_root_visits=tuple(x.cpu() for x in mc.root_visits()))
+        if self.explore_table is not None:
+            rec.update(mcts_root_noise=tuple(x.cpu() for x in mc.root_noise()))
+        return rec

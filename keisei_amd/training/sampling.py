@@ -31,6 +31,8 @@ import torch
 
 from keisei_amd import _lib
 
+from ._forked_rows import check_int, table_of
+
 __all__ = ["SamplingControls", "ControlledSample", "controls_table", "sample_controlled", "sample_uniform",
            "arena_controls", "league_controls", "MAX_TOP_K", "MAX_OPENING_PLIES", "GAME_PLY_BYTE"]
 
@@ -64,10 +66,7 @@ class SamplingControls:
         if self.opening_temperature is not None:
             object.__setattr__(self, "opening_temperature", _temperature("opening_temperature", self.opening_temperature))
         for name, hi in (("opening_plies", MAX_OPENING_PLIES), ("top_k", MAX_TOP_K)):
-            v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= hi:
-                raise ValueError(f"{name} must be an integer in [0, {hi}], got {v!r}")
-            object.__setattr__(self, name, int(v))
+            object.__setattr__(self, name, check_int(name, getattr(self, name), 0, hi))
 
     def row(self) -> np.ndarray:
         """The table row: fp32 temperature, fp32 opening temperature, int32 opening_plies, int32 top_k, as four int32."""
@@ -154,20 +153,6 @@ class ControlledSample:
     probs: Optional[torch.Tensor] = None  # (B, A) fp64, the distribution drawn from: host path only
 
 
-def _table_of(controls, K: Optional[int]) -> np.ndarray:
-    if isinstance(controls, torch.Tensor):
-        controls = controls.detach().cpu().numpy()
-    if isinstance(controls, np.ndarray):              # a table as it lies in device memory: taken as it is
-        if controls.dtype != np.int32 or controls.ndim != 2 or controls.shape[1] != 4 or controls.shape[0] < 1:
-            raise ValueError(f"a controls table is a (K, 4) int32 array, got {controls.dtype} {controls.shape}")
-        if K is not None and controls.shape[0] != K:
-            raise ValueError(f"expected a table of {K} rows, got {controls.shape[0]}")
-        return np.ascontiguousarray(controls)
-    if K is None:
-        K = len(controls) if isinstance(controls, (list, tuple)) else 1
-    return controls_table(controls, K)
-
-
 def sample_controlled(logits: torch.Tensor, legal: torch.Tensor, seed, *, controls, model_of: Optional[torch.Tensor] = None,
                       plies: Optional[torch.Tensor] = None, num_models: Optional[int] = None) -> ControlledSample:
     """One draw per row.  ``logits`` (B, A) or (B, 9, 9, 139), fp32 or bf16; ``legal`` bool rows or packed int32 rows
@@ -191,7 +176,7 @@ def sample_controlled(logits: torch.Tensor, legal: torch.Tensor, seed, *, contro
         packed = True
     else:
         raise ValueError(f"legal must be bool (B, {A}) or packed int32 (B, {words}), got {legal.dtype} {tuple(legal.shape)}")
-    table = _table_of(controls, num_models)
+    table = table_of(controls, num_models, controls_table, "controls")
     K = table.shape[0]
     model_of = None if model_of is None else torch.as_tensor(model_of)
     plies = None if plies is None else torch.as_tensor(plies)

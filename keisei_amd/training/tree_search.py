@@ -27,7 +27,6 @@ operation is the root's ``q + prior_weight * prior``.  ``expansions = 1`` is the
 """
 from __future__ import annotations
 
-import math
 import struct
 from dataclasses import dataclass
 from typing import ClassVar, List, Optional, Tuple
@@ -36,8 +35,10 @@ import numpy as np
 import torch
 
 from keisei_amd import _lib
+from keisei_amd.shogi_gym import ACTION_SPACE
 
-from ._forked_rows import NodePool, check_search_env, controls_rows
+from ._forked_rows import (ERR_VALUE, NodePool, PlyStage, check_int, check_weight, controls_rows, refuse_shared_place,
+                           table_of)
 from .lookahead import (FLAG_ACTIVE, MAX_SKIP_PLIES, MAX_WIDTH, REC_CAND, REC_FLAGS, REC_NCAND, _check_width,
                         _loss_minus_win, _row_controls, lookahead_words)
 
@@ -46,13 +47,10 @@ __all__ = ["SearchControls", "SearchStats", "SearchTree", "TreeSearch", "search_
 
 MAX_EXPANSIONS = 16
 FLAG_DEEPENED = 8
-ERR_VALUE, ERR_STEP = 1, 2
 
 
 def _check_expansions(expansions, lo: int = 1) -> int:
-    if isinstance(expansions, bool) or not isinstance(expansions, (int, np.integer)) or not lo <= expansions <= MAX_EXPANSIONS:
-        raise ValueError(f"expansions must be an integer in [{lo}, {MAX_EXPANSIONS}], got {expansions!r}")
-    return int(expansions)
+    return check_int("expansions", expansions, lo, MAX_EXPANSIONS)
 
 
 @dataclass(frozen=True)
@@ -67,17 +65,9 @@ class SearchControls:
 
     def __post_init__(self) -> None:
         for name, hi in (("width", MAX_WIDTH), ("skip_plies", MAX_SKIP_PLIES)):
-            v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= hi:
-                raise ValueError(f"{name} must be an integer in [0, {hi}], got {v!r}")
-            object.__setattr__(self, name, int(v))
+            object.__setattr__(self, name, check_int(name, getattr(self, name), 0, hi))
         object.__setattr__(self, "expansions", _check_expansions(self.expansions))
-        w = self.prior_weight
-        if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w) or w < 0:
-            raise ValueError(f"prior_weight must be finite and >= 0, got {w!r}")
-        object.__setattr__(self, "prior_weight", float(w))
-        if self.prior_weight > 3.0e38:
-            raise ValueError(f"prior_weight must fit a float32 (at most 3.0e38), got {w!r}")
+        object.__setattr__(self, "prior_weight", check_weight("prior_weight", self.prior_weight))
         if self.expansions > 1 and self.width == 0:
             raise ValueError(f"expansions {self.expansions} needs a width above 0: there is no node to expand")
 
@@ -116,9 +106,7 @@ def arena_search(search, num_models: int, collect: bool, lookahead=None) -> Tupl
     search stands where the lookahead stands) and with ``collect=True`` (a searched move is no draw from the policy)."""
     if search is None:
         return None, 0, 0
-    if lookahead is not None:
-        raise ValueError("search= cannot be combined with lookahead=: the search stands where the lookahead stands in the "
-                         "ply, and with expansions=1 it is the lookahead")
+    refuse_shared_place(lookahead=lookahead, search=search)
     if collect:
         raise ValueError("a search cannot be combined with collect=True: DynamicTrainer treats the recorded actions as "
                          "draws from the entry's own policy, and a move chosen by the search is not one")
@@ -126,23 +114,11 @@ def arena_search(search, num_models: int, collect: bool, lookahead=None) -> Tupl
     return search_table(rows, num_models), max(r.width for r in rows), max(r.expansions for r in rows)
 
 
-def _table_of(controls, K: Optional[int] = None) -> np.ndarray:
-    if isinstance(controls, torch.Tensor):
-        controls = controls.detach().cpu().numpy()
-    if isinstance(controls, np.ndarray):                  # a table as it lies in device memory: taken as it is
-        if controls.dtype != np.int32 or controls.ndim != 2 or controls.shape[1] != 4 or controls.shape[0] < 1:
-            raise ValueError(f"a search table is a (K, 4) int32 array, got {controls.dtype} {controls.shape}")
-        return np.ascontiguousarray(controls)
-    if K is None:
-        K = len(controls) if isinstance(controls, (list, tuple)) else 1
-    return search_table(controls, K)
-
-
 def search_expansions(controls, model_of, *, expansions: int = MAX_EXPANSIONS):
     """Per row: ``(prior_weight, expansions)`` as ``ka_search_advance`` reads them from the table: the weight of a row that
     is on (else 0), word 3 outside [1, 16] or a model outside ``[0, K)`` reads as 1, a value above ``expansions`` (the
     launch's) is cut to it."""
-    table = _table_of(controls)
+    table = table_of(controls, None, search_table, "search")
     mo = np.asarray(torch.as_tensor(model_of).cpu().numpy(), np.int64).reshape(-1)
     weights, exps = np.zeros(mo.shape[0], np.float64), np.ones(mo.shape[0], np.int64)
     for b, m in enumerate(mo):
@@ -299,31 +275,15 @@ class TreeSearch(NodePool):
     the stages of the search.  Everything is allocated once.  Slice ``t`` of the pool is rows ``[t * envs * width, (t + 1) *
     envs * width)``; node ``(t, j)`` of env ``e`` is row ``(t * envs + e) * width + j``."""
 
-    _SLICE = "expansion"
+    _WORDS, _WHAT, _SLICE = "ka_search_words", "the search", "expansion"
 
     def __init__(self, env, group, width: int, expansions: int) -> None:
         width = _check_width(width)
-        expansions = _check_expansions(expansions)
-        check_search_env(env, group, "the search")
-        self.expansions = expansions
-        words = _lib.query("ka_search_words", 0, width, expansions)
-        self.tree_words = _lib.query("ka_search_words", 1, width, expansions)
-        assert words == lookahead_words(width) and self.tree_words == expansions + 2 * expansions * width
+        self.expansions = expansions = _check_expansions(expansions)
         assert width <= _lib.query("ka_search_words", 3, 0, 0) == MAX_WIDTH
         assert expansions <= _lib.query("ka_search_words", 4, 0, 0) == MAX_EXPANSIONS
-        super().__init__(env, group, width, expansions, words)
-        n, dev = env.num_envs, env.device
-        with torch.cuda.device(dev):
-            self._tree = torch.zeros(n, self.tree_words, dtype=torch.int32, device=dev)
-            self._pv = torch.full((n, expansions), -1, dtype=torch.int32, device=dev)
-            self._nstats = _lib.query("ka_search_words", 2, width, expansions)
-            self._counters = torch.zeros(self._nstats + 1, dtype=torch.int32, device=dev)    # stats, then the error word
-            self._counters_host = torch.zeros(self._counters.shape, dtype=torch.int32).pin_memory()
-
-    def clear(self) -> None:
-        """Zero the counters, the error word and the refusal latches of every slice's step (a round's start)."""
-        self._counters.zero_()
-        self._step_err.zero_()
+        super().__init__(env, group, width, expansions)
+        assert self.words == lookahead_words(width) and self.tree_words == expansions + 2 * expansions * width
 
     # ------------------------------------------------------------------ the stages
     def advance(self, t: int, actions, model_of, table, stream) -> None:
@@ -337,18 +297,7 @@ class TreeSearch(NodePool):
     # ------------------------------------------------------------------ host side
     def read(self) -> SearchStats:
         """At a sync point: the counters since ``clear()`` (one small device -> host copy).  Raises on the error word."""
-        self._counters_host.copy_(self._counters)
-        c = self._counters_host.numpy()
-        err = int(c[self._nstats])
-        if err & ERR_STEP:
-            words = self._step_err.cpu()
-            t = int(torch.nonzero(words.ne(0).any(1))[0]) if bool(words.ne(0).any()) else 0
-            raise RuntimeError(f"the search's step of expansion {t} refused an action (word "
-                               f"{int(words[t, 1]) or int(words[t, 0]):#x}): a forked row does not match the mask it was "
-                               "forked with")
-        if err & ERR_VALUE:
-            raise RuntimeError("non-finite value logits in the search (a model has diverged)")
-        return SearchStats(*(int(v) for v in c[:5]))
+        return SearchStats(*(int(v) for v in self._read_counters()[:5]))
 
     def tree(self) -> dict:
         """The trees of the last ``step`` (copies on the device): ``parent`` (envs, expansions) int32, ``val`` (envs,
@@ -358,6 +307,41 @@ class TreeSearch(NodePool):
         return {"parent": t[:, :E], "val": t[:, E:E + E * W].view(torch.float32).reshape(n, E, W),
                 "by": t[:, E + E * W:].reshape(n, E, W)}
 
-    def principal_variations(self) -> torch.Tensor:
-        """(envs, expansions) int32: per env the chosen action and the line behind it, padded with -1."""
-        return self._pv.clone()
+
+def node_record(pool: NodePool, prefix: str) -> dict:
+    """What a recorded ply keeps of a node pool's last ``step``: the records, the trees and the lines under ``prefix``, the
+    pool's rows under ``node_*``, (slices, envs, width) each."""
+    shape = (pool.slices, pool.env.num_envs, pool.width)
+    return {f"{prefix}_records": pool.records().cpu(), f"{prefix}_tree": {k: v.cpu() for k, v in pool.tree().items()},
+            f"{prefix}_pv": pool.principal_variations().cpu(), "node_value_logits": pool.value_logits.cpu().reshape(*shape, 3),
+            "node_rewards": pool.rewards.cpu().reshape(shape),
+            "node_done": (pool.terminated | pool.truncated).cpu().reshape(shape),
+            "node_logits": pool.logits.cpu().reshape(-1, ACTION_SPACE), "node_mask_bits": pool.mask_bits.cpu(),
+            "node_model_of": pool.model_of.cpu().reshape(shape)}
+
+
+class SearchStage(PlyStage):
+    """The tree search as a loop builds it into its ply (``search=``: a ``SearchControls`` for every model, or one per
+    model), where the lookahead stands.  The node pool is sized by the largest ``width`` and ``expansions`` given;
+    ``set_search`` goes up to them.  ``RoundStats.search`` carries the counters."""
+
+    name, shares_place, STATS = "search", True, SearchStats
+    _ROWS = "node pool's rows"
+
+    @classmethod
+    def parse(cls, search, num_models: int, collect: bool) -> Optional["SearchStage"]:
+        table, width, expansions = arena_search(search, num_models, collect)
+        return None if table is None else cls(table, width=width, expansions=expansions)
+
+    @classmethod
+    def _off(cls, num_models: int) -> "SearchStage":
+        return cls(search_table(None, num_models), width=0, expansions=1)
+
+    def _engine(self, env, group) -> Optional[TreeSearch]:
+        return TreeSearch(env, group, **self.sizes) if self.sizes["width"] else None
+
+    def _launch(self, logits, mask_bits, actions, model_of, seed, stream) -> None:
+        self.engine.step(logits, mask_bits, actions, model_of, self.table, stream)
+
+    def _record(self) -> dict:
+        return node_record(self.engine, "search")

@@ -501,24 +501,24 @@ def test_graph_equals_no_graph():
     assert graph._graph is not None and eager._graph is None
     assert _key(r1) == _key(r2) and s1.round_plies == s2.round_plies and _games(r1) == _games(r2)
     assert s1.lookahead == s2.lookahead and s1.lookahead.searched > 100 and s1.lookahead.changed > 0
-    assert torch.equal(eager._la.records(), graph._la.records())
+    assert torch.equal(eager.ply.stages["lookahead"].engine.records(), graph.ply.stages["lookahead"].engine.records())
     assert torch.equal(eager.env.current().observations, graph.env.current().observations)
 
 
 def test_rows_that_are_off_play_the_games_of_no_lookahead_and_set_lookahead_needs_no_capture():
     plain = MatchArena(_group(), N, PER, MAX_PLY, sync_every=2, graph=True, seed=29, game_log=256)
     arena = MatchArena(_group(), N, PER, MAX_PLY, sync_every=2, graph=True, seed=29, game_log=256, lookahead=CTL)
-    assert plain._la is None and plain._la_table is None and arena._la.width == 3
+    assert "lookahead" not in plain.ply.stages and arena.ply.stages["lookahead"].engine.width == 3
     arena.set_lookahead(OFF)                                  # the launches stay in the ply, every row is off
     r0, s0 = plain.run_round(PAIRINGS, games_per_match=4)
     r1, s1 = arena.run_round(PAIRINGS, games_per_match=4)
     assert s0.lookahead is None and s1.lookahead.searched == 0 and s1.lookahead.changed == 0
     assert _key(r0) == _key(r1) and _games(r0) == _games(r1) and sum(len(g) for g in _games(r0)) >= 8
-    graph, table = arena._graph, arena._la_table
+    graph, table = arena._graph, arena.ply.stages["lookahead"].table
     assert graph is not None
     arena.set_lookahead(CTL)
     r2, s2 = arena.run_round(PAIRINGS, games_per_match=4)
-    assert arena._graph is graph and arena._la_table is table
+    assert arena._graph is graph and arena.ply.stages["lookahead"].table is table
     assert s2.lookahead.searched > 100 and s2.lookahead.changed > 0 and _games(r2) != _games(r0)
     arena.set_lookahead(None)
     assert not bool(table.any())
@@ -526,7 +526,7 @@ def test_rows_that_are_off_play_the_games_of_no_lookahead_and_set_lookahead_need
     assert np.array_equal(table.cpu().numpy(), lookahead_table([OFF, LookaheadControls(1)], 2))
     # an arena whose rows are all off at construction allocates nothing and launches nothing
     idle = MatchArena(_group(), N, PER, MAX_PLY, sync_every=2, graph=True, seed=29, game_log=256, lookahead=OFF)
-    assert idle._la is None and idle._la_table is not None
+    assert idle.ply.stages["lookahead"].engine is None and idle.ply.stages["lookahead"].table is not None
     r3, s3 = idle.run_round(PAIRINGS, games_per_match=4)
     assert _key(r3) == _key(r0) and _games(r3) == _games(r0) and s3.lookahead.searched == 0
     with pytest.raises(ValueError, match="above the width"):

@@ -513,7 +513,7 @@ def _u_bound(vls_a, vls_b, weight):
 def test_every_recorded_arena_ply_is_the_restatement():
     grp = _group()
     arena = MatchArena(grp, N, PER, MAX_PLY, sync_every=2, graph=False, seed=21, record=True, lookahead=CTL)
-    assert arena._la.width == 3 and arena._la.reply_width == 2
+    assert arena.ply.stages["lookahead"].engine.width == 3 and arena.ply.stages["lookahead"].engine.reply_width == 2
     results, stats = arena.run_round(PAIRINGS, games_per_match=4)
     recs = arena.record
     assert len(recs) >= 20 and stats.lookahead.searched > 100
@@ -627,16 +627,16 @@ def test_graph_equals_no_graph():
     assert graph._graph is not None and eager._graph is None
     assert _key(r1) == _key(r2) and s1.round_plies == s2.round_plies and _games(r1) == _games(r2)
     assert s1.lookahead == s2.lookahead and s1.lookahead.searched > 100 and s1.lookahead.reply_changed > 0
-    assert torch.equal(eager._la.records(), graph._la.records())
-    assert torch.equal(eager._la.reply_records(), graph._la.reply_records())
+    assert torch.equal(eager.ply.stages["lookahead"].engine.records(), graph.ply.stages["lookahead"].engine.records())
+    assert torch.equal(eager.ply.stages["lookahead"].engine.reply_records(), graph.ply.stages["lookahead"].engine.reply_records())
     assert torch.equal(eager.env.current().observations, graph.env.current().observations)
 
 
 def test_reply_width_0_everywhere_plays_the_games_of_the_one_ply_arena():
     plain = _arena(ONE_PLY, True, seed=29)
     zero = _arena([LookaheadControls(3, 0.25, reply_width=0), LookaheadControls(2, 0.0, 4, 0)], True, seed=29)
-    assert plain._la._grand is None and zero._la._grand is None and zero._la.reply_width == 0    # nothing more is allocated
-    assert np.array_equal(plain._la_table.cpu().numpy(), zero._la_table.cpu().numpy())
+    assert plain.ply.stages["lookahead"].engine._grand is None and zero.ply.stages["lookahead"].engine._grand is None and zero.ply.stages["lookahead"].engine.reply_width == 0    # nothing more is allocated
+    assert np.array_equal(plain.ply.stages["lookahead"].table.cpu().numpy(), zero.ply.stages["lookahead"].table.cpu().numpy())
     r0, s0 = plain.run_round(PAIRINGS, games_per_match=4)
     r1, s1 = zero.run_round(PAIRINGS, games_per_match=4)
     assert _key(r0) == _key(r1) and _games(r0) == _games(r1) and s0.lookahead == s1.lookahead and s0.lookahead.reply_changed == 0
@@ -645,21 +645,21 @@ def test_reply_width_0_everywhere_plays_the_games_of_the_one_ply_arena():
     built.set_lookahead(ONE_PLY)
     r2, s2 = built.run_round(PAIRINGS, games_per_match=4)
     assert _key(r0) == _key(r2) and _games(r0) == _games(r2) and s0.lookahead == s2.lookahead
-    assert torch.equal(plain._la.records(), built._la.records())
+    assert torch.equal(plain.ply.stages["lookahead"].engine.records(), built.ply.stages["lookahead"].engine.records())
     assert sum(len(g) for g in _games(r0)) >= 8
 
 
 def test_set_lookahead_switches_the_replies_on_and_off_without_a_capture():
     arena, fresh = _arena(CTL, True, seed=31), _arena(CTL, True, seed=31)
     r0, s0 = arena.run_round(PAIRINGS, games_per_match=4)
-    graph, table = arena._graph, arena._la_table
+    graph, table = arena._graph, arena.ply.stages["lookahead"].table
     assert graph is not None and s0.lookahead.reply_changed > 0
     arena.set_lookahead(ONE_PLY)
     assert table[:, 3].tolist() == [0, 0]
     r1, s1 = arena.run_round(PAIRINGS, games_per_match=4)
     assert s1.lookahead.reply_changed == 0 and s1.lookahead.searched > 100
     arena.set_lookahead(CTL)
-    assert arena._graph is graph and arena._la_table is table and table[:, 3].tolist() == [2, 0]
+    assert arena._graph is graph and arena.ply.stages["lookahead"].table is table and table[:, 3].tolist() == [2, 0]
     r2, s2 = arena.run_round(PAIRINGS, games_per_match=4)
     assert s2.lookahead.reply_changed > 0
     # the rounds depend on the table alone: a fresh arena plays the same three rounds

@@ -83,7 +83,7 @@ def test_model_zero_mates_in_three_and_graph_equals_eager():
     r1, s1 = eager.run_round(PAIRINGS, games_per_match=8)
     r2, s2 = graph.run_round(PAIRINGS, games_per_match=8)
     assert graph._graph is not None and eager._graph is None
-    assert (eager._mt.cap, eager._mt3.rows, eager._mt3.reply_cap) == M.POOL_CAPS and eager._mt3.root is eager._mt
+    assert (eager.ply.stages["mate"].mate.cap, eager.ply.stages["mate"].mate3.rows, eager.ply.stages["mate"].mate3.reply_cap) == M.POOL_CAPS and eager.ply.stages["mate"].mate3.root is eager.ply.stages["mate"].mate
     count = _won_in_three(r1)
     assert count >= 4 and s1.mate3.mates >= count and s1.mate.mates >= count and s1.games_dropped == 0
     assert s1.mate3.positions >= s1.mate3.mates >= s1.mate3.changed and s1.mate3.rows >= s1.mate3.positions
@@ -93,13 +93,13 @@ def test_model_zero_mates_in_three_and_graph_equals_eager():
     assert slow and any(len(g.actions) != 3 or g.reason != CHECKMATE for g in slow)
     assert _key(r1) == _key(r2) and _games(r1) == _games(r2) and s1.round_plies == s2.round_plies
     assert s1.mate == s2.mate and s1.mate3 == s2.mate3
-    assert torch.equal(eager._mt.records(), graph._mt.records()) and torch.equal(eager._mt3.records(), graph._mt3.records())
+    assert torch.equal(eager.ply.stages["mate"].mate.records(), graph.ply.stages["mate"].mate.records()) and torch.equal(eager.ply.stages["mate"].mate3.records(), graph.ply.stages["mate"].mate3.records())
     assert all("mate3_records" in rec and rec["mate3_records"].shape == (N, 6 + 2 * 16) for rec in eager.record)
 
 
 def test_evasion_rows_zero_is_the_mate_in_one_arena_and_set_mate_switches_between_rounds():
     one, arena = _arena(True, ONE), _arena(True, DEEP)
-    assert one._mt3 is None and one._mt3_table is None and one._mt is not None
+    assert one.ply.stages["mate"].mate3 is None and one.ply.stages["mate"].reply_table is None and one.ply.stages["mate"].mate is not None
     r0, s0 = one.run_round(PAIRINGS, games_per_match=8)
     r_on, s_on = arena.run_round(PAIRINGS, games_per_match=8)
     graph = arena._graph
@@ -124,7 +124,7 @@ def test_refusals():
         with pytest.raises(ValueError, match=f"{text} is above the largest"):
             arena.set_mate(controls)
     arena.set_mate(MateControls(4, 0, 8, 1))
-    assert arena._mt_table.tolist() == [[4, 0, 8, 1]] * 2 and arena._mt3_table.tolist() == [[1, 0, 0, 0]] * 2
+    assert arena.ply.stages["mate"].table.tolist() == [[4, 0, 8, 1]] * 2 and arena.ply.stages["mate"].reply_table.tolist() == [[1, 0, 0, 0]] * 2
     one = MatchArena(_group(), N, PER, MAX_PLY, graph=False, mate=MateControls(4))
     with pytest.raises(ValueError, match="evasion_rows 1 is above the largest"):
         one.set_mate(MateControls(4, 0, 1, 1))

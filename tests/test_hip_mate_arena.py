@@ -79,7 +79,7 @@ def test_model_zero_mates_at_once_and_graph_equals_eager():
     eager, graph = _arena(False, ON), _arena(True, ON)
     r1, s1 = eager.run_round(PAIRINGS, games_per_match=8)
     r2, s2 = graph.run_round(PAIRINGS, games_per_match=8)
-    assert graph._graph is not None and eager._graph is None and eager._mt.cap == 16
+    assert graph._graph is not None and eager._graph is None and eager.ply.stages["mate"].mate.cap == 16
     count = _won_at_once(r1)
     assert count >= 4 and s1.mate.mates >= count and s1.mate.positions >= s1.mate.mates and s1.games_dropped == 0
     assert s1.mate.forked >= s1.mate.positions and s1.mate.changed <= s1.mate.mates
@@ -87,12 +87,12 @@ def test_model_zero_mates_at_once_and_graph_equals_eager():
     slow = [g for r in r1 for g in r.recorded_games if not g.carried and _first_mover(g) == 1]
     assert slow and any(len(g.actions) > 1 for g in slow)
     assert _key(r1) == _key(r2) and _games(r1) == _games(r2) and s1.round_plies == s2.round_plies
-    assert s1.mate == s2.mate and torch.equal(eager._mt.records(), graph._mt.records())
+    assert s1.mate == s2.mate and torch.equal(eager.ply.stages["mate"].mate.records(), graph.ply.stages["mate"].mate.records())
 
 
 def test_an_all_off_table_is_the_plain_arena_and_set_mate_switches_between_rounds():
     plain, arena = _arena(True, None), _arena(True, ON)
-    assert plain._mt is None and plain._mt_table is None
+    assert "mate" not in plain.ply.stages
     r0, s0 = plain.run_round(PAIRINGS, games_per_match=8)
     r_on, s_on = arena.run_round(PAIRINGS, games_per_match=8)
     graph = arena._graph
@@ -107,7 +107,7 @@ def test_an_all_off_table_is_the_plain_arena_and_set_mate_switches_between_round
     assert _won_at_once(r2) >= 4
     # built with every row off: nothing is allocated and nothing is launched, and nothing can be switched on later
     idle = _arena(True, MateControls.OFF)
-    assert idle._mt is None and idle._mt_table is not None
+    assert idle.ply.stages["mate"].mate is None and idle.ply.stages["mate"].table is not None
     r3, s3 = idle.run_round(PAIRINGS, games_per_match=8)
     assert _key(r3) == _key(r0) and _games(r3) == _games(r0) and s3.mate == type(s3.mate)()
     with pytest.raises(ValueError, match="above the largest"):

@@ -500,7 +500,7 @@ def test_graph_equals_no_graph_move_for_move():
 def test_set_mcts_rewrites_the_table_under_the_same_graph():
     arena, fresh, plain = _arena(True, seed=31, mcts=CTL), _arena(True, seed=31, mcts=CTL), _arena(True, seed=31)
     r0, s0 = arena.run_round(PAIRINGS, games_per_match=4)
-    graph, table = arena._graph, arena._mc_table
+    graph, table = arena._graph, arena.ply.stages["mcts"].table
     assert graph is not None and s0.mcts.simulations > 2 * s0.mcts.searched
     arena.set_mcts(ONE)
     assert table[:, 3].tolist() == [1, 1]
@@ -511,7 +511,7 @@ def test_set_mcts_rewrites_the_table_under_the_same_graph():
     p3, t3 = plain.run_round(PAIRINGS, games_per_match=4)
     assert s3.mcts == type(s3.mcts)() and t3.mcts is None and _key(r3) == _key(p3) and _games(r3) == _games(p3)
     arena.set_mcts(CTL)
-    assert arena._graph is graph and arena._mc_table is table and table[:, 3].tolist() == [6, 2]
+    assert arena._graph is graph and arena.ply.stages["mcts"].table is table and table[:, 3].tolist() == [6, 2]
     r2, s2 = arena.run_round(PAIRINGS, games_per_match=4)
     f0, _ = fresh.run_round(PAIRINGS, games_per_match=4)      # the rounds depend on the table alone
     fresh.set_mcts(ONE)
@@ -526,7 +526,7 @@ def test_mcts_none_leaves_the_ply_record_what_it_was():
     kw = dict(sync_every=2, graph=False, seed=22, record=True)
     none = MatchArena(_group(), N, PER, MAX_PLY, mcts=None, **kw)
     plain = MatchArena(_group(), N, PER, MAX_PLY, **kw)
-    assert none.mcts is None and none._mc_table is None and none.ply.mcts is None
+    assert none.mcts is None and "mcts" not in none.ply.stages and none.ply.mcts is None
     r0, s0 = none.run_round(PAIRINGS, games_per_match=2)
     r1, s1 = plain.run_round(PAIRINGS, games_per_match=2)
     assert _key(r0) == _key(r1) and s0.mcts is None and len(none.record) == len(plain.record) >= 10
@@ -535,7 +535,7 @@ def test_mcts_none_leaves_the_ply_record_what_it_was():
         assert all(torch.equal(a[k], b[k]) if isinstance(a[k], torch.Tensor) else a[k] == b[k] for k in a)
     # every row off: nothing is allocated and nothing is launched
     off = MatchArena(_group(), N, PER, MAX_PLY, mcts=MctsControls.OFF, **kw)
-    assert off.mcts is None and off._mc_table is not None
+    assert off.mcts is None and off.ply.stages["mcts"].table is not None
     r2, s2 = off.run_round(PAIRINGS, games_per_match=2)
     assert _key(r2) == _key(r0) and s2.mcts == type(s2.mcts)()
     assert all(torch.equal(a["actions"], b["actions"]) for a, b in zip(off.record, none.record))

@@ -303,17 +303,17 @@ def test_exploration_is_what_makes_the_games_differ():
     r_other, _ = other.run_round(PAIRINGS, games_per_match=16)
     assert _games(r_other) != _games(r_on)
     # off again under the same captured graph: the games of an arena that never explored, move for move
-    graph, table = on._graph, on._xp_table
+    graph, table = on._graph, on.ply.stages["mcts"].explore_table
     on.set_mcts_explore(None)
     r_back, s_back = on.run_round(PAIRINGS, games_per_match=16)
-    assert on._graph is graph and on._xp_table is table and not bool(table.any())
+    assert on._graph is graph and on.ply.stages["mcts"].explore_table is table and not bool(table.any())
     assert _games(r_back) == _games(r_off) and _key(r_back) == _key(r_off) and s_back.mcts == s_off.mcts
     on.set_mcts_explore(XP)
     r_again, s_again = on.run_round(PAIRINGS, games_per_match=16)
     assert _games(r_again) == _games(r_on) and s_again.mcts == s_on.mcts
     with pytest.raises(ValueError, match="built without mcts_explore="):
         off.set_mcts_explore(XP)
-    assert off.ply.mcts_explore_table is None and off.mcts._eta is None and off.mcts._counters.numel() == 7
+    assert off.ply.stages["mcts"].explore_table is None and off.mcts._eta is None and off.mcts._counters.numel() == 7
 
 
 def test_the_counters_and_the_samples_follow_the_recorded_plies():

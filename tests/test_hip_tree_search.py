@@ -428,7 +428,7 @@ LA = [LookaheadControls(3, 0.25), LookaheadControls(2, 0.0, skip_plies=4)]
 def test_every_recorded_arena_ply_is_the_restatement():
     grp = _group()
     arena = MatchArena(grp, N, PER, MAX_PLY, sync_every=2, graph=False, seed=21, record=True, search=CTL)
-    assert arena._se.width == 3 and arena._se.expansions == 4
+    assert arena.ply.stages["search"].engine.width == 3 and arena.ply.stages["search"].engine.expansions == 4
     results, stats = arena.run_round(PAIRINGS, games_per_match=4)
     recs = arena.record
     assert len(recs) >= 20 and stats.search.searched > 100
@@ -544,15 +544,15 @@ def test_graph_equals_no_graph():
     assert graph._graph is not None and eager._graph is None
     assert _key(r1) == _key(r2) and s1.round_plies == s2.round_plies and _games(r1) == _games(r2)
     assert s1.search == s2.search and s1.search.searched > 100 and s1.search.expansions > 1.5 * s1.search.searched
-    assert torch.equal(eager._se.records(), graph._se.records()) and torch.equal(eager._se._tree, graph._se._tree)
-    assert torch.equal(eager._se.principal_variations(), graph._se.principal_variations())
+    assert torch.equal(eager.ply.stages["search"].engine.records(), graph.ply.stages["search"].engine.records()) and torch.equal(eager.ply.stages["search"].engine._tree, graph.ply.stages["search"].engine._tree)
+    assert torch.equal(eager.ply.stages["search"].engine.principal_variations(), graph.ply.stages["search"].engine.principal_variations())
     assert torch.equal(eager.env.current().observations, graph.env.current().observations)
 
 
 def test_rows_that_are_off_play_the_games_of_no_search_and_one_expansion_those_of_the_lookahead():
     none = _arena(True, seed=29)
     off = _arena(True, seed=29, search=[SearchControls.OFF, SearchControls(0, 1, 0.5)])
-    assert none._se is None and none._se_table is None and off._se is None and off._se_table is not None     # nothing is allocated
+    assert "search" not in none.ply.stages and off.ply.stages["search"].engine is None and off.ply.stages["search"].table is not None     # nothing is allocated
     r0, s0 = none.run_round(PAIRINGS, games_per_match=4)
     r1, s1 = off.run_round(PAIRINGS, games_per_match=4)
     assert _key(r0) == _key(r1) and _games(r0) == _games(r1) and s0.search is None and s1.search == type(s1.search)()
@@ -575,7 +575,7 @@ def test_rows_that_are_off_play_the_games_of_no_search_and_one_expansion_those_o
 def test_set_search_rewrites_the_table_under_the_same_graph():
     arena, fresh = _arena(True, seed=31, search=CTL), _arena(True, seed=31, search=CTL)
     r0, s0 = arena.run_round(PAIRINGS, games_per_match=4)
-    graph, table = arena._graph, arena._se_table
+    graph, table = arena._graph, arena.ply.stages["search"].table
     assert graph is not None and s0.search.expansions > 1.5 * s0.search.searched
     one = [SearchControls(3, 1, 0.25), SearchControls(2, 1, 0.0, skip_plies=4)]
     arena.set_search(one)
@@ -583,7 +583,7 @@ def test_set_search_rewrites_the_table_under_the_same_graph():
     r1, s1 = arena.run_round(PAIRINGS, games_per_match=4)
     assert s1.search.expansions == s1.search.searched > 100 and s1.search.deepened == 0
     arena.set_search(CTL)
-    assert arena._graph is graph and arena._se_table is table and table[:, 3].tolist() == [4, 1]
+    assert arena._graph is graph and arena.ply.stages["search"].table is table and table[:, 3].tolist() == [4, 1]
     r2, s2 = arena.run_round(PAIRINGS, games_per_match=4)
     f0, _ = fresh.run_round(PAIRINGS, games_per_match=4)      # the rounds depend on the table alone
     fresh.set_search(one)

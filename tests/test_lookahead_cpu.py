@@ -213,3 +213,52 @@ def test_choose_refuses_other_shapes():
                  ("child_rewards", torch.zeros(2, 2)), ("prior_weight", -1.0), ("prior_weight", INF)):
         with pytest.raises(ValueError):
             lookahead_choose(**dict(ok, **{k: v}))
+
+
+# ------------------------------------------------------------------ the shared table reader and field checks
+def check_table_of(make_table, what, one, two):
+    """``table_of`` for one kind of table (the other ``*_cpu.py`` files call this for theirs): ``one`` a controls object,
+    ``two`` a sequence of two."""
+    from keisei_amd.training._forked_rows import table_of
+    assert np.array_equal(table_of(one, None, make_table, what), make_table(one, 1))
+    assert np.array_equal(table_of(one, 3, make_table, what), make_table(one, 3))
+    assert np.array_equal(table_of(two, None, make_table, what), make_table(two, 2))
+    raw = make_table(two, 2)
+    for given in (raw, torch.from_numpy(raw)):                 # a table as it lies on the device: unchanged
+        got = table_of(given, None, make_table, what)
+        assert got.dtype == np.int32 and got.shape == (2, 4) and np.array_equal(got, raw)
+        assert np.array_equal(table_of(given, 2, make_table, what), raw)
+    for bad in (raw.astype(np.int64), raw.view(np.float32), raw[:, :3], raw.reshape(-1), raw[:0]):
+        with pytest.raises(ValueError, match=f"a {what} table is a \\(K, 4\\) int32 array"):
+            table_of(bad, None, make_table, what)
+    with pytest.raises(ValueError, match="expected a table of 3 rows, got 2"):
+        table_of(raw, 3, make_table, what)
+
+
+def check_field_refusals(make, ints=(), weights=()):
+    """``make(**{field: value})`` refuses what ``check_int`` / ``check_weight`` refuse, under the field's own name.
+    ``ints``: ``(field, hi)`` pairs, ``weights``: field names."""
+    for field, hi in ints:
+        for bad in (True, 1.0, hi + 1, -1):
+            with pytest.raises(ValueError, match=f"{field} must be an integer in"):
+                make(**{field: bad})
+    for field in weights:
+        for bad, text in ((True, "be finite and >= 0"), (float("nan"), "be finite and >= 0"), (-0.5, "be finite and >= 0"),
+                          (3.1e38, "fit a float32")):
+            with pytest.raises(ValueError, match=f"{field} must {text}"):
+                make(**{field: bad})
+
+
+def test_the_shared_table_reader_and_field_checks():
+    from keisei_amd.training._forked_rows import check_int, check_weight
+    check_table_of(lookahead_table, "lookahead", LookaheadControls(3, 0.25), [LookaheadControls(3, 0.25, 2, 1), LookaheadControls()])
+    check_field_refusals(lambda **kw: LookaheadControls(**dict({"width": 1}, **kw)),
+                         ints=(("width", 8), ("skip_plies", 65535), ("reply_width", 8)), weights=("prior_weight",))
+    assert check_int("n", np.int64(7), 1, 7) == 7 and type(check_int("n", np.int64(7), 1, 7)) is int
+    assert check_weight("w", 2) == 2.0 and type(check_weight("w", 2)) is float and check_weight("w", 3.0e38) == 3.0e38
+    for bad in (True, 2.0, 8, 0, "3", None):
+        with pytest.raises(ValueError, match=r"n must be an integer in \[1, 7\]"):
+            check_int("n", bad, 1, 7)
+    for bad in (float("inf"), "1", None):
+        with pytest.raises(ValueError, match="w must be finite and >= 0"):
+            check_weight("w", bad)

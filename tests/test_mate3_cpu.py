@@ -16,7 +16,7 @@ import mate_search_helpers as H
 from keisei_amd import _lib
 from keisei_amd.shogi_gym import parse_sfen
 from keisei_amd.training import MatchArena, MateControls
-from keisei_amd.training.mate_search import (MAX_CHECKS, MAX_EVASION_ROWS, Mate3Stats, arena_mate, arena_mate3,
+from keisei_amd.training.mate_search import (MAX_CHECKS, MAX_EVASION_ROWS, Mate3Stats, MateStage, arena_mate, arena_mate3,
                                              mate3_reply_table, mate3_words, mate_table)
 from keisei_amd.training.match_arena import RoundStats
 from oracle import shogi as S
@@ -164,13 +164,13 @@ def test_arena_reading_of_the_option():
 
 def test_set_mate_refuses_what_is_above_the_built_sizes():
     arena = object.__new__(MatchArena)                         # the refusals come before anything touches the device
-    arena.group, arena.collect, arena._mt_table = [0, 1], False, object()
-    arena._mt, arena._mt3 = SimpleNamespace(cap=16), SimpleNamespace(rows=32, reply_cap=8)
+    arena.group, arena.collect, arena._ctl = [0, 1], False, None
+    arena.ply = SimpleNamespace(stages={"mate": MateStage(mate_table(None, 2), 16, 32, 8)})    # the sizes built, no engine
     for controls, text in ((MateControls(17, 0, 32, 8), "max_checks 17"), (MateControls(16, 0, 33, 8), "evasion_rows 33"),
                            (MateControls(16, 0, 32, 9), "reply_checks 9")):
         with pytest.raises(ValueError, match=f"{text} is above the largest"):
             arena.set_mate(controls)
-    arena._mt3 = None                                          # built for the mate in one alone
+    arena.ply.stages["mate"] = MateStage(mate_table(None, 2), 16)    # built for the mate in one alone
     with pytest.raises(ValueError, match="evasion_rows 1 is above the largest"):
         arena.set_mate({0: MateControls(16, 0, 1, 1)})
     arena.collect = True

@@ -181,3 +181,9 @@ def test_arena_with_mate_on_a_cpu_group_raises_like_the_lookahead():
         MatchArena(g, 8, 4, 40, sync_every=2, mate=MateControls())
     with pytest.raises(ValueError, match="GPU group"):
         MatchArena(g, 8, 4, 40, sync_every=2, graph=False, mate=[MateControls(4), MateControls.OFF])
+
+
+def test_the_shared_field_checks():
+    from test_lookahead_cpu import check_field_refusals
+    check_field_refusals(MateControls, ints=(("max_checks", MAX_CHECKS), ("skip_plies", 65535), ("evasion_rows", 128),
+                                             ("reply_checks", MAX_CHECKS)))

@@ -280,3 +280,10 @@ def test_no_selection_of_the_synthetic_worlds_is_closer_than_fp32_can_tell(W, E)
         assert changed.sum() >= 1 and (root & ~changed).sum() >= 1
         contested = sum(1 for sel in r.selections for s in sel for _, scores, _ in s if len(scores) > 1)
         assert contested > levels // 2
+
+
+def test_the_shared_table_reader_and_field_checks():
+    from test_lookahead_cpu import check_field_refusals, check_table_of
+    check_table_of(mcts_table, "mcts", MctsControls(3, 4, 1.25), [MctsControls(3, 4, 1.25, 2), MctsControls()])
+    check_field_refusals(lambda **kw: MctsControls(**dict({"width": 1}, **kw)),
+                         ints=(("width", 8), ("skip_plies", 65535), ("simulations", MAX_SIMULATIONS)), weights=("c_puct",))

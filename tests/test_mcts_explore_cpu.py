@@ -13,6 +13,7 @@ from keisei_amd import _lib, build
 from keisei_amd.training import MatchArena, MctsControls, MctsExploration, MctsStats, explore_table, root_noise_host, visit_choice_host
 from keisei_amd.training import mcts_explore as X
 from keisei_amd.training._device_ply import DevicePly
+from keisei_amd.training.mcts_search import MctsStage
 from keisei_amd.training.sampling import sample_uniform
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -90,8 +91,8 @@ def test_the_refusals_need_no_device():
             return 2
     with pytest.raises(ValueError, match="mcts_explore= needs mcts="):
         MatchArena(Group(), 16, 8, 24, graph=False, mcts_explore=on)
-    with pytest.raises(ValueError, match="mcts_explore_table needs mcts_table"):
-        DevicePly(Group(), 16, 24, mcts_explore_table=explore_table(on, 2))
+    with pytest.raises(ValueError, match="an exploration needs mcts="):     # the stage that would own the table refuses
+        DevicePly(Group(), 16, 24, stages=[MctsStage.parse(None, 2, False, explore_table(on, 2))])
     assert MctsStats() == MctsStats(0, 0, 0, 0, 0, 0) and MctsStats(1, 2, 3, 4, 5, 6) == MctsStats(1, 2, 3, 4, 5, 6, 0, 0, 0)
     assert (MctsStats().noised, MctsStats().sampled, MctsStats().diverged) == (0, 0, 0)
 
@@ -221,3 +222,9 @@ def test_nor_is_one_of_the_real_env_step():
     for n in range(1, XH.STEP_W + 1):
         for e in range(XH.STEP_ENVS):
             assert X.dirichlet_gammas_host(XH.STEP_SEED, e, n, float(np.float32(XH.STEP_ALPHA)))[1] >= XH.MARGIN, (n, e)
+
+
+def test_the_shared_table_reader_and_field_checks():
+    from test_lookahead_cpu import check_field_refusals, check_table_of
+    check_table_of(explore_table, "mcts_explore", MctsExploration(0.25, 0.15, 30), [MctsExploration(0.5, 1.0, 2), MctsExploration()])
+    check_field_refusals(MctsExploration, ints=(("sample_plies", 65535),))

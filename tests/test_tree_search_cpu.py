@@ -221,3 +221,23 @@ def test_the_sign_of_the_backup_and_the_max_decide_these_trees():
     minmax = {(): [(0.1, False), (0.0, False)], (0,): [(0.5, False), (-0.5, False)]}
     t = _drive([_world(minmax)], 2, 2, SearchControls(2, 2))[0][1]
     assert t.val[0, 0].tolist() == [-0.5, 0.0] and t.choice[0] == 1 and t.slot[1, 0] == 0
+
+
+def test_the_shared_table_reader_field_checks_and_the_one_place_rule():
+    from test_lookahead_cpu import check_field_refusals, check_table_of
+    check_table_of(search_table, "search", SearchControls(3, 4, 0.25), [SearchControls(3, 4, 0.25, 2), SearchControls()])
+    check_field_refusals(lambda **kw: SearchControls(**dict({"width": 1}, **kw)),
+                         ints=(("width", 8), ("skip_plies", 65535), ("expansions", MAX_EXPANSIONS)), weights=("prior_weight",))
+    # stated once, over the stage list: refused before the ply touches a device
+    from keisei_amd.training._device_ply import DevicePly
+    from keisei_amd.training.lookahead import LookaheadStage
+    from keisei_amd.training.mcts_search import MctsControls, MctsStage
+    from keisei_amd.training.tree_search import SearchStage
+    la, se, mc = (LookaheadStage.parse(LookaheadControls(2), 2, False), SearchStage.parse(SearchControls(2, 2), 2, False),
+                  MctsStage.parse(MctsControls(2, 2), 2, False))
+    for stages, text in (((la, se), "search= cannot be combined with lookahead="), ((se, mc), "mcts= cannot be combined with search="),
+                         ((la, None, mc), "mcts= cannot be combined with lookahead=")):
+        with pytest.raises(ValueError, match=text):
+            DevicePly(None, 16, 24, stages=stages)
+    assert (la.sizes, se.sizes, mc.sizes) == (dict(width=2, reply_width=0), dict(width=2, expansions=2), dict(width=2, simulations=2))
+    assert la.engine is None and la.table is None and LookaheadStage.parse(None, 2, False) is None
