@@ -195,6 +195,29 @@ template <int THREADS> __device__ __forceinline__ int ka_block_max(int v, int* r
     for (int w = 1; w < THREADS / 64; ++w) r = max(r, red[w]);
     return r;
 }
+// The same over floats.  The order of the additions is part of the result: the wave's butterfly, then wave 0's partial plus
+// those of waves 1, 2, ... in turn.  Every kernel that reduces a policy row (loss.hip, sampling.hip, insight.hip,
+// lookahead.hip) sums through this body, which is why their normalisers agree to the bit.
+template <int THREADS> __device__ __forceinline__ float ka_block_sum(float v, float* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float r = red[0];
+    for (int w = 1; w < THREADS / 64; ++w) r += red[w];
+    return r;
+}
+template <int THREADS> __device__ __forceinline__ float ka_block_max(float v, float* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float r = red[0];
+    for (int w = 1; w < THREADS / 64; ++w) r = fmaxf(r, red[w]);
+    return r;
+}
 
 // One fp32 row copied by a workgroup of THREADS threads: 8-byte vectors where the row length and both addresses allow it
 // (a 50 x 9 x 9 observation row is 16 200 B: 8-byte aligned, not 16).

@@ -16,9 +16,11 @@
 // A row whose model_of lies outside [0, K) or that has no legal action is written as all zeros (record and heat).
 // Ranks and the candidate order compare raw logits, so they do not depend on rounding; a legal logit that is -inf or NaN is
 // never a candidate.  Kernel nodes only, caller-owned buffers, no workgroup waits for another.
+//
+// The walk over the set bits, the staged row, the candidate order and the round are csrc/policy_row.h's: the sampling
+// controls' cut and the lookahead's fork run the same bodies, so their candidates are these.
 #include "ply_rows.h"
-
-#include <climits>
+#include "policy_row.h"
 
 namespace {
 
@@ -35,39 +37,13 @@ struct InsightArgs {
     uint32_t* last; float* heat; uint32_t* hist; int row_len; const int* count; int* flags;
 };
 
-__device__ __forceinline__ float in_reduce(float v, float* red, bool is_max) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const float t = __shfl_xor(v, o); v = is_max ? fmaxf(v, t) : v + t; }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = red[0];
-    for (int w = 1; w < kInWaves; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
-    return r;
-}
-
-// f(j) for every legal action j of this thread's mask words, in ascending j
-template <class F>
-__device__ __forceinline__ void in_for_legal(const uint32_t* msk, F f) {
-    for (int w = threadIdx.x; w < kInWords; w += kInThreads) {
-        uint32_t m = msk[w];
-        while (m) {
-            f((w << 5) + __builtin_ctz(m));
-            m &= m - 1u;
-        }
-    }
-}
-
-// (v, i) comes before (bv, bi) in the candidate order: greater logit, equal logits by lower action
-__device__ __forceinline__ bool in_before(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-
 __global__ __launch_bounds__(kInThreads) void policy_insight_kernel(InsightArgs a) {
     __shared__ float row[kInA];
     __shared__ uint32_t msk[kInWords];
     __shared__ float red[kInWaves];
     __shared__ int red_i[kInWaves];
     __shared__ uint32_t rec[in_words(kInMaxTop)];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int W = in_words(a.top_k);
     uint32_t* last = a.last + (size_t)b * W;
     float* heat = a.heat + (size_t)b * kInHeat;
@@ -79,27 +55,20 @@ __global__ __launch_bounds__(kInThreads) void policy_insight_kernel(InsightArgs 
     const uint32_t* lw = a.legal + (size_t)b * a.legal_words;
     const int m = a.model_of ? a.model_of[b] : 0;
     const bool seated = !a.model_of || (m >= 0 && m < a.K);    // (uniform over the workgroup)
-    float mx = -INFINITY, nl = 0.f;
-    int nan_seen = 0;
+    PolicyRowHead h{-INFINITY, 0.f, 0.f, INT_MAX};
     if (seated) {
         for (int w = tid; w < kInWords; w += kInThreads) msk[w] = mask_word(lw, w);
-        in_for_legal(msk, [&](int j) {                         // (a thread reads back the words it wrote itself)
-            const float v = a.logits_bf16 ? bf2f(static_cast<const uint16_t*>(a.logits)[(size_t)b * kInA + j])
-                                          : static_cast<const float*>(a.logits)[(size_t)b * kInA + j];
-            row[j] = v;
-            nan_seen |= (v != v);
-            mx = fmaxf(mx, v);
-            nl += 1.f;
-        });
-        nl = in_reduce(nl, red, false);                        // (at most 11259: exact in fp32; row and msk are visible behind it)
+        h = policy_stage_legal<kInThreads>(a.logits, a.logits_bf16, (size_t)b * kInA, msk, kInWords, row);
+        h.nlegal = ka_block_sum<kInThreads>(h.nlegal, red);    // (at most 11259: exact in fp32; row and msk are visible behind it)
     }
+    const float nl = h.nlegal;
     if (!seated || nl == 0.f) {                                // an invalid row: all zeros
         if (tid < W) { last[tid] = 0u; if (slot) slot[tid] = 0u; }
         if (tid < kInHeat) heat[tid] = 0.f;
         return;
     }
-    mx = in_reduce(mx, red, true);
-    const float nan_any = in_reduce((float)nan_seen, red, false);
+    const float mx = ka_block_max<kInThreads>(h.mx, red);
+    const float nan_any = ka_block_sum<kInThreads>(h.nan, red);
     const long long act64 = a.actions[b];
     const bool in_range = act64 >= 0 && act64 < kInA;
     const int act = in_range ? (int)act64 : (act64 < 0 ? -1 : kInA);
@@ -107,16 +76,16 @@ __global__ __launch_bounds__(kInThreads) void policy_insight_kernel(InsightArgs 
     const float la = legal_act ? row[act] : 0.f;
     // the normaliser, the entropy sum and the rank in one pass: p = e / S, ln p = z - ln S, H = ln S - sum(e z) / S
     float s = 0.f, t = 0.f, above = 0.f;
-    in_for_legal(msk, [&](int j) {
+    policy_for_legal<kInThreads>(msk, kInWords, [&](int j) {
         const float v = row[j];
         if (legal_act && v > la) above += 1.f;
         const float z = (v - mx) * a.inv_t, e = expf(z);       // (a legal logit of -inf: e = 0)
         s += e;
         if (e > 0.f) t += e * z;
     });
-    s = in_reduce(s, red, false);
-    t = in_reduce(t, red, false);
-    above = in_reduce(above, red, false);
+    s = ka_block_sum<kInThreads>(s, red);
+    t = ka_block_sum<kInThreads>(t, red);
+    above = ka_block_sum<kInThreads>(above, red);
     if (tid == 0) {
         if (nan_any > 0.f) atomicOr(&a.flags[0], 1);
         float win = 0.f;
@@ -142,24 +111,7 @@ __global__ __launch_bounds__(kInThreads) void policy_insight_kernel(InsightArgs 
     for (int r = 0; r < a.top_k; ++r) {                        // (prev_i is uniform over the workgroup, so is every branch on it)
         float bv = -INFINITY;
         int bi = INT_MAX;
-        if (r == 0 || prev_i != INT_MAX) {
-            in_for_legal(msk, [&](int j) {
-                const float v = row[j];
-                if (v > -INFINITY && in_before(prev_v, prev_i, v, j) && v > bv) { bv = v; bi = j; }     // (j ascends: ties keep the lower)
-            });
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(bv, o);
-                const int oi = __shfl_xor(bi, o);
-                if (in_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-            }
-            __syncthreads();
-            if (lane == 0) { red[wave] = bv; red_i[wave] = bi; }
-            __syncthreads();
-            bv = red[0]; bi = red_i[0];
-            for (int w = 1; w < kInWaves; ++w)
-                if (in_before(red[w], red_i[w], bv, bi)) { bv = red[w]; bi = red_i[w]; }
-        }
+        if (r == 0 || prev_i != INT_MAX) bi = policy_next<kInThreads, false>(row, msk, kInWords, prev_v, prev_i, red, red_i, &bv);
         if (tid == 0) {
             rec[kInTop + r] = (uint32_t)(bi == INT_MAX ? -1 : bi);
             rec[kInTop + a.top_k + r] = __float_as_uint(bi == INT_MAX ? 0.f : expf((bv - mx) * a.inv_t) / s);

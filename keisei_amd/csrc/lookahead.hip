@@ -50,9 +50,11 @@
 //
 //   ka_search_expand      the fork kernel with a row of the pool as "env", named per env by parent_row / active
 //   ka_search_advance     one thread per env: leaf q, the backup by max and negation, the next leaf, at the end the choice
+//
+// The fork's candidates -- the walk over the set bits, the staged row, the candidate order and the round -- are
+// csrc/policy_row.h's, the bodies the insight and the sampling controls run: that is why the orders are one order.
 #include "lookahead_record.h"
-
-#include <climits>
+#include "policy_row.h"
 
 namespace {
 
@@ -83,32 +85,6 @@ struct ChooseArgs {
     uint32_t* r_rec; int rwidth; const float* g_vl; const float* g_rewards; const uint8_t* g_term; const uint8_t* g_trunc;
     const unsigned long long* g_err;
 };
-
-__device__ __forceinline__ float la_reduce(float v, float* red, bool is_max) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const float t = __shfl_xor(v, o); v = is_max ? fmaxf(v, t) : v + t; }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = red[0];
-    for (int w = 1; w < kLaWaves; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
-    return r;
-}
-
-// f(j) for every legal action j of this thread's mask words, in ascending j
-template <class F>
-__device__ __forceinline__ void la_for_legal(const uint32_t* msk, F f) {
-    for (int w = threadIdx.x; w < kPlyWords; w += kLaThreads) {
-        uint32_t m = msk[w];
-        while (m) {
-            f((w << 5) + __builtin_ctz(m));
-            m &= m - 1u;
-        }
-    }
-}
-
-// (v, i) comes before (bv, bi) in the candidate order: greater logit, equal logits by lower action
-__device__ __forceinline__ bool la_before(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
 // the reply width of model m: word 3 of a row that is on; a word outside [0, 8] reads as 0
 __device__ __forceinline__ int la_reply_width(const uint32_t* table, int m, int K) {
@@ -164,42 +140,20 @@ __global__ __launch_bounds__(kLaThreads) void lookahead_fork_kernel(ForkArgs a) 
     int n_cand = 0;
     if (want > 0) {
         for (int w = tid; w < kPlyWords; w += kLaThreads) msk[w] = mask_word(lw, w);
-        float mx = -INFINITY;
-        la_for_legal(msk, [&](int j) {                         // (a thread reads back the words it wrote itself)
-            const float v = a.logits_bf16 ? bf2f(static_cast<const uint16_t*>(a.logits)[(size_t)src * kPlyA + j])
-                                          : static_cast<const float*>(a.logits)[(size_t)src * kPlyA + j];
-            row[j] = v;
-            mx = fmaxf(mx, v);                                 // (a NaN is passed over)
-        });
-        mx = la_reduce(mx, red, true);
+        const PolicyRowHead h = policy_stage_legal<kLaThreads>(a.logits, a.logits_bf16, (size_t)src * kPlyA, msk, kPlyWords, row);
+        const float mx = ka_block_max<kLaThreads>(h.mx, red);  // (a NaN is passed over)
         float s = 0.f;
-        la_for_legal(msk, [&](int j) {
+        policy_for_legal<kLaThreads>(msk, kPlyWords, [&](int j) {
             const float v = row[j];
             if (v == v) s += expf(v - mx);                     // (a NaN logit weighs nothing; -inf gives 0)
         });
-        s = la_reduce(s, red, false);
+        s = ka_block_sum<kLaThreads>(s, red);
         // round r takes the first action behind round r - 1's winner in the candidate order
         float prev_v = INFINITY;
         int prev_i = -1;
         for (int r = 0; r < want; ++r) {
-            float bv = -INFINITY;
-            int bi = INT_MAX;
-            la_for_legal(msk, [&](int j) {
-                const float v = row[j];
-                if (v > -INFINITY && la_before(prev_v, prev_i, v, j) && v > bv) { bv = v; bi = j; }     // (j ascends: ties keep the lower)
-            });
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(bv, o);
-                const int oi = __shfl_xor(bi, o);
-                if (la_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-            }
-            __syncthreads();
-            if (lane == 0) { red[wave] = bv; red_i[wave] = bi; }
-            __syncthreads();
-            bv = red[0]; bi = red_i[0];
-            for (int w = 1; w < kLaWaves; ++w)
-                if (la_before(red[w], red_i[w], bv, bi)) { bv = red[w]; bi = red_i[w]; }
+            float bv;
+            const int bi = policy_next<kLaThreads, false>(row, msk, kPlyWords, prev_v, prev_i, red, red_i, &bv);
             if (bi == INT_MAX) break;                          // nothing behind the last winner
             if (tid == 0) { s_cand[r] = bi; s_prior[r] = expf(bv - mx) / s; }
             prev_v = bv; prev_i = bi;

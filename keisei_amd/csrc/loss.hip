@@ -12,7 +12,11 @@
 // Reference: keisei/training/katago_ppo.py:33-57 (ppo_clip_loss, wdl_cross_entropy_loss),
 // :857-924 (loss assembly), value_adapter.py:98-126; gradients follow torch autograd
 // (torch.minimum ties split 1/2-1/2, clamp passes gradient on the closed interval).
-#include "common.h"
+//
+// The masked row -- the mask read, the staged row of the softmax and the samplers, the normaliser, the draw with its uniform
+// and the endings -- is csrc/policy_row.h's, shared with sampling.hip, insight.hip and lookahead.hip; the float reductions
+// are common.h's ka_block_sum / ka_block_max.
+#include "policy_row.h"
 
 namespace {
 
@@ -36,21 +40,10 @@ struct PolicyArgs {
     int A, legal_words;
 };
 
-__device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const float t = __shfl_xor(v, o); v = is_max ? fmaxf(v, t) : v + t; }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = red[0];
-    for (int w = 1; w < kPolThreads / 64; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
-    return r;
-}
-
 __global__ __launch_bounds__(kPolThreads) void policy_loss_kernel(PolicyArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* row = reinterpret_cast<float*>(smem);
-    uint8_t* msk = reinterpret_cast<uint8_t*>(smem + ((size_t)a.A * 4 + 15) / 16 * 16);
+    uint8_t* msk = reinterpret_cast<uint8_t*>(smem + policy_row_bytes(a.A));
     __shared__ float red[kPolThreads / 64];
     const int b = blockIdx.x, tid = threadIdx.x;
     const long long src = a.idx ? a.idx[b] : b;
@@ -67,7 +60,7 @@ __global__ __launch_bounds__(kPolThreads) void policy_loss_kernel(PolicyArgs a) 
         for (int u = 0; u < 4; ++u) {
             const int j = j0 + u * kPolThreads;
             v[u] = j < a.A ? lg[j] : 0.f;
-            k[u] = j < a.A ? (a.legal_words ? (uint8_t)((lw[j >> 5] >> (j & 31)) & 1u) : lm[j]) : (uint8_t)0;
+            k[u] = j < a.A ? policy_legal(lm, lw, a.legal_words, j) : (uint8_t)0;
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -78,9 +71,9 @@ __global__ __launch_bounds__(kPolThreads) void policy_loss_kernel(PolicyArgs a) 
             if (k[u]) { mx = fmaxf(mx, v[u]); nlegal += 1.f; }
         }
     }
-    mx = block_reduce(mx, red, true);
-    nlegal = block_reduce(nlegal, red, false);
-    const float nanf_ = block_reduce((float)nan_seen, red, false);
+    mx = ka_block_max<kPolThreads>(mx, red);
+    nlegal = ka_block_sum<kPolThreads>(nlegal, red);
+    const float nanf_ = ka_block_sum<kPolThreads>((float)nan_seen, red);
     if (tid == 0) {
         if (nanf_ > 0.f) atomicOr(&a.flags[0], 1);
         if (nlegal == 0.f) atomicOr(&a.flags[1], 1);
@@ -99,9 +92,9 @@ __global__ __launch_bounds__(kPolThreads) void policy_loss_kernel(PolicyArgs a) 
                 t += e * row[j];
             }
         }
-    s = block_reduce(s, red, false);
-    t = block_reduce(t, red, false);
-    td = block_reduce(td, red, false);
+    s = ka_block_sum<kPolThreads>(s, red);
+    t = ka_block_sum<kPolThreads>(t, red);
+    td = ka_block_sum<kPolThreads>(td, red);
     const float logs = logf(s);
     const float lse = mx + logs;
     const float H = lse - t / s;
@@ -150,31 +143,16 @@ __global__ __launch_bounds__(kPolThreads) void masked_softmax_kernel(const float
                                                                      int* __restrict__ flags, int A, int legal_words) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* row = reinterpret_cast<float*>(smem);
-    uint8_t* msk = reinterpret_cast<uint8_t*>(smem + ((size_t)A * 4 + 15) / 16 * 16);
+    uint8_t* msk = reinterpret_cast<uint8_t*>(smem + policy_row_bytes(A));
     __shared__ float red[kPolThreads / 64];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const float* lg = logits + (size_t)b * A;
-    const uint8_t* lm = legal + (size_t)b * A;
-    const uint32_t* lw = reinterpret_cast<const uint32_t*>(legal) + (size_t)b * legal_words;
-    float mx = -INFINITY, nlegal = 0.f;
-    int nan_seen = 0;
-    for (int j = tid; j < A; j += kPolThreads) {
-        const float v = lg[j];
-        const uint8_t k = legal_words ? (uint8_t)((lw[j >> 5] >> (j & 31)) & 1u) : lm[j];
-        row[j] = v; msk[j] = k;
-        nan_seen |= (v != v);
-        if (k) { mx = fmaxf(mx, v); nlegal += 1.f; }
-    }
-    mx = block_reduce(mx, red, true);
-    nlegal = block_reduce(nlegal, red, false);
-    const float nanf_ = block_reduce((float)nan_seen, red, false);
-    float s = 0.f;
-    for (int j = tid; j < A; j += kPolThreads)
-        if (msk[j]) s += expf(row[j] - mx);
-    s = block_reduce(s, red, false);
+    PolicyRowHead h = policy_stage<kPolThreads, false, false>(logits, 0, legal, legal_words, b, A, row, msk, nullptr);
+    h.reduce<kPolThreads>(red);
+    const float mx = h.mx;
+    const float s = policy_normaliser<kPolThreads>(A, [&](int j) { return msk[j] != 0; }, [&](int j) { return expf(row[j] - mx); }, red);
     if (tid == 0) {
-        if (nanf_ > 0.f) atomicOr(&flags[0], 1);
-        nlegal_out[b] = (int)nlegal;
+        if (h.nan > 0.f) atomicOr(&flags[0], 1);
+        nlegal_out[b] = (int)h.nlegal;
     }
     const float inv = 1.f / s;
     float* pr = probs + (size_t)b * A;
@@ -202,11 +180,11 @@ __device__ __forceinline__ float policy_ce_row_pass(const float* __restrict__ lg
         nan_seen |= (v != v);
         mx = fmaxf(mx, v);
     }
-    mx = block_reduce(mx, red, true);
-    *nan_count = block_reduce((float)nan_seen, red, false);
+    mx = ka_block_max<kPolThreads>(mx, red);
+    *nan_count = ka_block_sum<kPolThreads>((float)nan_seen, red);
     float s = 0.f;
     for (int j = tid; j < A; j += kPolThreads) s += expf(row[j] - mx);
-    s = block_reduce(s, red, false);
+    s = ka_block_sum<kPolThreads>(s, red);
     return mx + logf(s);
 }
 
@@ -432,11 +410,11 @@ __global__ __launch_bounds__(kPolThreads) void sl_eval_rows_kernel(SlEvalArgs a)
         nan_seen |= (v != v);
         mx = fmaxf(mx, v);
     }
-    mx = block_reduce(mx, red, true);
-    const float nanf_ = block_reduce((float)nan_seen, red, false);
+    mx = ka_block_max<kPolThreads>(mx, red);
+    const float nanf_ = ka_block_sum<kPolThreads>((float)nan_seen, red);
     float s = 0.f;
     for (int j = tid; j < a.A; j += kPolThreads) s += expf(row[j] - mx);
-    s = block_reduce(s, red, false);
+    s = ka_block_sum<kPolThreads>(s, red);
     const float lse = mx + logf(s);
     const long long tgt = a.policy_t[b];
     const bool ok = tgt >= 0 && tgt < a.A;
@@ -541,92 +519,30 @@ template <bool Play>
 __global__ __launch_bounds__(kPolThreads) void policy_sample_kernel(SampleArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* row = reinterpret_cast<float*>(smem);
-    uint8_t* msk = reinterpret_cast<uint8_t*>(smem + ((size_t)a.A * 4 + 15) / 16 * 16);
+    uint8_t* msk = reinterpret_cast<uint8_t*>(smem + policy_row_bytes(a.A));
     __shared__ float red[kPolThreads / 64];
-    __shared__ float wave_tot[kPolThreads / 64];
-    __shared__ int s_first, s_last, s_lo;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, A = a.A;
-    int lo = A;                                                // play form: this thread's lowest legal action
-    const uint8_t* lm = a.legal + (size_t)b * A;
-    const uint32_t* lw = reinterpret_cast<const uint32_t*>(a.legal) + (size_t)b * a.legal_words;
-    float mx = -INFINITY, nlegal = 0.f;
-    int nan_seen = 0;
-    for (int j = tid; j < A; j += kPolThreads) {
-        const float v = a.logits_bf16 ? bf2f(static_cast<const uint16_t*>(a.logits)[(size_t)b * A + j])
-                                      : static_cast<const float*>(a.logits)[(size_t)b * A + j];
-        const uint8_t k = a.legal_words ? (uint8_t)((lw[j >> 5] >> (j & 31)) & 1u) : lm[j];
-        row[j] = v; msk[j] = k;
-        nan_seen |= (v != v);
-        if (k) { mx = fmaxf(mx, v); nlegal += 1.f; }
-        if constexpr (Play) { if (k && j < lo) lo = j; }
-    }
-    if (tid == 0) { s_first = kPolThreads; s_last = -1; s_lo = A; }
-    mx = block_reduce(mx, red, true);
-    nlegal = block_reduce(nlegal, red, false);
-    const float nanf_ = block_reduce((float)nan_seen, red, false);
+    __shared__ PolicyDrawLds<kPolThreads> draw;
+    const int b = blockIdx.x, tid = threadIdx.x, A = a.A;
+    PolicyRowHead h = policy_stage<kPolThreads, Play, false>(a.logits, a.logits_bf16, a.legal, a.legal_words, b, A, row, msk, nullptr);
+    draw.reset(A);
+    h.reduce<kPolThreads>(red);
     if constexpr (Play) {
         const int m = a.model_of[b];
         if (m < 0 || m >= a.K) {                               // unseated row (uniform over the workgroup)
-            if (lo < A) atomicMin(&s_lo, lo);
-            __syncthreads();
-            if (tid == 0) {
-                if (nanf_ > 0.f) atomicOr(&a.flags[0], 1);
-                if (nlegal == 0.f) atomicOr(&a.flags[1], 1);
-                a.nlegal[b] = (int)nlegal;
-                a.actions[b] = s_lo < A ? s_lo : 0;
-                a.logp[b] = 0.f;
-            }
+            policy_end_unseated(h, A, draw, a.flags, &a.nlegal[b], &a.actions[b], &a.logp[b]);
             return;
         }
     }
-    float s = 0.f;
-    for (int j = tid; j < A; j += kPolThreads)
-        if (msk[j]) s += expf(row[j] - mx);
-    s = block_reduce(s, red, false);                           // the normaliser of the masked-softmax path (same order)
-    // contiguous chunk per thread, inclusive prefix over the threads
-    const int chunk = (A + kPolThreads - 1) / kPolThreads, j0 = tid * chunk, j1 = min(j0 + chunk, A);
-    float local = 0.f;
-    for (int j = j0; j < j1; ++j) if (msk[j]) local += expf(row[j] - mx);
-    float incl = local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const float t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    float base = 0.f, total = 0.f;
-    for (int w = 0; w < kPolThreads / 64; ++w) { if (w < wave) base += wave_tot[w]; total += wave_tot[w]; }
-    incl += base;
+    const float mx = h.mx;
+    const auto legal = [&](int j) { return msk[j] != 0; };
+    const auto weight = [&](int j) { return expf(row[j] - mx); };
+    const float s = policy_normaliser<kPolThreads>(A, legal, weight, red);   // the normaliser of the masked-softmax path (same order)
     const unsigned long long seed = Play ? (unsigned long long)*a.seed_dev : a.seed;
-    const unsigned long long h = ka_mix64(seed ^ ka_mix64((unsigned long long)b + 0x5851F42D4C957F2Dull));
-    const float u = (float)(h >> 40) * (1.0f / 16777216.0f);   // 24 bits: [0, 1)
-    const float target = u * total;
-    if (local > 0.f) {
-        if (incl > target) atomicMin(&s_first, tid);
-        atomicMax(&s_last, tid);
-    }
-    __syncthreads();
-    const int winner = s_first < kPolThreads ? s_first : s_last;          // (rounding can leave target >= total: last legal chunk)
+    policy_draw(A, b, seed, s, legal, weight, draw, &a.actions[b], &a.logp[b]);
     if (tid == 0) {
-        if (nanf_ > 0.f) atomicOr(&a.flags[0], 1);
-        if (nlegal == 0.f) { atomicOr(&a.flags[1], 1); a.actions[b] = 0; a.logp[b] = 0.f; }
-        a.nlegal[b] = (int)nlegal;
+        policy_report(h, a.flags, &a.nlegal[b], &a.actions[b], &a.logp[b]);
         if (a.values)                                          // katago_ppo.py:536-541 / value_adapter.py:56-65
             a.values[b] = ka_blended_value(a.vlogits + b * 3, a.score ? a.score + b : nullptr, a.alpha);
-    }
-    if (tid == winner) {
-        float run = incl - local;
-        int pick = -1, last = -1;
-        for (int j = j0; j < j1; ++j) {
-            if (!msk[j]) continue;
-            last = j;
-            run += expf(row[j] - mx);
-            if (run > target) { pick = j; break; }
-        }
-        if (pick < 0) pick = last;
-        a.actions[b] = pick;
-        // Categorical(probs).log_prob (katago_ppo.py:603-605) = log(clamp(p, eps, 1 - eps)), eps = FLT_EPSILON: an action
-        // more than ~88 nats below the maximum gives log(eps), not -inf
-        const float p = expf(row[pick] - mx) * (1.f / s);
-        a.logp[b] = logf(fminf(fmaxf(p, 1.1920929e-7f), 1.f - 1.1920929e-7f));
     }
 }
 
@@ -638,11 +554,11 @@ extern "C" int ka_policy_loss(const float* logits, const void* legal, const long
                               float w_entropy, int B, int A, int legal_words, void* stream) {
     KA_REQUIRE(logits && legal && actions && old_lp && adv && new_lp && rowloss && rowent && flags && B > 0 && A > 0,
                "policy_loss: null tensor");
-    KA_REQUIRE(legal_words == 0 || legal_words == (A + 31) / 32, "policy_loss: packed mask rows must hold %d words", (A + 31) / 32);
+    KA_REQUIRE_MASK_ROW("policy_loss", A, legal_words);
     PolicyArgs a{logits, static_cast<const uint8_t*>(legal), actions, old_lp, adv, idx, dlogits, new_lp, rowloss,
                  rowent, flags, gscale, clip_eps, w_policy, w_entropy, A, legal_words};
-    const size_t lds = ((size_t)A * 4 + 15) / 16 * 16 + ((size_t)A + 15) / 16 * 16;
-    KA_REQUIRE(lds <= 64 * 1024, "policy_loss: action space %d too large for the LDS row", A);
+    const size_t lds = policy_row_bytes(A) + policy_mask_bytes(A);
+    KA_REQUIRE_ROW_LDS("policy_loss", lds, A);
     hipLaunchKernelGGL(policy_loss_kernel, dim3(B), dim3(kPolThreads), lds, static_cast<hipStream_t>(stream), a);
     return ka_check_launch("policy_loss");
 }
@@ -650,9 +566,9 @@ extern "C" int ka_policy_loss(const float* logits, const void* legal, const long
 extern "C" int ka_masked_softmax(const float* logits, const void* legal, float* probs, int* nlegal, int* flags, int B, int A,
                                  int legal_words, void* stream) {
     KA_REQUIRE(logits && legal && probs && nlegal && flags && B > 0 && A > 0, "masked_softmax: null tensor");
-    KA_REQUIRE(legal_words == 0 || legal_words == (A + 31) / 32, "masked_softmax: packed mask rows must hold %d words", (A + 31) / 32);
-    const size_t lds = ((size_t)A * 4 + 15) / 16 * 16 + ((size_t)A + 15) / 16 * 16;
-    KA_REQUIRE(lds <= 64 * 1024, "masked_softmax: action space %d too large for the LDS row", A);
+    KA_REQUIRE_MASK_ROW("masked_softmax", A, legal_words);
+    const size_t lds = policy_row_bytes(A) + policy_mask_bytes(A);
+    KA_REQUIRE_ROW_LDS("masked_softmax", lds, A);
     hipLaunchKernelGGL(masked_softmax_kernel, dim3(B), dim3(kPolThreads), lds, static_cast<hipStream_t>(stream), logits,
                        static_cast<const uint8_t*>(legal), probs, nlegal, flags, A, legal_words);
     return ka_check_launch("masked_softmax");
@@ -662,10 +578,10 @@ extern "C" int ka_policy_sample(const void* logits, int logits_bf16, const void*
                                 const float* vlogits, const float* score, float alpha, long long* actions, float* logp,
                                 float* values, int* nlegal, int* flags, int B, int A, void* stream) {
     KA_REQUIRE(logits && legal && actions && logp && nlegal && flags && B > 0 && A > 0, "policy_sample: null tensor");
-    KA_REQUIRE(legal_words == 0 || legal_words == (A + 31) / 32, "policy_sample: packed mask rows must hold %d words", (A + 31) / 32);
+    KA_REQUIRE_MASK_ROW("policy_sample", A, legal_words);
     KA_REQUIRE((values == nullptr) || vlogits, "policy_sample: values need the value logits");
-    const size_t lds = ((size_t)A * 4 + 15) / 16 * 16 + ((size_t)A + 15) / 16 * 16;
-    KA_REQUIRE(lds <= 64 * 1024, "policy_sample: action space %d too large for the LDS row", A);
+    const size_t lds = policy_row_bytes(A) + policy_mask_bytes(A);
+    KA_REQUIRE_ROW_LDS("policy_sample", lds, A);
     SampleArgs a{logits, logits_bf16, static_cast<const uint8_t*>(legal), legal_words, (unsigned long long)seed, vlogits, score, alpha,
                  actions, logp, values, nlegal, flags, A, nullptr, nullptr, 0};
     hipLaunchKernelGGL(policy_sample_kernel<false>, dim3(B), dim3(kPolThreads), lds, static_cast<hipStream_t>(stream), a);
@@ -677,9 +593,9 @@ extern "C" int ka_policy_sample_play(const void* logits, int logits_bf16, const 
                                      int* nlegal, int* flags, int B, int A, void* stream) {
     KA_REQUIRE(logits && legal && seed_dev && model_of && actions && logp && nlegal && flags && B > 0 && A > 0,
                "policy_sample_play: null tensor");
-    KA_REQUIRE(legal_words == 0 || legal_words == (A + 31) / 32, "policy_sample_play: packed mask rows must hold %d words", (A + 31) / 32);
-    const size_t lds = ((size_t)A * 4 + 15) / 16 * 16 + ((size_t)A + 15) / 16 * 16;
-    KA_REQUIRE(lds <= 64 * 1024, "policy_sample_play: action space %d too large for the LDS row", A);
+    KA_REQUIRE_MASK_ROW("policy_sample_play", A, legal_words);
+    const size_t lds = policy_row_bytes(A) + policy_mask_bytes(A);
+    KA_REQUIRE_ROW_LDS("policy_sample_play", lds, A);
     SampleArgs a{logits, logits_bf16, static_cast<const uint8_t*>(legal), legal_words, 0ull, nullptr, nullptr, 0.f,
                  actions, logp, nullptr, nlegal, flags, A, seed_dev, model_of, K};
     hipLaunchKernelGGL(policy_sample_kernel<true>, dim3(B), dim3(kPolThreads), lds, static_cast<hipStream_t>(stream), a);
@@ -690,8 +606,8 @@ extern "C" int ka_policy_ce(const float* logits, const long long* targets, const
                             float* rowloss, int* flags, const float* gscale, float w_policy, int B, int A, void* stream) {
     KA_REQUIRE(logits && targets && rowloss && flags && B > 0 && A > 0, "policy_ce: null tensor");
     PolicyCeArgs a{logits, targets, idx, dlogits, rowloss, flags, gscale, w_policy, A};
-    const size_t lds = ((size_t)A * 4 + 15) / 16 * 16;
-    KA_REQUIRE(lds <= 64 * 1024, "policy_ce: action space %d too large for the LDS row", A);
+    const size_t lds = policy_row_bytes(A);
+    KA_REQUIRE_ROW_LDS("policy_ce", lds, A);
     hipLaunchKernelGGL(policy_ce_kernel, dim3(B), dim3(kPolThreads), lds, static_cast<hipStream_t>(stream), a);
     return ka_check_launch("policy_ce");
 }
@@ -701,7 +617,7 @@ extern "C" int ka_policy_ce_soft(const float* logits, const int* actions, const 
     KA_REQUIRE(logits && actions && weights && rowloss && flags && B > 0 && A > 0, "policy_ce_soft: null tensor");
     KA_REQUIRE(K >= 1 && K <= kSoftSlots, "policy_ce_soft: K %d (1..%d)", K, kSoftSlots);
     PolicyCeSoftArgs a{logits, actions, weights, K, dlogits, rowloss, flags, gscale, w_policy, A};
-    const size_t lds = ((size_t)A * 4 + 15) / 16 * 16;
+    const size_t lds = policy_row_bytes(A);
     KA_REQUIRE(lds <= 63 * 1024, "policy_ce_soft: action space %d too large for the LDS row", A);
     hipLaunchKernelGGL(policy_ce_soft_kernel, dim3(B), dim3(kPolThreads), lds, static_cast<hipStream_t>(stream), a);
     return ka_check_launch("policy_ce_soft");
@@ -729,8 +645,8 @@ extern "C" int ka_sl_eval(const float* logits, const float* vlogits, const float
     KA_REQUIRE(B > 0 && A > 0, "sl_eval: B %d, A %d", B, A);
     KA_REQUIRE(k >= 1 && k <= A, "sl_eval: k %d outside [1, %d]", k, A);
     KA_REQUIRE((reinterpret_cast<uintptr_t>(acc) & 7) == 0, "sl_eval: the accumulator must be 8-byte aligned");
-    const size_t lds = ((size_t)A * 4 + 15) / 16 * 16;
-    KA_REQUIRE(lds <= 64 * 1024, "sl_eval: action space %d too large for the LDS row", A);
+    const size_t lds = policy_row_bytes(A);
+    KA_REQUIRE_ROW_LDS("sl_eval", lds, A);
     SlEvalArgs a{logits, vlogits, score, policy_t, value_t, score_t, rowloss, rank, static_cast<long long*>(acc),
                  reinterpret_cast<double*>(static_cast<char*>(acc) + 32), flags, B, A, k};
     hipLaunchKernelGGL(sl_eval_rows_kernel, dim3(B), dim3(kPolThreads), lds, static_cast<hipStream_t>(stream), a);

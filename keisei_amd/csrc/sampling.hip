@@ -25,9 +25,10 @@
 // legal moves, so most threads find no bit and a round is little more than its reduction.  Exact under the tie rule, at
 // most 64 rounds, and the usual cuts are a handful of rounds; a bisection over the float's integer image costs 32 counting
 // rounds at any top_k plus a second search for the tie.
-#include "common.h"
-
-#include <climits>
+//
+// The candidate order, the round, the staged row, the draw and its uniform are csrc/policy_row.h's: the bodies the play
+// sampler, the insight and the fork run, which is what keeps the promises above.
+#include "policy_row.h"
 
 namespace {
 
@@ -40,51 +41,19 @@ struct CtlArgs {
     long long* actions; float* logp; int* nlegal; int* flags; int A;
 };
 
-__device__ __forceinline__ float sc_reduce(float v, float* red, bool is_max) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const float t = __shfl_xor(v, o); v = is_max ? fmaxf(v, t) : v + t; }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = red[0];
-    for (int w = 1; w < kScWaves; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
-    return r;
-}
-
-// (v, i) comes before (bv, bi) in the candidate order: greater logit, equal logits by lower action (a NaN never does)
-__device__ __forceinline__ bool sc_before(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-
 __global__ __launch_bounds__(kScThreads) void policy_sample_ctl_kernel(CtlArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* row = reinterpret_cast<float*>(smem);
-    uint8_t* msk = reinterpret_cast<uint8_t*>(smem + ((size_t)a.A * 4 + 15) / 16 * 16);
-    uint32_t* bits = reinterpret_cast<uint32_t*>(msk + ((size_t)a.A + 15) / 16 * 16);      // the mask again, packed: the rounds walk set bits
+    uint8_t* msk = reinterpret_cast<uint8_t*>(smem + policy_row_bytes(a.A));
+    uint32_t* bits = reinterpret_cast<uint32_t*>(msk + policy_mask_bytes(a.A));          // the mask again, packed: the rounds walk set bits
     __shared__ float red[kScWaves];
     __shared__ int red_i[kScWaves];
-    __shared__ float wave_tot[kScWaves];
-    __shared__ int s_first, s_last, s_lo;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, A = a.A;
-    int lo = A;                                                // this thread's lowest legal action
-    const uint8_t* lm = a.legal + (size_t)b * A;
-    const uint32_t* lw = reinterpret_cast<const uint32_t*>(a.legal) + (size_t)b * a.legal_words;
-    float mx = -INFINITY, nlegal = 0.f;
-    int nan_seen = 0;
-    for (int j = tid; j < A; j += kScThreads) {
-        const float v = a.logits_bf16 ? bf2f(static_cast<const uint16_t*>(a.logits)[(size_t)b * A + j])
-                                      : static_cast<const float*>(a.logits)[(size_t)b * A + j];
-        const uint8_t k = a.legal_words ? (uint8_t)((lw[j >> 5] >> (j & 31)) & 1u) : lm[j];
-        row[j] = v; msk[j] = k;
-        const unsigned long long bal = __ballot(k != 0);       // a wave stages 64 consecutive actions: two mask words
-        if (lane == 0) { bits[j >> 5] = (uint32_t)bal; bits[(j >> 5) + 1] = (uint32_t)(bal >> 32); }
-        nan_seen |= (v != v);
-        if (k) { mx = fmaxf(mx, v); nlegal += 1.f; }
-        if (k && j < lo) lo = j;
-    }
-    const bool mine = lo < A;                                  // this thread's stride holds a legal action
-    if (tid == 0) { s_first = kScThreads; s_last = -1; s_lo = A; }
-    mx = sc_reduce(mx, red, true);
-    nlegal = sc_reduce(nlegal, red, false);
-    const float nanf_ = sc_reduce((float)nan_seen, red, false);
+    __shared__ PolicyDrawLds<kScThreads> draw;
+    const int b = blockIdx.x, tid = threadIdx.x, A = a.A;
+    PolicyRowHead h = policy_stage<kScThreads, true, true>(a.logits, a.logits_bf16, a.legal, a.legal_words, b, A, row, msk, bits);
+    draw.reset(A);
+    h.reduce<kScThreads>(red);
+    const float mx = h.mx, nlegal = h.nlegal;
     const int m = a.model_of[b];
     const bool seated = m >= 0 && m < a.K;                     // (uniform over the workgroup, as every branch below)
 
@@ -111,49 +80,23 @@ __global__ __launch_bounds__(kScThreads) void policy_sample_ctl_kernel(CtlArgs a
     float tv = INFINITY;
     int ti = -1, first_i = INT_MAX;
     for (int r = 0; r < rounds; ++r) {
-        float bv = -INFINITY;
-        int bi = INT_MAX;
-        for (int w = tid; w < words; w += kScThreads) {
-            uint32_t mw = bits[w];
-            while (mw) {
-                const int j = (w << 5) + __builtin_ctz(mw);
-                mw &= mw - 1u;
-                const float v = row[j];
-                if (sc_before(tv, ti, v, j) && sc_before(v, j, bv, bi)) { bv = v; bi = j; }
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o);
-            const int oi = __shfl_xor(bi, o);
-            if (sc_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
-        __syncthreads();
-        if (lane == 0) { red[wave] = bv; red_i[wave] = bi; }
-        __syncthreads();
-        bv = red[0]; bi = red_i[0];
-        for (int w = 1; w < kScWaves; ++w)
-            if (sc_before(red[w], red_i[w], bv, bi)) { bv = red[w]; bi = red_i[w]; }
+        float bv;
+        const int bi = policy_next<kScThreads, true>(row, bits, words, tv, ti, red, red_i, &bv);
         if (bi == INT_MAX) break;                              // nothing behind the last winner (NaN logits only): it stays the threshold
         tv = bv; ti = bi;
         if (r == 0) first_i = bi;
     }
 
-    if (!seated || (greedy && nlegal > 0.f)) {
-        // an unseated row takes its first legal action (log-prob 0); a greedy row the first action of the order (probability 1)
-        if (mine) atomicMin(&s_lo, lo);
-        __syncthreads();
+    if (!seated) {                                             // its first legal action, log-prob 0
+        policy_end_unseated(h, A, draw, a.flags, &a.nlegal[b], &a.actions[b], &a.logp[b]);
+        return;
+    }
+    if (greedy && nlegal > 0.f) {                              // the first action of the order, probability 1
+        const int lowest = policy_lowest(h, A, draw);
         if (tid == 0) {
-            if (nanf_ > 0.f) atomicOr(&a.flags[0], 1);
-            if (nlegal == 0.f) atomicOr(&a.flags[1], 1);
-            a.nlegal[b] = (int)nlegal;
-            if (!seated) {
-                a.actions[b] = s_lo < A ? s_lo : 0;
-                a.logp[b] = 0.f;
-            } else {
-                a.actions[b] = first_i != INT_MAX ? first_i : s_lo;
-                a.logp[b] = logf(1.f - 1.1920929e-7f);
-            }
+            policy_report(h, a.flags, &a.nlegal[b], &a.actions[b], &a.logp[b]);
+            a.actions[b] = first_i != INT_MAX ? first_i : lowest;
+            a.logp[b] = logf(1.f - 1.1920929e-7f);
         }
         return;
     }
@@ -161,54 +104,11 @@ __global__ __launch_bounds__(kScThreads) void policy_sample_ctl_kernel(CtlArgs a
     // T > 0 from here on (a greedy row without a legal action ends below as every such row does)
     const float inv_t = greedy ? 1.f : fminf(1.f / T, 3.0e38f);
     const bool limited = cut && ti >= 0;                       // S = the legal actions not behind the threshold (tv, ti)
-    auto in_s = [&](int j) -> bool { return msk[j] && (!limited || !sc_before(tv, ti, row[j], j)); };
-    float s = 0.f;
-    for (int j = tid; j < A; j += kScThreads)
-        if (in_s(j)) s += expf((row[j] - mx) * inv_t);
-    s = sc_reduce(s, red, false);                              // the normaliser of the masked-softmax path (same order)
-    // contiguous chunk per thread, inclusive prefix over the threads
-    const int chunk = (A + kScThreads - 1) / kScThreads, j0 = tid * chunk, j1 = min(j0 + chunk, A);
-    float local = 0.f;
-    for (int j = j0; j < j1; ++j) if (in_s(j)) local += expf((row[j] - mx) * inv_t);
-    float incl = local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const float t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    float base = 0.f, total = 0.f;
-    for (int w = 0; w < kScWaves; ++w) { if (w < wave) base += wave_tot[w]; total += wave_tot[w]; }
-    incl += base;
-    const unsigned long long seed = (unsigned long long)*a.seed_dev;
-    // the play sampler's draw (loss.hip): the same (seed, row) gives the same uniform
-    const unsigned long long h = ka_mix64(seed ^ ka_mix64((unsigned long long)b + 0x5851F42D4C957F2Dull));
-    const float u = (float)(h >> 40) * (1.0f / 16777216.0f);   // 24 bits: [0, 1)
-    const float target = u * total;
-    if (local > 0.f) {                                         // (as the play sampler: a chunk whose weights all underflow is no chunk of S)
-        if (incl > target) atomicMin(&s_first, tid);
-        atomicMax(&s_last, tid);
-    }
-    __syncthreads();
-    const int winner = s_first < kScThreads ? s_first : s_last;           // (rounding can leave target >= total: last chunk of S)
-    if (tid == 0) {
-        if (nanf_ > 0.f) atomicOr(&a.flags[0], 1);
-        if (nlegal == 0.f) { atomicOr(&a.flags[1], 1); a.actions[b] = 0; a.logp[b] = 0.f; }
-        a.nlegal[b] = (int)nlegal;
-    }
-    if (tid == winner) {
-        float run = incl - local;
-        int pick = -1, last = -1;
-        for (int j = j0; j < j1; ++j) {
-            if (!in_s(j)) continue;
-            last = j;
-            run += expf((row[j] - mx) * inv_t);
-            if (run > target) { pick = j; break; }
-        }
-        if (pick < 0) pick = last;
-        a.actions[b] = pick;
-        // Categorical(probs).log_prob = log(clamp(q, eps, 1 - eps)), eps = FLT_EPSILON
-        const float q = expf((row[pick] - mx) * inv_t) * (1.f / s);
-        a.logp[b] = logf(fminf(fmaxf(q, 1.1920929e-7f), 1.f - 1.1920929e-7f));
-    }
+    const auto in_s = [&](int j) -> bool { return msk[j] && (!limited || !policy_before(tv, ti, row[j], j)); };
+    const auto weight = [&](int j) { return expf((row[j] - mx) * inv_t); };
+    const float s = policy_normaliser<kScThreads>(A, in_s, weight, red);
+    policy_draw(A, b, (unsigned long long)*a.seed_dev, s, in_s, weight, draw, &a.actions[b], &a.logp[b]);
+    if (tid == 0) policy_report(h, a.flags, &a.nlegal[b], &a.actions[b], &a.logp[b]);
 }
 
 }  // namespace
@@ -219,9 +119,9 @@ extern "C" int ka_policy_sample_ctl(const void* logits, int logits_bf16, const v
                                     void* stream) {
     KA_REQUIRE(logits && legal && seed_dev && model_of && ctl && actions && logp && nlegal && flags && B > 0 && A > 0,
                "policy_sample_ctl: null tensor");
-    KA_REQUIRE(legal_words == 0 || legal_words == (A + 31) / 32, "policy_sample_ctl: packed mask rows must hold %d words", (A + 31) / 32);
-    const size_t lds = ((size_t)A * 4 + 15) / 16 * 16 + ((size_t)A + 15) / 16 * 16 + ((size_t)A + 63) / 64 * 8;
-    KA_REQUIRE(lds <= 64 * 1024, "policy_sample_ctl: action space %d too large for the LDS row", A);
+    KA_REQUIRE_MASK_ROW("policy_sample_ctl", A, legal_words);
+    const size_t lds = policy_row_bytes(A) + policy_mask_bytes(A) + policy_bits_bytes(A);
+    KA_REQUIRE_ROW_LDS("policy_sample_ctl", lds, A);
     KA_REQUIRE(K >= 1, "policy_sample_ctl: the controls table needs at least one row, got K = %d", K);
     KA_REQUIRE(!plies || ply_stride >= 4, "policy_sample_ctl: ply_stride must be at least 4 bytes, got %d", ply_stride);
     KA_REQUIRE((uintptr_t)ctl % 4 == 0 && (!plies || ((uintptr_t)plies % 4 == 0 && ply_stride % 4 == 0)),
